@@ -779,6 +779,27 @@ def emit(full):
     print(json.dumps(compact_line(full)), flush=True)
 
 
+DUMP_SAMPLE = 1 << 20   # --dump-outputs: elements kept of a larger array (4 arrays x (4 MB sample + 8 MB index) <= 48 MB written)
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: what the last timed evaluate() returned, as DIR/<name>.npy: output_ids (float64, exact for token ids),
+    pred_masks_left / pred_masks_right (every [SEG]'s mask, frame after frame) and taxonomies (float32). An array of more than
+    DUMP_SAMPLE elements is written as a fixed, seeded sample of its flattened elements, with their flat positions beside it as
+    <name>_index.npy, so that two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    ids, left, right, tax = out
+    arrays = {"output_ids": ids.double(), "pred_masks_left": torch.cat(left).float(),
+              "pred_masks_right": torch.cat(right).float(), "taxonomies": torch.cat(tax).float()}
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
 def base_line(fps, world, steps, warmup, ms_per_step, workload, B, extra_cfg):
     cfg = {"workload": workload, "frames_per_step_per_gpu": B,
            "parallelism": "frame-sharded replicas x%d (no collective)" % world}
@@ -1104,7 +1125,13 @@ def main(argv=None):
     ap.add_argument("--stub-step-ms", type=float, default=None,
                     help="TEST ONLY (tests/test_dist_gloo.py): replace the model by a sleep of this many ms and rendezvous "
                          "over gloo on the CPU, to exercise the multi-rank fence / timing / reporting path without GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, <= 64 MB in all: see dump_outputs()")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and (args.stub_step_ms is not None or args.mode == "train"):
+        raise SystemExit("bench.py: --dump-outputs writes the inference step's outputs: not with --stub-step-ms or --mode train")
 
     # --gpus N must mean N ranks: under torchrun WORLD_SIZE says so; bare, this process becomes the launcher. Never an n_gpus: 1
     # line for --gpus 8.
@@ -1175,9 +1202,14 @@ def main(argv=None):
 
     for _ in range(args.warmup):
         step()
-    outs = []
-    elapsed = hdist.timed_steps(lambda: outs.append(step()), args.steps, device)  # fence | K steps | fence | max over ranks
-    out = outs[-1]
+    out = None
+
+    def timed_step():
+        nonlocal out
+        out = step()    # only the last step's outputs are kept: K steps hold one step's outputs in HBM, not K
+    elapsed = hdist.timed_steps(timed_step, args.steps, device)  # fence | K steps | fence | max over ranks
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(out, args.dump_outputs)
     chain_timed = bool(getattr(model, "last_decode_chain", False))
     plan_timed = model.last_plan     # (workgroup caps per encoder chunk, encoder waits for the prefill, frames per chunk) of the timed steps
     ms_per_step = 1e3 * elapsed / args.steps

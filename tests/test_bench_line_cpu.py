@@ -74,3 +74,49 @@ def test_stub_run_prints_exactly_one_line_within_the_budget(tmp_path, monkeypatc
     assert line["n_gpus"] == 1 and line["steps"] == 2 and line["config"]["stub"] is True and line["cpu_baseline"] is None
     detail = os.path.join(ROOT, line["detail"])
     assert os.path.exists(detail) and json.load(open(detail))["steps"] == 2
+
+
+def _fake_evaluate_out(seed):
+    """evaluate()'s return value at 3 frames of 640^2: ids, per-frame left / right masks and taxonomies of one [SEG] each."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(0, 32000, (3, 9), generator=g)
+    masks = lambda: [torch.randn((1, 640, 640), generator=g) for _ in range(3)]   # noqa: E731
+    return ids, masks(), masks(), [torch.randn((1, 4), generator=g) for _ in range(3)]
+
+
+def test_dump_outputs_writes_every_output_within_the_budget(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files of what evaluate() returned; an array over DUMP_SAMPLE elements (the masks: 3 x
+    640^2) is a fixed sample of its flat elements with the positions beside it; the same outputs give the same files."""
+    import numpy as np
+    import torch
+    out = _fake_evaluate_out(0)
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["output_ids.npy", "pred_masks_left.npy", "pred_masks_left_index.npy", "pred_masks_right.npy",
+                     "pred_masks_right_index.npy", "taxonomies.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 10 ** 6
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n)), n
+    assert got["output_ids"].dtype == np.float64 and np.array_equal(got["output_ids"], out[0].numpy())
+    assert got["taxonomies"].dtype == np.float32 and np.array_equal(got["taxonomies"], torch.cat(out[3]).numpy())
+    for side, masks in (("left", out[1]), ("right", out[2])):
+        v, idx = got[f"pred_masks_{side}"], got[f"pred_masks_{side}_index"]
+        assert v.dtype == np.float32 and idx.dtype == np.float64 and 0.6 * bench.DUMP_SAMPLE < v.size <= bench.DUMP_SAMPLE
+        flat = torch.cat(masks).reshape(-1).numpy()
+        assert idx[-1] < flat.size and np.all(np.diff(idx) > 0) and np.array_equal(v, flat[idx.astype(np.int64)])
+    bench.dump_outputs(_fake_evaluate_out(1), str(tmp_path / "c"))      # other outputs: same positions, other values
+    assert np.array_equal(np.load(tmp_path / "c" / "pred_masks_left_index.npy"), got["pred_masks_left_index"])
+    assert not np.array_equal(np.load(tmp_path / "c" / "pred_masks_left.npy"), got["pred_masks_left"])
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"], ["--stub-step-ms", "5", "--dump-outputs", "x"],
+                                  ["--mode", "train", "--dump-outputs", "x"]])
+def test_bench_refuses_arguments_it_cannot_honour(argv, monkeypatch):
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    with pytest.raises(SystemExit) as e:
+        bench.main(["--gpus", "1"] + argv)
+    assert "bench.py:" in str(e.value)
