@@ -66,8 +66,9 @@ typedef __attribute__((address_space(3))) bf16x4* lds_v4_ptr;
 // sums exactly the bf16-rounded probabilities the numerator uses).
 // FULL: Nq % 128 == 0 and Nk % 64 == 0 (and no causal mask, no grid remap): every tile is whole, so the clamped /
 // remapped load path, the key masks and the row guards are compiled out (the SAM global blocks: 4096 x 4096).
-template <int DP, int BIAS, bool CAUSAL, int NDT = DP / 16, bool LSUM = false, bool FULL = false>
+template <int DP, int BIAS, bool CAUSAL, int NDT = DP / 16, bool LSUM = false, bool FULL = false, bool F16 = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
+  using E = h16<F16>;   // F16: fp16 q / k / v / o and probabilities (v_mfma_f32_16x16x32_f16), bf16 otherwise
   static_assert(!FULL || (!CAUSAL && BIAS != 3), "FULL tiles only");
   // K rows: the fragment read (lane = (key fr, d-chunk fh): 16 B at row fr, column 16 fh) is conflict-free exactly for row strides
   // of 32 modulo 64 bytes (tools/probes/lds_b128_pattern.hip; the DP * 2 + 16 of rounds 1-3 ran every K read at half rate)
@@ -132,11 +133,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
         // `q * self.scale`): scores then leave the MFMA already in the log2 domain with the bias folded into
         // the accumulator's initial value — no per-element fma/zero-fill in the tile loop.
         float qv[8];
-        load8(qb + (long)qc * p.q_st + col, qv);
+        load8h<F16>(qb + (long)qc * p.q_st + col, qv);
 #pragma unroll
         for (int j = 0; j < 8; ++j) qv[j] *= sl2;
-        r.x = pack_bf16x2(qv[0], qv[1]); r.y = pack_bf16x2(qv[2], qv[3]);
-        r.z = pack_bf16x2(qv[4], qv[5]); r.w = pack_bf16x2(qv[6], qv[7]);
+        r.x = E::pack2(qv[0], qv[1]); r.y = E::pack2(qv[2], qv[3]);
+        r.z = E::pack2(qv[4], qv[5]); r.w = E::pack2(qv[6], qv[7]);
       }
       qf[qt][kd] = __builtin_bit_cast(bf16x8, r);
     }
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
   for (int i = 0; i < NCH; ++i) {
     if (!col_ok[i]) {
       uint4 vpad = make_uint4(0, 0, 0, 0);
-      if (LSUM && st_c[i] * 8 == p.d) vpad.x = 0x3f80u;   // bf16 1.0 in column d
+      if (LSUM && st_c[i] * 8 == p.d) vpad.x = F16 ? 0x3c00u : 0x3f80u;   // 1.0 (f16 / bf16) in column d
 #pragma unroll
       for (int b2 = 0; b2 < 2; ++b2) {
         unsigned char* wK = sKV + b2 * STAGE_BYTES;
@@ -327,8 +328,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sK + (16 * t + fr) * KSTRIDE + (kd * 4 + fh) * 16);
-        sacc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[0][kd], sacc[t][0], 0, 0, 0);
-        sacc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[1][kd], sacc[t][1], 0, 0, 0);
+        sacc[t][0] = E::mfma16(kf, qf[0][kd], sacc[t][0]);
+        sacc[t][1] = E::mfma16(kf, qf[1][kd], sacc[t][1]);
       }
     }
 
@@ -423,10 +424,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         uint4 u;
-        u.x = pack_bf16x2(sacc[2 * ks][qt][0], sacc[2 * ks][qt][1]);
-        u.y = pack_bf16x2(sacc[2 * ks][qt][2], sacc[2 * ks][qt][3]);
-        u.z = pack_bf16x2(sacc[2 * ks + 1][qt][0], sacc[2 * ks + 1][qt][1]);
-        u.w = pack_bf16x2(sacc[2 * ks + 1][qt][2], sacc[2 * ks + 1][qt][3]);
+        u.x = E::pack2(sacc[2 * ks][qt][0], sacc[2 * ks][qt][1]);
+        u.y = E::pack2(sacc[2 * ks][qt][2], sacc[2 * ks][qt][3]);
+        u.z = E::pack2(sacc[2 * ks + 1][qt][0], sacc[2 * ks + 1][qt][1]);
+        u.w = E::pack2(sacc[2 * ks + 1][qt][2], sacc[2 * ks + 1][qt][3]);
         pf[qt][ks] = __builtin_bit_cast(bf16x8, u);
       }
     }
@@ -442,8 +443,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
         const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4_ptr)(a0));
         const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4_ptr)(a1));
         const bf16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        oacc[dt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[0][ks], oacc[dt][0], 0, 0, 0);
-        oacc[dt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[1][ks], oacc[dt][1], 0, 0, 0);
+        oacc[dt][0] = E::mfma16(vf, pf[0][ks], oacc[dt][0]);
+        oacc[dt][1] = E::mfma16(vf, pf[1][ks], oacc[dt][1]);
       }
     }
     // registers -> the OTHER stage (last read one iteration ago, every wave is past that barrier), then ONE barrier:
@@ -472,20 +473,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
         const int col = 16 * dt + 4 * fh;
         if (col < p.d) {
           float v[4] = {oacc[dt][qt][0] * inv, oacc[dt][qt][1] * inv, oacc[dt][qt][2] * inv, oacc[dt][qt][3] * inv};
-          store4(ob + (long)qrow[qt] * p.o_st + col, v);
+          store4h<F16>(ob + (long)qrow[qt] * p.o_st + col, v);
         }
       }
     }
   }
 }
 
-template <int DP, int BIAS, bool CAUSAL, int NDT = DP / 16, bool LSUM = false, bool FULL = false>
+template <int DP, int BIAS, bool CAUSAL, int NDT = DP / 16, bool LSUM = false, bool FULL = false, bool F16 = false>
 int launch_attn(const AttnArgs& p, hipStream_t s) {
   constexpr int KSTRIDE = (DP * 2) % 64 == 32 ? DP * 2 : DP * 2 + 32, VSTRIDE = DP * 2 + 32;   // (the kernel's)
   size_t lds = 2 * ((size_t)KT * KSTRIDE + (size_t)KT * VSTRIDE);
   if (BIAS == 1) lds += (size_t)QB * (2 * 32 + 1) * sizeof(float);
   dim3 grid(((p.Nq + QB - 1) / QB) * p.H * p.B), block(256);
-  hipLaunchKernelGGL((attn_fwd_kernel<DP, BIAS, CAUSAL, NDT, LSUM, FULL>), grid, block, lds, s, p);
+  hipLaunchKernelGGL((attn_fwd_kernel<DP, BIAS, CAUSAL, NDT, LSUM, FULL, F16>), grid, block, lds, s, p);
   return haff_check_launch();
 }
 
@@ -553,8 +554,9 @@ __device__ unsigned long long haff_pp_trace_buf[256 * 2 * 4 * 8];
 // query on the column side, like the score MFMA. A wave's 32 queries share qh, so rel_h lands in its LDS rows by a plain
 // index flip; rel_w's row index depends on the query's own qw, so the products pass through a wave-private LDS scratch
 // (in the K/V stage area, before the first K/V request) indexed [query][kw] and come back as the 16 values a lane keeps.
-template <bool FUSED_REL>
+template <bool FUSED_REL, bool F16 = false>
 __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
+  using E = h16<F16>;   // F16: fp16 q / k / v / o / tables and probabilities, bf16 otherwise
   constexpr int NKD = 3, ND = 5;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   typedef __attribute__((address_space(3))) unsigned char* lds_ptr;
@@ -656,11 +658,11 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
       uint4 r = make_uint4(0, 0, 0, 0);
       if (col < PP_D) {
         float qv[8];
-        load8(qb + (long)qi * p.q_st + col, qv);
+        load8h<F16>(qb + (long)qi * p.q_st + col, qv);
 #pragma unroll
         for (int j = 0; j < 8; ++j) qv[j] *= sl2;
-        r.x = pack_bf16x2(qv[0], qv[1]); r.y = pack_bf16x2(qv[2], qv[3]);
-        r.z = pack_bf16x2(qv[4], qv[5]); r.w = pack_bf16x2(qv[6], qv[7]);
+        r.x = E::pack2(qv[0], qv[1]); r.y = E::pack2(qv[2], qv[3]);
+        r.z = E::pack2(qv[4], qv[5]); r.w = E::pack2(qv[6], qv[7]);
       }
       qf[qt][kd] = __builtin_bit_cast(bf16x8, r);
     }
@@ -696,8 +698,8 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
 #pragma unroll
       for (int kd = 0; kd < NKD; ++kd) {
         const bf16x8 tf = table_frag(p.tab_h, qh + 16 * j + fr, kd);
-        a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, qr[0][kd], a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf, qr[1][kd], a1, 0, 0, 0);
+        a0 = E::mfma16(tf, qr[0][kd], a0);
+        a1 = E::mfma16(tf, qr[1][kd], a1);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -715,7 +717,7 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
         f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kd = 0; kd < NKD; ++kd)
-          a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(table_frag(p.tab_w, qwb + 16 * qt + 16 * j + fr, kd), qr[qt][kd], a, 0, 0, 0);
+          a = E::mfma16(table_frag(p.tab_w, qwb + 16 * qt + 16 * j + fr, kd), qr[qt][kd], a);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int kw = KT - 1 + fr - 16 * j - 4 * fh - r;
@@ -771,7 +773,8 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
   }
   // row sums: one more MFMA per (k-step, q-tile) against a register fragment of ones — the issue port is what this kernel is
   // bound by, and 32 f32 adds per tile cost it four times what 4 MFMAs do; every row of lacc[qt] holds the same sums
-  const bf16x8 ones = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};
+  constexpr short ONE = F16 ? 0x3c00 : 0x3f80;   // 1.0 in f16 / bf16
+  const bf16x8 ones = {ONE, ONE, ONE, ONE, ONE, ONE, ONE, ONE};
   f32x4 lacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
   float m_run[2] = {0.f, 0.f};
   bf16x8 pf[2][2];
@@ -823,11 +826,11 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
     constexpr int ks = decltype(ks_tag)::value;
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) {
-      oacc[dt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf[0][ks], oacc[dt][0], 0, 0, 0);
-      oacc[dt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt], pf[1][ks], oacc[dt][1], 0, 0, 0);
+      oacc[dt][0] = E::mfma16(vf[dt], pf[0][ks], oacc[dt][0]);
+      oacc[dt][1] = E::mfma16(vf[dt], pf[1][ks], oacc[dt][1]);
     }
-    lacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[0][ks], lacc[0], 0, 0, 0);
-    lacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[1][ks], lacc[1], 0, 0, 0);
+    lacc[0] = E::mfma16(ones, pf[0][ks], lacc[0]);
+    lacc[1] = E::mfma16(ones, pf[1][ks], lacc[1]);
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -889,8 +892,8 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
       constexpr int kd = decltype(kd_tag)::value;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        sacc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t], qf[0][kd], sacc[t][0], 0, 0, 0);
-        sacc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t], qf[1][kd], sacc[t][1], 0, 0, 0);
+        sacc[t][0] = E::mfma16(kf[t], qf[0][kd], sacc[t][0]);
+        sacc[t][1] = E::mfma16(kf[t], qf[1][kd], sacc[t][1]);
       }
     };
     // (sched_group_barrier: the phase's reads go out BEFORE its MFMAs — left alone, hipcc reuses the registers of the
@@ -966,8 +969,8 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
 #endif
           }
           uint4 u;
-          u.x = pack_bf16x2(e[0], e[1]); u.y = pack_bf16x2(e[2], e[3]);
-          u.z = pack_bf16x2(e[4], e[5]); u.w = pack_bf16x2(e[6], e[7]);
+          u.x = E::pack2(e[0], e[1]); u.y = E::pack2(e[2], e[3]);
+          u.z = E::pack2(e[4], e[5]); u.w = E::pack2(e[6], e[7]);
           pf[qt][ks] = __builtin_bit_cast(bf16x8, u);
         }
       };
@@ -1060,7 +1063,7 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) {
       float v[4] = {oacc[dt][qt][0] * inv, oacc[dt][qt][1] * inv, oacc[dt][qt][2] * inv, oacc[dt][qt][3] * inv};
-      store4(ob + qi * p.o_st + 16 * dt + 4 * fh, v);
+      store4h<F16>(ob + qi * p.o_st + 16 * dt + 4 * fh, v);
     }
   }
 }
@@ -1087,14 +1090,14 @@ static bool attn_global_pp_ok(const AttnArgs& p, bool fused_rel) {
   return (reinterpret_cast<uintptr_t>(p.relh) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.relw) & 15) == 0;
 }
 
-template <bool FUSED_REL>
+template <bool FUSED_REL, bool F16 = false>
 static int launch_attn_global_pp(const AttnArgs& p, hipStream_t s) {
   // the attribute is per device and this entry point keeps no state: set it on every call (a host-side table write)
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_global_pp_kernel<FUSED_REL>),
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_global_pp_kernel<FUSED_REL, F16>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS) != hipSuccess)
     return HAFF_ERR_LAUNCH;
   dim3 grid((p.Nq / PPQ) * p.H * p.B), block(512);
-  hipLaunchKernelGGL(attn_global_pp_kernel<FUSED_REL>, grid, block, PP_LDS, s, p);
+  hipLaunchKernelGGL((attn_global_pp_kernel<FUSED_REL, F16>), grid, block, PP_LDS, s, p);
   return haff_check_launch();
 }
 
@@ -1121,8 +1124,10 @@ __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes 
 // B*H: one wave per head left the step latency-bound — 35 us per layer at batch 1 for 4.7 MB of K/V); their partial
 // (max, sum, P.V) meet in LDS.
 // rotate-half RoPE of the 8 values a lane holds of a 128-wide head row (lane c: dims 8c .. 8c+7; the partner half sits 8
-// lanes away in the same 16-lane row), rounded to bf16 as the stand-alone rope kernel stores it
+// lanes away in the same 16-lane row), rounded to bf16 (fp16) as the stand-alone rope kernel stores it
+template <bool F16>
 __device__ __forceinline__ void rope8(float (&x)[8], const float* cs_row, int c) {
+  using E = h16<F16>;
   const int ci = (c & 7) * 8;
   float cv[8], sv[8];
   load8(cs_row + ci, cv);
@@ -1130,15 +1135,19 @@ __device__ __forceinline__ void rope8(float (&x)[8], const float* cs_row, int c)
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float other = __shfl_xor(x[j], 8, 64);
-    const float r = c < 8 ? x[j] * cv[j] - other * sv[j] : x[j] * cv[j] + other * sv[j];
-    x[j] = bf16_to_f32(f32_to_bf16(r));
+    float r = c < 8 ? x[j] * cv[j] - other * sv[j] : x[j] * cv[j] + other * sv[j];
+    // f16: r is rounded to f32 first, as the stand-alone rope kernel stores it (without the barrier the last fma and the f16
+    // conversion fuse into v_fma_mixlo_f16: ONE rounding, a last-bit difference from rope_cache_rows on q)
+    if constexpr (F16) asm volatile("" : "+v"(r));
+    x[j] = E::to_f32(E::from_f32(r));
   }
 }
 
 // NW: waves per workgroup. SPLIT with 16 waves (few (batch, head) pairs: batch 1..4): each wave takes ONE trip of 16 keys
 // per 256 — a 300-key cache is one or two round trips per wave instead of five (10.7 -> ~6 us per layer at batch 1).
-template <bool SPLIT, bool ROPE = false, int NW = 4>
+template <bool SPLIT, bool ROPE = false, int NW = 4, bool F16 = false>
 __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
+  using E = h16<F16>;
   static_assert(NW == 4 || SPLIT, "the one-wave-per-head form packs 4 heads per workgroup");
   __shared__ float s_ml[NW][2];
   __shared__ float s_o[NW][DEC_D];
@@ -1154,17 +1163,17 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
   const bf16_t* vb = p.v + (long)b * p.v_sb + (long)h * p.v_sh + c * 8;
 
   float qv[8];
-  load8(qb + c * 8, qv);
+  load8h<F16>(qb + c * 8, qv);
   uint4 knew_bits = make_uint4(0, 0, 0, 0), vnew_bits = make_uint4(0, 0, 0, 0);
   if (ROPE) {
     // position of this step = Nk - 1: rotate q and the new k (transformers apply_rotary_pos_emb), append k, v to the caches
     const float* cs_row = p.cos_sin + (long)(Nk - 1) * DEC_D;
-    rope8(qv, cs_row, c);
+    rope8<F16>(qv, cs_row, c);
     float kn[8];
-    load8(p.knew + (long)b * p.q_sb + (long)h * p.q_sh + c * 8, kn);
-    rope8(kn, cs_row, c);
-    knew_bits.x = pack_bf16x2(kn[0], kn[1]); knew_bits.y = pack_bf16x2(kn[2], kn[3]);
-    knew_bits.z = pack_bf16x2(kn[4], kn[5]); knew_bits.w = pack_bf16x2(kn[6], kn[7]);
+    load8h<F16>(p.knew + (long)b * p.q_sb + (long)h * p.q_sh + c * 8, kn);
+    rope8<F16>(kn, cs_row, c);
+    knew_bits.x = E::pack2(kn[0], kn[1]); knew_bits.y = E::pack2(kn[2], kn[3]);
+    knew_bits.z = E::pack2(kn[4], kn[5]); knew_bits.w = E::pack2(kn[6], kn[7]);
     vnew_bits = *reinterpret_cast<const uint4*>(p.vnew + (long)b * p.q_sb + (long)h * p.q_sh + c * 8);
     if (g == 0 && (!SPLIT || wave == 0)) {
       *reinterpret_cast<uint4*>(const_cast<bf16_t*>(kb) + (long)(Nk - 1) * p.k_st) = knew_bits;
@@ -1200,8 +1209,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
       float s = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        s += qv[2 * j] * __builtin_bit_cast(float, kw[j] << 16);
-        s += qv[2 * j + 1] * __builtin_bit_cast(float, kw[j] & 0xffff0000u);
+        s += qv[2 * j] * E::lo(kw[j]);
+        s += qv[2 * j + 1] * E::hi(kw[j]);
       }
       s = row16_sum(s);
       s = key < Nk ? s : -INFINITY;
@@ -1213,8 +1222,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
       const unsigned vw[4] = {vr[u].x, vr[u].y, vr[u].z, vr[u].w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        o[2 * j] = o[2 * j] * alpha + pr * __builtin_bit_cast(float, vw[j] << 16);
-        o[2 * j + 1] = o[2 * j + 1] * alpha + pr * __builtin_bit_cast(float, vw[j] & 0xffff0000u);
+        o[2 * j] = o[2 * j] * alpha + pr * E::lo(vw[j]);
+        o[2 * j + 1] = o[2 * j + 1] * alpha + pr * E::hi(vw[j]);
       }
     }
   }
@@ -1235,7 +1244,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
   if (!SPLIT) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] /= l;
-    if (g == 0) store8(p.o + (long)b * p.o_sb + (long)h * p.o_sh + c * 8, o);
+    if (g == 0) store8h<F16>(p.o + (long)b * p.o_sb + (long)h * p.o_sh + c * 8, o);
     return;
   }
   if (g == 0) {
@@ -1258,7 +1267,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] /= L;
-    store8(p.o + (long)b * p.o_sb + (long)h * p.o_sh + c * 8, acc);
+    store8h<F16>(p.o + (long)b * p.o_sb + (long)h * p.o_sh + c * 8, acc);
   }
 }
 
@@ -1267,6 +1276,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
 // q/k/v/o: bf16; strides in elements (batch, head, token). d % 8 == 0, d <= 128.
 // causal != 0: key j visible to query i iff j <= i + q_pos0.
 // relh/relw (may be null): fp32 [B*H][Nq][S] decomposed rel-pos terms; key index -> (kh, kw) = (j / S, j % S).
+template <bool F16 = false>
 static int attention_bf16_impl(const void* q, long q_sb, long q_sh, long q_st,
                                const void* k, long k_sb, long k_sh, long k_st,
                                const void* v, long v_sb, long v_sh, long v_st,
@@ -1281,6 +1291,8 @@ static int attention_bf16_impl(const void* q, long q_sb, long q_sh, long q_st,
     return HAFF_ERR_BAD_ARG;
   const bool rel = relh != nullptr && relw != nullptr;
   if (rel && (causal || S <= 0 || (Nk % S) != 0)) return HAFF_ERR_BAD_ARG;
+  // fp16: the rel-pos instances stop at d <= 96 (ViT-H: 80); the d = 128 ones use scratch, and no fp16 caller needs them
+  if (F16 && rel && d > 96) return HAFF_ERR_UNSUPPORTED;
   AttnArgs p{reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const bf16_t*>(v),
              reinterpret_cast<bf16_t*>(o), q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st,
              B, H, Nq, Nk, d, scale, q_pos0, relh, relw, S, nk_rows, nullptr, nullptr, nullptr};
@@ -1288,9 +1300,9 @@ static int attention_bf16_impl(const void* q, long q_sb, long q_sh, long q_st,
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (!lse && !rel && Nq == 1 && d == DEC_D && (!causal || q_pos0 >= Nk - 1) && (o_sh & 7) == 0 && (o_sb & 7) == 0 &&
       (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-    if (B * H <= 128) hipLaunchKernelGGL((attn_decode_kernel<true, false, 16>), dim3(B * H), dim3(1024), 0, s, p);
-    else if (B * H <= 1024) hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(B * H), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(attn_decode_kernel<false>, dim3((B * H + 3) / 4), dim3(256), 0, s, p);
+    if (B * H <= 128) hipLaunchKernelGGL((attn_decode_kernel<true, false, 16, F16>), dim3(B * H), dim3(1024), 0, s, p);
+    else if (B * H <= 1024) hipLaunchKernelGGL((attn_decode_kernel<true, false, 4, F16>), dim3(B * H), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((attn_decode_kernel<false, false, 4, F16>), dim3((B * H + 3) / 4), dim3(256), 0, s, p);
     return haff_check_launch();
   }
   const int dp = d <= 64 ? 64 : (d <= 96 ? 96 : 128);
@@ -1298,30 +1310,32 @@ static int attention_bf16_impl(const void* q, long q_sb, long q_sh, long q_st,
     const int mode = (S == 64) ? 2 : (S <= 16 && Nk == S * S ? 3 : 1);
     if (mode == 1 && S > 32) return HAFF_ERR_UNSUPPORTED;
     if (mode == 3) {
-      if (dp == 64) return launch_attn<64, 3, false>(p, s);
-      if (dp == 96) return launch_attn<96, 3, false>(p, s);
-      return launch_attn<128, 3, false>(p, s);
+      if (dp == 64) return launch_attn<64, 3, false, 64 / 16, false, false, F16>(p, s);
+      if (dp == 96) return launch_attn<96, 3, false, 96 / 16, false, false, F16>(p, s);
+      if constexpr (!F16) return launch_attn<128, 3, false, 128 / 16, false, false, F16>(p, s);
+      return HAFF_ERR_UNSUPPORTED;
     }
-    if (dp == 64) return mode == 2 ? launch_attn<64, 2, false>(p, s) : launch_attn<64, 1, false>(p, s);
+    if (dp == 64) return mode == 2 ? launch_attn<64, 2, false, 64 / 16, false, false, F16>(p, s) : launch_attn<64, 1, false, 64 / 16, false, false, F16>(p, s);
     if (dp == 96 && mode == 2 && d == 80) {   // SAM global blocks
 #ifdef HAFF_TUNING
-      if (getenv("HAFF_ATTN_NO_PP")) return launch_attn<96, 2, false, 6, true, true>(p, s);
+      if (getenv("HAFF_ATTN_NO_PP")) return launch_attn<96, 2, false, 6, true, true, F16>(p, s);
 #endif
-      if (attn_global_pp_ok(p, false)) return launch_attn_global_pp<false>(p, s);
-      if ((Nq % 128) == 0 && (Nk % KT) == 0 && !nk_rows) return launch_attn<96, 2, false, 6, true, true>(p, s);
-      return launch_attn<96, 2, false, 6, true>(p, s);
+      if (attn_global_pp_ok(p, false)) return launch_attn_global_pp<false, F16>(p, s);
+      if ((Nq % 128) == 0 && (Nk % KT) == 0 && !nk_rows) return launch_attn<96, 2, false, 6, true, true, F16>(p, s);
+      return launch_attn<96, 2, false, 6, true, false, F16>(p, s);
     }
-    if (dp == 96) return mode == 2 ? launch_attn<96, 2, false>(p, s) : launch_attn<96, 1, false>(p, s);
-    return mode == 2 ? launch_attn<128, 2, false>(p, s) : launch_attn<128, 1, false>(p, s);
+    if (dp == 96) return mode == 2 ? launch_attn<96, 2, false, 96 / 16, false, false, F16>(p, s) : launch_attn<96, 1, false, 96 / 16, false, false, F16>(p, s);
+    if constexpr (!F16) return mode == 2 ? launch_attn<128, 2, false, 128 / 16, false, false, F16>(p, s) : launch_attn<128, 1, false, 128 / 16, false, false, F16>(p, s);
+    return HAFF_ERR_UNSUPPORTED;
   }
   if (causal) {
-    if (dp == 64) return launch_attn<64, 0, true>(p, s);
-    if (dp == 96) return launch_attn<96, 0, true>(p, s);
-    return launch_attn<128, 0, true>(p, s);
+    if (dp == 64) return launch_attn<64, 0, true, 64 / 16, false, false, F16>(p, s);
+    if (dp == 96) return launch_attn<96, 0, true, 96 / 16, false, false, F16>(p, s);
+    return launch_attn<128, 0, true, 128 / 16, false, false, F16>(p, s);
   }
-  if (dp == 64) return launch_attn<64, 0, false>(p, s);
-  if (dp == 96) return launch_attn<96, 0, false>(p, s);
-  return launch_attn<128, 0, false>(p, s);
+  if (dp == 64) return launch_attn<64, 0, false, 64 / 16, false, false, F16>(p, s);
+  if (dp == 96) return launch_attn<96, 0, false, 96 / 16, false, false, F16>(p, s);
+  return launch_attn<128, 0, false, 128 / 16, false, false, F16>(p, s);
 }
 
 extern "C" int haff_attention_bf16(const void* q, long q_sb, long q_sh, long q_st,
@@ -1333,6 +1347,18 @@ extern "C" int haff_attention_bf16(const void* q, long q_sb, long q_sh, long q_s
                                    const float* relh, const float* relw, int S, void* stream) {
   return attention_bf16_impl(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq, Nk, d,
                              scale, causal, q_pos0, relh, relw, S, nullptr, stream);
+}
+
+// fp16 instance of haff_attention_bf16 (q / k / v / o IEEE binary16, probabilities rounded to fp16 for the P.V product)
+extern "C" int haff_attention_f16(const void* q, long q_sb, long q_sh, long q_st,
+                                  const void* k, long k_sb, long k_sh, long k_st,
+                                  const void* v, long v_sb, long v_sh, long v_st,
+                                  void* o, long o_sb, long o_sh, long o_st,
+                                  int B, int H, int Nq, int Nk, int d, float scale,
+                                  int causal, int q_pos0,
+                                  const float* relh, const float* relw, int S, void* stream) {
+  return attention_bf16_impl<true>(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq,
+                                   Nk, d, scale, causal, q_pos0, relh, relw, S, nullptr, stream);
 }
 
 // haff_attention_bf16 that also returns the per-row log-sum-exp of the scores, LOG2 domain (log2 sum_k 2^(scale*log2(e)*q.k)), f32
@@ -1353,12 +1379,13 @@ extern "C" int haff_attention_lse_bf16(const void* q, long q_sb, long q_sh, long
 // haff_attention_bf16 — no fp32 [B*H][N][S] tables are written or read. q/k/v/o: bf16 [B][H][S*S][d] views by strides, k and v in
 // one fused row layout (same strides, v behind k); tab_*: bf16 [2S-1][d]. Supported geometry: S == 64, d == 80 (ViT-H global
 // blocks); otherwise HAFF_ERR_UNSUPPORTED and the caller takes the two-kernel path.
-extern "C" int haff_global_attention_bf16(const void* q, long q_sb, long q_sh, long q_st,
-                                          const void* k, long k_sb, long k_sh, long k_st,
-                                          const void* v, long v_sb, long v_sh, long v_st,
-                                          void* o, long o_sb, long o_sh, long o_st,
-                                          int B, int H, int S, int d, float scale,
-                                          const void* tab_h, const void* tab_w, void* stream) {
+template <bool F16 = false>
+static int global_attention_impl(const void* q, long q_sb, long q_sh, long q_st,
+                                 const void* k, long k_sb, long k_sh, long k_st,
+                                 const void* v, long v_sb, long v_sh, long v_st,
+                                 void* o, long o_sb, long o_sh, long o_st,
+                                 int B, int H, int S, int d, float scale,
+                                 const void* tab_h, const void* tab_w, void* stream) {
   if (B <= 0 || H <= 0 || S <= 0 || d <= 0 || !tab_h || !tab_w) return HAFF_ERR_BAD_ARG;
   if ((q_st & 7) || (k_st & 7) || (v_st & 7) || (o_st & 3) || (q_sh & 7) || (k_sh & 7) || (v_sh & 7) || (o_sh & 3) ||
       (q_sb & 7) || (k_sb & 7) || (v_sb & 7) || (o_sb & 3))
@@ -1368,7 +1395,26 @@ extern "C" int haff_global_attention_bf16(const void* q, long q_sb, long q_sh, l
              B, H, S * S, S * S, d, scale, 0, nullptr, nullptr, S, nullptr, nullptr, nullptr, nullptr,
              reinterpret_cast<const bf16_t*>(tab_h), reinterpret_cast<const bf16_t*>(tab_w)};
   if (!attn_global_pp_ok(p, true)) return HAFF_ERR_UNSUPPORTED;
-  return launch_attn_global_pp<true>(p, reinterpret_cast<hipStream_t>(stream));
+  return launch_attn_global_pp<true, F16>(p, reinterpret_cast<hipStream_t>(stream));
+}
+extern "C" int haff_global_attention_bf16(const void* q, long q_sb, long q_sh, long q_st,
+                                          const void* k, long k_sb, long k_sh, long k_st,
+                                          const void* v, long v_sb, long v_sh, long v_st,
+                                          void* o, long o_sb, long o_sh, long o_st,
+                                          int B, int H, int S, int d, float scale,
+                                          const void* tab_h, const void* tab_w, void* stream) {
+  return global_attention_impl(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, S, d, scale,
+                               tab_h, tab_w, stream);
+}
+// fp16 instance: q / k / v / o and the tables are f16
+extern "C" int haff_global_attention_f16(const void* q, long q_sb, long q_sh, long q_st,
+                                         const void* k, long k_sb, long k_sh, long k_st,
+                                         const void* v, long v_sb, long v_sh, long v_st,
+                                         void* o, long o_sb, long o_sh, long o_st,
+                                         int B, int H, int S, int d, float scale,
+                                         const void* tab_h, const void* tab_w, void* stream) {
+  return global_attention_impl<true>(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, S, d,
+                                     scale, tab_h, tab_w, stream);
 }
 
 // KV-cached decode over RAGGED caches (batched prompts of different lengths): one query per (batch, head), batch b
@@ -1384,6 +1430,17 @@ extern "C" int haff_attention_decode_rows_bf16(const void* q, long q_sb, long q_
                              Nk, d, scale, 0, 0, nullptr, nullptr, 0, nk_rows, stream);
 }
 
+// fp16 instance of haff_attention_decode_rows_bf16
+extern "C" int haff_attention_decode_rows_f16(const void* q, long q_sb, long q_sh,
+                                              const void* k, long k_sb, long k_sh, long k_st,
+                                              const void* v, long v_sb, long v_sh, long v_st,
+                                              void* o, long o_sb, long o_sh,
+                                              int B, int H, int Nk, int d, float scale, const int* nk_rows, void* stream) {
+  if (!nk_rows) return HAFF_ERR_BAD_ARG;
+  return attention_bf16_impl<true>(q, q_sb, q_sh, (long)H * d, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, (long)H * d,
+                                   B, H, 1, Nk, d, scale, 0, 0, nullptr, nullptr, 0, nk_rows, stream);
+}
+
 // One KV-cached decode position per (batch, head) with RoPE and the cache append fused in — replaces haff_rope_cache_rows +
 // haff_attention_decode_rows_bf16 (two launches per layer per generated token) on the Llama decode path (transformers
 // LlamaAttention.forward with a KV cache, reached from llava_llama.py:93-102; rotate-half RoPE, theta from cos_sin).
@@ -1391,9 +1448,10 @@ extern "C" int haff_attention_decode_rows_bf16(const void* q, long q_sb, long q_
 // [B][Tmax][H*d]; cos_sin f32 [Tmax][d] = cos(0..d/2) | sin(0..d/2); nk_rows[b] = position of the new token + 1
 // (DEVICE int32 [B]): the new k (rotated) and v are written at cache row nk_rows[b] - 1 and attended with every older row.
 // out: [B][H*d]. d must be 128. Bit-identical to the two-kernel path.
-extern "C" int haff_decode_attention_rope_rows_bf16(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin,
-                                                    void* out, int B, int H, int d, int Tmax, float scale, const int* nk_rows,
-                                                    void* stream) {
+template <bool F16 = false>
+static int decode_attention_rope_rows_impl(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin,
+                                           void* out, int B, int H, int d, int Tmax, float scale, const int* nk_rows,
+                                           void* stream) {
   if (B <= 0 || H <= 0 || d != DEC_D || Tmax <= 0 || !nk_rows || !cos_sin || (ld & 7)) return HAFF_ERR_BAD_ARG;
   if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(kcache) & 15) ||
       (reinterpret_cast<uintptr_t>(vcache) & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
@@ -1404,16 +1462,27 @@ extern "C" int haff_decode_attention_rope_rows_bf16(const void* qkv, long ld, vo
              ld, d, hd, (long)Tmax * hd, d, hd, (long)Tmax * hd, d, hd, hd, d, hd,
              B, H, 1, Tmax, d, scale, 0, nullptr, nullptr, 0, nk_rows, q + hd, q + 2 * hd, cos_sin};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (B * H <= 128) hipLaunchKernelGGL((attn_decode_kernel<true, true, 16>), dim3(B * H), dim3(1024), 0, s, p);
-  else if (B * H <= 1024) hipLaunchKernelGGL((attn_decode_kernel<true, true>), dim3(B * H), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((attn_decode_kernel<false, true>), dim3((B * H + 3) / 4), dim3(256), 0, s, p);
+  if (B * H <= 128) hipLaunchKernelGGL((attn_decode_kernel<true, true, 16, F16>), dim3(B * H), dim3(1024), 0, s, p);
+  else if (B * H <= 1024) hipLaunchKernelGGL((attn_decode_kernel<true, true, 4, F16>), dim3(B * H), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((attn_decode_kernel<false, true, 4, F16>), dim3((B * H + 3) / 4), dim3(256), 0, s, p);
   return haff_check_launch();
+}
+extern "C" int haff_decode_attention_rope_rows_bf16(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin,
+                                                    void* out, int B, int H, int d, int Tmax, float scale, const int* nk_rows,
+                                                    void* stream) {
+  return decode_attention_rope_rows_impl(qkv, ld, kcache, vcache, cos_sin, out, B, H, d, Tmax, scale, nk_rows, stream);
+}
+// fp16 instance: qkv, caches and out IEEE binary16, the rotated k rounded to fp16 as it enters the cache
+extern "C" int haff_decode_attention_rope_rows_f16(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin,
+                                                   void* out, int B, int H, int d, int Tmax, float scale, const int* nk_rows,
+                                                   void* stream) {
+  return decode_attention_rope_rows_impl<true>(qkv, ld, kcache, vcache, cos_sin, out, B, H, d, Tmax, scale, nk_rows, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // Decomposed rel-pos tables (image_encoder.py:376-384): relh[bh][q][kh] = q_vec . Rh[qh - kh + S - 1],
 // relw[bh][q][kw] = q_vec . Rw[qw - kw + S - 1], with the UNSCALED q (image_encoder.py:244-248).
-// q: bf16 (dtype 0) or f32 (dtype 1) with (batch, head, token) strides; tables: fp32 [2S-1][d]; outputs fp32 [B*H][N][S], N = S*S.
+// q: bf16 (dtype 0), f32 (dtype 1) or f16 (dtype 3) with (batch, head, token) strides; tables: fp32 [2S-1][d]; outputs fp32 [B*H][N][S], N = S*S.
 namespace {
 template <typename T>
 __global__ __launch_bounds__(256) void relpos_tables_kernel(const T* q, long q_sb, long q_sh, long q_st,
@@ -1593,6 +1662,9 @@ extern "C" int haff_relpos_tables(const void* q, long q_sb, long q_sh, long q_st
   if (dtype == 0)
     hipLaunchKernelGGL((relpos_tables_kernel<bf16_t>), grid, block, lds, reinterpret_cast<hipStream_t>(stream),
                        reinterpret_cast<const bf16_t*>(q), q_sb, q_sh, q_st, tab_h, tab_w, relh, relw, H, S, d);
+  else if (dtype == 3)
+    hipLaunchKernelGGL((relpos_tables_kernel<f16_t>), grid, block, lds, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const f16_t*>(q), q_sb, q_sh, q_st, tab_h, tab_w, relh, relw, H, S, d);
   else
     hipLaunchKernelGGL((relpos_tables_kernel<float>), grid, block, lds, reinterpret_cast<hipStream_t>(stream),
                        reinterpret_cast<const float*>(q), q_sb, q_sh, q_st, tab_h, tab_w, relh, relw, H, S, d);

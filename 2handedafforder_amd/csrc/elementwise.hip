@@ -238,7 +238,7 @@ inline int grid_for(long total, int block) {
 
 #define HAFF_STREAM(s) reinterpret_cast<hipStream_t>(s)
 
-// in_dtype/out_dtype: 0 = bf16, 1 = f32
+// in_dtype/out_dtype: 0 = bf16, 1 = f32, 3 = f16 (dtype codes of include/haff_hip.h; below, too)
 extern "C" int haff_patchify_nchw(const void* x, void* out, int B, int Cin, int Hin, int Win, int P, int gh, int gw,
                                   int Kp, int in_dtype, int out_dtype, void* stream) {
   if (B <= 0 || P <= 0 || gh * P > Hin || gw * P > Win || Kp < Cin * P * P) return HAFF_ERR_BAD_ARG;
@@ -253,6 +253,10 @@ extern "C" int haff_patchify_nchw(const void* x, void* out, int B, int Cin, int 
     hipLaunchKernelGGL((patchify_nchw_kernel<float, float>), g, b, 0, s, (const float*)x, (float*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
   else if (in_dtype == 0 && out_dtype == 1)
     hipLaunchKernelGGL((patchify_nchw_kernel<bf16_t, float>), g, b, 0, s, (const bf16_t*)x, (float*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
+  else if (in_dtype == 3 && out_dtype == 3)
+    hipLaunchKernelGGL((patchify_nchw_kernel<f16_t, f16_t>), g, b, 0, s, (const f16_t*)x, (f16_t*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
+  else if (in_dtype == 1 && out_dtype == 3)
+    hipLaunchKernelGGL((patchify_nchw_kernel<float, f16_t>), g, b, 0, s, (const float*)x, (f16_t*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
   else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
@@ -266,6 +270,9 @@ extern "C" int haff_patchify_u8(const void* frames, void* out, int B, int Hf, in
   if (out_dtype == 0)
     hipLaunchKernelGGL((patchify_u8_kernel<bf16_t>), g, b, 0, s, (const unsigned char*)frames, (bf16_t*)out, B, Hf, Wf, P, gh, gw, Kp,
                        mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  else if (out_dtype == 3)
+    hipLaunchKernelGGL((patchify_u8_kernel<f16_t>), g, b, 0, s, (const unsigned char*)frames, (f16_t*)out, B, Hf, Wf, P, gh, gw, Kp,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
   else
     hipLaunchKernelGGL((patchify_u8_kernel<float>), g, b, 0, s, (const unsigned char*)frames, (float*)out, B, Hf, Wf, P, gh, gw, Kp,
                        mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
@@ -277,6 +284,7 @@ extern "C" int haff_im2col3x3(const void* x, void* out, int B, int H, int W, int
   const long total = (long)B * H * W * 9 * (C / 8);
   dim3 g(grid_for(total, 256)), b(256);
   if (dtype == 0) hipLaunchKernelGGL((im2col3x3_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (const bf16_t*)x, (bf16_t*)out, B, H, W, C);
+  else if (dtype == 3) hipLaunchKernelGGL((im2col3x3_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (const f16_t*)x, (f16_t*)out, B, H, W, C);
   else hipLaunchKernelGGL((im2col3x3_kernel<float>), g, b, 0, HAFF_STREAM(stream), (const float*)x, (float*)out, B, H, W, C);
   return haff_check_launch();
 }
@@ -286,6 +294,7 @@ extern "C" int haff_embed_splice(const long* ids, const int* img_pos, const void
   if (B <= 0 || L <= 0 || n_img <= 0 || (Hd & 7)) return HAFF_ERR_BAD_ARG;
   dim3 g(B * (L + n_img - 1)), b(128);
   if (dtype == 0) hipLaunchKernelGGL((embed_splice_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const bf16_t*)embed, (const bf16_t*)img, (bf16_t*)out, L, n_img, Hd);
+  else if (dtype == 3) hipLaunchKernelGGL((embed_splice_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const f16_t*)embed, (const f16_t*)img, (f16_t*)out, L, n_img, Hd);
   else hipLaunchKernelGGL((embed_splice_kernel<float>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const float*)embed, (const float*)img, (float*)out, L, n_img, Hd);
   return haff_check_launch();
 }
@@ -296,6 +305,7 @@ extern "C" int haff_rope_cache(void* qkv, long ld, void* kcache, void* vcache, c
   const long total = (long)B * Tq * (Hq + 2 * Hkv) * (d / 16);
   dim3 g(grid_for(total, 256)), b(256);
   if (dtype == 0) hipLaunchKernelGGL((rope_cache_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (bf16_t*)qkv, ld, (bf16_t*)kcache, (bf16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
+  else if (dtype == 3) hipLaunchKernelGGL((rope_cache_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (f16_t*)qkv, ld, (f16_t*)kcache, (f16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
   else hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
   return haff_check_launch();
 }
@@ -308,6 +318,7 @@ extern "C" int haff_rope_cache_rows(void* qkv, long ld, void* kcache, void* vcac
   const long total = (long)B * Tq * (Hq + 2 * Hkv) * (d / 16);
   dim3 g(grid_for(total, 256)), b(256);
   if (dtype == 0) hipLaunchKernelGGL((rope_cache_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (bf16_t*)qkv, ld, (bf16_t*)kcache, (bf16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
+  else if (dtype == 3) hipLaunchKernelGGL((rope_cache_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (f16_t*)qkv, ld, (f16_t*)kcache, (f16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
   else hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
   return haff_check_launch();
 }
@@ -341,6 +352,7 @@ extern "C" int haff_add_bcast(const void* a, const void* b, void* out, long rows
   if (rows <= 0 || (C & 7) || mod <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(rows * (C / 8), 256)), blk(256);
   if (dtype == 0) hipLaunchKernelGGL((add_bcast_kernel<bf16_t>), g, blk, 0, HAFF_STREAM(stream), (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, rows, C, mod);
+  else if (dtype == 3) hipLaunchKernelGGL((add_bcast_kernel<f16_t>), g, blk, 0, HAFF_STREAM(stream), (const f16_t*)a, (const f16_t*)b, (f16_t*)out, rows, C, mod);
   else hipLaunchKernelGGL((add_bcast_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)a, (const float*)b, (float*)out, rows, C, mod);
   return haff_check_launch();
 }
@@ -349,6 +361,7 @@ extern "C" int haff_softmax_rows(const void* x, float* out, int rows, int C, int
   if (rows <= 0 || C <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g((rows + 63) / 64), blk(64);
   if (dtype == 0) hipLaunchKernelGGL((softmax_rows_kernel<bf16_t>), g, blk, 0, HAFF_STREAM(stream), (const bf16_t*)x, out, rows, C);
+  else if (dtype == 3) hipLaunchKernelGGL((softmax_rows_kernel<f16_t>), g, blk, 0, HAFF_STREAM(stream), (const f16_t*)x, out, rows, C);
   else hipLaunchKernelGGL((softmax_rows_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)x, out, rows, C);
   return haff_check_launch();
 }

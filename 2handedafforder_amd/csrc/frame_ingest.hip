@@ -100,7 +100,7 @@ extern "C" int haff_resample_u8(const void* in, void* out, int B, int Hin, int W
   return haff_check_launch();
 }
 
-// in u8 [B][Hin][Win][3]; the S x S window at (top, left) -> out [B][3][S][S] (out_dtype 0 = bf16, 1 = f32) through
+// in u8 [B][Hin][Win][3]; the S x S window at (top, left) -> out [B][3][S][S] (out_dtype 0 = bf16, 1 = f32, 3 = f16) through
 // lut f32 [3][256] (DEVICE pointer).
 extern "C" int haff_clip_normalize_u8(const void* in, void* out, int B, int Hin, int Win, int top, int left, int S,
                                       const float* lut, int out_dtype, void* stream) {
@@ -109,6 +109,8 @@ extern "C" int haff_clip_normalize_u8(const void* in, void* out, int B, int Hin,
   const unsigned g = grid_1d((long)B * 3 * S * S);
   if (out_dtype == 0)
     hipLaunchKernelGGL((clip_normalize_kernel<bf16_t>), dim3(g), dim3(256), 0, s, (const unsigned char*)in, (bf16_t*)out, B, Hin, Win, top, left, S, lut);
+  else if (out_dtype == 3)
+    hipLaunchKernelGGL((clip_normalize_kernel<f16_t>), dim3(g), dim3(256), 0, s, (const unsigned char*)in, (f16_t*)out, B, Hin, Win, top, left, S, lut);
   else if (out_dtype == 1)
     hipLaunchKernelGGL((clip_normalize_kernel<float>), dim3(g), dim3(256), 0, s, (const unsigned char*)in, (float*)out, B, Hin, Win, top, left, S, lut);
   else

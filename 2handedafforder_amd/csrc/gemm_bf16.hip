@@ -215,12 +215,16 @@ __device__ unsigned long long haff_gemm_trace_buf[8192 * 8];
 // The launcher sets it for outputs of 64 MB and more (decode-sized outputs are re-read from L2 by the next kernel).
 typedef unsigned int haff_u32x4 __attribute__((ext_vector_type(4)));
 typedef float haff_f32x4 __attribute__((ext_vector_type(4)));
+template <bool F16>
 __device__ __forceinline__ void store8_c(bf16_t* p, const float (&v)[8], bool nt) {
+  using E = h16<F16>;
   if (nt) {
-    haff_u32x4 r = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+    haff_u32x4 r = {E::pack2(v[0], v[1]), E::pack2(v[2], v[3]), E::pack2(v[4], v[5]), E::pack2(v[6], v[7])};
     asm volatile("");   // keeps hipcc from merging this store with the plain one of the other branch (the hint would be dropped)
     __builtin_nontemporal_store(r, reinterpret_cast<haff_u32x4*>(p));
     asm volatile("");
+  } else if constexpr (F16) {
+    store8(reinterpret_cast<f16_t*>(p), v);
   } else {
     store8(p, v);
   }
@@ -285,8 +289,9 @@ enum : unsigned {
   GF_ACT_SHIFT = 16
 };
 
-template <int BM, int BN, int WM, int WN, bool OUT_F32, bool SWIGLU, unsigned FLAGS = 0>
+template <int BM, int BN, int WM, int WN, bool OUT_F32, bool SWIGLU, unsigned FLAGS = 0, bool F16 = false>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
+  using E = h16<F16>;   // F16: fp16 operands and output (v_mfma_f32_16x16x32_f16), bf16 otherwise
   constexpr bool PP = (WM * WN == 8);   // the 8-wave tile runs the persistent ping-pong ring loop
   constexpr bool SPEC = (FLAGS & GF_SPEC) != 0;
   constexpr bool MFULL = SPEC && !(FLAGS & GF_RAGM);   // every M-tile is whole
@@ -514,7 +519,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     for (int mi = mi_lo; mi < mi_hi; ++mi)
 #pragma unroll
       for (int ni = 0; ni < TN; ++ni)
-        acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][ni], af[ks][mi], acc[ni][mi], 0, 0, 0);
+        acc[ni][mi] = E::mfma16(wf[ks][ni], af[ks][mi], acc[ni][mi]);
   };
 
   int buf0 = 0;           // LDS buffer that holds K-tile 0 of the current tile
@@ -601,7 +606,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
         for (int t = 0; t < TMH; ++t)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            acc[N0 + j][M0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[ks][j], pa[ks][t], acc[N0 + j][M0 + t], 0, 0, 0);
+            acc[N0 + j][M0 + t] = E::mfma16(wq[ks][j], pa[ks][t], acc[N0 + j][M0 + t]);
     };
 #if defined(HAFF_TUNING) && defined(HAFF_EXP_MFMA32)
     // timing experiment only (results are wrong): the same fragment reads feeding v_mfma_f32_32x32x16_bf16 — half as many
@@ -617,7 +622,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
           for (int j = 0; j < 2; ++j) {
             constexpr int dummy = 0;
             const int idx = (N0 / 2) * 4 + (M0 / 4) * 2 + j;
-            accw[idx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[ks][j], pa[ks][2 * j + tt], accw[idx], 0, 0, 0);
+            accw[idx] = E::mfma32(wq[ks][j], pa[ks][2 * j + tt], accw[idx]);
           }
     };
 #define quad quad32
@@ -1127,11 +1132,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             const unsigned w[4] = {rcur[j].x, rcur[j].y, rcur[j].z, rcur[j].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              v8[2 * e] += __builtin_bit_cast(float, w[e] << 16);
-              v8[2 * e + 1] += __builtin_bit_cast(float, w[e] & 0xffff0000u);
+              v8[2 * e] += E::lo(w[e]);
+              v8[2 * e + 1] += E::hi(w[e]);
             }
             }
-            q = haff_u32x4{pack_bf16x2(v8[0], v8[1]), pack_bf16x2(v8[2], v8[3]), pack_bf16x2(v8[4], v8[5]), pack_bf16x2(v8[6], v8[7])};
+            q = haff_u32x4{E::pack2(v8[0], v8[1]), E::pack2(v8[2], v8[3]), E::pack2(v8[4], v8[5]), E::pack2(v8[6], v8[7])};
             if constexpr (ALL) {
               if (has_stat) {   // (wave-uniform) the lane's 8 columns of this row; the row's other columns sit in 3 more lanes
 #pragma unroll
@@ -1142,8 +1147,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
               }
             }
           } else {
-            unsigned x0 = pack_bf16x2(val[2 * j][0], val[2 * j][1]), y0 = pack_bf16x2(val[2 * j + 1][0], val[2 * j + 1][1]);
-            unsigned x1 = pack_bf16x2(val[2 * j][2], val[2 * j][3]), y1 = pack_bf16x2(val[2 * j + 1][2], val[2 * j + 1][3]);
+            unsigned x0 = E::pack2(val[2 * j][0], val[2 * j][1]), y0 = E::pack2(val[2 * j + 1][0], val[2 * j + 1][1]);
+            unsigned x1 = E::pack2(val[2 * j][2], val[2 * j][3]), y1 = E::pack2(val[2 * j + 1][2], val[2 * j + 1][3]);
             permlane16_swap(x0, y0);
             permlane16_swap(x1, y1);
             q = haff_u32x4{x0, x1, y0, y1};
@@ -1302,14 +1307,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
               const unsigned int w[4] = {rcur[st].x, rcur[st].y, rcur[st].z, rcur[st].w};
 #pragma unroll
               for (int j = 0; j < 4; ++j) {
-                v[2 * j] += __builtin_bit_cast(float, w[j] << 16);
-                v[2 * j + 1] += __builtin_bit_cast(float, w[j] & 0xffff0000u);
+                v[2 * j] += E::lo(w[j]);
+                v[2 * j + 1] += E::hi(w[j]);
               }
             }
 #ifdef HAFF_EXP_NOSTORE   // timing experiment: everything but the global store
             asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
 #else
-            store8_c(reinterpret_cast<bf16_t*>(p.C) + (long)orow * p.ldc + n_out, v, nt_out);
+            store8_c<F16>(reinterpret_cast<bf16_t*>(p.C) + (long)orow * p.ldc + n_out, v, nt_out);
 #endif
           }
         }
@@ -1330,8 +1335,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             if (p.resid) x += reinterpret_cast<const float*>(p.resid)[(long)orow * p.ldr + n];
             reinterpret_cast<float*>(p.C)[(long)orow * p.ldc + n] = x;
           } else {
-            if (p.resid) x += bf16_to_f32(reinterpret_cast<const bf16_t*>(p.resid)[(long)orow * p.ldr + n]);
-            reinterpret_cast<bf16_t*>(p.C)[(long)orow * p.ldc + n] = f32_to_bf16(x);
+            if (p.resid) x += E::to_f32(reinterpret_cast<const bf16_t*>(p.resid)[(long)orow * p.ldr + n]);
+            reinterpret_cast<bf16_t*>(p.C)[(long)orow * p.ldc + n] = E::from_f32(x);
           }
         }
       }
@@ -1378,8 +1383,9 @@ constexpr int skinny_batch(int nt, int mt) {   // k-steps per batch of loads: tw
   return u >= 8 ? 8 : (u >= 4 ? 4 : 2);
 }
 
-template <int MT, int NT, bool SWIGLU, int KW = 4>
+template <int MT, int NT, bool SWIGLU, int KW = 4, bool F16 = false>
 __global__ __launch_bounds__(64 * KW) void gemm_skinny_kernel(GemmArgs p) {
+  using E = h16<F16>;
   static_assert(!SWIGLU || (NT % 2) == 0, "SwiGLU pairs a gate tile with an up tile");
   constexpr int U = skinny_batch(NT, MT);
   __shared__ float red[KW][MT][64][4];
@@ -1457,8 +1463,7 @@ __global__ __launch_bounds__(64 * KW) void gemm_skinny_kernel(GemmArgs p) {
         for (int t = 0; t < NT; ++t)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
-            acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[set][t][u]),
-                                                                 __builtin_bit_cast(bf16x8, xv[set][mt][u]), acc[t][mt], 0, 0, 0);
+            acc[t][mt] = E::mfma16(__builtin_bit_cast(bf16x8, wv[set][t][u]), __builtin_bit_cast(bf16x8, xv[set][mt][u]), acc[t][mt]);
       }
     }
   };
@@ -1576,23 +1581,23 @@ __global__ __launch_bounds__(64 * KW) void gemm_skinny_kernel(GemmArgs p) {
       if (whole && ((reinterpret_cast<uintptr_t>(c) & 7) == 0) && (!rs || (reinterpret_cast<uintptr_t>(rs) & 7) == 0)) {
         if (rs) {
           const uint2 rv = *reinterpret_cast<const uint2*>(rs);
-          val[0] += __builtin_bit_cast(float, rv.x << 16); val[1] += __builtin_bit_cast(float, rv.x & 0xffff0000u);
-          val[2] += __builtin_bit_cast(float, rv.y << 16); val[3] += __builtin_bit_cast(float, rv.y & 0xffff0000u);
+          val[0] += E::lo(rv.x); val[1] += E::hi(rv.x);
+          val[2] += E::lo(rv.y); val[3] += E::hi(rv.y);
         }
         uint2 ov;
-        ov.x = pack_bf16x2(val[0], val[1]);
-        ov.y = pack_bf16x2(val[2], val[3]);
+        ov.x = E::pack2(val[0], val[1]);
+        ov.y = E::pack2(val[2], val[3]);
         *reinterpret_cast<uint2*>(c) = ov;
-        const float q0 = __builtin_bit_cast(float, ov.x << 16), q1 = __builtin_bit_cast(float, ov.x & 0xffff0000u);
-        const float q2 = __builtin_bit_cast(float, ov.y << 16), q3 = __builtin_bit_cast(float, ov.y & 0xffff0000u);
+        const float q0 = E::lo(ov.x), q1 = E::hi(ov.x);
+        const float q2 = E::lo(ov.y), q3 = E::hi(ov.y);
         ssq_acc += (q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (nb + r < n_total_out) {
-            const bf16_t q = f32_to_bf16(val[r] + (rs ? bf16_to_f32(rs[r]) : 0.f));
+            const bf16_t q = E::from_f32(val[r] + (rs ? E::to_f32(rs[r]) : 0.f));
             c[r] = q;
-            ssq_acc += bf16_to_f32(q) * bf16_to_f32(q);
+            ssq_acc += E::to_f32(q) * E::to_f32(q);
           }
       }
     }
@@ -1607,7 +1612,9 @@ __global__ __launch_bounds__(64 * KW) void gemm_skinny_kernel(GemmArgs p) {
 
 // Second half of a split-K weight-streaming product: out[m][n] = epi(sum over slices of ws[slice][m][n]), slices added
 // in index order (deterministic), 4 consecutive columns per thread. bias -> act -> +resid, row map, bf16 / f32 output.
+template <bool F16 = false>
 __global__ __launch_bounds__(256) void skinny_reduce_kernel(GemmArgs p) {
+  using E = h16<F16>;
   if (p.swiglu) {
     // partial tiles hold the interleaved [gate x16 | up x16] columns; 4 consecutive OUTPUT columns per thread (they sit in
     // one 16-column group): out = silu(sum gate + bias_g) * (sum up + bias_u)
@@ -1635,7 +1642,7 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(GemmArgs p) {
       const float gg = g[r] + (p.bias ? p.bias[ng + r] : 0.f), uu = u[r] + (p.bias ? p.bias[ng + 16 + r] : 0.f);
       const float x = gg * __builtin_amdgcn_rcpf(1.0f + __expf(-gg)) * uu;
       if (p.out_f32) reinterpret_cast<float*>(p.C)[orow * p.ldc + n + r] = x;
-      else reinterpret_cast<bf16_t*>(p.C)[orow * p.ldc + n + r] = f32_to_bf16(x);
+      else reinterpret_cast<bf16_t*>(p.C)[orow * p.ldc + n + r] = E::from_f32(x);
     }
     return;
   }
@@ -1670,8 +1677,8 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(GemmArgs p) {
       if (p.resid) x += reinterpret_cast<const float*>(p.resid)[orow * p.ldr + n + r];
       reinterpret_cast<float*>(p.C)[orow * p.ldc + n + r] = x;
     } else {
-      if (p.resid) x += bf16_to_f32(reinterpret_cast<const bf16_t*>(p.resid)[orow * p.ldr + n + r]);
-      reinterpret_cast<bf16_t*>(p.C)[orow * p.ldc + n + r] = f32_to_bf16(x);
+      if (p.resid) x += E::to_f32(reinterpret_cast<const bf16_t*>(p.resid)[orow * p.ldr + n + r]);
+      reinterpret_cast<bf16_t*>(p.C)[orow * p.ldc + n + r] = E::from_f32(x);
     }
   }
 }
@@ -1680,6 +1687,7 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(GemmArgs p) {
 // workgroup every workgroup re-reads the whole activation matrix from L2 (4x the weight bytes at K = 4096, 1.4 MB per
 // workgroup at K = 11008) and the fabric, not HBM, sets the time. 64 (or 32) rows per workgroup and 4 (or 2) K slices keep
 // >= 192 workgroups while each reads only its slice of the activations. Returns false when no such split applies.
+template <bool F16 = false>
 static bool launch_skinny_splitk(GemmArgs& p, hipStream_t s) {
   if (!p.ws || p.swiglu || p.ln_stats || p.M <= 32 || p.N > 8192) return false;
   const int tiles = (p.N + 15) / 16;
@@ -1695,14 +1703,14 @@ static bool launch_skinny_splitk(GemmArgs& p, hipStream_t s) {
   if (!nt) return false;
   p.ksplit = ks;
   const dim3 b(256);
-  if (nt == 4) hipLaunchKernelGGL((gemm_skinny_kernel<4, 4, false>), dim3((tiles + 3) / 4, ks), b, 0, s, p);
-  else hipLaunchKernelGGL((gemm_skinny_kernel<4, 2, false>), dim3((tiles + 1) / 2, ks), b, 0, s, p);
+  if (nt == 4) hipLaunchKernelGGL((gemm_skinny_kernel<4, 4, false, 4, F16>), dim3((tiles + 3) / 4, ks), b, 0, s, p);
+  else hipLaunchKernelGGL((gemm_skinny_kernel<4, 2, false, 4, F16>), dim3((tiles + 1) / 2, ks), b, 0, s, p);
   const long n_thr = (long)p.M * ((p.N + 3) / 4);
-  hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)((n_thr + 255) / 256)), b, 0, s, p);
+  hipLaunchKernelGGL(skinny_reduce_kernel<F16>, dim3((unsigned)((n_thr + 255) / 256)), b, 0, s, p);
   return true;
 }
 
-template <int MT>
+template <int MT, bool F16 = false>
 static void launch_skinny(const GemmArgs& p, int N, int swiglu, hipStream_t s) {
   // Weight rows per workgroup (16 * NT): every workgroup re-reads the activations (from L2), so the bytes a launch moves
   // are N*K*2 * (1 + MT/NT) and the fabric delivers ~7 TB/s of that mix: take the widest workgroup that still leaves
@@ -1713,12 +1721,12 @@ static void launch_skinny(const GemmArgs& p, int N, int swiglu, hipStream_t s) {
   const bool nt4 = MT >= 2 && tiles / 4 >= 192;
   const bool nt2 = MT >= 2 && tiles / 2 >= 192;
   if (swiglu) {
-    if (nt4) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 4, true>), dim3((tiles + 3) / 4), b, 0, s, p);
-    else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2, true>), dim3((tiles + 1) / 2), b, 0, s, p);
+    if (nt4) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 4, true, 4, F16>), dim3((tiles + 3) / 4), b, 0, s, p);
+    else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2, true, 4, F16>), dim3((tiles + 1) / 2), b, 0, s, p);
   } else {
-    if (nt4) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 4, false>), dim3((tiles + 3) / 4), b, 0, s, p);
-    else if (nt2) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2, false>), dim3((tiles + 1) / 2), b, 0, s, p);
-    else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 1, false>), dim3(tiles), b, 0, s, p);
+    if (nt4) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 4, false, 4, F16>), dim3((tiles + 3) / 4), b, 0, s, p);
+    else if (nt2) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2, false, 4, F16>), dim3((tiles + 1) / 2), b, 0, s, p);
+    else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 1, false, 4, F16>), dim3(tiles), b, 0, s, p);
   }
 }
 
@@ -1775,7 +1783,7 @@ static bool haff_gemm_spec_enabled() {
 #endif
 }
 
-template <int BM, int BN, int WM, int WN>
+template <int BM, int BN, int WM, int WN, bool F16 = false>
 static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   int gx = tiles;
@@ -1812,7 +1820,7 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
       const bool mfull = (p.M % 256) == 0;
 #define HAFF_SPEC(FL, SW)                                                                                                   \
   if (f == ((FL) & ~(GF_SPEC | GF_RAGM)) && (p.swiglu != 0) == (SW) && (mfull || ((FL) & GF_RAGM))) {                       \
-    hipLaunchKernelGGL((gemm_bf16_kernel<256, 256, 2, 4, false, SW, (FL) | GF_SPEC>), grid, block, 0, s, pl);               \
+    hipLaunchKernelGGL((gemm_bf16_kernel<256, 256, 2, 4, false, SW, (FL) | GF_SPEC, F16>), grid, block, 0, s, pl);               \
     return haff_check_launch();                                                                                             \
   }
       constexpr unsigned GELU_ = (unsigned)HAFF_ACT_GELU << GF_ACT_SHIFT, QGELU_ = (unsigned)HAFF_ACT_QUICK_GELU << GF_ACT_SHIFT;
@@ -1842,7 +1850,7 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
       const unsigned f = (p.bias ? GF_BIAS : 0u) | (p.resid ? GF_RES : 0u);
 #define HAFF_SPEC192(FL, SW)                                                                                               \
   if (f == ((FL) & ~(GF_SPEC | GF_RAGM)) && (p.swiglu != 0) == (SW)) {                                                       \
-    hipLaunchKernelGGL((gemm_bf16_kernel<192, 256, 2, 4, false, SW, (FL) | GF_SPEC | GF_RAGM>), grid, block, 0, s, pl);     \
+    hipLaunchKernelGGL((gemm_bf16_kernel<192, 256, 2, 4, false, SW, (FL) | GF_SPEC | GF_RAGM, F16>), grid, block, 0, s, pl);     \
     return haff_check_launch();                                                                                             \
   }
       HAFF_SPEC192(0u, false)
@@ -1855,11 +1863,11 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
   }
   if (p.res32) return HAFF_ERR_UNSUPPORTED;   // the fp32 residual stream exists in its specialised instance only
   if (p.swiglu) {
-    if (p.out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, true, true>), grid, block, 0, s, pl);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, false, true>), grid, block, 0, s, pl);
+    if (p.out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, true, true, 0, F16>), grid, block, 0, s, pl);
+    else hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, false, true, 0, F16>), grid, block, 0, s, pl);
   } else {
-    if (p.out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, true, false>), grid, block, 0, s, pl);
-    else hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, false, false>), grid, block, 0, s, pl);
+    if (p.out_f32) hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, true, false, 0, F16>), grid, block, 0, s, pl);
+    else hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, false, false, 0, F16>), grid, block, 0, s, pl);
   }
   return haff_check_launch();
 }
@@ -1870,6 +1878,7 @@ extern "C" int haff_gemm_trace_read(unsigned long long* host, int n_words) {
 }
 #endif
 
+template <bool F16 = false>
 static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw, void* C,
                           long ldc, const float* bias, const void* resid, long ldr, const int* row_map, int M, int N,
                           int K, int act, int out_f32, int swiglu, int tile_cfg, void* stream,
@@ -1904,12 +1913,12 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
   if (M <= skinny_max_m && (K % 128) == 0 && tile_cfg == 0 && !(M > 32 && N >= 16384) && !tile_rows) {
     if (M > 32 && workspace && workspace_bytes >= 4L * 4 * M * N && !a_map) {
       p.ws = reinterpret_cast<float*>(workspace);
-      if (launch_skinny_splitk(p, s)) return haff_check_launch();
+      if (launch_skinny_splitk<F16>(p, s)) return haff_check_launch();
       p.ws = nullptr;
     }
-    if (M <= 16) launch_skinny<1>(p, N, swiglu, s);
-    else if (M <= 32) launch_skinny<2>(p, N, swiglu, s);
-    else launch_skinny<4>(p, N, swiglu, s);
+    if (M <= 16) launch_skinny<1, F16>(p, N, swiglu, s);
+    else if (M <= 32) launch_skinny<2, F16>(p, N, swiglu, s);
+    else launch_skinny<4, F16>(p, N, swiglu, s);
     return haff_check_launch();
   }
   // Few output tiles, long K (prefill-sized o_proj / down_proj, the CLIP tower at one frame): K is split over
@@ -1932,12 +1941,12 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
       q.C = workspace; q.ldc = N; q.bias = nullptr; q.resid = nullptr; q.ldr = 0; q.row_map = nullptr;
       q.K = kchunk * BK; q.k_total = K; q.act = 0; q.out_f32 = 1; q.swiglu = 0;   // raw interleaved columns: the reduce kernel pairs them
       q.nb_inner = ks; q.sAo = 0; q.sWo = 0; q.sCo = 0; q.sAi = q.K; q.sWi = q.K; q.sCi = (long)M * N;
-      const int rc = launch_gemm<128, 128, 2, 2>(q, s, ks);
+      const int rc = launch_gemm<128, 128, 2, 2, F16>(q, s, ks);
       if (rc) return rc;
       p.ws = reinterpret_cast<float*>(workspace);
       p.ksplit = ks;
       const long n_thr = swiglu ? (long)M * (N / 8) : (long)M * ((N + 3) / 4);
-      hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, s, p);
+      hipLaunchKernelGGL(skinny_reduce_kernel<F16>, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, s, p);
       return haff_check_launch();
     }
   }
@@ -1983,8 +1992,8 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
 #ifndef HAFF_GEMM_NO_NT
   p.nt_out = (long)M * (swiglu ? N / 2 : N) * (out_f32 ? 4 : 2) >= (64L << 20);
 #endif
-  if (mid_tile) return launch_gemm<192, 256, 2, 4>(p, s);
-  return big ? launch_gemm<256, 256, 2, 4>(p, s) : launch_gemm<128, 128, 2, 2>(p, s);
+  if (mid_tile) return launch_gemm<192, 256, 2, 4, F16>(p, s);
+  return big ? launch_gemm<256, 256, 2, 4, F16>(p, s) : launch_gemm<128, 128, 2, 2, F16>(p, s);
 }
 
 // tile_cfg: 0 = auto, 1 = force the 128x128 tile, 2 = force the 256x256 tile, 3 = force the 192x256 tile (tests and A/B measurements)
@@ -2014,6 +2023,30 @@ extern "C" int haff_gemm_bf16_ws(const void* A, long lda, const void* W, long ld
                         stream, nullptr, nullptr, workspace, workspace_bytes);
 }
 
+// fp16 instances of the three entry points above (inference in fp16: A, W and a 16-bit C or resid are IEEE binary16,
+// v_mfma_f32_16x16x32_f16 with fp32 accumulation; out_f32 as before). Same host dispatcher, same arguments and contracts.
+extern "C" int haff_gemm_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc,
+                             const float* bias, const void* resid, long ldr, const int* row_map,
+                             int M, int N, int K, int act, int out_f32, int swiglu, void* stream) {
+  return gemm_bf16_impl<true>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
+                              stream);
+}
+
+extern "C" int haff_gemm_f16_cfg(const void* A, long lda, const void* W, long ldw, void* C, long ldc,
+                                 const float* bias, const void* resid, long ldr, const int* row_map,
+                                 int M, int N, int K, int act, int out_f32, int swiglu, int tile_cfg, void* stream) {
+  return gemm_bf16_impl<true>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu,
+                              tile_cfg, stream);
+}
+
+extern "C" int haff_gemm_f16_ws(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                                const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
+                                int swiglu, void* workspace, long workspace_bytes, void* stream) {
+  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15)) return HAFF_ERR_BAD_ARG;
+  return gemm_bf16_impl<true>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
+                              stream, nullptr, nullptr, workspace, workspace_bytes);
+}
+
 // Decode-sized product (M <= 16; with ssq_in M <= 8 and ssq_n <= 512; K % 128 == 0; weight-streaming kernel) that carries Llama's RMSNorm between products
 // without a norm kernel (LlamaDecoderLayer as reached from llava_llama.py:93-102: input_layernorm -> q/k/v,
 // post_attention_layernorm -> gate/up):
@@ -2022,9 +2055,10 @@ extern "C" int haff_gemm_bf16_ws(const void* A, long lda, const void* W, long ld
 //   ssq_out != NULL: (bf16 output) workgroup b also writes ssq_out[b][m] = sum over its output columns of bf16(C[m][n])^2,
 //                    m < 16 — the partials the next product's ssq_in consumes; *n_parts_out = number of workgroups b.
 // Both are fp32 [parts][16] device arrays. Sums run in a fixed order: results are bit-repeatable.
-extern "C" int haff_gemm_bf16_rms(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
-                                  const void* resid, long ldr, int M, int N, int K, int act, int out_f32, int swiglu,
-                                  const float* ssq_in, int ssq_n, float eps, float* ssq_out, int* n_parts_out, void* stream) {
+template <bool F16 = false>
+static int gemm_rms_impl(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                         const void* resid, long ldr, int M, int N, int K, int act, int out_f32, int swiglu,
+                         const float* ssq_in, int ssq_n, float eps, float* ssq_out, int* n_parts_out, void* stream) {
   if (M <= 0 || M > 16 || N <= 0 || K <= 0 || (K % 128) || (lda & 7) || (ldw & 7)) return HAFF_ERR_BAD_ARG;
   if (ssq_in && (M > 8 || ssq_n > 512)) return HAFF_ERR_BAD_ARG;   // consumer side: <= 8 rows, <= 512 producer workgroups
   if (ssq_in && (reinterpret_cast<uintptr_t>(ssq_in) & 15)) return HAFF_ERR_BAD_ARG;
@@ -2036,20 +2070,43 @@ extern "C" int haff_gemm_bf16_rms(const void* A, long lda, const void* W, long l
   p.ssq_in = ssq_in; p.ssq_n = ssq_n; p.ssq_eps = eps; p.ssq_out = ssq_out;
   // launch_skinny<1>: 16 weight rows per workgroup (32 for SwiGLU pairs)
   if (n_parts_out) *n_parts_out = swiglu ? (N + 31) / 32 : (N + 15) / 16;
-  launch_skinny<1>(p, N, swiglu, reinterpret_cast<hipStream_t>(stream));
+  launch_skinny<1, F16>(p, N, swiglu, reinterpret_cast<hipStream_t>(stream));
   return haff_check_launch();
+}
+extern "C" int haff_gemm_bf16_rms(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                                  const void* resid, long ldr, int M, int N, int K, int act, int out_f32, int swiglu,
+                                  const float* ssq_in, int ssq_n, float eps, float* ssq_out, int* n_parts_out, void* stream) {
+  return gemm_rms_impl(A, lda, W, ldw, C, ldc, bias, resid, ldr, M, N, K, act, out_f32, swiglu, ssq_in, ssq_n, eps, ssq_out, n_parts_out, stream);
+}
+extern "C" int haff_gemm_f16_rms(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                                 const void* resid, long ldr, int M, int N, int K, int act, int out_f32, int swiglu,
+                                 const float* ssq_in, int ssq_n, float eps, float* ssq_out, int* n_parts_out, void* stream) {
+  return gemm_rms_impl<true>(A, lda, W, ldw, C, ldc, bias, resid, ldr, M, N, K, act, out_f32, swiglu, ssq_in, ssq_n, eps, ssq_out, n_parts_out, stream);
 }
 
 // Same with a gather on the A side: logical row m of the product reads A row a_map[m] (0 <= a_map[m] < a_rows).
 // Used to run the window-unpartition projection only over real tokens (image_encoder.py:186-188,291-318: the padded
 // window rows are dropped right after the projection, so they are never multiplied).
+template <bool F16 = false>
+static int gemm_gather_impl(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
+                            void* C, long ldc, const float* bias, const void* resid, long ldr,
+                            const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
+                            void* stream) {
+  if (!a_map || a_rows <= 0) return HAFF_ERR_BAD_ARG;
+  return gemm_bf16_impl<F16>(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu,
+                        0, stream);
+}
 extern "C" int haff_gemm_bf16_gather(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
                                      void* C, long ldc, const float* bias, const void* resid, long ldr,
                                      const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
                                      void* stream) {
-  if (!a_map || a_rows <= 0) return HAFF_ERR_BAD_ARG;
-  return gemm_bf16_impl(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu,
-                        0, stream);
+  return gemm_gather_impl(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, stream);
+}
+extern "C" int haff_gemm_f16_gather(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
+                                    void* C, long ldc, const float* bias, const void* resid, long ldr,
+                                    const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
+                                    void* stream) {
+  return gemm_gather_impl<true>(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, stream);
 }
 
 // Llama prefill q|k|v projection with rotate-half RoPE and the KV-cache append in the epilogue (transformers LlamaAttention.forward
@@ -2059,9 +2116,10 @@ extern "C" int haff_gemm_bf16_gather(const void* A, long lda, const int* a_map, 
 // GemmArgs::rope_cs; ops.rope_permute_rows builds it once); q_out [M][ldq] receives the rotated q (H*d columns);
 // kcache / vcache [B][Tmax][H*d] rows pos0 .. pos0+T-1 receive the rotated k and v; cos_sin f32 [Tmax][128].
 // d == 128, (H*d) % 256 == 0, K % 64 == 0, M < 2^22; otherwise HAFF_ERR_UNSUPPORTED.
-extern "C" int haff_gemm_bf16_qkv_rope(const void* A, long lda, const void* Wp, long ldw, void* q_out, long ldq, void* kcache,
-                                       void* vcache, const float* cos_sin, int B, int T, int Tmax, int pos0, int H, int d, int K,
-                                       void* stream) {
+template <bool F16 = false>
+static int gemm_qkv_rope_impl(const void* A, long lda, const void* Wp, long ldw, void* q_out, long ldq, void* kcache,
+                              void* vcache, const float* cos_sin, int B, int T, int Tmax, int pos0, int H, int d, int K,
+                              void* stream) {
   if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || !q_out || !kcache || !vcache || !cos_sin || pos0 < 0 || pos0 + T > Tmax)
     return HAFF_ERR_BAD_ARG;
   if ((K & 7) || (lda & 7) || (ldw & 7) || (ldq & 7)) return HAFF_ERR_BAD_ARG;
@@ -2080,7 +2138,17 @@ extern "C" int haff_gemm_bf16_qkv_rope(const void* A, long lda, const void* Wp, 
   if (tn <= 5) p.group_m = 1;
   else if (K >= 5120 && tn <= 8) p.group_m = 2;
   else if (tn <= 16) p.group_m = 4;
-  return launch_gemm<256, 256, 2, 4>(p, reinterpret_cast<hipStream_t>(stream));
+  return launch_gemm<256, 256, 2, 4, F16>(p, reinterpret_cast<hipStream_t>(stream));
+}
+extern "C" int haff_gemm_bf16_qkv_rope(const void* A, long lda, const void* Wp, long ldw, void* q_out, long ldq, void* kcache,
+                                       void* vcache, const float* cos_sin, int B, int T, int Tmax, int pos0, int H, int d, int K,
+                                       void* stream) {
+  return gemm_qkv_rope_impl(A, lda, Wp, ldw, q_out, ldq, kcache, vcache, cos_sin, B, T, Tmax, pos0, H, d, K, stream);
+}
+extern "C" int haff_gemm_f16_qkv_rope(const void* A, long lda, const void* Wp, long ldw, void* q_out, long ldq, void* kcache,
+                                      void* vcache, const float* cos_sin, int B, int T, int Tmax, int pos0, int H, int d, int K,
+                                      void* stream) {
+  return gemm_qkv_rope_impl<true>(A, lda, Wp, ldw, q_out, ldq, kcache, vcache, cos_sin, B, T, Tmax, pos0, H, d, K, stream);
 }
 
 // Residual product whose epilogue also emits the LayerNorm statistics of its OUTPUT rows (see GemmArgs::stat_out): proj and
@@ -2089,9 +2157,10 @@ extern "C" int haff_gemm_bf16_qkv_rope(const void* A, long lda, const void* Wp, 
 // statistics pass reads the stream again. C = A.W^T + bias + resid in bf16 (C may alias resid); a_map optional (gather on
 // the A side, as haff_gemm_bf16_gather). stat_out: f32 [M][N/64][2]. Needs whole 8-wave tiles: M % 256 == 0, N % 256 == 0,
 // K % 64 == 0; otherwise HAFF_ERR_UNSUPPORTED (the caller keeps haff_row_stats).
-extern "C" int haff_gemm_bf16_rowstats(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
-                                       void* C, long ldc, const float* bias, const void* resid, long ldr, int M, int N, int K,
-                                       float* stat_out, void* stream) {
+template <bool F16 = false>
+static int gemm_rowstats_impl(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
+                              void* C, long ldc, const float* bias, const void* resid, long ldr, int M, int N, int K,
+                              float* stat_out, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || !resid || !stat_out) return HAFF_ERR_BAD_ARG;
   if ((K & 7) || (lda & 7) || (ldw & 7) || (ldc & 7) || (ldr & 7)) return HAFF_ERR_BAD_ARG;
   if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(C) & 15) ||
@@ -2107,7 +2176,17 @@ extern "C" int haff_gemm_bf16_rowstats(const void* A, long lda, const int* a_map
   if (tn <= 5) p.group_m = 1;
   else if (K >= 5120 && tn <= 8) p.group_m = 2;
   else if (tn <= 16) p.group_m = 4;
-  return launch_gemm<256, 256, 2, 4>(p, reinterpret_cast<hipStream_t>(stream));
+  return launch_gemm<256, 256, 2, 4, F16>(p, reinterpret_cast<hipStream_t>(stream));
+}
+extern "C" int haff_gemm_bf16_rowstats(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
+                                       void* C, long ldc, const float* bias, const void* resid, long ldr, int M, int N, int K,
+                                       float* stat_out, void* stream) {
+  return gemm_rowstats_impl(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, M, N, K, stat_out, stream);
+}
+extern "C" int haff_gemm_f16_rowstats(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
+                                      void* C, long ldc, const float* bias, const void* resid, long ldr, int M, int N, int K,
+                                      float* stat_out, void* stream) {
+  return gemm_rowstats_impl<true>(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, M, N, K, stat_out, stream);
 }
 
 // haff_gemm_bf16_rowstats on an fp32 residual stream (round 6; the "fused fp32 stream" of DESIGN.md section 2): X32 f32 [M][ldx] is
@@ -2141,13 +2220,26 @@ extern "C" int haff_gemm_bf16_rowstats32(const void* A, long lda, const int* a_m
 // HBM. The caller scales W's columns by gamma, adds W.beta to the bias (haff side: sam.py / llava.py at load time) and
 // passes the per-row {mean, rstd} from haff_row_stats. Replaces norm1->qkv and norm2->lin1 of the SAM blocks
 // (image_encoder.py:179,191), input/post-attention RMSNorm -> qkv / gate-up of Llama, layer_norm1/2 of CLIP.
+template <bool F16 = false>
+static int gemm_ln_impl(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                        const void* resid, long ldr, const int* row_map, const float* ln_stats,
+                        const float* ln_colsum, int M, int N, int K, int act, int out_f32, int swiglu,
+                        void* stream) {
+  if (!ln_stats) return HAFF_ERR_BAD_ARG;
+  return gemm_bf16_impl<F16>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
+                        stream, ln_stats, ln_colsum);
+}
 extern "C" int haff_gemm_bf16_ln(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                                  const void* resid, long ldr, const int* row_map, const float* ln_stats,
                                  const float* ln_colsum, int M, int N, int K, int act, int out_f32, int swiglu,
                                  void* stream) {
-  if (!ln_stats) return HAFF_ERR_BAD_ARG;
-  return gemm_bf16_impl(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
-                        stream, ln_stats, ln_colsum);
+  return gemm_ln_impl(A, lda, W, ldw, C, ldc, bias, resid, ldr, row_map, ln_stats, ln_colsum, M, N, K, act, out_f32, swiglu, stream);
+}
+extern "C" int haff_gemm_f16_ln(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                                const void* resid, long ldr, const int* row_map, const float* ln_stats,
+                                const float* ln_colsum, int M, int N, int K, int act, int out_f32, int swiglu,
+                                void* stream) {
+  return gemm_ln_impl<true>(A, lda, W, ldw, C, ldc, bias, resid, ldr, row_map, ln_stats, ln_colsum, M, N, K, act, out_f32, swiglu, stream);
 }
 
 // Product (optionally with a folded norm, as haff_gemm_bf16_ln) whose output is scattered HEAD-MAJOR: the windowed q|k|v
@@ -2160,9 +2252,10 @@ extern "C" int haff_gemm_bf16_ln(const void* A, long lda, const void* W, long ld
 // bias f32 [N]; ln_stats / ln_colsum as haff_gemm_bf16_ln or both null. Whole 256 x 256 tiles only (M % 256 == 0, N % 256 == 0,
 // K % 64 == 0), N == parts * heads * d with parts <= 3, d % 8 == 0: otherwise HAFF_ERR_UNSUPPORTED (-2) and the caller keeps the
 // token-major layout.
-extern "C" int haff_gemm_bf16_heads(const void* A, long lda, const void* W, long ldw, void* C, const float* bias, const int* row_map,
-                                    const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads,
-                                    long part_stride, long head_stride, void* stream) {
+template <bool F16 = false>
+static int gemm_heads_impl(const void* A, long lda, const void* W, long ldw, void* C, const float* bias, const int* row_map,
+                           const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads,
+                           long part_stride, long head_stride, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || d <= 0 || heads <= 0 || !row_map || !C) return HAFF_ERR_BAD_ARG;
   if ((K & 7) || (lda & 7) || (ldw & 7) || (part_stride & 7) || (head_stride & 7)) return HAFF_ERR_BAD_ARG;
   if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(C) & 15))
@@ -2178,7 +2271,17 @@ extern "C" int haff_gemm_bf16_heads(const void* A, long lda, const void* W, long
   else if (K >= 5120 && tn <= 8) p.group_m = 2;
   else if (tn <= 16) p.group_m = 4;
   p.nt_out = (long)M * N * 2 >= (64L << 20);
-  return launch_gemm<256, 256, 2, 4>(p, reinterpret_cast<hipStream_t>(stream));
+  return launch_gemm<256, 256, 2, 4, F16>(p, reinterpret_cast<hipStream_t>(stream));
+}
+extern "C" int haff_gemm_bf16_heads(const void* A, long lda, const void* W, long ldw, void* C, const float* bias, const int* row_map,
+                                    const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads,
+                                    long part_stride, long head_stride, void* stream) {
+  return gemm_heads_impl(A, lda, W, ldw, C, bias, row_map, ln_stats, ln_colsum, M, N, K, d, heads, part_stride, head_stride, stream);
+}
+extern "C" int haff_gemm_f16_heads(const void* A, long lda, const void* W, long ldw, void* C, const float* bias, const int* row_map,
+                                   const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads,
+                                   long part_stride, long head_stride, void* stream) {
+  return gemm_heads_impl<true>(A, lda, W, ldw, C, bias, row_map, ln_stats, ln_colsum, M, N, K, d, heads, part_stride, head_stride, stream);
 }
 
 // Batched C_z = A_z . W_z^T (no epilogue): z = zo * nb_inner + zi, operand offsets zo * s?o + zi * s?i (elements).

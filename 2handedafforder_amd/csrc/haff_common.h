@@ -42,6 +42,49 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f, haff_bf16x2));
 }
 
+// fp16 (IEEE binary16) rows: a C++ type of their own (bf16_t is unsigned short), so elem<>, load8 / store8 tell them apart.
+// f32 -> f16 is the IEEE conversion: round to nearest even, overflow gives +-inf (never a saturated value).
+typedef _Float16 f16_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) _Float16 haff_f16x2;
+__device__ __forceinline__ float f16_to_f32(unsigned short v) { return (float)__builtin_bit_cast(_Float16, v); }
+__device__ __forceinline__ unsigned short f32_to_f16(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+__device__ __forceinline__ unsigned pack_f16x2(float lo, float hi) {
+  const haff_f32x2 f = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, haff_f16x2));
+}
+
+// The 16-bit operand format of the MFMA kernels as a compile-time parameter (one kernel, two instances): operands travel as raw
+// 16-bit payloads through HBM, LDS and registers either way; h16<F16> supplies the conversions and the MFMA forms.
+// lo / hi: the element in the low / high half of a dword.
+template <bool F16> struct h16;
+template <> struct h16<false> {
+  static __device__ __forceinline__ float lo(unsigned w) { return __uint_as_float(w << 16); }
+  static __device__ __forceinline__ float hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+  static __device__ __forceinline__ float to_f32(unsigned short v) { return bf16_to_f32(v); }
+  static __device__ __forceinline__ unsigned short from_f32(float f) { return f32_to_bf16(f); }
+  static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_bf16x2(lo, hi); }
+  static __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  }
+};
+template <> struct h16<true> {
+  static __device__ __forceinline__ float lo(unsigned w) { return f16_to_f32((unsigned short)(w & 0xffffu)); }
+  static __device__ __forceinline__ float hi(unsigned w) { return f16_to_f32((unsigned short)(w >> 16)); }
+  static __device__ __forceinline__ float to_f32(unsigned short v) { return f16_to_f32(v); }
+  static __device__ __forceinline__ unsigned short from_f32(float f) { return f32_to_f16(f); }
+  static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_f16x2(lo, hi); }
+  static __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  }
+};
+
 template <typename T> struct elem;
 template <> struct elem<float> {
   static __device__ __forceinline__ float ld(const float* p) { return *p; }
@@ -50,6 +93,10 @@ template <> struct elem<float> {
 template <> struct elem<bf16_t> {
   static __device__ __forceinline__ float ld(const bf16_t* p) { return bf16_to_f32(*p); }
   static __device__ __forceinline__ void st(bf16_t* p, float v) { *p = f32_to_bf16(v); }
+};
+template <> struct elem<f16_t> {
+  static __device__ __forceinline__ float ld(const f16_t* p) { return (float)*p; }
+  static __device__ __forceinline__ void st(f16_t* p, float v) { *p = (f16_t)v; }
 };
 
 // 8-element vector load/store (16 B for bf16, 32 B for f32) into fp32 registers
@@ -95,8 +142,47 @@ __device__ __forceinline__ void store4(bf16_t* p, const float (&v)[4]) {
   r.y = pack_bf16x2(v[2], v[3]);
   *reinterpret_cast<uint2*>(p) = r;
 }
+__device__ __forceinline__ void load8(const f16_t* p, float (&v)[8]) {
+  uint4 r = *reinterpret_cast<const uint4*>(p);
+  unsigned w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = h16<true>::lo(w[i]);
+    v[2 * i + 1] = h16<true>::hi(w[i]);
+  }
+}
+__device__ __forceinline__ void store8(f16_t* p, const float (&v)[8]) {
+  uint4 r;
+  r.x = pack_f16x2(v[0], v[1]);
+  r.y = pack_f16x2(v[2], v[3]);
+  r.z = pack_f16x2(v[4], v[5]);
+  r.w = pack_f16x2(v[6], v[7]);
+  *reinterpret_cast<uint4*>(p) = r;
+}
+__device__ __forceinline__ void load4(const f16_t* p, float (&v)[4]) {
+  uint2 r = *reinterpret_cast<const uint2*>(p);
+  v[0] = h16<true>::lo(r.x); v[1] = h16<true>::hi(r.x);
+  v[2] = h16<true>::lo(r.y); v[3] = h16<true>::hi(r.y);
+}
+__device__ __forceinline__ void store4(f16_t* p, const float (&v)[4]) {
+  uint2 r;
+  r.x = pack_f16x2(v[0], v[1]);
+  r.y = pack_f16x2(v[2], v[3]);
+  *reinterpret_cast<uint2*>(p) = r;
+}
 __device__ __forceinline__ void store4(float* p, const float (&v)[4]) {
   *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// 16-bit rows carried as raw payloads (const bf16_t*) by the kernels templated on the operand format (h16<F16>)
+template <bool F16> __device__ __forceinline__ void load8h(const bf16_t* p, float (&v)[8]) {
+  if constexpr (F16) load8(reinterpret_cast<const f16_t*>(p), v); else load8(p, v);
+}
+template <bool F16> __device__ __forceinline__ void store8h(bf16_t* p, const float (&v)[8]) {
+  if constexpr (F16) store8(reinterpret_cast<f16_t*>(p), v); else store8(p, v);
+}
+template <bool F16> __device__ __forceinline__ void store4h(bf16_t* p, const float (&v)[4]) {
+  if constexpr (F16) store4(reinterpret_cast<f16_t*>(p), v); else store4(p, v);
 }
 
 __device__ __forceinline__ float apply_act(float x, int act) {

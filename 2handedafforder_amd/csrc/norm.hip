@@ -257,21 +257,23 @@ int launch_stats(const void* x, long ldx, float* stats, int rows, int C, float e
 }  // namespace
 
 // dtype: 0 = bf16, 1 = f32 (x and y), 2 = f32 x -> bf16 y (an fp32 residual stream feeding a bf16 product: one rounding, of the
-// NORMALISED row). w, b fp32 [C]. C % 8 == 0, C <= 8192, ldx/ldy % 8 == 0.
+// NORMALISED row), 3 = f16 (x and y). w, b fp32 [C]. C % 8 == 0, C <= 8192, ldx/ldy % 8 == 0.
 extern "C" int haff_layernorm(const void* x, long ldx, void* y, long ldy, const float* w, const float* b,
                               const int* in_map, int rows, int C, float eps, int dtype, void* stream) {
-  if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || (ldy & 7) || !w || !b || dtype < 0 || dtype > 2) return HAFF_ERR_BAD_ARG;
+  if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || (ldy & 7) || !w || !b || dtype < 0 || dtype > 3) return HAFF_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dtype == 2) return launch_norm<float, false, bf16_t>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s);
+  if (dtype == 3) return launch_norm<f16_t, false>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s);
   return dtype == 0 ? launch_norm<bf16_t, false>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s)
                     : launch_norm<float, false>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s);
 }
 
 extern "C" int haff_rmsnorm(const void* x, long ldx, void* y, long ldy, const float* w, int rows, int C,
                             float eps, int dtype, void* stream) {
-  if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || (ldy & 7) || !w || dtype < 0 || dtype > 2) return HAFF_ERR_BAD_ARG;
+  if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || (ldy & 7) || !w || dtype < 0 || dtype > 3) return HAFF_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dtype == 2) return launch_norm<float, true, bf16_t>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s);   // (as haff_layernorm)
+  if (dtype == 3) return launch_norm<f16_t, true>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s);
   return dtype == 0 ? launch_norm<bf16_t, true>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s)
                     : launch_norm<float, true>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s);
 }
@@ -308,11 +310,12 @@ extern "C" int haff_row_stats_finalize(const float* partials, float* stats, int 
 }
 
 // stats[rows][2] = {mean, rstd} of each row (rms != 0: {0, rsqrt(mean(x^2) + eps)} — LlamaRMSNorm). dtype: 0 = bf16,
-// 1 = f32. For haff_gemm_bf16_ln, which applies the normalisation inside the consumer product.
+// 1 = f32, 3 = f16. For haff_gemm_bf16_ln, which applies the normalisation inside the consumer product.
 extern "C" int haff_row_stats(const void* x, long ldx, float* stats, int rows, int C, float eps, int rms, int dtype,
                               void* stream) {
   if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || !stats) return HAFF_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dtype == 0) return rms ? launch_stats<bf16_t, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<bf16_t, false>(x, ldx, stats, rows, C, eps, s);
+  if (dtype == 3) return rms ? launch_stats<f16_t, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<f16_t, false>(x, ldx, stats, rows, C, eps, s);
   return rms ? launch_stats<float, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<float, false>(x, ldx, stats, rows, C, eps, s);
 }

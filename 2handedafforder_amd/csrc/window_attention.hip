@@ -107,8 +107,9 @@ struct WinCfg {
 // into registers; they are written to the other buffer after the compute, then ONE barrier per item. The load stream
 // never stops, which is what an HBM-bound kernel needs (the non-persistent version serialised load -> compute per
 // workgroup and reached 2.3 TB/s; see tools/window_attn_bench.py).
-template <int D, int S>
+template <int D, int S, bool F16 = false>
 __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(WinArgs p) {
+  using E = h16<F16>;   // F16: fp16 q / k / v / o / tables and probabilities (v_mfma_f32_16x16x32_f16), bf16 otherwise
   using C = WinCfg<D, S>;
   static_assert(D % 16 == 0 && D <= 96 && S <= 16 && 2 * S - 1 <= 32, "window kernel geometry");
   extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];
@@ -318,11 +319,11 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
           const unsigned w4[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            qv[2 * j] = __builtin_bit_cast(float, w4[j] << 16) * sl2;
-            qv[2 * j + 1] = __builtin_bit_cast(float, w4[j] & 0xffff0000u) * sl2;
+            qv[2 * j] = E::lo(w4[j]) * sl2;
+            qv[2 * j + 1] = E::hi(w4[j]) * sl2;
           }
-          rs.x = pack_bf16x2(qv[0], qv[1]); rs.y = pack_bf16x2(qv[2], qv[3]);
-          rs.z = pack_bf16x2(qv[4], qv[5]); rs.w = pack_bf16x2(qv[6], qv[7]);
+          rs.x = E::pack2(qv[0], qv[1]); rs.y = E::pack2(qv[2], qv[3]);
+          rs.z = E::pack2(qv[4], qv[5]); rs.w = E::pack2(qv[6], qv[7]);
         }
         qraw[kd] = __builtin_bit_cast(bf16x8, r);
         qs[kd] = __builtin_bit_cast(bf16x8, rs);
@@ -334,8 +335,8 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
         f32x4 t0 = f32x4{0.f, 0.f, 0.f, 0.f}, t1 = t0;
 #pragma unroll
         for (int kd = 0; kd < C::NKD; ++kd) {
-          t0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tw[0][kd], qraw[kd], t0, 0, 0, 0);
-          t1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tw[1][kd], qraw[kd], t1, 0, 0, 0);
+          t0 = E::mfma16(tw[0][kd], qraw[kd], t0);
+          t1 = E::mfma16(tw[1][kd], qraw[kd], t1);
         }
         float a[4] = {t0[0], t0[1], t0[2], t0[3]}, b[4] = {t1[0], t1[1], t1[2], t1[3]};
 #ifdef HAFF_WIN_NOSCR
@@ -358,8 +359,8 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
         f32x4 t0 = f32x4{0.f, 0.f, 0.f, 0.f}, t1 = t0;
 #pragma unroll
         for (int kd = 0; kd < C::NKD; ++kd) {
-          t0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[0][kd], qraw[kd], t0, 0, 0, 0);
-          t1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[1][kd], qraw[kd], t1, 0, 0, 0);
+          t0 = E::mfma16(th[0][kd], qraw[kd], t0);
+          t1 = E::mfma16(th[1][kd], qraw[kd], t1);
         }
         float a[4] = {t0[0], t0[1], t0[2], t0[3]}, b[4] = {t1[0], t1[1], t1[2], t1[3]};
 #ifdef HAFF_WIN_NOSCR
@@ -408,7 +409,7 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
 #else
             const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sK + (kt * S + qcol) * C::KSTR + (kd == C::NKD - 1 ? koff_last : fh * 16 + kd * 64));
 #endif
-            sacc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qs[kd], sacc[kt], 0, 0, 0);
+            sacc[kt] = E::mfma16(kf, qs[kd], sacc[kt]);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -450,10 +451,10 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
         constexpr int dummy = 0; (void)dummy;
         const int t0 = 2 * ks, t1 = (2 * ks + 1 < S) ? 2 * ks + 1 : 2 * ks;
         uint4 u;
-        u.x = pack_bf16x2(sacc[t0][0], sacc[t0][1]);
-        u.y = pack_bf16x2(sacc[t0][2], sacc[t0][3]);
-        u.z = (2 * ks + 1 < S) ? pack_bf16x2(sacc[t1][0], sacc[t1][1]) : 0u;
-        u.w = (2 * ks + 1 < S) ? pack_bf16x2(sacc[t1][2], sacc[t1][3]) : 0u;
+        u.x = E::pack2(sacc[t0][0], sacc[t0][1]);
+        u.y = E::pack2(sacc[t0][2], sacc[t0][3]);
+        u.z = (2 * ks + 1 < S) ? E::pack2(sacc[t1][0], sacc[t1][1]) : 0u;
+        u.w = (2 * ks + 1 < S) ? E::pack2(sacc[t1][2], sacc[t1][3]) : 0u;
         const bf16x8 pf = __builtin_bit_cast(bf16x8, u);
         const unsigned char* v0 = sV + (t0 * S + vkw) * C::VSTR + 8 * tr_p;
         const unsigned char* v1 = sV + (t1 * S + vkw) * C::VSTR + 8 * tr_p;
@@ -467,7 +468,7 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
           const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wlds_v4_ptr)(v1 + 32 * dt));
           const bf16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 #endif
-          oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[dt], 0, 0, 0);
+          oacc[dt] = E::mfma16(vf, pf, oacc[dt]);
         }
       }
 
@@ -480,7 +481,7 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
 #pragma unroll
         for (int dt = 0; dt < C::ND; ++dt) {
           float v[4] = {oacc[dt][0] * inv, oacc[dt][1] * inv, oacc[dt][2] * inv, oacc[dt][3] * inv};
-          store4(orow + 16 * dt, v);
+          store4h<F16>(orow + 16 * dt, v);
         }
       }
     }
@@ -512,13 +513,14 @@ extern "C" int haff_win_trace_read(unsigned long long* host, int n_words) {
 // image_encoder.py:179-183). grid_h == 0: every row of every window is real. tab_h/tab_w: bf16 [2S-1][d] contiguous (image_encoder.py:322-351 with
 // q_size == k_size: no interpolation). Supported geometry: S == 14, d == 80 (SAM ViT-H windowed blocks);
 // anything else returns HAFF_ERR_UNSUPPORTED and the caller uses haff_relpos_tables + haff_attention_bf16.
-extern "C" int haff_window_attention_bf16(const void* q, long q_sb, long q_sh, long q_st,
-                                          const void* k, long k_sb, long k_sh, long k_st,
-                                          const void* v, long v_sb, long v_sh, long v_st,
-                                          void* o, long o_sb, long o_sh, long o_st,
-                                          int n_windows, int H, int S, int d, float scale,
-                                          const void* tab_h, const void* tab_w, int grid_h, int grid_w,
-                                          long pad_token, void* stream) {
+template <bool F16 = false>
+static int window_attention_impl(const void* q, long q_sb, long q_sh, long q_st,
+                                 const void* k, long k_sb, long k_sh, long k_st,
+                                 const void* v, long v_sb, long v_sh, long v_st,
+                                 void* o, long o_sb, long o_sh, long o_st,
+                                 int n_windows, int H, int S, int d, float scale,
+                                 const void* tab_h, const void* tab_w, int grid_h, int grid_w,
+                                 long pad_token, void* stream) {
   if (n_windows <= 0 || H <= 0 || S <= 0 || d <= 0 || !tab_h || !tab_w) return HAFF_ERR_BAD_ARG;
   if ((q_st & 7) || (k_st & 7) || (v_st & 7) || (o_st & 3) || (q_sh & 7) || (k_sh & 7) || (v_sh & 7) || (o_sh & 3) ||
       (q_sb & 7) || (k_sb & 7) || (v_sb & 7) || (o_sb & 3))
@@ -555,12 +557,35 @@ extern "C" int haff_window_attention_bf16(const void* q, long q_sb, long q_sh, l
   }
   using C = WinCfg<80, 14>;
   // the attribute is per device and this entry point keeps no state: set it on every call (a host-side table write)
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&window_attn_kernel<80, 14>),
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&window_attn_kernel<80, 14, F16>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess)
     return HAFF_ERR_LAUNCH;
   // persistent: one 7-wave workgroup per CU (150 KB LDS); a multiple of 8 workgroups keeps the item -> XCD mapping
   const int n_items = n_windows * H;
   dim3 grid(n_items < 256 ? n_items : 256), block(C::NTHREADS);
-  hipLaunchKernelGGL((window_attn_kernel<80, 14>), grid, block, C::LDS_BYTES, reinterpret_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL((window_attn_kernel<80, 14, F16>), grid, block, C::LDS_BYTES, reinterpret_cast<hipStream_t>(stream), p);
   return haff_check_launch();
+}
+
+extern "C" int haff_window_attention_bf16(const void* q, long q_sb, long q_sh, long q_st,
+                                          const void* k, long k_sb, long k_sh, long k_st,
+                                          const void* v, long v_sb, long v_sh, long v_st,
+                                          void* o, long o_sb, long o_sh, long o_st,
+                                          int n_windows, int H, int S, int d, float scale,
+                                          const void* tab_h, const void* tab_w, int grid_h, int grid_w,
+                                          long pad_token, void* stream) {
+  return window_attention_impl(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, n_windows, H, S,
+                               d, scale, tab_h, tab_w, grid_h, grid_w, pad_token, stream);
+}
+
+// fp16 instance: q / k / v / o and the tables tab_h / tab_w are f16
+extern "C" int haff_window_attention_f16(const void* q, long q_sb, long q_sh, long q_st,
+                                         const void* k, long k_sb, long k_sh, long k_st,
+                                         const void* v, long v_sb, long v_sh, long v_st,
+                                         void* o, long o_sb, long o_sh, long o_st,
+                                         int n_windows, int H, int S, int d, float scale,
+                                         const void* tab_h, const void* tab_w, int grid_h, int grid_w,
+                                         long pad_token, void* stream) {
+  return window_attention_impl<true>(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, n_windows, H,
+                                     S, d, scale, tab_h, tab_w, grid_h, grid_w, pad_token, stream);
 }

@@ -49,15 +49,27 @@ def parse_args(args):
     return parser.parse_args(args)
 
 
+PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+
+
+def precision_dtype(precision):
+    """--precision -> the model dtype (inference.py:170-186 of the reference: fp32 | bf16 | fp16). fp16 is the inference mode on the
+    f16 MFMA kernels (the ViT-H neck and the decoder tail in f32, README "Precision modes")."""
+    if precision not in PRECISIONS:
+        raise SystemExit(f"--precision {precision}: one of {', '.join(PRECISIONS)}")
+    return PRECISIONS[precision]
+
+
 def build_model_and_tokenizer(args):
-    if args.load_in_8bit or args.load_in_4bit or args.precision == "fp16":
-        raise SystemExit("bitsandbytes 4/8-bit and the DeepSpeed fp16 kernel-inject mode are outside this build's scope "
-                         "(SURVEY §2.2); use --precision bf16 or fp32")
-    dtype = torch.bfloat16 if args.precision == "bf16" else torch.float32
+    if args.load_in_8bit or args.load_in_4bit:
+        raise SystemExit("bitsandbytes 4/8-bit quantisation is outside this build's scope (SURVEY §2.2); "
+                         "use --precision bf16, fp16 or fp32")
+    dtype = precision_dtype(args.precision)
     device = f"cuda:{args.local_rank}"
     if args.synthetic:
         cfg = {"tiny": hcfg.tiny, "mid": hcfg.mid, "7b": hcfg.haff_7b, "13b": hcfg.haff_13b}[args.synthetic]()
-        sd = checkpoint.synthetic_state_dict(cfg, 1234, device, dtype)
+        # fp16: the bf16 values of the same seed, so that --precision bf16 and fp16 run one model
+        sd = checkpoint.synthetic_state_dict(cfg, 1234, device, torch.bfloat16 if dtype == torch.float16 else dtype)
         tokenizer = checkpoint.ByteTokenizer(cfg)
     else:
         # inference.py:115-127,158-168: slow (sentencepiece) Llama tokenizer of the checkpoint + [SEG]; the model from

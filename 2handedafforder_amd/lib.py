@@ -29,6 +29,24 @@ _PROTOS = {
                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "haff_gemm_bf16_heads": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                              c_int, c_int, c_long, c_long, c_void_p],
+    "haff_gemm_f16": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_gemm_f16_cfg": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                          c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_gemm_f16_ws": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p],
+    "haff_gemm_f16_rms": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_int, c_int, c_int,
+                           c_int, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],
+    "haff_gemm_f16_gather": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p,
+                              c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_gemm_f16_qkv_rope": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_gemm_f16_rowstats": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p,
+                                c_long, c_int, c_int, c_int, c_void_p, c_void_p],
+    "haff_gemm_f16_ln": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                          c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_gemm_f16_heads": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                             c_int, c_int, c_long, c_long, c_void_p],
     "haff_gemm_stream_cap": [c_void_p, c_int],
     "haff_decode_chain_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p],
@@ -49,16 +67,24 @@ _PROTOS = {
                             c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                             c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_int,
                             c_void_p],
+    "haff_attention_f16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                           c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                           c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_int,
+                           c_void_p],
     "haff_attention_f32": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                            c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                            c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_int,
                            c_void_p],
     "haff_attention_decode_rows_bf16": [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                         c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
+    "haff_attention_decode_rows_f16": [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                                       c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "haff_attention_decode_rows_f32": [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                        c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p],
     "haff_decode_attention_rope_rows_bf16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_float, c_void_p, c_void_p],
+    "haff_decode_attention_rope_rows_f16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                            c_float, c_void_p, c_void_p],
     "haff_rope_cache_rows": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                              c_int, c_int, c_void_p],
     "haff_relpos_tables": [c_void_p, c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -66,6 +92,10 @@ _PROTOS = {
     "haff_relpos_tables_bf16": [c_void_p, c_long, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int, c_int, c_int, c_int, c_void_p],
     "haff_window_attention_bf16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                                   c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                                   c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_long,
+                                   c_void_p],
+    "haff_window_attention_f16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_long,
                                    c_void_p],
@@ -86,6 +116,9 @@ _PROTOS = {
     "haff_lora_tn": [c_void_p, c_long, c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int,
                      c_int, c_float, c_void_p],
     "haff_global_attention_bf16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                                   c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                                   c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
+    "haff_global_attention_f16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "haff_layernorm": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,

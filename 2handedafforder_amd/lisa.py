@@ -26,6 +26,27 @@ IMAGE_TOKEN_INDEX = -200
 N_IMG_PAD = 255  # LISA.py:461
 
 
+def _check_fp16_weights(sd, device):
+    """The fp16 mode's weight conversion (the reference's `model.half()`), checked tensor by tensor on the device: a value that turns
+    non-finite (|w| > 65504) raises ValueError naming the tensor. Returns how many nonzero weights flushed to zero (|w| below half the
+    smallest fp16 subnormal) and warns when there are any."""
+    flushed = 0
+    for name, t in sd.items():
+        if not torch.is_floating_point(t):
+            continue
+        src = t.to(device)
+        h = src.to(torch.float16)
+        bad = int((~torch.isfinite(h) & torch.isfinite(src)).sum())
+        if bad:
+            raise ValueError(f"fp16 mode: {bad} weights of {name} do not fit fp16 (|w| > 65504; max |w| = {src.abs().max().item():.6g})")
+        flushed += int(((h == 0) & (src != 0)).sum())
+        del src, h
+    if flushed:
+        import warnings
+        warnings.warn(f"fp16 mode: {flushed} nonzero weights flushed to zero in the fp16 conversion")
+    return flushed
+
+
 class LisaMI355:
     def __init__(self, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", sam_chunk=8, fp32_tail=True, fp32_stream=False,
                  neck_f32=False):
@@ -33,6 +54,11 @@ class LisaMI355:
             raise RuntimeError("LisaMI355 needs an MI355X (HIP device); there is no CPU fallback for the hot path")
         from .lib import load_library
         load_library()  # fail loudly if the HIP library is absent
+        if dtype == torch.float16 and (fp32_stream or neck_f32 or not fp32_tail):
+            # the fused fp32 stream is a bf16 epilogue, the fp16 mode runs the ViT-H neck in f32 by contract, and the decoder tail's
+            # kernels (sam_decoder.hip) have no f16 rows: the fp16 mode's tail is fp32
+            raise ValueError("LisaMI355(dtype=torch.float16): fp32_stream, neck_f32 and fp32_tail=False are bf16-mode options "
+                             "(the fp16 neck and decoder tail are always f32)")
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         self.seg_token_idx = cfg.seg_token_idx
         self.sam_chunk = sam_chunk
@@ -75,12 +101,13 @@ class LisaMI355:
         self._graph_pool = None
         self._caches = {}
         sd, dev = state_dict, self.device
+        self.fp16_flushed_weights = _check_fp16_weights(sd, dev) if dtype == torch.float16 else 0
         assert cfg.clip.n_patches == N_IMG_PAD + 1, "the reference hard-codes 256 image tokens (LISA.py:461)"
         # fp32 decoder tail (throughput mode): image embeddings leave the neck in fp32 and text_hidden_fcs, the prompt
         # encoder, both two-way mask decoders, the hypernetwork / IoU / taxonomy MLPs and the upscaler run on the
         # f32-input matrix cores (csrc/gemm_f32.hip) — 7 GFLOP of the 10 TFLOP per frame (hard part 3).
         # The ViT-H / CLIP / Llama stacks stay bf16 MFMA. False = the all-bf16 path of round 1.
-        self.fp32_tail = fp32_tail and dtype == torch.bfloat16
+        self.fp32_tail = fp32_tail and dtype in (torch.bfloat16, torch.float16)
         tail = torch.float32 if self.fp32_tail else dtype
         self.tail_dtype = tail
         self.sam_encoder = SamEncoderHip(sd, cfg.sam, dtype, dev)
@@ -92,7 +119,7 @@ class LisaMI355:
         # stream kept in fp32 between the bf16 MFMA products (2.8x closer to the reference on the image embedding at depth 32)
         self.sam_encoder.fp32_stream = fp32_stream in (True, "sam", "both")
         self.llm.fp32_stream = fp32_stream in (True, "llm", "both")
-        self.sam_encoder.neck_f32 = bool(neck_f32) and dtype == torch.bfloat16    # the ViT-H neck on the f32-input MFMA path (sam.py)
+        self.sam_encoder.neck_f32 = (bool(neck_f32) and dtype == torch.bfloat16) or dtype == torch.float16  # the ViT-H neck on the f32-input MFMA path (sam.py)
         self.w_proj = sd["model.mm_projector.weight"].to(dev, dtype).contiguous()
         self.b_proj = _f32(sd["model.mm_projector.bias"], dev)
         self.fc0 = (sd["model.text_hidden_fcs.0.0.weight"].to(dev, tail).contiguous(), _f32(sd["model.text_hidden_fcs.0.0.bias"], dev))

@@ -124,13 +124,13 @@ class LlamaHip:
         self.lm_head = sd["lm_head.weight"].to(dev, dtype).contiguous()
         # Decode steps of <= 8 rows (round 5; <= 4 before) carry RMSNorm between the products (ops.linear_rms): no norm kernels, the q/k/v and gate/up
         # weights get a second copy with the norm weight folded in (built on first use; +9 GB at 7B, +18 GB at 13B of 288)
-        self.carry_rms = dtype == torch.bfloat16 and self.hd == 128 and l.hidden % 128 == 0 and l.ffn % 128 == 0
+        self.carry_rms = dtype in (torch.bfloat16, torch.float16) and self.hd == 128 and l.hidden % 128 == 0 and l.ffn % 128 == 0
         self.carry_rms_max_rows = 8   # the consumer side of haff_gemm_bf16_rms gathers the partials of <= 8 rows
         self._folded = None
         # Round 6: the whole <= 8-row decode step as ONE launch (ops.decode_chain, csrc/decode_chain.hip): the five stages of every
         # layer are workgroup ranges chained by arrival counters, weights are requested before a workgroup waits for its inputs.
         # Same arithmetic as the five-launch layer below (bit-identical at 5..8 rows). False: the five launches per layer.
-        self.decode_chain = True      # "stages": the same kernel as one launch per (layer, stage) (tests, A/B)
+        self.decode_chain = dtype != torch.float16   # "stages": the same kernel as one launch per (layer, stage) (tests, A/B); a bf16 kernel
         self._cs = None
         # Prefill-sized batches (>= 1024 rows: where the 8-wave tile runs anyway): RoPE and the KV-cache append ride in the q|k|v projection's epilogue
         # (ops.qkv_rope): the weights get a second, row-permuted copy on first use (+3.2 GB at 7B, +6.3 GB at 13B of 288)
@@ -213,6 +213,8 @@ class LlamaHip:
         sits at position cache["pos"][b] (device int32 [B]) and attends that row's first pos+1 cached keys — greedy decode
         of right-padded prompts of different lengths (padding rule of utils/dataset.py:90-93). The caller advances
         cache["pos"] / cache["nk"] (nk = pos + 1). Returns post-norm hidden [B,1,H]."""
+        if self.decode_chain and self.dtype == torch.float16:
+            raise ValueError("LlamaHip.decode_chain: the chained decode step is a bf16 kernel; fp16 decodes with five launches per layer")
         l = self.cfg
         B, T, H = x1.shape
         assert T == 1
@@ -230,7 +232,7 @@ class LlamaHip:
             h = ops.rmsnorm(x, L["n1"], l.rms_eps, out_dtype=nd)
             qkv = ops.linear(h, L["wqkv"])
             kc, vc = cache["k"][li], cache["v"][li]
-            if self.dtype == torch.bfloat16 and hd == 128:
+            if self.dtype in (torch.bfloat16, torch.float16) and hd == 128:
                 # RoPE of q and the new k, the cache append and the attention over the row's pos+1 keys in ONE launch
                 a = ops.decode_attention_rope(qkv, kc, vc, cs, nh, hd, hd ** -0.5, nk)
             else:
@@ -249,8 +251,8 @@ class LlamaHip:
         """The q|k|v and gate|up weights with their RMSNorm's gamma folded into the columns (what the norm-carrying decode products
         multiply the RAW residual stream with); built once, on first use."""
         if self._folded is None:
-            self._folded = [((L["wqkv"].float() * L["n1"][None, :]).to(torch.bfloat16).contiguous(),
-                             (L["wgu"].float() * L["n2"][None, :]).to(torch.bfloat16).contiguous()) for L in self.layers]
+            self._folded = [((L["wqkv"].float() * L["n1"][None, :]).to(self.dtype).contiguous(),
+                             (L["wgu"].float() * L["n2"][None, :]).to(self.dtype).contiguous()) for L in self.layers]
         return self._folded
 
     def _decode_rows_carry(self, x, cache, cs, nk):

@@ -2,7 +2,8 @@
 
 torch is used here only for device memory and the current HIP stream; every arithmetic op below is a
 hand-written HIP kernel. All functions require CUDA(HIP) tensors and raise if the library is missing.
-dtype policy: torch.bfloat16 = throughput mode (bf16 MFMA, fp32 accumulate), torch.float32 = parity mode.
+dtype policy: torch.bfloat16 = throughput mode (bf16 MFMA, fp32 accumulate), torch.float32 = parity mode, torch.float16 = the
+fp16 inference mode (f16 MFMA, fp32 accumulate: the *_f16 instances of the 16-bit kernels, dtype code 3 elsewhere).
 """
 import ctypes
 
@@ -18,7 +19,14 @@ def _dt(t):
         return 0
     if t.dtype == torch.float32:
         return 1
+    if t.dtype == torch.float16:
+        return 3
     raise TypeError(f"unsupported dtype {t.dtype}")
+
+
+def _fn(lib, name, dtype):
+    """The entry point of the 16-bit format: haff_*_bf16 for bf16, its haff_*_f16 sibling for fp16 (same arguments)."""
+    return getattr(lib, name.replace("_bf16", "_f16") if dtype == torch.float16 else name)
 
 
 def _stream():
@@ -68,7 +76,7 @@ def row_stats(x, eps, rms=False):
 def linear_rowstats_supported(M, N, K, dtype, min_tiles=160):
     """Shapes whose residual product can emit the LayerNorm statistics of its output rows (haff_gemm_bf16_rowstats): whole
     256 x 256 tiles, and (min_tiles) enough of them that the 8-wave tile is what linear() would launch anyway."""
-    return dtype == torch.bfloat16 and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and (M // 256) * (N // 256) >= min_tiles
+    return dtype in (torch.bfloat16, torch.float16) and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and (M // 256) * (N // 256) >= min_tiles
 
 
 def rowstats_gemm(x, w, bias, resid, out, a_map=None):
@@ -77,7 +85,7 @@ def rowstats_gemm(x, w, bias, resid, out, a_map=None):
     M = a_map.numel() if a_map is not None else x.shape[0]
     N, K = w.shape
     part = torch.empty((M, N // 64, 2), dtype=torch.float32, device=x.device)
-    rc = lib.haff_gemm_bf16_rowstats(x.data_ptr(), x.stride(0), _p(a_map), x.shape[0], w.data_ptr(), w.stride(0), out.data_ptr(),
+    rc = _fn(lib, "haff_gemm_bf16_rowstats", x.dtype)(x.data_ptr(), x.stride(0), _p(a_map), x.shape[0], w.data_ptr(), w.stride(0), out.data_ptr(),
                                      out.stride(0), _p(bias), resid.data_ptr(), resid.stride(0), M, N, K, part.data_ptr(), _stream())
     check(rc, "haff_gemm_bf16_rowstats")
     return part
@@ -93,8 +101,8 @@ def linear_rowstats(x, w, bias, resid, eps, out=None, a_map=None):
         assert a_map.dtype == torch.int32
         M = a_map.numel()
     N = w.shape[0]
-    assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K
-    assert linear_rowstats_supported(M, N, K, x.dtype, 0) and resid is not None and resid.dtype == torch.bfloat16
+    assert x.dtype in (torch.bfloat16, torch.float16) and w.dtype == x.dtype and x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K
+    assert linear_rowstats_supported(M, N, K, x.dtype, 0) and resid is not None and resid.dtype == x.dtype
     if out is None:
         out = torch.empty((M, N), dtype=x.dtype, device=x.device)
     part = rowstats_gemm(x, w, bias, resid, out, a_map)
@@ -124,7 +132,8 @@ def linear_rowstats32(x, w, bias, x32, out16, eps, a_map=None):
     M = a_map.numel() if a_map is not None else x.shape[0]
     N, K = w.shape
     assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.stride(1) == 1 and w.stride(1) == 1 and x.shape[1] == K
-    assert linear_rowstats_supported(M, N, K, x.dtype, 0) and x32.dtype == torch.float32 and out16.dtype == torch.bfloat16
+    assert x.dtype == torch.bfloat16 and x32.dtype == torch.float32 and out16.dtype == torch.bfloat16   # a bf16 epilogue
+    assert linear_rowstats_supported(M, N, K, x.dtype, 0)
     assert x32.shape == (M, N) and out16.shape == (M, N) and x32.stride(1) == 1 and out16.stride(1) == 1 and bias is not None
     part = rowstats32_gemm(x, w, bias, x32, out16, a_map)
     stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
@@ -148,7 +157,7 @@ def rope_permute_rows(w):
 def qkv_rope_supported(M, H, d, K, dtype, min_rows=1024):
     """Prefill-sized batches whose q|k|v projection can carry RoPE and the cache append (haff_gemm_bf16_qkv_rope): (min_rows)
     enough rows that the 8-wave tile is what linear() would launch anyway."""
-    return dtype == torch.bfloat16 and d == 128 and (H * d) % 256 == 0 and K % 64 == 0 and min_rows <= M < (1 << 22)
+    return dtype in (torch.bfloat16, torch.float16) and d == 128 and (H * d) % 256 == 0 and K % 64 == 0 and min_rows <= M < (1 << 22)
 
 
 def qkv_rope(x, w_perm, kcache, vcache, cos_sin, B, T, H, d, pos0):
@@ -157,21 +166,21 @@ def qkv_rope(x, w_perm, kcache, vcache, cos_sin, B, T, H, d, pos0):
     _req(x, "x")
     M, K = x.shape
     assert M == B * T and w_perm.shape == (3 * H * d, K) and x.stride(1) == 1 and w_perm.stride(1) == 1
-    assert x.dtype == torch.bfloat16 and w_perm.dtype == torch.bfloat16 and kcache.dtype == torch.bfloat16
+    assert x.dtype in (torch.bfloat16, torch.float16) and w_perm.dtype == x.dtype and kcache.dtype == x.dtype and vcache.dtype == x.dtype
     assert kcache.is_contiguous() and vcache.is_contiguous() and kcache.shape == vcache.shape and kcache.shape[2] == H * d
     assert cos_sin.dtype == torch.float32 and cos_sin.is_contiguous() and cos_sin.shape[0] >= kcache.shape[1] and cos_sin.shape[1] == d
     q = torch.empty((M, H * d), dtype=x.dtype, device=x.device)
-    rc = lib.haff_gemm_bf16_qkv_rope(x.data_ptr(), x.stride(0), w_perm.data_ptr(), w_perm.stride(0), q.data_ptr(), q.stride(0),
+    rc = _fn(lib, "haff_gemm_bf16_qkv_rope", x.dtype)(x.data_ptr(), x.stride(0), w_perm.data_ptr(), w_perm.stride(0), q.data_ptr(), q.stride(0),
                                      kcache.data_ptr(), vcache.data_ptr(), cos_sin.data_ptr(), B, T, kcache.shape[1], int(pos0),
                                      H, d, K, _stream())
     check(rc, "haff_gemm_bf16_qkv_rope")
     return q
 
 
-def fold_norm(w, gamma, beta=None, bias=None):
-    """Fold y = norm(x) * gamma + beta followed by y @ w.T + bias into the weights: returns (w_bf16 = bf16(w * gamma),
+def fold_norm(w, gamma, beta=None, bias=None, dtype=torch.bfloat16):
+    """Fold y = norm(x) * gamma + beta followed by y @ w.T + bias into the weights: returns (w16 = dtype(w * gamma),
     colsum fp32 [N] of the ROUNDED folded weights, bias' = bias + w @ beta)."""
-    wf = (w.float() * gamma.float()[None, :]).to(torch.bfloat16).contiguous()
+    wf = (w.float() * gamma.float()[None, :]).to(dtype).contiguous()
     colsum = wf.float().sum(1).contiguous()
     b = None
     if beta is not None or bias is not None:
@@ -199,7 +208,7 @@ def linear(x, w, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, ou
     assert x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.stride(1) == 1
     M, K = x.shape
     if a_map is not None:  # gather: logical row m reads x[a_map[m]] (bf16 only)
-        assert a_map.dtype == torch.int32 and x.dtype == torch.bfloat16
+        assert a_map.dtype == torch.int32 and x.dtype in (torch.bfloat16, torch.float16)
         M = a_map.numel()
     N = w.shape[0]
     assert w.shape[1] == K, (x.shape, w.shape)
@@ -215,7 +224,7 @@ def linear(x, w, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, ou
         assert bias.dtype == torch.float32 and bias.numel() == N
     if row_map is not None:
         assert row_map.dtype == torch.int32 and row_map.numel() == M
-    if (SPLIT_ROW_TAIL and x.dtype == torch.bfloat16 and M > 4096 and 0 < (M & 255) <= 64 and row_map is None and a_map is None
+    if (SPLIT_ROW_TAIL and x.dtype in (torch.bfloat16, torch.float16) and M > 4096 and 0 < (M & 255) <= 64 and row_map is None and a_map is None
             and ln_stats is None and not swiglu and not tile_cfg and out_rows is None and N >= 256):
         # A short row tail that costs the persistent 256 x 256 tile a whole extra round (CLIP at 64 frames: 16448 rows = 64.25
         # row tiles; N = 1024 gives 260 tiles on 256 CUs, the last 4 alone in a second round: 758 TFLOP/s): the whole row
@@ -227,31 +236,31 @@ def linear(x, w, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, ou
             _LINEAR(x[m0:], w, bias, act, None if resid is None else resid[m0:], out=out[m0:])
             return out
     if ln_stats is not None:
-        assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and a_map is None
+        assert x.dtype in (torch.bfloat16, torch.float16) and w.dtype == x.dtype and a_map is None
         assert ln_stats.dtype == torch.float32 and ln_stats.shape == (M, 2) and ln_stats.is_contiguous()
         if ln_colsum is not None:
             assert ln_colsum.dtype == torch.float32 and ln_colsum.numel() == N
-        rc = lib.haff_gemm_bf16_ln(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
+        rc = _fn(lib, "haff_gemm_bf16_ln", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
                                    out.stride(0), _p(bias), _p(resid), 0 if resid is None else resid.stride(0),
                                    _p(row_map), ln_stats.data_ptr(), _p(ln_colsum), M, N, K, act,
                                    1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, _stream())
     elif a_map is not None:
-        assert w.dtype == torch.bfloat16
-        rc = lib.haff_gemm_bf16_gather(x.data_ptr(), x.stride(0), a_map.data_ptr(), x.shape[0], w.data_ptr(),
+        assert w.dtype == x.dtype
+        rc = _fn(lib, "haff_gemm_bf16_gather", x.dtype)(x.data_ptr(), x.stride(0), a_map.data_ptr(), x.shape[0], w.data_ptr(),
                                        w.stride(0), out.data_ptr(), out.stride(0), _p(bias), _p(resid),
                                        0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
                                        1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, _stream())
-    elif x.dtype == torch.bfloat16 and 32 < M <= 1024 and not tile_cfg:
+    elif x.dtype in (torch.bfloat16, torch.float16) and 32 < M <= 1024 and not tile_cfg:
         # few output tiles (decode at batch 33..64 on narrow weights, prefill / CLIP at one frame): the library may split K
         # over workgroups through a per-stream fp32 workspace (partials summed in a fixed order)
-        assert w.dtype == torch.bfloat16
+        assert w.dtype == x.dtype
         ws = _workspace(x.device, 64 << 20)
-        rc = lib.haff_gemm_bf16_ws(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
+        rc = _fn(lib, "haff_gemm_bf16_ws", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
                                    _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
                                    1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, ws.data_ptr(), ws.numel(), _stream())
-    elif x.dtype == torch.bfloat16:
-        assert w.dtype == torch.bfloat16
-        rc = lib.haff_gemm_bf16_cfg(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
+    elif x.dtype in (torch.bfloat16, torch.float16):
+        assert w.dtype == x.dtype
+        rc = _fn(lib, "haff_gemm_bf16_cfg", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
                                     out.stride(0), _p(bias), _p(resid), 0 if resid is None else resid.stride(0),
                                     _p(row_map), M, N, K, act, 1 if out.dtype == torch.float32 else 0,
                                     1 if swiglu else 0, tile_cfg, _stream())
@@ -266,7 +275,7 @@ def linear(x, w, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, ou
 
 def linear_heads_supported(M, N, K, d, heads, dtype):
     """Shapes haff_gemm_bf16_heads serves: whole 256 x 256 tiles of the 8-wave kernel, N = parts * heads * d."""
-    return (dtype == torch.bfloat16 and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and d % 8 == 0 and N % (heads * d) == 0
+    return (dtype in (torch.bfloat16, torch.float16) and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and d % 8 == 0 and N % (heads * d) == 0
             and N // (heads * d) <= 3 and heads * d < (1 << 16) and M * K * 2 < (1 << 32) and N * K * 2 < (1 << 32))
 
 
@@ -288,20 +297,24 @@ def linear_heads(x, w, bias, row_map, out, d, heads, part_stride, head_stride, l
     _req(x, "x")
     M, K = x.shape
     N = w.shape[0]
-    assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and out.is_contiguous()
+    assert x.dtype in (torch.bfloat16, torch.float16) and w.dtype == x.dtype and out.dtype == x.dtype and out.is_contiguous()
     assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K and row_map.dtype == torch.int32 and row_map.numel() == M
     assert bias is None or (bias.dtype == torch.float32 and bias.numel() == N)
     if ln_stats is not None:
         assert ln_stats.dtype == torch.float32 and ln_stats.shape == (M, 2) and ln_stats.is_contiguous()
     parts = N // (heads * d)
     assert out.numel() >= (parts - 1) * part_stride + heads * head_stride   # (the row map's range is the caller's contract)
-    rc = lib.haff_gemm_bf16_heads(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), _p(bias), row_map.data_ptr(),
+    rc = _fn(lib, "haff_gemm_bf16_heads", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), _p(bias), row_map.data_ptr(),
                                   _p(ln_stats), _p(ln_colsum), M, N, K, d, heads, part_stride, head_stride, _stream())
     check(rc, "haff_gemm_bf16_heads")
     return out
 
 
 _LINEAR = linear   # the function itself: linear()'s own two-launch form must not go through a wrapper installed on ops.linear (bench.py's meter)
+
+
+def _half(t):
+    return t.dtype in (torch.bfloat16, torch.float16)
 
 
 def linear_rms(x, w, resid=None, out=None, swiglu=False, ssq_in=None, ssq_out=None, eps=0.0):
@@ -312,18 +325,18 @@ def linear_rms(x, w, resid=None, out=None, swiglu=False, ssq_in=None, ssq_out=No
     _req(x, "x")
     M, K = x.shape
     N = w.shape[0]
-    assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K
+    assert x.dtype in (torch.bfloat16, torch.float16) and w.dtype == x.dtype and x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K
     n_out = N // 2 if swiglu else N
     if out is None:
         out = torch.empty((M, n_out), dtype=x.dtype, device=x.device)
-    assert out.dtype == torch.bfloat16 and out.stride(1) == 1 and out.shape == (M, n_out)
+    assert out.dtype == x.dtype and out.stride(1) == 1 and out.shape == (M, n_out)
     if resid is not None:
         assert resid.dtype == out.dtype and resid.stride(1) == 1
     if ssq_in is not None:
         assert ssq_in.dtype == torch.float32 and ssq_in.is_contiguous() and ssq_in.shape[1] == 16
     if ssq_out is not None:
         assert ssq_out.dtype == torch.float32 and ssq_out.is_contiguous() and ssq_out.shape[1] == 16 and ssq_out.shape[0] * 16 >= N
-    rc = lib.haff_gemm_bf16_rms(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0), None,
+    rc = _fn(lib, "haff_gemm_bf16_rms", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0), None,
                                 _p(resid), 0 if resid is None else resid.stride(0), M, N, K, ACT_NONE, 0, 1 if swiglu else 0,
                                 _p(ssq_in), 0 if ssq_in is None else ssq_in.shape[0], float(eps), _p(ssq_out), None, _stream())
     check(rc, "haff_gemm_bf16_rms")
@@ -404,6 +417,8 @@ def attention(q, k, v, scale, causal=False, q_pos0=0, relh=None, relw=None, S=0,
         assert relh.dtype == torch.float32 and relh.is_contiguous() and relw.is_contiguous()
     if q.dtype == torch.bfloat16:
         rc = lib.haff_attention_bf16(*args)
+    elif q.dtype == torch.float16:
+        rc = lib.haff_attention_f16(*args)
     else:
         rc = lib.haff_attention_f32(*args)
     check(rc, "haff_attention")
@@ -413,11 +428,12 @@ def attention(q, k, v, scale, causal=False, q_pos0=0, relh=None, relw=None, S=0,
 _BF16_TABLES = {}
 
 
-def _bf16_table(t):
-    key = (t.data_ptr(), tuple(t.shape))
+def _bf16_table(t, dtype=torch.bfloat16):
+    """t rounded to the 16-bit format of the fused rel-pos kernels (bf16, or fp16 in the fp16 mode), once per tensor."""
+    key = (t.data_ptr(), tuple(t.shape), dtype)
     hit = _BF16_TABLES.get(key)
     if hit is None or hit[0] is not t:
-        _BF16_TABLES[key] = (t, t.to(torch.bfloat16).contiguous())
+        _BF16_TABLES[key] = (t, t.to(dtype).contiguous())
     return _BF16_TABLES[key][1]
 
 
@@ -443,7 +459,7 @@ def relpos_tables(q, tab_h, tab_w, S):
 
 def window_attention_supported(q, S):
     """Geometry served by the fused window kernel (haff_window_attention_bf16)."""
-    return q.dtype == torch.bfloat16 and S == 14 and q.shape[3] == 80 and q.shape[2] == S * S
+    return q.dtype in (torch.bfloat16, torch.float16) and S == 14 and q.shape[3] == 80 and q.shape[2] == S * S
 
 
 def window_attention(q, k, v, scale, tab_h, tab_w, S, out=None, grid=0, pad_token=0):
@@ -455,11 +471,11 @@ def window_attention(q, k, v, scale, tab_h, tab_w, S, out=None, grid=0, pad_toke
     _req(q, "q")
     B, H, N, d = q.shape
     assert window_attention_supported(q, S) and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
-    th, tw = _bf16_table(tab_h), _bf16_table(tab_w)
+    th, tw = _bf16_table(tab_h, q.dtype), _bf16_table(tab_w, q.dtype)
     if out is None:
         out = torch.empty((B, N, H * d), dtype=q.dtype, device=q.device)
     o4 = out.view(B, N, H, d).permute(0, 2, 1, 3)
-    rc = lib.haff_window_attention_bf16(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
+    rc = _fn(lib, "haff_window_attention_bf16", q.dtype)(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
                                         k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
                                         v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
                                         out.data_ptr(), o4.stride(0), o4.stride(1), o4.stride(2),
@@ -471,7 +487,7 @@ def window_attention(q, k, v, scale, tab_h, tab_w, S, out=None, grid=0, pad_toke
 
 def global_attention_supported(q, k, v, S):
     """Geometry served by the fused global kernel (haff_global_attention_bf16): ViT-H global blocks, k|v in one row layout."""
-    return (q.dtype == torch.bfloat16 and S == 64 and q.shape[3] == 80 and q.shape[2] == S * S and k.shape[2] == S * S
+    return (q.dtype in (torch.bfloat16, torch.float16) and S == 64 and q.shape[3] == 80 and q.shape[2] == S * S and k.shape[2] == S * S
             and k.stride() == v.stride() and v.data_ptr() >= k.data_ptr()
             and (v.data_ptr() - k.data_ptr()) + k.shape[2] * k.stride(2) * 2 < (1 << 31))
 
@@ -483,11 +499,11 @@ def global_attention(q, k, v, scale, tab_h, tab_w, S, out=None):
     _req(q, "q")
     B, H, N, d = q.shape
     assert global_attention_supported(q, k, v, S) and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
-    th, tw = _bf16_table(tab_h), _bf16_table(tab_w)
+    th, tw = _bf16_table(tab_h, q.dtype), _bf16_table(tab_w, q.dtype)
     if out is None:
         out = torch.empty((B, N, H * d), dtype=q.dtype, device=q.device)
     o4 = out.view(B, N, H, d).permute(0, 2, 1, 3)
-    rc = lib.haff_global_attention_bf16(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
+    rc = _fn(lib, "haff_global_attention_bf16", q.dtype)(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
                                         k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
                                         v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
                                         out.data_ptr(), o4.stride(0), o4.stride(1), o4.stride(2),
@@ -497,7 +513,7 @@ def global_attention(q, k, v, scale, tab_h, tab_w, S, out=None):
 
 
 def _norm_dt(x, out):
-    """dtype code of the norm kernels: 0 bf16, 1 f32, 2 = f32 rows in, bf16 rows out (fp32 residual stream -> bf16 product)."""
+    """dtype code of the norm kernels: 0 bf16, 1 f32, 3 f16, 2 = f32 rows in, bf16 rows out (fp32 residual stream -> bf16 product)."""
     if x.dtype == torch.float32 and out.dtype == torch.bfloat16:
         return 2
     assert out.dtype == x.dtype, (x.dtype, out.dtype)
@@ -620,7 +636,8 @@ def attention_decode_rows(q, k, v, scale, nk_rows, out=None):
     assert nk_rows.dtype == torch.int32 and nk_rows.is_cuda and nk_rows.numel() == B
     if out is None:
         out = torch.empty((B, 1, H * d), dtype=q.dtype, device=q.device)
-    fn = lib.haff_attention_decode_rows_bf16 if q.dtype == torch.bfloat16 else lib.haff_attention_decode_rows_f32
+    fn = {torch.bfloat16: lib.haff_attention_decode_rows_bf16, torch.float16: lib.haff_attention_decode_rows_f16}.get(
+        q.dtype, lib.haff_attention_decode_rows_f32)
     rc = fn(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
             v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), out.data_ptr(), H * d, d, B, H, k.shape[2], d, float(scale),
             nk_rows.data_ptr(), _stream())
@@ -629,17 +646,18 @@ def attention_decode_rows(q, k, v, scale, nk_rows, out=None):
 
 
 def decode_attention_rope(qkv, kcache, vcache, cos_sin, H, d, scale, nk_rows):
-    """bf16 decode position with RoPE + cache append fused: qkv [B, 3*H*d] raw -> [B, 1, H*d]; nk_rows int32 [B] = new pos + 1."""
+    """bf16 / fp16 decode position with RoPE + cache append fused: qkv [B, 3*H*d] raw -> [B, 1, H*d]; nk_rows int32 [B] = new pos + 1."""
     lib = load_library()
     _req(qkv, "qkv")
     B = qkv.shape[0]
-    assert qkv.dtype == torch.bfloat16 and qkv.stride(1) == 1 and kcache.is_contiguous() and vcache.is_contiguous()
+    assert _half(qkv) and qkv.stride(1) == 1 and kcache.is_contiguous() and vcache.is_contiguous()
+    assert kcache.dtype == qkv.dtype and vcache.dtype == qkv.dtype
     assert nk_rows.dtype == torch.int32 and nk_rows.is_cuda and nk_rows.numel() == B and cos_sin.dtype == torch.float32
     out = torch.empty((B, 1, H * d), dtype=qkv.dtype, device=qkv.device)
-    rc = lib.haff_decode_attention_rope_rows_bf16(qkv.data_ptr(), qkv.stride(0), kcache.data_ptr(), vcache.data_ptr(),
-                                                  cos_sin.data_ptr(), out.data_ptr(), B, H, d, kcache.shape[1], float(scale),
-                                                  nk_rows.data_ptr(), _stream())
-    check(rc, "haff_decode_attention_rope_rows_bf16")
+    fn = lib.haff_decode_attention_rope_rows_bf16 if qkv.dtype == torch.bfloat16 else lib.haff_decode_attention_rope_rows_f16
+    rc = fn(qkv.data_ptr(), qkv.stride(0), kcache.data_ptr(), vcache.data_ptr(), cos_sin.data_ptr(), out.data_ptr(), B, H, d,
+            kcache.shape[1], float(scale), nk_rows.data_ptr(), _stream())
+    check(rc, "haff_decode_attention_rope_rows")
     return out
 
 

@@ -42,8 +42,8 @@ class SamEncoderHip:
         # cfg.fold_norms = True / False forces it
         fold = getattr(cfg, "fold_norms", None)
         if fold is None:
-            fold = dtype == torch.bfloat16 and s.embed_dim == 1280 and s.window == 14
-        fold = bool(fold) and dtype == torch.bfloat16
+            fold = dtype in (torch.bfloat16, torch.float16) and s.embed_dim == 1280 and s.window == 14
+        fold = bool(fold) and dtype in (torch.bfloat16, torch.float16)   # (the fp16 mode follows the bf16 branches)
         for i in range(s.depth):
             B = f"{E}.blocks.{i}"
             is_global = i in s.global_idx
@@ -60,8 +60,8 @@ class SamEncoderHip:
                 "w2": sd[B + ".mlp.lin2.weight"].to(dev, dtype).contiguous(), "b2": _f32(sd[B + ".mlp.lin2.bias"], dev),
             }
             if fold:
-                blk["wqkv_f"], blk["sqkv"], blk["bqkv_f"] = ops.fold_norm(blk["wqkv"], blk["n1w"], blk["n1b"], blk["bqkv"])
-                blk["w1_f"], blk["s1"], blk["b1_f"] = ops.fold_norm(blk["w1"], blk["n2w"], blk["n2b"], blk["b1"])
+                blk["wqkv_f"], blk["sqkv"], blk["bqkv_f"] = ops.fold_norm(blk["wqkv"], blk["n1w"], blk["n1b"], blk["bqkv"], dtype)
+                blk["w1_f"], blk["s1"], blk["b1_f"] = ops.fold_norm(blk["w1"], blk["n2w"], blk["n2b"], blk["b1"], dtype)
             self.blocks.append(blk)
         self.w_neck0 = sd[E + ".neck.0.weight"].reshape(s.out_chans, C).to(dev, dtype).contiguous()
         self.neck1 = (_f32(sd[E + ".neck.1.weight"], dev), _f32(sd[E + ".neck.1.bias"], dev))
@@ -93,7 +93,7 @@ class SamEncoderHip:
         # >= 2 frames per pass). False: round 5's unfused form everywhere (A/B).
         self.fused_fp32_stream = True
         # the neck on the f32-input MFMA path (bf16 mode): see forward_rows
-        self.neck_f32 = False
+        self.neck_f32 = dtype == torch.float16   # fp16: always (the reference's own overflow guard, image_encoder.py:118-124)
         self._neck32 = None
         self._pos32 = None
 
@@ -198,7 +198,7 @@ class SamEncoderHip:
             x = ops.linear(rows, self.w_patch, bias=self.b_patch)
             x = ops.add_bcast(x, self.pos, mod=N, out=x)
         scale = hd ** -0.5
-        compact_ok = self.compact_windows and self.dtype == bf and s.window == 14 and hd == 80
+        compact_ok = self.compact_windows and self.dtype in (bf, torch.float16) and s.window == 14 and hd == 80
         # folded norms: {mean, rstd} of the rows of x, handed from the product that WROTE x (proj / lin2 epilogues sum their own
         # results: ops.linear_rowstats) to the product that normalises it; None = take a statistics pass (ops.row_stats)
         carry = self.fold_norms and self.producer_stats and \
@@ -273,7 +273,7 @@ class SamEncoderHip:
             if taps is not None:
                 taps[f"block{i}"] = x.float().view(B, g, g, C).cpu()
         o = None if out is None else out.view(B * N, s.out_chans)
-        if self.neck_f32 and self.dtype == bf:
+        if self.neck_f32 and self.dtype in (bf, torch.float16):
             # the neck (image_encoder.py:88-107: 1x1 conv, LayerNorm2d, 3x3 conv, LayerNorm2d) on the f32-input MFMA path: its four
             # tensors are the last roundings in front of the embedding and nothing averages them out afterwards; 7.5 GFLOP per frame
             if self._neck32 is None:
@@ -283,7 +283,7 @@ class SamEncoderHip:
             cols = ops.im2col3x3(y.view(B, g, g, s.out_chans))
             y = ops.linear(cols, self._neck32[1])
             if not self.emb_f32:
-                return ops.layernorm(y, self.neck3[0], self.neck3[1], 1e-6, out=o, out_dtype=bf).view(B, N, s.out_chans)
+                return ops.layernorm(y, self.neck3[0], self.neck3[1], 1e-6, out=o, out_dtype=self.dtype).view(B, N, s.out_chans)
             return ops.layernorm(y, self.neck3[0], self.neck3[1], 1e-6, out=o).view(B, N, s.out_chans)
         y = ops.linear(x16 if fused32 else (x.to(bf) if s32 else x), self.w_neck0)
         y = ops.layernorm(y, self.neck1[0], self.neck1[1], 1e-6)

@@ -12,8 +12,11 @@
  *     the one piece of state the library keeps is haff_gemm_stream_cap's table, keyed by stream and guarded by a mutex
  *     (scheduling only, results never depend on it) — host threads that enqueue on different streams do not interact.
  *   - return value: 0 ok, -1 bad argument, -2 unsupported shape, -3 launch error. No exceptions cross the ABI.
- *   - dtype codes: 0 = bf16 (raw 16-bit payload), 1 = f32. bf16 = throughput mode (bf16 MFMA, fp32 accumulate,
- *     fp32 softmax/norm statistics); f32 = parity mode (every op in fp32, for the 1e-3 mask-logit criterion).
+ *   - dtype codes: 0 = bf16 (raw 16-bit payload), 1 = f32, 3 = f16 (IEEE binary16). bf16 = throughput mode (bf16 MFMA,
+ *     fp32 accumulate, fp32 softmax/norm statistics); f32 = parity mode (every op in fp32, for the 1e-3 mask-logit criterion);
+ *     f16 = the inference mode of the reference's `--precision fp16` (f16 MFMA, otherwise as bf16). Code 2 is the norms'
+ *     "f32 x -> bf16 y". Entry points named *_bf16 take no dtype; those the fp16 path needs have *_f16 siblings with the
+ *     same arguments and contracts (one kernel template, two instances).
  *   - strides/leading dimensions are in ELEMENTS.
  *   - activation codes: 0 none, 1 GELU(erf), 2 quick-GELU (x*sigmoid(1.702x)), 3 ReLU, 4 SiLU.
  */
@@ -47,6 +50,36 @@ int haff_gemm_bf16_cfg(const void* A, long lda, const void* W, long ldw, void* C
 int haff_gemm_bf16_ws(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                       const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
                       int swiglu, void* workspace, long workspace_bytes, void* stream);
+/* fp16 instances of haff_gemm_bf16 / _cfg / _ws: A, W and a 16-bit C / resid are f16 (v_mfma_f32_16x16x32_f16, fp32 accumulate) */
+int haff_gemm_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                  const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
+                  int swiglu, void* stream);
+int haff_gemm_f16_cfg(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                      const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
+                      int swiglu, int tile_cfg, void* stream);
+int haff_gemm_f16_ws(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                     const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
+                     int swiglu, void* workspace, long workspace_bytes, void* stream);
+/* fp16 instances of the fused products below (_rms, _gather, _qkv_rope, _rowstats, _ln, _heads): same arguments and contracts, f16
+ * operands / 16-bit outputs / caches / residuals; statistics, biases and RoPE tables stay f32 */
+int haff_gemm_f16_rms(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                      const void* resid, long ldr, int M, int N, int K, int act, int out_f32, int swiglu,
+                      const float* ssq_in, int ssq_n, float eps, float* ssq_out, int* n_parts_out, void* stream);
+int haff_gemm_f16_gather(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw, void* C,
+                         long ldc, const float* bias, const void* resid, long ldr, const int* row_map, int M, int N,
+                         int K, int act, int out_f32, int swiglu, void* stream);
+int haff_gemm_f16_qkv_rope(const void* A, long lda, const void* Wp, long ldw, void* q_out, long ldq, void* kcache,
+                           void* vcache, const float* cos_sin, int B, int T, int Tmax, int pos0, int H, int d, int K,
+                           void* stream);
+int haff_gemm_f16_rowstats(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw, void* C,
+                           long ldc, const float* bias, const void* resid, long ldr, int M, int N, int K,
+                           float* stat_out, void* stream);
+int haff_gemm_f16_ln(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
+                     const void* resid, long ldr, const int* row_map, const float* ln_stats, const float* ln_colsum,
+                     int M, int N, int K, int act, int out_f32, int swiglu, void* stream);
+int haff_gemm_f16_heads(const void* A, long lda, const void* W, long ldw, void* C, const float* bias, const int* row_map,
+                        const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads, long part_stride,
+                        long head_stride, void* stream);
 /* Decode-sized product (M <= 16; with ssq_in: M <= 8, ssq_n <= 512, ssq_in 16-B aligned; K % 128 == 0) that carries Llama's RMSNorm between products without a norm kernel
  * (transformers LlamaDecoderLayer as reached from 2Haff/model/llava/model/language_model/llava_llama.py:93-102:
  * input_layernorm -> q/k/v_proj, post_attention_layernorm -> gate/up_proj). ssq_in != NULL: row m of A . W^T is scaled by
@@ -164,6 +197,11 @@ int haff_attention_bf16(const void* q, long q_sb, long q_sh, long q_st, const vo
                         const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb, long o_sh, long o_st,
                         int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
                         const float* relh, const float* relw, int S, void* stream);
+/* fp16 instance of haff_attention_bf16 (q/k/v/o f16; the probabilities enter the P.V product as f16) */
+int haff_attention_f16(const void* q, long q_sb, long q_sh, long q_st, const void* k, long k_sb, long k_sh, long k_st,
+                       const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb, long o_sh, long o_st,
+                       int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
+                       const float* relh, const float* relw, int S, void* stream);
 int haff_attention_f32(const float* q, long q_sb, long q_sh, long q_st, const float* k, long k_sb, long k_sh, long k_st,
                        const float* v, long v_sb, long v_sh, long v_st, float* o, long o_sb, long o_sh, long o_st,
                        int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
@@ -175,6 +213,9 @@ int haff_attention_f32(const float* q, long q_sb, long q_sh, long q_st, const fl
 int haff_attention_decode_rows_bf16(const void* q, long q_sb, long q_sh, const void* k, long k_sb, long k_sh, long k_st,
                                     const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb, long o_sh, int B,
                                     int H, int Nk, int d, float scale, const int* nk_rows, void* stream);
+int haff_attention_decode_rows_f16(const void* q, long q_sb, long q_sh, const void* k, long k_sb, long k_sh, long k_st,
+                                   const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb, long o_sh, int B,
+                                   int H, int Nk, int d, float scale, const int* nk_rows, void* stream);
 int haff_attention_decode_rows_f32(const float* q, long q_sb, long q_sh, const float* k, long k_sb, long k_sh, long k_st,
                                    const float* v, long v_sb, long v_sh, long v_st, float* o, long o_sb, long o_sh, int B,
                                    int H, int Nk, int d, float scale, const int* nk_rows, void* stream);
@@ -184,6 +225,8 @@ int haff_attention_decode_rows_f32(const float* q, long q_sb, long q_sh, const f
  * (DEVICE int32 [B]); out [B][H*d]; d == 128. Results are bit-identical to the two-kernel path. */
 int haff_decode_attention_rope_rows_bf16(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, void* out,
                                          int B, int H, int d, int Tmax, float scale, const int* nk_rows, void* stream);
+int haff_decode_attention_rope_rows_f16(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, void* out,
+                                        int B, int H, int d, int Tmax, float scale, const int* nk_rows, void* stream);
 /* decomposed rel-pos terms (image_encoder.py:376-384, from the UNSCALED q, :244-248):
  * relh[bh][q][kh] = q . Rh[qh - kh + S - 1], relw[bh][q][kw] = q . Rw[qw - kw + S - 1]; N = S*S queries.
  * tab_*: [2S-1][d] (f32 for the generic entry, bf16 for the MFMA entry). */
@@ -253,6 +296,12 @@ int haff_window_attention_bf16(const void* q, long q_sb, long q_sh, long q_st, c
                                long o_sh, long o_st, int n_windows, int H, int S, int d, float scale,
                                const void* tab_h, const void* tab_w, int grid_h, int grid_w, long pad_token,
                                void* stream);
+/* fp16 instance: q / k / v / o and tab_h / tab_w f16 */
+int haff_window_attention_f16(const void* q, long q_sb, long q_sh, long q_st, const void* k, long k_sb, long k_sh,
+                              long k_st, const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb,
+                              long o_sh, long o_st, int n_windows, int H, int S, int d, float scale,
+                              const void* tab_h, const void* tab_w, int grid_h, int grid_w, long pad_token,
+                              void* stream);
 
 /* fused SAM GLOBAL attention (the 4 global ViT-H blocks, 64 x 64 tokens): Attention.forward (image_encoder.py:235-260) +
  * add_decomposed_rel_pos (:354-392), the rel-pos terms computed in the kernel's prologue from the parameter tables (replaces
@@ -264,18 +313,23 @@ int haff_global_attention_bf16(const void* q, long q_sb, long q_sh, long q_st, c
                                long k_st, const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb,
                                long o_sh, long o_st, int B, int H, int S, int d, float scale,
                                const void* tab_h, const void* tab_w, void* stream);
+/* fp16 instance: q / k / v / o and tab_h / tab_w f16 */
+int haff_global_attention_f16(const void* q, long q_sb, long q_sh, long q_st, const void* k, long k_sb, long k_sh,
+                              long k_st, const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb,
+                              long o_sh, long o_st, int B, int H, int S, int d, float scale,
+                              const void* tab_h, const void* tab_w, void* stream);
 
 /* ---- row norms ----------------------------------------------------------------------------------------------
  * haff_layernorm: nn.LayerNorm / LayerNorm2d on channels-last rows (common.py:31-43; image_encoder.py:179,191;
  * transformer.py:134-144; CLIP layer norms). in_map (int32[rows], may be null): out row i normalises in row
  * in_map[i]; negative = zero row (window_partition's zero pad AFTER norm1, image_encoder.py:179-183,276-288).
  * haff_rmsnorm: LlamaRMSNorm (fp32 variance). w, b: f32[C]. C % 8 == 0, C <= 8192.
- * dtype: 0 = bf16 rows, 1 = f32 rows, 2 = f32 x -> bf16 y (an fp32 residual stream feeding a bf16 product). */
+ * dtype: 0 = bf16 rows, 1 = f32 rows, 2 = f32 x -> bf16 y (an fp32 residual stream feeding a bf16 product), 3 = f16 rows. */
 int haff_layernorm(const void* x, long ldx, void* y, long ldy, const float* w, const float* b, const int* in_map,
                    int rows, int C, float eps, int dtype, void* stream);
 int haff_rmsnorm(const void* x, long ldx, void* y, long ldy, const float* w, int rows, int C, float eps, int dtype,
                  void* stream);
-/* per-row {mean, rstd} only (rms != 0: {0, rsqrt(mean(x^2)+eps)}): stats f32 [rows][2]; dtype 0 = bf16, 1 = f32. */
+/* per-row {mean, rstd} only (rms != 0: {0, rsqrt(mean(x^2)+eps)}): stats f32 [rows][2]; dtype 0 = bf16, 1 = f32, 3 = f16. */
 int haff_row_stats(const void* x, long ldx, float* stats, int rows, int C, float eps, int rms, int dtype, void* stream);
 
 /* stats[rows][2] = {mean, rstd} from haff_gemm_bf16_rowstats' partials f32 [rows][slots][2] (slots added in order); C = row length. */
