@@ -535,6 +535,10 @@ constexpr int PP_NST = 4;
 constexpr int PP_RSTR = KT + 1;                  // rel_h row stride in floats (odd: 16 query lanes -> 16 banks)
 constexpr int PP_LDS = PP_NST * (PP_KBYTES + PP_VBYTES) + PPQ * PP_RSTR * 4;   // stages, rel_h
 constexpr float PP_LAZY = 40.f;                  // log2 units a score may exceed the softmax reference before the reference is moved
+// ... with fp16 probabilities: p = 2^(s - m_run) is packed to f16 for the P.V and row-sum MFMAs, whose largest finite value is
+// 65504 < 2^16, so the reference moves once a score is more than 15 above it (p <= 2^15). 40 turned p into inf and the output
+// into NaN wherever a later key tile scored more than 16 log2 units above the first one (rel-pos biases of that size occur).
+constexpr float PP_LAZY_F16 = 15.f;
 static_assert(PP_KBYTES % 1024 == 0 && PP_VBYTES % 1024 == 0, "whole DMA instructions per tile");
 static_assert(PP_LDS <= 160 * 1024, "LDS");
 
@@ -1013,7 +1017,7 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
           mx = fmaxf(fmaxf(mx, sacc[t][qt][0]), sacc[t][qt][1]);
           mx = fmaxf(fmaxf(mx, sacc[t][qt][2]), sacc[t][qt][3]);
         }
-        if (__any(mx > PP_LAZY)) move_reference();   // rare (never on SAM's logits)
+        if (__any(mx > (F16 ? PP_LAZY_F16 : PP_LAZY))) move_reference();   // rare (never on SAM's logits in bf16)
         exp_pack();
       }
 #endif
