@@ -511,11 +511,12 @@ int launch_attn(const AttnArgs& p, hipStream_t s) {
 // The softmax denominator comes out of one extra MFMA per (k-step, q-tile) against a register fragment of ones (the same
 // bf16-rounded probabilities the numerator sums; attn_fwd_kernel's LSUM did this through a ones-column staged in LDS).
 //
-// Measured (32 frames x 16 heads, tools/attn_variant.py, profiles/r3_attn_pp_ablate.txt): 3.41 ms against 4.18 ms for
-// attn_fwd_kernel on the same box (0.81x; 806 vs 657 TFLOP/s of useful work). What bounds it now is the SIMD's single vector
-// issue port, which the two co-resident waves share: the MFMA slot's 48 MFMAs take ~1150 cycles, not 768, because the
-// partner's exponentials / conversions / DMA requests are issued between them (an 8-cycle v_exp_f32 in flight delays the next
-// MFMA; s_setprio cannot preempt it); without the DMA requests the launch takes 2.90 ms, without the exponentials 2.87 ms.
+// Measured (32 frames x 16 heads, profiles/r3_attn_pp_ablate.txt; tools/attn_variant.py and the ablation builds it timed
+// were removed after 58cf410): 3.41 ms against 4.18 ms for attn_fwd_kernel on the same box (0.81x; 806 vs 657 TFLOP/s of
+// useful work). What bounds it now is the SIMD's single vector issue port, which the two co-resident waves share: the MFMA
+// slot's 48 MFMAs take ~1150 cycles, not 768, because the partner's exponentials / conversions / DMA requests are issued
+// between them (an 8-cycle v_exp_f32 in flight delays the next MFMA; s_setprio cannot preempt it); without the DMA requests
+// the launch takes 2.90 ms, without the exponentials 2.87 ms.
 // Ten forms were timed on the way (header of profiles/r3_attn_pp_ablate.txt): reading next slot's fragments in the VALU slot
 // made THAT slot the long one (24 LDS reads against the other group's: 3.9-4.1 ms); a per-tile cross-lane maximum with an
 // eager rescale cost 14 % (rescales fired on 60 % of the tiles of random data); joined rescale arms make hipcc copy all 72
@@ -541,15 +542,6 @@ constexpr float PP_LAZY = 40.f;                  // log2 units a score may excee
 constexpr float PP_LAZY_F16 = 15.f;
 static_assert(PP_KBYTES % 1024 == 0 && PP_VBYTES % 1024 == 0, "whole DMA instructions per tile");
 static_assert(PP_LDS <= 160 * 1024, "LDS");
-
-#if defined(HAFF_TUNING) && defined(HAFF_PP_TRACE)
-// cycle stamps of waves 0 and 4 of the first 256 workgroups, KV tiles 16..19: [wg][group][tile][8]
-__device__ unsigned long long haff_pp_trace_buf[256 * 2 * 4 * 8];
-#define PP_STAMP(i) do { if ((tid & 255) == 0 && blockIdx.x < 256 && kt >= 16 && kt < 20) \
-    haff_pp_trace_buf[((blockIdx.x * 2 + grp) * 4 + (kt - 16)) * 8 + (i)] = clock64(); } while (0)
-#else
-#define PP_STAMP(i) do {} while (0)
-#endif
 
 // FUSED_REL: rel_h / rel_w do not arrive as fp32 [B*H][N][64] tables (1.07 GB written by haff_relpos_tables and read back
 // per 32-frame launch): the prologue computes them for the workgroup's 256 queries from the raw q rows and the two bf16
@@ -806,9 +798,6 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
   // LDS -> fragment loads. Stage bases are compile-time, so each is one ds_read with an immediate offset.
   auto load_v = [&](auto stage, auto ks_tag, bf16x8 (&vf)[ND]) {   // V^T fragments of k-step ks (keys 32ks .. 32ks+31)
     constexpr int ST = decltype(stage)::value, ks = decltype(ks_tag)::value;
-#if defined(HAFF_TUNING) && defined(HAFF_PP_NOVREAD)   // counter / timing experiment: the V^T fragment reads are left out (wrong results)
-    if (ST >= 0) return;
-#endif
     const unsigned char* v0 = smem_raw + PP_NST * PP_KBYTES + ST * PP_VBYTES + v_lane + (32 * ks) * PP_VSTR;
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) {
@@ -819,9 +808,6 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
   };
   auto load_k = [&](auto stage, auto kd_tag, bf16x8 (&kf)[4]) {    // K fragments of head-dim step kd, the 4 key tiles
     constexpr int ST = decltype(stage)::value, kd = decltype(kd_tag)::value;
-#if defined(HAFF_TUNING) && defined(HAFF_PP_NOKREAD)   // counter / timing experiment: the K fragment reads are left out (wrong results)
-    if (ST >= 0) return;
-#endif
     const unsigned char* k0 = smem_raw + ST * PP_KBYTES + (kd < 2 ? k_lane01 + kd * 64 : k_lane2);
 #pragma unroll
     for (int t = 0; t < 4; ++t) kf[t] = *reinterpret_cast<const bf16x8*>(k0 + 16 * t * PP_KSTR);
@@ -854,10 +840,6 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
   // slot X-3 and waits at the end of its VALU slot X-1 (two newer batches in flight). The stages those requests overwrite
   // (K[X-3], V[X-4]) were last read two or more barriers earlier by both groups.
   bf16x8 vf0[ND], vf1[ND], kf0[4];
-#if defined(HAFF_TUNING) && (defined(HAFF_PP_NOVREAD) || defined(HAFF_PP_NOKREAD))
-  for (int i = 0; i < ND; ++i) { vf0[i] = ones; vf1[i] = ones; }
-  for (int i = 0; i < 4; ++i) kf0[i] = ones;
-#endif
   f32x4 sacc[4][2];
   auto batch_cnt = [&](int x) { return (x + 1 < nkt ? n_kins : 0) + (x < nkt ? n_vins : 0); };
   auto wait_vm = [&](int n) {   // wave-uniform n: at most n of my requests still in flight
@@ -884,14 +866,9 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
     constexpr int ST = decltype(stage)::value;
     constexpr bool FIRST = decltype(first_tag)::value;
     using PrevStage = std::integral_constant<int, (ST + PP_NST - 1) % PP_NST>;
-    PP_STAMP(0);
     // ================= MFMA slot =================
     bf16x8 kf1[4], kf2[4];
-#if defined(HAFF_TUNING) && defined(HAFF_PP_NOKREAD)
-    for (int i = 0; i < 4; ++i) { kf1[i] = ones; kf2[i] = ones; }
-#endif
     __builtin_amdgcn_s_setprio(1);
-#if !(defined(HAFF_TUNING) && defined(HAFF_PP_NOMFMA))
     auto qk = [&](auto kd_tag, const bf16x8 (&kf)[4]) {   // S^T += K . Q^T over head-dim step kd
       constexpr int kd = decltype(kd_tag)::value;
 #pragma unroll
@@ -932,23 +909,16 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
       qk(I1{}, kf1);
       qk(I2{}, kf2);
     }
-#endif
     __builtin_amdgcn_s_setprio(0);
-    PP_STAMP(1);
     // my LDS reads are done (the stages go back to the DMA). Group 0: batch kt has landed (batch kt+1 may be in flight).
     if (grp == 0) wait_vm(FIRST ? 0 : batch_cnt(kt + 1));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    PP_STAMP(2);
     fence_barrier();
-    PP_STAMP(3);
     // ================= VALU slot =================
     // (the two small LDS reads of this slot go first: LDS returns in order, a value read behind the 24 fragment reads
     // below would be waited for behind all of them)
-#if !(defined(HAFF_TUNING) && defined(HAFF_PP_NODMA))
     if (grp == 0) issue(kt + 3, kt + 2);
     else issue(kt + 4, kt + 3);
-#endif
-    PP_STAMP(4);
     // fragments for the MFMA slot behind the next barrier — V[kt] whole, K[kt+1] kd0 — requested NOW: they land under the
     // softmax arithmetic below (issued behind it, this wave would sit in the issue stage until most of them had returned:
     // 14 KB per wave, four waves at once, against the other group's reads)
@@ -966,11 +936,7 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const float sv = sacc[2 * ks + (j >> 2)][qt][j & 3];
-#if defined(HAFF_TUNING) && defined(HAFF_PP_NOSOFTMAX)
-            e[j] = sv;
-#else
             e[j] = __builtin_amdgcn_exp2f(sv);
-#endif
           }
           uint4 u;
           u.x = E::pack2(e[0], e[1]); u.y = E::pack2(e[2], e[3]);
@@ -1003,9 +969,6 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) sacc[t][qt][r] -= delta;
       };
-#if defined(HAFF_TUNING) && defined(HAFF_PP_NOSOFTMAX)
-      exp_pack();
-#else
       if (FIRST) {
         move_reference();
         exp_pack();
@@ -1020,17 +983,12 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
         if (__any(mx > (F16 ? PP_LAZY_F16 : PP_LAZY))) move_reference();   // rare (never on SAM's logits in bf16)
         exp_pack();
       }
-#endif
     }
     phase();
-#if !(defined(HAFF_TUNING) && defined(HAFF_PP_NOMFMA))
     load_v(stage, I0{}, vf0);   // the first fragments the next MFMA slot consumes; nothing behind them in this slot reads LDS
-#endif
-    PP_STAMP(5);
     // group 1: batch kt+1 has landed (batches kt+2, kt+3 may be in flight) — group 0 reads it right behind this barrier
     if (grp == 1) wait_vm((kt >= 1 ? batch_cnt(kt + 2) : 0) + batch_cnt(kt + 3));
     fence_barrier();
-    PP_STAMP(6);
   };
 
   using S0 = std::integral_constant<int, 0>;
@@ -1071,12 +1029,6 @@ __global__ __launch_bounds__(512, 1) void attn_global_pp_kernel(AttnArgs p) {
     }
   }
 }
-
-#if defined(HAFF_TUNING) && defined(HAFF_PP_TRACE)
-extern "C" int haff_pp_trace_read(void* dst, int n) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(haff_pp_trace_buf), (size_t)n * 8) == hipSuccess ? 0 : -1;
-}
-#endif
 
 // host-side admission for attn_global_pp_kernel: whole tiles, the fused q|k|v row layout (V a fixed, non-negative
 // distance behind K, same strides), 32-bit source offsets; fused_rel: rel-pos from the parameter tables in the prologue
@@ -1321,9 +1273,6 @@ static int attention_bf16_impl(const void* q, long q_sb, long q_sh, long q_st,
     }
     if (dp == 64) return mode == 2 ? launch_attn<64, 2, false, 64 / 16, false, false, F16>(p, s) : launch_attn<64, 1, false, 64 / 16, false, false, F16>(p, s);
     if (dp == 96 && mode == 2 && d == 80) {   // SAM global blocks
-#ifdef HAFF_TUNING
-      if (getenv("HAFF_ATTN_NO_PP")) return launch_attn<96, 2, false, 6, true, true, F16>(p, s);
-#endif
       if (attn_global_pp_ok(p, false)) return launch_attn_global_pp<false, F16>(p, s);
       if ((Nq % 128) == 0 && (Nk % KT) == 0 && !nk_rows) return launch_attn<96, 2, false, 6, true, true, F16>(p, s);
       return launch_attn<96, 2, false, 6, true, false, F16>(p, s);

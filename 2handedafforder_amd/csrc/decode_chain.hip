@@ -22,7 +22,8 @@
 //    agent-scope add on one word made 768 arrivals 9 us, a tenth of a layer;
 //  * o_proj / down_proj split K over TWO workgroups per 16-row tile: the dispatcher does not deal a stage's workgroups one per CU
 //    (down_proj's 256 landed on 210 CUs, 46 of them carrying two) and a CU takes in ~22 GB/s whatever runs on it, so the stage ran
-//    32 us for 90 MB; 512 half-K workgroups land two per CU on every CU (tools/chain_trace.py, -DCH_PLACE): 21 us;
+//    32 us for 90 MB; 512 half-K workgroups land two per CU on every CU (placement traces of an experiment build removed after
+//    58cf410): 21 us;
 //  * the counters are zeroed WRITE-THROUGH by a kernel in front of the launch: behind a hipMemsetAsync node the chained step was
 //    bit-repeatable eagerly and a different result on every hipGraph replay (tools/chain_stress.py) — and 25 % faster, because the
 //    waits saw the previous replay's counts and let stages start early.
@@ -57,20 +58,9 @@ constexpr int CH_STAGES = 5;
 constexpr int CH_D = 128;        // head dim
 constexpr int CH_KW = 4;         // waves per workgroup: K quarters of a product, key quarters of a head
 constexpr int CH_U = 8;          // k-steps per register set (skinny_batch(1, 1) == skinny_batch(2, 1) == 8)
-// experiment knobs (tools/build_chain_variant.sh -DCH_...): the product build takes the defaults below
-#ifndef CH_PRE_TRIPS
-#define CH_PRE_TRIPS 4
-#endif
-#ifndef CH_SLEEP
-#define CH_SLEEP 16
-#endif
-#ifndef CH_W_NT
-#define CH_W_NT 0               // 1: non-temporal loads on the weight stream
-#endif
-#ifndef CH_U_GU
-#define CH_U_GU 8               // k-steps per register set of the gate|up stage (two weight tiles per workgroup)
-#endif
-constexpr int CH_PRE = CH_PRE_TRIPS;        // attention: trips of 16 key groups (64 keys each) whose K / V rows are requested BEFORE the wait (128 registers at 4 trips: 256 keys)
+constexpr int CH_U_GU = 8;       // k-steps per register set of the gate|up stage (two weight tiles per workgroup)
+constexpr int CH_SLEEP = 16;     // s_sleep argument between two polls of an arrival counter
+constexpr int CH_PRE = 4;        // attention: trips of 16 key groups (64 keys each) whose K / V rows are requested BEFORE the wait (128 registers at 4 trips: 256 keys)
 constexpr int CH_SPIN_LIMIT = 400000;
 constexpr float CH_LOG2E = 1.4426950408889634f;
 
@@ -100,42 +90,12 @@ struct ChainArgs {
 // completes a shard adds to every replica, 8 lanes of one instruction; a waiting workgroup polls ONE replica, so the pollers of a
 // stage spread over 8 lines). Every word on a 128-byte line of its own.
 constexpr int CH_SHARDS = 8;
-#ifndef CH_LINE_WORDS
-#define CH_LINE_WORDS 32
-#endif
-constexpr int CH_LINE = CH_LINE_WORDS;                       // words per counter line (32 = one 128-byte line each)
+constexpr int CH_LINE = 32;                                  // words per counter line (32 = one 128-byte line each)
 constexpr int CH_STAGE_WORDS = 2 * CH_SHARDS * CH_LINE;      // 8 shard lines + 8 replica lines
-
-#ifdef CH_PLACE   // experiment builds only: where layer 2's workgroups ran (no atomics: the timing is the product build's)
-__device__ unsigned ch_place_buf[CH_STAGES][1024];   // (xcc << 16) | HW_ID[15:0] of wave 0
-__device__ unsigned long long ch_place_t[CH_STAGES][1024];
-extern "C" int haff_decode_chain_place_read(unsigned* host, unsigned long long* t) {
-  if (t && hipMemcpyFromSymbol(t, HIP_SYMBOL(ch_place_t), sizeof(unsigned long long) * CH_STAGES * 1024) != hipSuccess) return 1;
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(ch_place_buf), sizeof(unsigned) * CH_STAGES * 1024) == hipSuccess ? 0 : 1;
-}
-#endif
-#ifdef CH_TRACE   // experiment builds only: per (layer, stage) {first start, first wait satisfied, last wait satisfied, last end} (100 MHz clock)
-__device__ unsigned long long ch_trace_buf[CH_MAXL * CH_STAGES][4];
-#define CH_TRACE_MIN(slot, k) do { if (threadIdx.x == 0 && (blockIdx.x & 15) == 0) atomicMin(&ch_trace_buf[slot][k], (unsigned long long)wall_clock64()); } while (0)
-#define CH_TRACE_MAX(slot, k) do { if (threadIdx.x == 0 && (blockIdx.x & 15) == 0) atomicMax(&ch_trace_buf[slot][k], (unsigned long long)wall_clock64()); } while (0)
-extern "C" int haff_decode_chain_trace_read(unsigned long long* host, int reset) {
-  if (host && hipMemcpyFromSymbol(host, HIP_SYMBOL(ch_trace_buf), sizeof(unsigned long long) * CH_MAXL * CH_STAGES * 4) != hipSuccess) return 1;
-  if (reset) {
-    static unsigned long long init[CH_MAXL * CH_STAGES][4];
-    for (int i = 0; i < CH_MAXL * CH_STAGES; ++i) { init[i][0] = ~0ull; init[i][1] = ~0ull; init[i][2] = 0; init[i][3] = 0; }
-    if (hipMemcpyToSymbol(HIP_SYMBOL(ch_trace_buf), init, sizeof(init)) != hipSuccess) return 1;
-  }
-  return 0;
-}
-#else
-#define CH_TRACE_MIN(slot, k) do {} while (0)
-#define CH_TRACE_MAX(slot, k) do {} while (0)
-#endif
 
 // nb_dep: workgroups of the stage waited for (its non-empty shards: min(nb_dep, 8) — the q|k|v / attention stages of a narrow model
 // have fewer workgroups than shards)
 __device__ __forceinline__ void chain_wait(unsigned* sync, int idx, int replica, unsigned* err, int nb_dep) {
-  CH_TRACE_MIN(idx + 1, 0);
   if (idx < 0) return;
   const unsigned full = (unsigned)min(nb_dep, CH_SHARDS);
   if (threadIdx.x == 0) {
@@ -148,8 +108,6 @@ __device__ __forceinline__ void chain_wait(unsigned* sync, int idx, int replica,
       if (spins > CH_SPIN_LIMIT) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
     }
   }
-  CH_TRACE_MIN(idx + 1, 1);
-  CH_TRACE_MAX(idx + 1, 2);
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // no instruction: keeps the compiler from moving the sc1 loads above the poll
 }
@@ -158,7 +116,6 @@ __device__ __forceinline__ void chain_wait(unsigned* sync, int idx, int replica,
 // r = index of the workgroup within its stage, nb = workgroups of the stage
 __device__ __forceinline__ void chain_signal(unsigned* sync, int idx, int r, int nb) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  CH_TRACE_MAX(idx, 3);
   unsigned* base = sync + (long)idx * CH_STAGE_WORDS;
   const int lane = threadIdx.x & 63;
   const int shard = r & (CH_SHARDS - 1);
@@ -230,17 +187,8 @@ __device__ __forceinline__ void chain_product(const bf16_t* __restrict__ W, int 
       const int k0 = min(k + 32 * u, kq - 32), k1 = min(k + 32 * u + 32, kq - 32);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-#if CH_W_NT
-        {
-          const ch_u32x4 w0 = __builtin_nontemporal_load(reinterpret_cast<const ch_u32x4*>(wrow[t] + k0));
-          const ch_u32x4 w1 = __builtin_nontemporal_load(reinterpret_cast<const ch_u32x4*>(wrow[t] + k1));
-          wv[set][t][u] = make_uint4(w0[0], w0[1], w0[2], w0[3]);
-          wv[set][t][u + 1] = make_uint4(w1[0], w1[1], w1[2], w1[3]);
-        }
-#else
         wv[set][t][u] = *reinterpret_cast<const uint4*>(wrow[t] + k0);
         wv[set][t][u + 1] = *reinterpret_cast<const uint4*>(wrow[t] + k1);
-#endif
       }
     }
   };
@@ -248,13 +196,8 @@ __device__ __forceinline__ void chain_product(const bf16_t* __restrict__ W, int 
 #pragma unroll
     for (int u = 0; u < U; u += 2) {
       const int k0 = min(k + 32 * u, kq - 32), k1 = min(k + 32 * u + 32, kq - 32);
-#ifdef CH_EXP_PLAINX   // timing only: plain (L1-served) activation loads — stale data
-      xv[set][u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(X) + xoff + 2 * k0);
-      xv[set][u + 1] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(X) + xoff + 2 * k1);
-#else
       xv[set][u] = ld16_sc1(xr, xoff + 2 * k0);
       xv[set][u + 1] = ld16_sc1(xr, xoff + 2 * k1);
-#endif
     }
   };
   auto compute = [&](int set, int k) {
@@ -599,12 +542,6 @@ __global__ __launch_bounds__(64 * CH_KW) void decode_chain_kernel(ChainArgs a) {
   int stage = 0;
   while (stage < CH_STAGES - 1 && r >= a.nb[stage]) { r -= a.nb[stage]; ++stage; }
   const ChainLayer& L = a.L[layer];
-#ifdef CH_PLACE
-  if (layer == 2 && threadIdx.x == 0 && r < 1024) {
-    ch_place_buf[stage][r] = ((unsigned)__builtin_amdgcn_s_getreg(6164) << 16) | ((unsigned)__builtin_amdgcn_s_getreg(63492) & 0xffffu);
-    ch_place_t[stage][r] = wall_clock64();
-  }
-#endif
   unsigned* err = a.sync + (long)a.n_layers * CH_STAGES * CH_STAGE_WORDS;
   const int me = layer * CH_STAGES + stage;
   const int dep = me - 1;   // stage 0 of layer l waits for stage 4 of layer l-1; (0, 0): dep = -1, no wait

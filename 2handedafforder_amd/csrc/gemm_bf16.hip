@@ -31,26 +31,8 @@
 // the 4 MiB per-XCD L2 holds the A and W panels the concurrently running tiles share (read hit rate 87 % measured).
 #include <type_traits>
 
-#include <cstdlib>
 #include "haff_common.h"
 #include <mutex>
-
-// Tuning hooks (ablation switches HAFF_EXP_*, phase traces HAFF_GEMM_TRACE / _TRACE2, A/B switches HAFF_EPI_LDS /
-// HAFF_GEMM_NO_NT / HAFF_GEMM_GELU_SCALAR, environment overrides of the raster) exist only in builds made with
-// -DHAFF_TUNING (tools/build_gemm_variant.sh); the product library carries none of them and reads no environment.
-#ifndef HAFF_TUNING
-#undef HAFF_EXP_NODMA
-#undef HAFF_EXP_NOREAD
-#undef HAFF_EXP_NOSTORE
-#undef HAFF_EXP_NOEPI
-#undef HAFF_EXP_SAMETILE
-#undef HAFF_GEMM_TRACE
-#undef HAFF_GEMM_TRACE2
-#undef HAFF_GEMM_TRACE3
-#undef HAFF_EPI_LDS
-#undef HAFF_GEMM_NO_NT
-#undef HAFF_GEMM_GELU_SCALAR
-#endif
 
 namespace {
 
@@ -156,8 +138,7 @@ __device__ __forceinline__ float gemm_act(float x) {
 }
 
 // The same polynomial on two values at once: v_pk_fma_f32 / v_pk_mul_f32 (the epilogue has no MFMA beside it, where the
-// packed forms are an anti-lever; here they halve the instruction count of the 13-op chain). -DHAFF_GEMM_GELU_SCALAR: the
-// scalar form, for A/B.
+// packed forms are an anti-lever; here they halve the instruction count of the 13-op chain).
 typedef float haff_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ haff_f2 gelu_pair(haff_f2 x) {
   const haff_f2 lo = {-3.0f, -3.0f}, hi = {3.0f, 3.0f};
@@ -178,40 +159,10 @@ __device__ __forceinline__ haff_f2 gelu_pair(haff_f2 x) {
   return __builtin_elementwise_fma(hx, z * pz, hx);
 }
 
-#ifdef HAFF_GEMM_TRACE2  // fine timestamps (100 MHz wall clock) of waves 0 and 4 around the epilogue of a workgroup's LAST tile
-__device__ unsigned long long haff_gemm_trace2_buf[256 * 2 * 16];
-#define HAFF_TRACE2(i) do { if ((tid & 255) == 0 && blockIdx.x < 256 && blockIdx.y == 0) haff_gemm_trace2_buf[(blockIdx.x * 2 + (tid >> 8)) * 16 + (i)] = wall_clock64(); } while (0)
-extern "C" int haff_gemm_trace2_read(unsigned long long* host, int n_words) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(haff_gemm_trace2_buf), sizeof(unsigned long long) * n_words) == hipSuccess ? 0 : 1;
-}
-#else
-#define HAFF_TRACE2(i) do {} while (0)
-#endif
-#ifdef HAFF_GEMM_TRACE3  // round 5: 32 stamps per (workgroup, wave 0 / wave 4) of a MIDDLE tile (one that has a successor): tile start, the
-// last K-tile's slots and its wait for the next tile's first K-tile, the epilogue's passes (pass 0 and 4 in four sub-steps), the
-// barrier behind it. tools/gemm_trace3.py
-__device__ unsigned long long haff_gemm_trace3_buf[256 * 2 * 32];
-// stamps go to LDS (a global store per stamp sat in vmcnt and the next vmcnt(0) of the traced wave waited for it: "pre" read 1 us)
-// and are flushed once per tile, behind the barrier that follows the epilogue
-#define HAFF_TRACE3(i) do { __builtin_amdgcn_sched_barrier(0); if (has_next && (tid & 255) == 0) haff_t3s[tid >> 8][(i)] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define HAFF_TRACE3_FLUSH() do { if ((tid & 255) < 32 && blockIdx.x < 256 && blockIdx.y == 0) haff_gemm_trace3_buf[(blockIdx.x * 2 + (tid >> 8)) * 32 + (tid & 255)] = haff_t3s[tid >> 8][tid & 255]; } while (0)
-extern "C" int haff_gemm_trace3_read(unsigned long long* host, int n_words) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(haff_gemm_trace3_buf), sizeof(unsigned long long) * n_words) == hipSuccess ? 0 : 1;
-}
-#else
-#define HAFF_TRACE3(i) do {} while (0)
-#define HAFF_TRACE3_FLUSH() do {} while (0)
-#endif
-#ifdef HAFF_GEMM_TRACE  // phase timestamps (100 MHz wall clock) of each workgroup's first tile, for tools/gemm_trace.py
-__device__ unsigned long long haff_gemm_trace_buf[8192 * 8];
-#define HAFF_TRACE(i) do { if (tid == 0 && blockIdx.x < 8192 && blockIdx.y == 0) haff_gemm_trace_buf[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define HAFF_TRACE(i) do {} while (0)
-#endif
-
 // Output stores of the tile kernel. nt: non-temporal — a C tile of a LARGE output is written once and next read by
 // another kernel after hundreds of MB of other traffic; keeping it out of the XCD's L2 leaves the A/W panels resident
-// (+3 % on 131072x5120x1280, +6 % with a residual epilogue; neutral on the K >= 4096 shapes; tools/gemm_variant.py).
+// (+3 % on 131072x5120x1280, +6 % with a residual epilogue; neutral on the K >= 4096 shapes; measured with
+// tools/gemm_variant.py, an experiment build removed after 58cf410).
 // The launcher sets it for outputs of 64 MB and more (decode-sized outputs are re-read from L2 by the next kernel).
 typedef unsigned int haff_u32x4 __attribute__((ext_vector_type(4)));
 typedef float haff_f32x4 __attribute__((ext_vector_type(4)));
@@ -324,13 +275,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef HAFF_GEMM_TRACE3
-  __shared__ unsigned long long haff_t3s[2][32];
-#endif
-#if defined(HAFF_TUNING) && defined(HAFF_EXP_FORCE_PLAIN)   // experiment: what a compile-time-specialised epilogue would cost (bias only, interior tiles)
-  p.act = 0; p.ln_stats = nullptr; p.ln_colsum = nullptr; p.resid = nullptr; p.row_map = nullptr; p.a_map = nullptr; p.rope_cs = nullptr;
-  p.stat_out = nullptr; p.hm_d = 0; p.nb_inner = 0; p.nt_out = 0;
-#endif
   if (!SPEC && p.nb_inner > 0) {
     const int zo = blockIdx.y / p.nb_inner, zi = blockIdx.y - zo * p.nb_inner;
     p.A += zo * p.sAo + zi * p.sAi;
@@ -358,9 +302,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     const int in_g = lin - g * per_group;
     tm0 = (first_m + in_g % gsz) * BM;
     tn0 = (in_g / gsz) * BN;
-#ifdef HAFF_EXP_SAMETILE   // timing experiment: every workgroup computes tile (0, 0): all operand bytes come from L2
-    tm0 = 0; tn0 = 0;
-#endif
   };
   // The 8-wave tile is PERSISTENT when the launcher caps the grid (one workgroup per CU): a workgroup takes tiles
   // blockIdx.x, blockIdx.x + gridDim.x, ... (same XCD, consecutive waves of its raster), and the first K-tile of the next
@@ -370,7 +311,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
   int tile = blockIdx.x;
   int m0, n0;
   tile_origin(tile, m0, n0);
-  HAFF_TRACE(0);
 
   // ---- per-thread staging coordinates: 16-B chunks of the K-tile ----
   // LDS position pos = i*NTHREADS + tid (lane-linear); row = pos>>3; logical chunk = (pos&7) ^ (row&7)
@@ -489,13 +429,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
   const int nk = (p.K + BK - 1) / BK;
 
   f32x4 acc[TN][TM];  // [ni][mi]
-#if defined(HAFF_TUNING) && defined(HAFF_EXP_MFMA32)
-  f32x16 accw[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) accw[i][j] = 0.f;
-#endif
   bf16x8 wf[2][TN], af[2][TM];  // fragments of one K-tile: [32-deep k-step][16-row tile] (unused by the PP loop)
   constexpr int TMH = TM / 2;               // 16-row A tiles per half of the wave tile (4; 3 for the 192-row tile)
   bf16x8 pa[2][TMH > 0 ? TMH : 1], pwl[2][2], pwh[2][2];   // PP loop: one half of the A fragments, both halves of the W fragments
@@ -536,15 +469,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
   int m0e = m0, n0e = n0;                       // this tile's origin (the PP loop moves m0 / n0 on to the next tile)
   const int tile_next = tile + (int)gridDim.x;
   const bool has_next = PP && tile_next < nwg;
-  HAFF_TRACE3(0);
   const bool pf_next = has_next && nk >= 2;   // the K loop requests the next tile's K-tile 0 (a single-K-tile product cannot: its
                                               // requests would have to go out before its own loop starts; see the loop's end)
   // K loop, software-pipelined ACROSS the workgroup barrier. One barrier per K-tile: after it every wave's share of
   // tile kt+1 has landed and every wave is done reading tile kt-1's buffer, so the DMA of tile kt+2 may overwrite it
   // and has a whole K-tile of MFMAs to land. The second half of k-step 1's MFMAs (operands already in registers) is
   // held back and issued AFTER the barrier, where it keeps the MFMA pipe busy while the first fragments of the
-  // next K-tile come back from LDS. (Measured alternatives, tools/gemm_variant.py: two barriers per K-tile -7 %,
-  // no hold-back -4 %, an LDS-counter split barrier and a ping-pong wave schedule no better than this.)
+  // next K-tile come back from LDS. (Measured alternatives, with experiment builds removed after 58cf410: two barriers
+  // per K-tile -7 %, no hold-back -4 %, an LDS-counter split barrier and a ping-pong wave schedule no better than this.)
   if constexpr (PP) {
     // ---- ping-pong ring loop (round 3) ----
     // The two wave groups (wm = 0: waves 0-3, wm = 1: waves 4-7; waves w and w+4 share a SIMD) run the same program ONE
@@ -608,25 +540,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
           for (int j = 0; j < 2; ++j)
             acc[N0 + j][M0 + t] = E::mfma16(wq[ks][j], pa[ks][t], acc[N0 + j][M0 + t]);
     };
-#if defined(HAFF_TUNING) && defined(HAFF_EXP_MFMA32)
-    // timing experiment only (results are wrong): the same fragment reads feeding v_mfma_f32_32x32x16_bf16 — half as many
-    // MFMA instructions of twice the length, i.e. the matrix pipe as busy as before while the SIMD's issue port is held
-    // 8 of 32 cycles instead of 8 of 16
-    auto quad32 = [&](const bf16x8 (&wq)[2][2], auto ni0, auto mi0) {
-      constexpr int N0 = decltype(ni0)::value, M0 = decltype(mi0)::value;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            constexpr int dummy = 0;
-            const int idx = (N0 / 2) * 4 + (M0 / 4) * 2 + j;
-            accw[idx] = E::mfma32(wq[ks][j], pa[ks][2 * j + tt], accw[idx]);
-          }
-    };
-#define quad quad32
-#endif
     auto slot_barrier = [&]() {
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
@@ -669,8 +582,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
       stage_w_q(buf0 ^ 1, BK, Q0{});
       stage_w_q(buf0 ^ 1, BK, Q1{});
     }
-    HAFF_TRACE(1);
-    HAFF_TRACE3(1);
     if (wm == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind group 0
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = (kt & 1) ^ buf0;
@@ -678,51 +589,35 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
       const int a_k0 = (kt + 1 < nk) ? (kt + 1) * BK : 0;
       const bool w_next = (kt + 2 < nk) || (kt + 2 == nk && pf_next);
       const int w_k0 = (kt + 2 < nk) ? (kt + 2) * BK : 0;
-#ifdef HAFF_EXP_NODMA     // timing experiments only (results are wrong): no operand requests / no fragment reads in the loop
-#define PP_DMA(x) do {} while (0)
-#else
-#define PP_DMA(x) x
-#endif
-#ifdef HAFF_EXP_NOREAD
-#define PP_READ(x) do { if (kt == 0) { x; } } while (0)
-#else
-#define PP_READ(x) x
-#endif
       // ---- load slot A: W lo, W hi, A lo; requests for the A quarters of K-tile kt+1 ----
-      if (kt == nk - 1) HAFF_TRACE3(2);
-      PP_READ(read_w(cur, pwl, Q0{}));
-      PP_READ(read_a(cur, Q0{}));
-      PP_READ(read_w(cur, pwh, Q1{}));
+      read_w(cur, pwl, Q0{});
+      read_a(cur, Q0{});
+      read_w(cur, pwh, Q1{});
       if (a_next) {
-        PP_DMA(stage_a_q(cur ^ 1, a_k0, Q0{}));
-        PP_DMA(stage_a_q(cur ^ 1, a_k0, Q1{}));
+        stage_a_q(cur ^ 1, a_k0, Q0{});
+        stage_a_q(cur ^ 1, a_k0, Q1{});
       }
       close_load();
-      if (kt == nk - 1) HAFF_TRACE3(3);
       // ---- multiply slot A: quadrants (A lo, W lo), (A lo, W hi) ----
       __builtin_amdgcn_s_setprio(1);
       quad(pwl, I0{}, I0{});
       quad(pwh, I2{}, I0{});
       __builtin_amdgcn_s_setprio(0);
       slot_barrier();
-      if (kt == nk - 1) HAFF_TRACE3(4);
       // ---- load slot B: A hi; requests for the W quarters of K-tile kt+2; the wait for K-tile kt+1 ----
       if (kt + 2 == nk && pf_next) {   // from here on the staging coordinates are the next tile's
         tile_origin(tile_next, m0, n0);
         stage_coords(m0, n0);
       }
-      PP_READ(read_a(cur, Q1{}));
-      if (kt == nk - 1) HAFF_TRACE3(5);
+      read_a(cur, Q1{});
       if (w_next) {
-        PP_DMA(stage_w_q(cur, w_k0, Q0{}));
-        PP_DMA(stage_w_q(cur, w_k0, Q1{}));
+        stage_w_q(cur, w_k0, Q0{});
+        stage_w_q(cur, w_k0, Q1{});
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // K-tile kt+1 landed (my share); W of K-tile kt+2 stays in flight
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      if (kt == nk - 1) HAFF_TRACE3(6);
       close_load();
-      if (kt == nk - 1) HAFF_TRACE3(7);
       // ---- multiply slot B: quadrants (A hi, W hi), (A hi, W lo) ----
       __builtin_amdgcn_s_setprio(1);
       quad(pwh, I2{}, IH{});
@@ -781,7 +676,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = kt & 1;
       if (kt + 1 < nk) stage(cur ^ 1, (kt + 1) * BK);   // (issuing it after the fragment reads instead measured -5 %)
-      if (kt == 0) HAFF_TRACE(1);
       read_frags(cur, 0);
       read_frags(cur, 1);
       mfma_rows(0, 0, TM);
@@ -800,21 +694,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     }
     }
   }
-#if defined(HAFF_TUNING) && defined(HAFF_EXP_MFMA32)
-#undef quad
-  if constexpr (PP) {   // keep the experiment's accumulators alive: hand them to the epilogue (garbage in, garbage out)
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[(i >> 2) * 2 + (j >> 1)][(i & 3) * 2 + (j & 1)] = f32x4{accw[i][4 * j], accw[i][4 * j + 1], accw[i][4 * j + 2], accw[i][4 * j + 3]};
-  }
-#endif
   // the epilogue reuses stage memory: every wave is done reading fragments (PP: the loop's last barrier says so)
   if constexpr (!PP) __builtin_amdgcn_s_barrier();
-  HAFF_TRACE(2);
-  HAFF_TRACE2(0);
-  HAFF_TRACE3(9);
   // the buffer the last K-tile was read from takes the LDS-staged epilogue's images (ragged tiles); the other one holds the
   // next tile's first K-tile, which the ring loop has requested AND waited for already
   const int ebuf = ((nk - 1) & 1) ^ buf0;
@@ -864,7 +745,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
         bias_r[ni][r] = (p.bias && n < p.N) ? p.bias[n] : 0.f;
       }
   }
-  HAFF_TRACE3(28);
   // folded norm: this wave's {mean, rstd} rows and column sums go through LDS (free stage memory past the staging
   // images) so the per-pass code reads them back instead of holding 2*TM + 4*TN more registers
   static_assert((WM * WN * 16 * RS + WM * WN * (2 * WROWS + WNC)) * 4 <= STAGE_ELEMS * 2, "epilogue LDS fits one stage");
@@ -896,7 +776,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     }
     __builtin_amdgcn_wave_barrier();
   }
-  HAFF_TRACE3(29);
   // output row of wave-row (lane) and (lane + 64): -1 = dropped. Distributed to the read-back lanes by ds_bpermute.
   int orow_l[(WROWS + 63) / 64];
   const bool map_staged = PP && BM == 256 && has_map && (MFULL || m0e + BM <= p.M) && al16(p.row_map);   // (the DMA above)
@@ -906,8 +785,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     if (map_staged) orow_l[h] = reinterpret_cast<const int*>(smem + 2 * STAGE_ELEMS)[1024 + wm * WROWS + h * 64 + lane];
     else orow_l[h] = ((MFULL || m < p.M) && h * 64 + lane < WROWS) ? (has_map ? p.row_map[m] : m) : -1;
   }
-  HAFF_TRACE3(30);
-#ifndef HAFF_EPI_LDS   // -DHAFF_EPI_LDS: every tile through the LDS-staged epilogue below (A/B runs)
   // ---- register epilogue (interior tiles, 16-B aligned rows) ----
   // The swapped MFMA orientation leaves 4 consecutive output columns of ONE row in each lane (chunk c = 16-column
   // group, columns 16c + 4fh .. +3). Two neighbouring chunks are made into 8 consecutive columns per lane by ONE
@@ -915,15 +792,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
   // columns of it from lane fh+1, which receives chunk 2j+1's previous four in return), so a lane stores 16 B and the
   // four lanes of a row cover 64 contiguous bytes of it: no LDS round trip, no wave barriers, no dependent
   // write -> read -> store chain per pass. (Measured on the LDS-staged form: its stores cost 8 % of a K = 1280 launch, the
-  // staging around them 20 %: tools/gemm_variant.py nostore / noepi.)
-#ifdef HAFF_EXP_NOEPI   // timing experiment: the accumulators are kept alive, nothing is computed or written
-  if (fast) {
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < TN; ++ni) asm volatile("" ::"v"(acc[ni][mi]));
-  } else
-#endif
+  // staging around them 20 %: store-less and epilogue-less experiment builds, removed after 58cf410.)
   if (fast) {
     // ALL = every row of the wave tile is written (no row map, not the ragged last M-tile): the loads and stores below are
     // then unconditional, which lets hipcc wait for a prefetched residual with a COUNTED vmcnt (behind an exec-masked
@@ -986,8 +855,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
         }
       }
     }
-    HAFF_TRACE2(1);
-    HAFF_TRACE3(10);
     // ALL: the lane's output address is affine in the pass index — one 64-bit base per tile and a scalar stride per pass
     // instead of a 64-bit multiply-add chain per store (the epilogue is instruction-bound: two waves per SIMD, ~60 VALU
     // per pass before this)
@@ -1011,8 +878,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
           for (int r = 0; r < 4; ++r) acc[ni][mi][r] = __builtin_fmaf(-st.x, cs[r], acc[ni][mi][r]);
         }
       }
-      if (mi == 0) HAFF_TRACE3(21);
-      if (mi == 4) HAFF_TRACE3(25);
       float val[NCH][4];
       if constexpr (!SWIGLU) {
         auto act_side = [&](auto tag) {   // the activation is resolved ONCE per pass (wave-uniform switch)
@@ -1046,8 +911,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             val[nj][r] = g * __builtin_amdgcn_rcpf(1.0f + __expf(-g)) * u;
           }
       }
-      if (mi == 0) HAFF_TRACE3(22);
-      if (mi == 4) HAFF_TRACE3(26);
       const int orow = out_row(mi);
       float st1 = 0.f, st2 = 0.f;   // row statistics of the final values (RES && ALL && p.stat_out)
       // RoPE + KV-cache append (see GemmArgs::rope_cs): rotate the lane's (c, c + 64) pairs, pick the destination row
@@ -1153,9 +1016,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             permlane16_swap(x1, y1);
             q = haff_u32x4{x0, x1, y0, y1};
           }
-#ifdef HAFF_EXP_NOSTORE   // timing experiment: everything but the global store
-          asm volatile("" ::"v"(q));
-#else
           if (ALL || orow >= 0) {
             bf16_t* dst = ALL ? reinterpret_cast<bf16_t*>(const_cast<char*>(c_lane) + mi * c_pass) + 32 * j
                               : reinterpret_cast<bf16_t*>(p.C) + (long)orow * p.ldc + n_wave_out + 32 * j + coff;
@@ -1169,11 +1029,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             // them, a non-temporal store would send each half to memory on its own (measured -2...-8 %)
             *reinterpret_cast<haff_u32x4*>(dst) = q;
           }
-#endif
         }
       }
-      if (mi == 0) HAFF_TRACE3(23);
-      if (mi == 4) HAFF_TRACE3(27);
       if constexpr (RES && ALL) {
         if (has_stat) {   // the four lanes of a row (same fr, fh = 0..3) -> one {sum, sum of squares} per (row, wave)
           st1 = quad_row_sum(st1);
@@ -1182,8 +1039,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
             *reinterpret_cast<float2*>(p.stat_out + ((long)orow * p.stat_slots + (n_wave_out >> 6)) * 2) = float2{st1, st2};
         }
       }
-      HAFF_TRACE2(2 + mi);
-      HAFF_TRACE3(11 + mi);
     }
     };   // reg_epilogue
     const bool all_rows = !has_map && (MFULL || m_wave + WROWS <= p.M);
@@ -1195,7 +1050,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
       else reg_epilogue(std::false_type{}, std::false_type{});
     }
   } else
-#endif
   {
   const int rb_r = lane / LPR, rb_c = (lane % LPR) * 8;   // read-back row within a step / first column
   const long n_out = n_wave_out + rb_c;
@@ -1218,12 +1072,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
   const bool pre_r = PREFETCH_R && fast && has_res;
   if (pre_r) fetch_resid(0);
 
-#ifdef HAFF_EXP_NOEPI   // timing experiment: the accumulators are kept alive, nothing is written
-#pragma unroll
-  for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni) asm volatile("" ::"v"(acc[ni][mi]));
-#else
 #pragma unroll
   for (int mi = 0; mi < TM; ++mi) {
     float* row = sEp + fr * RS + fh * 4;
@@ -1246,13 +1094,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
 #pragma unroll
         for (int ni = 0; ni < TN; ++ni) {
           float v[4];
-#ifndef HAFF_GEMM_GELU_SCALAR
           if constexpr (ACT == HAFF_ACT_GELU) {
             const haff_f2 a = gelu_pair(haff_f2{__builtin_fmaf(acc[ni][mi][0], rstd_m, bias_r[ni][0]), __builtin_fmaf(acc[ni][mi][1], rstd_m, bias_r[ni][1])});
             const haff_f2 b = gelu_pair(haff_f2{__builtin_fmaf(acc[ni][mi][2], rstd_m, bias_r[ni][2]), __builtin_fmaf(acc[ni][mi][3], rstd_m, bias_r[ni][3])});
             v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
           } else
-#endif
           {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = gemm_act<ACT>(__builtin_fmaf(acc[ni][mi][r], rstd_m, bias_r[ni][r]));
@@ -1311,11 +1157,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
                 v[2 * j + 1] += E::hi(w[j]);
               }
             }
-#ifdef HAFF_EXP_NOSTORE   // timing experiment: everything but the global store
-            asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
-#else
             store8_c<F16>(reinterpret_cast<bf16_t*>(p.C) + (long)orow * p.ldc + n_out, v, nt_out);
-#endif
           }
         }
       }
@@ -1343,16 +1185,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
     }
     __builtin_amdgcn_wave_barrier();
   }
-#endif
   }   // LDS-staged epilogue
-  HAFF_TRACE(3);
-#ifdef HAFF_GEMM_TRACE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  HAFF_TRACE(4);
-#endif
   if (!has_next) break;
-  HAFF_TRACE2(10);
-  HAFF_TRACE3(19);
   if constexpr (PP) {
     __builtin_amdgcn_s_barrier();   // every wave is past its epilogue: its staging buffer takes K-tile 1
     if (!pf_next) {                 // single-K-tile products: the next tile's only K-tile is requested and awaited here
@@ -1363,9 +1197,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(GemmArgs p) {
       __builtin_amdgcn_s_barrier();
     }
   }
-  HAFF_TRACE2(11);
-  HAFF_TRACE3(20);
-  HAFF_TRACE3_FLUSH();
   tile = tile_next;
   buf0 = ebuf ^ 1;
   }   // tile loop
@@ -1774,35 +1605,18 @@ extern "C" int haff_gemm_stream_cap(void* stream, int cap) {
   return old < 0 ? HAFF_ERR_UNSUPPORTED : old;
 }
 
-static bool haff_gemm_spec_enabled() {
-#ifdef HAFF_TUNING   // HAFF_GEMM_NO_SPEC=1: every launch through the generic instance (A/B)
-  static const bool off = [] { const char* e = getenv("HAFF_GEMM_NO_SPEC"); return e && atoi(e) != 0; }();
-  return !off;
-#else
-  return true;
-#endif
-}
-
 template <int BM, int BN, int WM, int WN, bool F16 = false>
 static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   int gx = tiles;
   if (WM * WN == 8) {   // persistent 8-wave tile: one workgroup per CU
     int cap = g_stream_caps.get((void*)s);
-#ifdef HAFF_TUNING       // HAFF_GEMM_PERSIST: other cap, 0 = one tile per workgroup
-    static const int cap_env = [] { const char* e = getenv("HAFF_GEMM_PERSIST"); return e ? atoi(e) : -1; }();
-    if (cap_env >= 0) cap = cap_env;
-#endif
     if (cap > 0 && gx > cap) gx = cap;
   }
   dim3 grid(gx, nbatch), block(64 * WM * WN);
   GemmArgs pd = p;
   if (WM * WN == 4) {
-    long deep_max = 1024;   // 128x128 work items (tiles x slices) up to which the launch takes the two-K-tiles-in-flight loop
-#ifdef HAFF_TUNING
-    static const long dm_env = [] { const char* e = getenv("HAFF_GEMM_DEEP_MAX"); return e ? atol(e) : 1024L; }();
-    deep_max = dm_env;
-#endif
+    constexpr long deep_max = 1024;   // 128x128 work items (tiles x slices) up to which the launch takes the two-K-tiles-in-flight loop
     pd.deep_k = (long)tiles * nbatch <= deep_max && ((p.K + BK - 1) / BK) >= 3;
   }
   const GemmArgs& pl = pd;
@@ -1812,7 +1626,7 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
     const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && a16(p.C) && (p.ldc & 7) == 0 && a16(p.bias) &&
                     a16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && a16(p.ln_stats) && a16(p.ln_colsum) && a16(p.row_map) &&
                     (!p.ln_colsum || p.ln_stats);
-    if (ok && haff_gemm_spec_enabled()) {
+    if (ok) {
       const unsigned f = (p.bias ? GF_BIAS : 0u) | (p.ln_stats ? GF_LN : 0u) | (p.ln_colsum ? GF_CSUM : 0u) |
                          ((p.resid || p.res32) ? GF_RES : 0u) | (p.res32 ? GF_RES32 : 0u) |
                          (p.stat_out ? GF_STAT : 0u) | (p.row_map ? GF_MAP : 0u) | (p.hm_d ? GF_HM : 0u) | (p.rope_cs ? GF_ROPE : 0u) |
@@ -1846,7 +1660,7 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
     const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && a16(p.C) && (p.ldc & 7) == 0 && a16(p.bias) &&
                     a16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && !p.ln_stats && !p.ln_colsum && !p.row_map && !p.stat_out && !p.hm_d &&
                     !p.rope_cs && p.act == 0;
-    if (ok && haff_gemm_spec_enabled()) {
+    if (ok) {
       const unsigned f = (p.bias ? GF_BIAS : 0u) | (p.resid ? GF_RES : 0u);
 #define HAFF_SPEC192(FL, SW)                                                                                               \
   if (f == ((FL) & ~(GF_SPEC | GF_RAGM)) && (p.swiglu != 0) == (SW)) {                                                       \
@@ -1872,12 +1686,6 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
   return haff_check_launch();
 }
 
-#ifdef HAFF_GEMM_TRACE
-extern "C" int haff_gemm_trace_read(unsigned long long* host, int n_words) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(haff_gemm_trace_buf), sizeof(unsigned long long) * n_words) == hipSuccess ? 0 : 1;
-}
-#endif
-
 template <bool F16 = false>
 static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw, void* C,
                           long ldc, const float* bias, const void* resid, long ldr, const int* row_map, int M, int N,
@@ -1893,22 +1701,10 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // weight-streaming kernel for decode-sized M; past 32 rows the 128x128 tile is faster again on very wide outputs
   // (M = 64: gate/up 53 vs 75 us, lm_head 68 vs 84 us; qkv 49 vs 42, o_proj 46 vs 24, down 113 vs 63)
-  int skinny_max_m = 64;
-#ifdef HAFF_TUNING   // HAFF_SKINNY_MAXM: rows up to which the weight-streaming kernel is taken (A/B against the split-K tile path)
-  {
-    static const int e = [] { const char* v = getenv("HAFF_SKINNY_MAXM"); return v ? atoi(v) : 64; }();
-    skinny_max_m = e;
-  }
-#endif
+  constexpr int skinny_max_m = 64;
   // 33..64 rows with a workspace: wide or deep weights go to the split-K tile path below (M = 64: qkv 31.7 vs 36.7 us, down_proj
   // 31.5 vs 42.4 us with 16 uneven K slices; o_proj stays here: 17.3 vs 20.6 us; tools/skinny64_ab.py)
-  int tile_min_m = 32;
-#ifdef HAFF_TUNING
-  {
-    static const int e = [] { const char* v = getenv("HAFF_TILE_MINM"); return v ? atoi(v) : 32; }();
-    tile_min_m = e;
-  }
-#endif
+  constexpr int tile_min_m = 32;
   const bool tile_rows = M > tile_min_m && workspace && (K % BK) == 0 && !ln_stats && (N >= 8192 || K >= 8192);
   if (M <= skinny_max_m && (K % 128) == 0 && tile_cfg == 0 && !(M > 32 && N >= 16384) && !tile_rows) {
     if (M > 32 && workspace && workspace_bytes >= 4L * 4 * M * N && !a_map) {
@@ -1926,7 +1722,7 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
   // 64-step K loop each on 96 CUs: 62 us; 4 slices: 384 workgroups x 16 steps). Each slice is a "batch" of the batched
   // launch — operands offset by slice * K/ks along K, fp32 partial tile into ws[slice][M][N] — and skinny_reduce_kernel
   // adds the slices in index order and applies the epilogue: deterministic.
-  if (tile_cfg == 0 && workspace && !ln_stats && M > (tile_min_m < 32 ? tile_min_m : 32) && (K % BK) == 0) {
+  if (tile_cfg == 0 && workspace && !ln_stats && M > tile_min_m && (K % BK) == 0) {
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     const int ksteps = K / BK;
     int ks = 0;
@@ -1973,9 +1769,9 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
   }
   // Raster group depth: 8 M-tiles share their A panels across the N sweep; with a long K loop (>= 5120) and few N tiles
   // the concurrently running tiles drift apart and a 2-deep group keeps more of the sweep in the 4 MiB L2
-  // (measured +5 % on 131072x1280x5120 and 18624x4096x11008, tools/gemm_variant.py).
+  // (measured +5 % on 131072x1280x5120 and 18624x4096x11008 with an experiment build removed after 58cf410).
   if (big || mid_tile) {
-    // (sweep of 1..32 on the bench shapes, tools/gemm_variant.py with HAFF_GEMM_GROUP_M: <= 5 N-tiles: 1 (+4 % on
+    // (sweep of 1..32 on the bench shapes, with an experiment build removed after 58cf410: <= 5 N-tiles: 1 (+4 % on
     // 131072x1280x1280), <= 16 N-tiles: 4 (+1.4 % on 131072x3840x1280), 20 N-tiles: 8; all within 3 % of each other)
     // (round 3, ring loop: <= 5 N-tiles 1; long K with <= 8 N-tiles 2; <= 16 N-tiles 4 (18624x4096x11008: 1351 vs 1315 at 2); 8)
     const int tn = (N + 255) / 256;
@@ -1983,15 +1779,7 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
     else if (K >= 5120 && tn <= 8) p.group_m = 2;
     else if (tn <= 16) p.group_m = 4;
   }
-#ifdef HAFF_TUNING
-  {   // A/B override of the raster group depth (tools/gemm_variant.py)
-    static const int gm_env = [] { const char* e = getenv("HAFF_GEMM_GROUP_M"); return e ? atoi(e) : 0; }();
-    if (gm_env > 0) p.group_m = gm_env;
-  }
-#endif
-#ifndef HAFF_GEMM_NO_NT
   p.nt_out = (long)M * (swiglu ? N / 2 : N) * (out_f32 ? 4 : 2) >= (64L << 20);
-#endif
   if (mid_tile) return launch_gemm<192, 256, 2, 4, F16>(p, s);
   return big ? launch_gemm<256, 256, 2, 4, F16>(p, s) : launch_gemm<128, 128, 2, 2, F16>(p, s);
 }

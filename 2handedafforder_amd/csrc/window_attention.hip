@@ -23,18 +23,6 @@
 // the P.V MFMA from registers and V^T fragments come from transposed LDS reads with the same permuted k order.
 #include "haff_common.h"
 
-// Ablation hooks (counter / timing experiments: WRONG results) exist only in builds made with -DHAFF_TUNING
-// (tools/build_window_variant.sh): HAFF_WIN_NOKREAD / _NOVREAD leave out the K / V^T fragment reads from LDS, HAFF_WIN_NOSCR the
-// trips of the rel-pos terms through the wave-private scratch, HAFF_WIN_NODMA the HBM -> LDS staging.
-#ifndef HAFF_TUNING
-#undef HAFF_WIN_NOKREAD
-#undef HAFF_WIN_NOVREAD
-#undef HAFF_WIN_NOSCR
-#undef HAFF_WIN_NODMA
-#undef HAFF_WIN_RS
-#undef HAFF_WIN_KLAST_OLD
-#endif
-
 namespace {
 
 struct WinArgs {
@@ -53,13 +41,6 @@ struct WinArgs {
   int grid_h, grid_w, wps;
   long pad_token;
 };
-
-#ifdef HAFF_WIN_TRACE  // phase timestamps (100 MHz wall clock) of workgroup 0 / wave 0, for tools/window_attn_trace.py
-__device__ unsigned long long haff_win_trace_buf[64 * 16];
-#define WTRACE(i) do { if (blockIdx.x == 0 && tid == 0 && it < 64) haff_win_trace_buf[it * 16 + (i)] = wall_clock64(); } while (0)
-#else
-#define WTRACE(i) do {} while (0)
-#endif
 
 constexpr float WLOG2E = 1.4426950408889634f;
 typedef __attribute__((address_space(3))) bf16x4* wlds_v4_ptr;
@@ -83,14 +64,11 @@ struct WinCfg {
   static constexpr int KSTR = D * 2 + 16 * KPC;   // bytes
   static constexpr int VSTR = D * 2;
   static constexpr int NKS = (S + 1) / 2;       // P.V k-steps: two key tiles (grid rows) each
-#ifdef HAFF_WIN_RS
-  static constexpr int RS = HAFF_WIN_RS;
-#else
   // scratch row stride in floats: 52 since round 6 (36 before). The scratch's 16-B writes at a 144-B row stride and the rel_w
-  // reads behind them were half of the kernel's LDS bank-conflict cycles (tools/pmc_window_lds.sh: 6.45e6 of 12.5e6 per 32-frame
-  // launch; 40 -> 19.8e6, 44 -> 6.6e6, 52 -> 6.3e6 in all, 68 = 36: profiles/r6_pmc_window_attn_lds_ablation.txt)
+  // reads behind them were half of the kernel's LDS bank-conflict cycles (6.45e6 of 12.5e6 per 32-frame launch; 40 -> 19.8e6,
+  // 44 -> 6.6e6, 52 -> 6.3e6 in all, 68 = 36: profiles/r6_pmc_window_attn_lds_ablation.txt, measured on ablation builds whose
+  // hooks and scripts were removed after 58cf410)
   static constexpr int RS = 52;
-#endif
   static constexpr int QPW = 2;                 // q-tiles (query-grid rows) per wave per item
   static constexpr int NWAVES = (S + QPW - 1) / QPW;   // 7 waves cover the 14 grid rows exactly
   static constexpr int NTHREADS = 64 * NWAVES;
@@ -211,8 +189,8 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
   // which would drain the prefetch at once. Completion is waited for by hand (vmcnt(0) before the end-of-item barrier).
   // M0 is otherwise unused here. The 10 instructions of an item are NOT issued in one go: the CU accepts requests at the
   // rate HBM serves them (~24 GB/s per CU), so a wave that issues its whole 9 KB share sits in the issue stage for
-  // ~4 us of an ~11 us item (tools/window_attn_trace.py); spread over the compute phases the requests queue behind
-  // the MFMA / softmax work instead.
+  // ~4 us of an ~11 us item (measured with a traced build removed after 58cf410); spread over the compute phases the
+  // requests queue behind the MFMA / softmax work instead.
   auto issue_dma = [&](int i0, int i1) {
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) {
@@ -220,10 +198,6 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
       const unsigned m0v = nx_lds0 + i * C::NTHREADS * 16;
       const bool is_pad = (int)(slot_pad[i] >> 28) >= nx_pad_h0 || (int)((slot_pad[i] >> 24) & 15u) >= nx_pad_w0;
       const unsigned off = is_pad ? nx_pad_base + (slot_pad[i] & 0xffu) + ((slot_pad[i] >> 23) & 1u) * vmk_bytes : slot_off[i];
-#ifdef HAFF_WIN_NODMA
-      asm volatile("" ::"v"(off), "s"(m0v));
-      continue;
-#endif
       if ((i + 1) * C::NTHREADS <= C::PAD_SLOTS || (i * C::NTHREADS + wave * 64) < C::PAD_SLOTS)   // wave-uniform
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(nx_kb), "s"(m0v)
                      : "memory");
@@ -297,12 +271,10 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
       for (int kd = 0; kd < C::NKD; ++kd) qcur[t][kd] = qnext[t][kd];
     const int next = item + gridDim.x;
     const bool has_next = next < n_items;
-    WTRACE(0);
     if (has_next) {   // HBM -> the other LDS buffer (last read one item ago), in flight during the compute
       begin_loads(next, buf ^ 1);
       issue_dma(0, DMA_Q1);
     }
-    WTRACE(1);
 
 #pragma unroll
     for (int t = 0; t < C::QPW; ++t) {
@@ -339,10 +311,6 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
           t1 = E::mfma16(tw[1][kd], qraw[kd], t1);
         }
         float a[4] = {t0[0], t0[1], t0[2], t0[3]}, b[4] = {t1[0], t1[1], t1[2], t1[3]};
-#ifdef HAFF_WIN_NOSCR
-#pragma unroll
-        for (int j = 0; j < 4; ++j) relw4[j] = kw_ok[j] ? (a[j] + b[j]) * WLOG2E : -INFINITY;
-#else
         store4(scr + fr * C::RS + 4 * fh, a);
         store4(scr + fr * C::RS + 16 + 4 * fh, b);
         __builtin_amdgcn_wave_barrier();
@@ -352,7 +320,6 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
           relw4[j] = kw_ok[j] ? scr[fr * C::RS + r] * WLOG2E : -INFINITY;   // masked key columns stay -inf through the MFMAs
         }
         __builtin_amdgcn_wave_barrier();
-#endif
       }
       // ---- rel_h: same through the same scratch; r = qh - kh + S-1 is wave-uniform per key tile ----
       {
@@ -363,20 +330,14 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
           t1 = E::mfma16(th[1][kd], qraw[kd], t1);
         }
         float a[4] = {t0[0], t0[1], t0[2], t0[3]}, b[4] = {t1[0], t1[1], t1[2], t1[3]};
-#ifdef HAFF_WIN_NOSCR
-#pragma unroll
-        for (int kt = 0; kt < S; ++kt) relh_t[kt] = (a[kt & 3] + b[kt & 3]) * WLOG2E;
-#else
         store4(scr + fr * C::RS + 4 * fh, a);
         store4(scr + fr * C::RS + 16 + 4 * fh, b);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int kt = 0; kt < S; ++kt) relh_t[kt] = scr[fr * C::RS + (qh - kt + S - 1)] * WLOG2E;
         __builtin_amdgcn_wave_barrier();
-#endif
       }
 
-      WTRACE(2 + 5 * t);
       // ---- scores S^T[key][q] for all S key tiles, accumulators start at the (log2-domain) bias ----
       f32x4 sacc[S];
 #pragma unroll
@@ -388,15 +349,12 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
       // the zero-padded last k-step (d = 80: columns 64..95) would read 32 bytes PAST an unpadded row for fh >= 2 — the next key's
       // first chunks, or V behind the last K row: finite only if the neighbour is (Inf / NaN x a zero Q column = NaN in ANOTHER
       // key's score). Those lanes re-read the row's own last chunk instead (the global kernel's k_lane2 does the same).
-#ifdef HAFF_WIN_KLAST_OLD
-      const int koff_last = min(fh * 16 + (C::NKD - 1) * 64, D * 2 - 16);
-#else
       // (round 6) ... and the two lanes groups past the row's end (fh >= 2, zero Q columns) take the two chunks IN FRONT of the last
       // k-step's, so that the four lanes of a key still cover 64 contiguous bytes of its row (rotated): the same bank pattern as the
-      // full k-steps. Three lanes on one chunk (rounds 4-5) made this read a 2-way bank conflict (tools/pmc_window_lds.sh).
+      // full k-steps. Three lanes on one chunk (rounds 4-5) made this read a 2-way bank conflict (measured with
+      // an ablation build removed after 58cf410).
       const int koff_last = (D * 2 - (C::NKD - 1) * 64 == 32) ? (C::NKD - 1) * 64 - 32 + ((fh + 2) & 3) * 16
                                                               : min(fh * 16 + (C::NKD - 1) * 64, D * 2 - 16);
-#endif
 #pragma unroll
       for (int g0 = 0; g0 < S; g0 += KG) {
 #pragma unroll
@@ -404,18 +362,13 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
 #pragma unroll
           for (int kt = g0; kt < g0 + KG && kt < S; ++kt) {
             // A operand row = key (kh = kt, kw = fr)
-#ifdef HAFF_WIN_NOKREAD
-            const bf16x8 kf = qs[(kd + 1) % C::NKD];
-#else
             const bf16x8 kf = *reinterpret_cast<const bf16x8*>(sK + (kt * S + qcol) * C::KSTR + (kd == C::NKD - 1 ? koff_last : fh * 16 + kd * 64));
-#endif
             sacc[kt] = E::mfma16(kf, qs[kd], sacc[kt]);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
       }
 
-      WTRACE(3 + 5 * t);
       if (has_next) {
         if (t == 0) issue_dma(DMA_Q1, DMA_Q2);
         else issue_dma(DMA_Q3, NDMA);
@@ -440,7 +393,6 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
       psum += __shfl_xor(psum, 16, 64);
       psum += __shfl_xor(psum, 32, 64);
 
-      WTRACE(4 + 5 * t);
       // ---- O^T += V^T . P^T: k-step ks covers key tiles 2ks (slots 0-3) and 2ks+1 (slots 4-7) ----
       f32x4 oacc[C::ND];
 #pragma unroll
@@ -460,19 +412,13 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
         const unsigned char* v1 = sV + (t1 * S + vkw) * C::VSTR + 8 * tr_p;
 #pragma unroll
         for (int dt = 0; dt < C::ND; ++dt) {
-#ifdef HAFF_WIN_NOVREAD
-          const bf16x8 vf = qs[dt % C::NKD];
-          asm volatile("" ::"v"(v0), "v"(v1));
-#else
           const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wlds_v4_ptr)(v0 + 32 * dt));
           const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wlds_v4_ptr)(v1 + 32 * dt));
           const bf16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-#endif
           oacc[dt] = E::mfma16(vf, pf, oacc[dt]);
         }
       }
 
-      WTRACE(5 + 5 * t);
       if (has_next && t == 0) issue_dma(DMA_Q2, DMA_Q3);
       // ---- out[q][16dt + 4fh + j] = O^T / sum ----
       const float inv = 1.0f / psum;
@@ -486,24 +432,15 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
       }
     }
 
-    WTRACE(12);
     if (!has_next) break;
     item = next;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // my share of the next item has landed in LDS
     settle_q();
-    WTRACE(13);
     __syncthreads();
-    WTRACE(14);
   }
 }
 
 }  // namespace
-
-#ifdef HAFF_WIN_TRACE
-extern "C" int haff_win_trace_read(unsigned long long* host, int n_words) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(haff_win_trace_buf), sizeof(unsigned long long) * n_words) == hipSuccess ? 0 : 1;
-}
-#endif
 
 // Fused window attention with in-kernel decomposed rel-pos (bf16). q/k/v/o: strides in elements (window, head,
 // token); n_tokens = S*S per window. grid_h/grid_w > 0: the windows tile images of grid_h x grid_w tokens

@@ -19,7 +19,6 @@ def main():
     ap.add_argument("--dummy-reps", type=int, default=1)
     ap.add_argument("--check", action="store_true", help="after timing: the chained step against itself eager / stage by stage / the five-launch layer")
     ap.add_argument("--fresh-pool", action="store_true", help="every configuration captures its graph into a memory pool of its own")
-    ap.add_argument("--place", action="store_true", help="-DCH_PLACE build: where and when layer 2's workgroups of the last launch started")
     ap.add_argument("--addr", action="store_true", help="print the device addresses of the chained step's scratch buffers")
     ap.add_argument("--no-chain", action="store_true", help="<= 8 rows: five launches per layer instead of the one chained launch per step")
     args = ap.parse_args()
@@ -81,23 +80,6 @@ def main():
             sc = h_lib.abs().max().item()
             print(f"   status ok {ok}; finite {bool(torch.isfinite(h_graph).all())}; graph vs eager chain {(h_graph - h_eager).abs().max().item():.3e}, vs stage-by-stage "
                   f"{(h_graph - h_stages).abs().max().item():.3e}, vs five launches {(h_graph - h_lib).abs().max().item():.3e} (scale {sc:.3e})", flush=True)
-        if args.place and "chain" in cache:
-            import ctypes
-            from collections import Counter
-            from haff import lib as hlib
-            pr = ctypes.CDLL(hlib.LIB_PATH).haff_decode_chain_place_read
-            pr.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-            pb, pt = (ctypes.c_uint * (5 * 1024))(), (ctypes.c_ulonglong * (5 * 1024))()
-            pr(pb, pt)
-            nbs = [3 * l.hidden // 16, B * l.heads, l.hidden // 8, 2 * l.ffn // 32, l.hidden // 8]
-            t0 = min(pt[i] for i in range(min(nbs[0], 1024)))
-            for st, name in enumerate(("qkv", "attn", "o_proj", "gate|up", "down")):
-                n = min(nbs[st], 1024)
-                keys = [((pb[st * 1024 + r] >> 16) & 15, (pb[st * 1024 + r] >> 13) & 7, (pb[st * 1024 + r] >> 12) & 1, (pb[st * 1024 + r] >> 8) & 15) for r in range(n)]
-                c = Counter(keys)
-                ts = sorted((pt[st * 1024 + r] - t0) / 100.0 for r in range(n))
-                xcd_of_first8 = [k[0] for k in keys[:8]]
-                print(f"   {name:8s} {n:4d} wgs on {len(c):3d} CUs, per CU {dict(sorted(Counter(c.values()).items()))}; start times us: first {ts[0]:.1f} median {ts[n // 2]:.1f} last {ts[-1]:.1f}; XCDs of workgroups 0..7: {xcd_of_first8}", flush=True)
         if args.addr and "chain" in cache:
             ch = cache["chain"]
             ent = model._graphs.get((B, cache["tmax"]))
