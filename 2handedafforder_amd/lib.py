@@ -47,6 +47,10 @@ _PROTOS = {
                           c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "haff_gemm_f16_heads": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                              c_int, c_int, c_long, c_long, c_void_p],
+    "haff_nf4_quantize_f16": [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
+    "haff_nf4_dequant_f16": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p],
+    "haff_gemm_nf4_f16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "haff_gemm_stream_cap": [c_void_p, c_int],
     "haff_decode_chain_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p],

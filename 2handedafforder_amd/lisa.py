@@ -49,7 +49,15 @@ def _check_fp16_weights(sd, device):
 
 class LisaMI355:
     def __init__(self, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", sam_chunk=8, fp32_tail=True, fp32_stream=False,
-                 neck_f32=False):
+                 neck_f32=False, load_in_4bit=False, bnb_4bit_use_double_quant=True, bnb_4bit_quant_type="nf4", nf4_lm_head=True):
+        # load_in_4bit: the reference's bitsandbytes 4-bit load (inference.py:133-146): the fp16 mode with the Llama projections,
+        # mm_projector, text_hidden_fcs and (nf4_lm_head) lm_head quantised to NF4 (quant.py). Refused combinations are ValueErrors
+        if load_in_4bit:
+            if dtype != torch.float16:
+                raise ValueError("load_in_4bit: the reference's 4-bit mode computes in float16 (bnb_4bit_compute_dtype=torch.float16); "
+                                 f"pass dtype=torch.float16, not {dtype}")
+            if bnb_4bit_quant_type != "nf4":
+                raise ValueError(f"load_in_4bit: bnb_4bit_quant_type={bnb_4bit_quant_type!r} is not supported (only 'nf4')")
         if not torch.cuda.is_available():
             raise RuntimeError("LisaMI355 needs an MI355X (HIP device); there is no CPU fallback for the hot path")
         from .lib import load_library
@@ -114,16 +122,29 @@ class LisaMI355:
         self.sam_encoder.emb_f32 = self.fp32_tail
         self.sam_decoder = SamPromptDecoderHip(sd, cfg.sam, tail, dev)
         self.clip = ClipTowerHip(sd, cfg.clip, dtype, dev)
-        self.llm = LlamaHip(sd, cfg.llm, dtype, dev)
+        self.load_in_4bit = bool(load_in_4bit)
+        self.llm = LlamaHip(sd, cfg.llm, dtype, dev, nf4=self.load_in_4bit, nf4_double_quant=bnb_4bit_use_double_quant,
+                            nf4_lm_head=nf4_lm_head)
         # fp32 residual streams in the bf16 mode: True / "sam" / "llm" — the ViT-H and / or Llama hidden-state
         # stream kept in fp32 between the bf16 MFMA products (2.8x closer to the reference on the image embedding at depth 32)
         self.sam_encoder.fp32_stream = fp32_stream in (True, "sam", "both")
         self.llm.fp32_stream = fp32_stream in (True, "llm", "both")
         self.sam_encoder.neck_f32 = (bool(neck_f32) and dtype == torch.bfloat16) or dtype == torch.float16  # the ViT-H neck on the f32-input MFMA path (sam.py)
-        self.w_proj = sd["model.mm_projector.weight"].to(dev, dtype).contiguous()
+        def lin_w(name, dt):
+            # 4-bit mode: mm_projector and text_hidden_fcs are NF4 Linears in the reference; their values are quantised and
+            # dequantised once here and their products keep the 16 / 32-bit paths (their bytes are not what a frame waits for)
+            if self.load_in_4bit:
+                from . import quant
+                return quant.round_trip(sd[name], dev, bnb_4bit_use_double_quant).to(dt).contiguous()
+            return sd[name].to(dev, dt).contiguous()
+        self.w_proj = lin_w("model.mm_projector.weight", dtype)
         self.b_proj = _f32(sd["model.mm_projector.bias"], dev)
-        self.fc0 = (sd["model.text_hidden_fcs.0.0.weight"].to(dev, tail).contiguous(), _f32(sd["model.text_hidden_fcs.0.0.bias"], dev))
-        self.fc2 = (sd["model.text_hidden_fcs.0.2.weight"].to(dev, tail).contiguous(), _f32(sd["model.text_hidden_fcs.0.2.bias"], dev))
+        self.fc0 = (lin_w("model.text_hidden_fcs.0.0.weight", tail), _f32(sd["model.text_hidden_fcs.0.0.bias"], dev))
+        self.fc2 = (lin_w("model.text_hidden_fcs.0.2.weight", tail), _f32(sd["model.text_hidden_fcs.0.2.bias"], dev))
+
+    def llm_weight_bytes(self):
+        """Device bytes of the Llama projections and lm_head (the weights a decode step streams)."""
+        return self.llm.weight_bytes()
 
     # ---- a4/a5: CLIP tower + projector -------------------------------------------------------------------
     def encode_images(self, images_clip):

@@ -97,7 +97,7 @@ class ClipTowerHip:
 
 
 class LlamaHip:
-    def __init__(self, sd, cfg, dtype, device):
+    def __init__(self, sd, cfg, dtype, device, nf4=False, nf4_double_quant=True, nf4_lm_head=True):
         l = self.cfg = cfg
         self.dtype, self.device = dtype, device
         dev = device
@@ -106,7 +106,15 @@ class LlamaHip:
         self.layers = []
         F = l.ffn
         assert F % 16 == 0, "SwiGLU interleave needs ffn % 16 == 0"
-        for i in range(l.layers):
+        # load_in_4bit (quant.py): the seven projections of every layer (and lm_head unless nf4_lm_head=False) are quant.Nf4Weight.
+        # Products of <= 64 rows stream the packed weights (ops.linear_nf4); larger ones dequantise the weight into one f16 scratch
+        # right before the existing f16 product (_lin)
+        self.nf4 = bool(nf4)
+        self._scratch = None
+        if self.nf4:
+            assert dtype == torch.float16
+            self._load_nf4(sd, nf4_double_quant, nf4_lm_head)
+        for i in range(0 if self.nf4 else l.layers):
             L = f"model.layers.{i}"
             wqkv = torch.cat([sd[f"{L}.self_attn.{n}_proj.weight"] for n in ("q", "k", "v")], 0)
             wg, wu = sd[L + ".mlp.gate_proj.weight"], sd[L + ".mlp.up_proj.weight"]
@@ -121,10 +129,12 @@ class LlamaHip:
                 "wd": sd[L + ".mlp.down_proj.weight"].to(dev, dtype).contiguous()})
             del wqkv, wgu
         self.norm = _f32(sd["model.norm.weight"], dev)
-        self.lm_head = sd["lm_head.weight"].to(dev, dtype).contiguous()
+        if not (self.nf4 and nf4_lm_head):
+            self.lm_head = sd["lm_head.weight"].to(dev, dtype).contiguous()
         # Decode steps of <= 8 rows (round 5; <= 4 before) carry RMSNorm between the products (ops.linear_rms): no norm kernels, the q/k/v and gate/up
         # weights get a second copy with the norm weight folded in (built on first use; +9 GB at 7B, +18 GB at 13B of 288)
-        self.carry_rms = dtype in (torch.bfloat16, torch.float16) and self.hd == 128 and l.hidden % 128 == 0 and l.ffn % 128 == 0
+        # (off with NF4 weights: folding gamma into them would change the quantised values)
+        self.carry_rms = dtype in (torch.bfloat16, torch.float16) and self.hd == 128 and l.hidden % 128 == 0 and l.ffn % 128 == 0 and not self.nf4
         self.carry_rms_max_rows = 8   # the consumer side of haff_gemm_bf16_rms gathers the partials of <= 8 rows
         self._folded = None
         # Round 6: the whole <= 8-row decode step as ONE launch (ops.decode_chain, csrc/decode_chain.hip): the five stages of every
@@ -140,6 +150,48 @@ class LlamaHip:
         # down_proj add their fp32 accumulators to it and write fp32, RMSNorm reads it and rounds the NORMALISED row to bf16 once
         # for the bf16 MFMA products. Off by default (it gives up the norm-carrying 5-launch decode layer at <= 8 rows).
         self.fp32_stream = False
+
+    def _load_nf4(self, sd, double_quant, lm_head):
+        from . import quant
+        l, dev = self.cfg, self.device
+        H, F = l.hidden, l.ffn
+        g_rows, u_rows = quant.swiglu_rows(F)
+        for i in range(l.layers):
+            L = f"model.layers.{i}"
+            q = lambda parts: quant.quantize(parts, dev, double_quant)   # noqa: E731
+            self.layers.append({
+                "n1": _f32(sd[L + ".input_layernorm.weight"], dev),
+                "wqkv": q([(sd[f"{L}.self_attn.{n}_proj.weight"], None) for n in ("q", "k", "v")]),
+                "wo": q([(sd[L + ".self_attn.o_proj.weight"], None)]),
+                "n2": _f32(sd[L + ".post_attention_layernorm.weight"], dev),
+                "wgu": q([(sd[L + ".mlp.gate_proj.weight"], g_rows), (sd[L + ".mlp.up_proj.weight"], u_rows)]),
+                "wd": q([(sd[L + ".mlp.down_proj.weight"], None)])})
+        if lm_head:
+            self.lm_head = quant.quantize([(sd["lm_head.weight"], None)], dev, double_quant)
+        # one f16 scratch for the dequantised weight of a prefill-sized product, sized to the largest one (gate|up)
+        self._scratch_rows = max(3 * H, 2 * F, H)
+        self._rope_map = quant.rope_row_map(3 * H, dev) if (3 * H) % 256 == 0 else None
+
+    def _deq(self, w, rope=False):
+        N, K = w.shape
+        if self._scratch is None or self._scratch.numel() < N * K:
+            n = max(N * K, self._scratch_rows * K, 0 if self._scratch is None else self._scratch.numel())
+            self._scratch = torch.empty((n,), dtype=torch.float16, device=self.device)
+        return w.dequant(row_map=self._rope_map if rope else None, out=self._scratch[:N * K].view(N, K))
+
+    def _lin(self, x, w, **kw):
+        """ops.linear on a weight of this model: f16 (or bf16 / f32), or NF4 — streamed for <= 64 rows, else dequantised first."""
+        if not self.nf4 or isinstance(w, torch.Tensor):
+            return ops.linear(x, w, **kw)
+        if x.shape[0] <= 64:
+            return ops.linear_nf4(x, w.packed, w.absmax, **kw)
+        return ops.linear(x, self._deq(w), **kw)
+
+    def weight_bytes(self):
+        """Device bytes of the decoder layers' seven projections and lm_head (NF4: packed codes + absmax)."""
+        def nb(w):
+            return w.numel() * w.element_size() if isinstance(w, torch.Tensor) else w.nbytes
+        return sum(nb(L[k]) for L in self.layers for k in ("wqkv", "wo", "wgu", "wd")) + nb(self.lm_head)
 
     def _cos_sin(self, tmax):
         if self._cs is None or self._cs.shape[0] < tmax:
@@ -178,16 +230,17 @@ class LlamaHip:
             x = x.float()
         fused = self.fused_qkv_rope and T > 1 and \
             ops.qkv_rope_supported(B * T, nh, hd, H, self.dtype, 1 if self.fused_qkv_rope == "force" else 1024)
-        if fused and self._wqkv_rope is None:
+        if fused and self._wqkv_rope is None and not self.nf4:
             self._wqkv_rope = [ops.rope_permute_rows(L["wqkv"]) for L in self.layers]
         for li, L in enumerate(self.layers):
             h = ops.rmsnorm(x, L["n1"], l.rms_eps, out_dtype=nd)
             kc, vc = cache["k"][li], cache["v"][li]
             tk = pos0 + T
             if fused:
-                q = ops.qkv_rope(h, self._wqkv_rope[li], kc, vc, cs, B, T, nh, hd, pos0).view(B, T, nh, hd).permute(0, 2, 1, 3)
+                wr = self._deq(L["wqkv"], rope=True) if self.nf4 else self._wqkv_rope[li]
+                q = ops.qkv_rope(h, wr, kc, vc, cs, B, T, nh, hd, pos0).view(B, T, nh, hd).permute(0, 2, 1, 3)
             else:
-                qkv = ops.linear(h, L["wqkv"])
+                qkv = self._lin(h, L["wqkv"])
                 ops.rope_cache(qkv, kc, vc, cs, B, T, nh, nh, hd, pos0)
                 q = qkv.view(B, T, 3, nh, hd)[:, :, 0].permute(0, 2, 1, 3)
             k = kc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)[:, :, :tk]
@@ -196,10 +249,10 @@ class LlamaHip:
             a2 = a.view(B * T, H)
             if keep_rows is not None and li == len(self.layers) - 1:
                 a2, x = a2.index_select(0, keep_rows), x.index_select(0, keep_rows)   # (row gathers: the products below see n rows)
-            x = ops.linear(a2, L["wo"], resid=x, out=x)
+            x = self._lin(a2, L["wo"], resid=x, out=x)
             h = ops.rmsnorm(x, L["n2"], l.rms_eps, out_dtype=nd)
-            g = ops.linear(h, L["wgu"], swiglu=True)
-            x = ops.linear(g, L["wd"], resid=x, out=x)
+            g = self._lin(h, L["wgu"], swiglu=True)
+            x = self._lin(g, L["wd"], resid=x, out=x)
         cache["len"] = pos0 + T
         y = ops.rmsnorm(x, self.norm, l.rms_eps, out_dtype=nd)
         if keep_rows is not None:
@@ -230,7 +283,7 @@ class LlamaHip:
             return self._decode_rows_carry(x, cache, cs, nk)
         for li, L in enumerate(self.layers):
             h = ops.rmsnorm(x, L["n1"], l.rms_eps, out_dtype=nd)
-            qkv = ops.linear(h, L["wqkv"])
+            qkv = self._lin(h, L["wqkv"])
             kc, vc = cache["k"][li], cache["v"][li]
             if self.dtype in (torch.bfloat16, torch.float16) and hd == 128:
                 # RoPE of q and the new k, the cache append and the attention over the row's pos+1 keys in ONE launch
@@ -241,10 +294,10 @@ class LlamaHip:
                 k = kc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)
                 v = vc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)
                 a = ops.attention_decode_rows(q, k, v, hd ** -0.5, nk)
-            x = ops.linear(a.view(B, H), L["wo"], resid=x, out=x)
+            x = self._lin(a.view(B, H), L["wo"], resid=x, out=x)
             h = ops.rmsnorm(x, L["n2"], l.rms_eps, out_dtype=nd)
-            g = ops.linear(h, L["wgu"], swiglu=True)
-            x = ops.linear(g, L["wd"], resid=x, out=x)
+            g = self._lin(h, L["wgu"], swiglu=True)
+            x = self._lin(g, L["wd"], resid=x, out=x)
         return ops.rmsnorm(x, self.norm, l.rms_eps, out_dtype=nd).view(B, 1, H)
 
     def fold_norm_weights(self):
@@ -298,4 +351,4 @@ class LlamaHip:
 
     def next_token_logits(self, hidden_last):
         """hidden_last [B,H] -> fp32 logits [B,V] (lm_head, no bias; llava_llama.py:105)."""
-        return ops.linear(hidden_last, self.lm_head, out_dtype=torch.float32)
+        return self._lin(hidden_last, self.lm_head, out_dtype=torch.float32)

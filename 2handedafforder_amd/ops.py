@@ -273,6 +273,77 @@ def linear(x, w, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, ou
     return out
 
 
+def nf4_quantize(w, double_quant=True, row_map=None, packed=None, absmax=None):
+    """NF4 codes of an f16 weight [N, K] on the device (haff_nf4_quantize_f16; format: quant.py): returns (packed uint8 [R, K/2],
+    dequantised absmax f32 [R, K/64], offset f32 [1]). row_map (int32 [N]): source row n goes to row row_map[n] of packed / absmax
+    (given, with R rows; the q|k|v concatenation and the SwiGLU interleave); None: R = N, new tensors."""
+    lib = load_library()
+    _req(w, "w")
+    assert w.dtype == torch.float16 and w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    if K % 64:
+        raise ValueError(f"NF4 needs K % 64 == 0 (K = {K})")
+    if row_map is None:
+        packed = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device) if packed is None else packed
+        absmax = torch.empty((N, K // 64), dtype=torch.float32, device=w.device) if absmax is None else absmax
+        assert packed.shape[0] == N
+    else:
+        assert row_map.dtype == torch.int32 and row_map.numel() == N and packed is not None and absmax is not None
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.shape[1] == K // 2
+    assert absmax.dtype == torch.float32 and absmax.is_contiguous() and absmax.shape == (packed.shape[0], K // 64)
+    offset = torch.empty((1,), dtype=torch.float32, device=w.device)
+    ws = torch.empty((N * (K // 64),), dtype=torch.float32, device=w.device)
+    check(lib.haff_nf4_quantize_f16(w.data_ptr(), w.stride(0), N, K, 1 if double_quant else 0, _p(row_map), packed.data_ptr(),
+                                    absmax.data_ptr(), offset.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream()),
+          "haff_nf4_quantize_f16")
+    return packed, absmax, offset
+
+
+def nf4_dequant(packed, absmax, row_map=None, out=None):
+    """f16 [N, K] = f16_rn(NF4[code] * absmax) of the stored rows; row_map (int32 [N]): stored row n goes to out row row_map[n]."""
+    lib = load_library()
+    _req(packed, "packed")
+    N, K = packed.shape[0], packed.shape[1] * 2
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and absmax.dtype == torch.float32 and absmax.is_contiguous()
+    assert absmax.shape == (N, K // 64)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float16, device=packed.device)
+    assert out.dtype == torch.float16 and out.stride(1) == 1 and out.shape[1] == K
+    if row_map is not None:
+        assert row_map.dtype == torch.int32 and row_map.numel() == N
+    check(lib.haff_nf4_dequant_f16(packed.data_ptr(), absmax.data_ptr(), N, K, _p(row_map), out.data_ptr(), out.stride(0), _stream()),
+          "haff_nf4_dequant_f16")
+    return out
+
+
+def linear_nf4(x, packed, absmax, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, out_dtype=None, swiglu=False):
+    """linear() with NF4 weights (haff_gemm_nf4_f16): x f16 [M <= 64, K], packed uint8 [N, K/2], absmax f32 [N, K/64]; same
+    epilogue contract as linear()."""
+    lib = load_library()
+    _req(x, "x")
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float16
+    M, K = x.shape
+    N = packed.shape[0]
+    assert packed.dtype == torch.uint8 and packed.shape[1] * 2 == K and absmax.shape == (N, K // 64)
+    n_out = N // 2 if swiglu else N
+    if out_dtype is None:
+        out_dtype = x.dtype
+    if out is None:
+        out = torch.empty((M, n_out), dtype=out_dtype, device=x.device)
+    assert out.stride(1) == 1 and out.shape[1] == n_out and out.dtype in (torch.float16, torch.float32)
+    if resid is not None:
+        assert resid.dtype == out.dtype and resid.stride(1) == 1
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == N
+    if row_map is not None:
+        assert row_map.dtype == torch.int32 and row_map.numel() == M
+    rc = lib.haff_gemm_nf4_f16(x.data_ptr(), x.stride(0), packed.data_ptr(), absmax.data_ptr(), out.data_ptr(), out.stride(0),
+                               _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
+                               1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, _stream())
+    check(rc, "haff_gemm_nf4_f16")
+    return out
+
+
 def linear_heads_supported(M, N, K, d, heads, dtype):
     """Shapes haff_gemm_bf16_heads serves: whole 256 x 256 tiles of the 8-wave kernel, N = parts * heads * d."""
     return (dtype in (torch.bfloat16, torch.float16) and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and d % 8 == 0 and N % (heads * d) == 0

@@ -1,0 +1,136 @@
+"""4-bit NF4 language-model weights: the reference's `load_in_4bit=True` (2Haff/inference.py:133-146, chat.py the same) on the fp16
+mode's kernels.
+
+The reference loads `LISAForCausalLM.from_pretrained(..., torch_dtype=torch.half, quantization_config=BitsAndBytesConfig(
+load_in_4bit=True, bnb_4bit_compute_dtype=torch.float16, bnb_4bit_use_double_quant=True, bnb_4bit_quant_type="nf4",
+llm_int8_skip_modules=["visual_model"]))`. bitsandbytes is not a dependency of this project; what follows RESTATES its format
+(README, "What stays unpinned"):
+
+Which Linears become NF4 (`nf4_linear`): every nn.Linear that exists when from_pretrained runs and whose name does not contain
+"visual_model" — the Llama q/k/v/o/gate/up/down_proj, model.mm_projector (llava_arch.py:35), both text_hidden_fcs Linears
+(LISA.py:71-77) and lm_head (transformers 4.31 uses llm_int8_skip_modules INSTEAD of its default keep-list, so lm_head is
+converted too; restated, 4.31 is not installed here: `nf4_lm_head=False` keeps it fp16). SAM, the CLIP tower (loaded later by
+initialize_vision_modules), embed_tokens, the norms and the biases stay fp16.
+
+NF4 quantisation of one weight tensor W (fp16, after the fp16 mode's conversion check):
+  * W flattened row-major into blocks of 64 (every Linear here has K % 64 == 0, so a block never crosses a row);
+  * absmax = fp32 max |w| of the block;
+  * code = index of the NF4 value nearest to w * (1/absmax) (fp32 reciprocal, correctly rounded, then one fp32 multiply);
+    the decision thresholds are the fp32 midpoints of neighbouring NF4 values and a value exactly on one takes the LOWER code;
+    an all-zero block (absmax 0) gets code 7 (the value 0) everywhere. Either way such weights dequantise to 0;
+  * two codes per byte, the first element in the high nibble.
+Double quantisation (bnb_4bit_use_double_quant=True):
+  * offset = mean of the tensor's absmax values (here: summed in double, in a fixed order, rounded once to fp32);
+  * absmax - offset (fp32) is quantised in blocks of 256 consecutive values with the signed 8-bit dynamic map
+    (`dynamic_map()`, bitsandbytes' create_dynamic_map(signed=True) restated from its construction): absmax2 = fp32 max |.| of
+    the block, code = nearest map value to (absmax - offset) * (1/absmax2) (same midpoint rule; absmax2 == 0: the code of 0);
+  * dequantised absmax = map[code] * absmax2 + offset: an fp32 multiply, then an fp32 add (not fused).
+What enters a product: f16_rn(NF4[code] * absmax_dq), one fp32 multiply and one rounding — what bitsandbytes' dequantize_4bit
+returns for an fp16 compute dtype — then the fp16 mode's f16 MFMA product with fp32 accumulation. (For one-row inputs bitsandbytes
+runs gemv_4bit instead, whose summation order differs: within fp16 noise of the same values.)
+
+Storage here is row-local (csrc/gemm_nf4.hip): packed uint8 [N][K/2] and the DEQUANTISED absmax fp32 [N][K/64], so the q|k|v
+concatenation, the SwiGLU interleave and the RoPE row permutation are row reorders of stored NF4 rows; each source tensor is still
+quantised on its own, as the reference quantises each Linear. 4.5 bits per weight (bitsandbytes keeps the 8-bit absmax codes: 4.13).
+"""
+import re
+
+import torch
+
+from . import ops
+
+# bitsandbytes' NF4 code values
+NF4_VALUES = (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635, -0.18477343022823334,
+              -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725, 0.24611230194568634, 0.33791524171829224,
+              0.44070982933044434, 0.5626170039176941, 0.7229568362236023, 1.0)
+
+
+def nf4_table():
+    return torch.tensor(NF4_VALUES, dtype=torch.float32)
+
+
+def dynamic_map():
+    """The signed 8-bit dynamic map (256 fp32 values, sorted): for decade i = 0..6, the 2^i means of neighbouring points of
+    linspace(0.1, 1, 2^i + 1) (float32) times 10^(i - 6), with both signs; then 0 and +1 (the construction has no -1)."""
+    data = []
+    for i in range(7):
+        b = torch.linspace(0.1, 1, 2 ** i + 1)
+        means = (b[:-1] + b[1:]) / 2.0
+        data += ((10 ** (i - 6)) * means).tolist()
+        data += (-(10 ** (i - 6)) * means).tolist()
+    data += [0.0, 1.0]
+    data.sort()
+    return torch.tensor(data, dtype=torch.float32)
+
+
+_LLAMA_PROJ = re.compile(r"^model\.layers\.\d+\.(self_attn\.(q|k|v|o)_proj|mlp\.(gate|up|down)_proj)\.weight$")
+
+
+def nf4_linear(name, lm_head=True):
+    """True for the weight of an nn.Linear the reference's 4-bit load converts (module selection above)."""
+    if "visual_model" in name or not name.endswith(".weight"):
+        return False
+    if _LLAMA_PROJ.match(name):
+        return True
+    if name in ("model.mm_projector.weight", "model.text_hidden_fcs.0.0.weight", "model.text_hidden_fcs.0.2.weight"):
+        return True
+    return lm_head and name == "lm_head.weight"
+
+
+class Nf4Weight:
+    """An NF4 weight on the device: packed uint8 [N, K/2], dequantised absmax f32 [N, K/64]."""
+
+    def __init__(self, packed, absmax):
+        self.packed, self.absmax = packed, absmax
+        self.shape = (packed.shape[0], packed.shape[1] * 2)
+
+    @property
+    def nbytes(self):
+        return self.packed.numel() + self.absmax.numel() * 4
+
+    def dequant(self, row_map=None, out=None):
+        return ops.nf4_dequant(self.packed, self.absmax, row_map=row_map, out=out)
+
+
+def quantize(parts, device, double_quant=True):
+    """One Nf4Weight from source weights quantised EACH ON ITS OWN (as the reference quantises each Linear): parts = [(w, rows)],
+    w [n_i, K] (any float dtype, any device), rows = int tensor [n_i] of destination rows, or None (the rows stacked in order)."""
+    K = parts[0][0].shape[1]
+    R = sum(w.shape[0] for w, _ in parts)
+    packed = torch.empty((R, K // 2), dtype=torch.uint8, device=device)
+    absmax = torch.empty((R, K // 64), dtype=torch.float32, device=device)
+    r0 = 0
+    for w, rows in parts:
+        n = w.shape[0]
+        if rows is None:
+            rows = torch.arange(r0, r0 + n)
+        rmap = rows.to(device=device, dtype=torch.int32)
+        w16 = w.to(device=device, dtype=torch.float16).contiguous()
+        ops.nf4_quantize(w16, double_quant=double_quant, row_map=rmap, packed=packed, absmax=absmax)
+        del w16
+        r0 += n
+    return Nf4Weight(packed, absmax)
+
+
+def swiglu_rows(F):
+    """Destination rows of gate and up in the [gate x16 | up x16] interleave of LlamaHip."""
+    r = torch.arange(F)
+    base = (r // 16) * 32 + r % 16
+    return base, base + 16
+
+
+def rope_row_map(N, device):
+    """Output row map of the dequantisation that yields ops.rope_permute_rows(w): stored row idx[r] -> row r."""
+    j = torch.arange(256)
+    wn, t, i = j // 64, (j // 16) % 4, j % 16
+    logical = (wn // 2) * 128 + (t // 2) * 64 + (wn % 2) * 32 + (t % 2) * 16 + i
+    idx = (torch.arange(0, N, 256)[:, None] + logical[None, :]).reshape(-1)
+    inv = torch.empty_like(idx)
+    inv[idx] = torch.arange(N)
+    return inv.to(device=device, dtype=torch.int32)
+
+
+def round_trip(w, device, double_quant=True):
+    """f16 dequant(quantize(w)): the values of an NF4 Linear whose product keeps its 16/32-bit path (mm_projector,
+    text_hidden_fcs)."""
+    return quantize([(w, None)], device, double_quant).dequant()

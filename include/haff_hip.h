@@ -80,6 +80,24 @@ int haff_gemm_f16_ln(const void* A, long lda, const void* W, long ldw, void* C, 
 int haff_gemm_f16_heads(const void* A, long lda, const void* W, long ldw, void* C, const float* bias, const int* row_map,
                         const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads, long part_stride,
                         long head_stride, void* stream);
+/* NF4 language-model weights of the fp16 mode (load_in_4bit; csrc/gemm_nf4.hip, format restated in quant.py). Row-local storage:
+ * packed uint8 [N][K/2] (code of W[n][k] in byte k/2, even k in the high nibble), absmax f32 [N][K/64] = the DEQUANTISED block
+ * absmax; K % 64 == 0. A weight enters a product as f16_rn(NF4[code] * absmax).
+ * haff_nf4_quantize_f16: f16 W [N][K] (row stride ldw, 16-B aligned) -> packed / absmax, source row n written to row row_map[n]
+ * (NULL: n) of both outputs. Codes: nearest NF4 value to w * (1/absmax) (a value on a midpoint takes the lower code; an all-zero
+ * block has codes 7). double_quant 1: absmax goes through bitsandbytes' double quantisation (offset = mean absmax, summed in
+ * double in a fixed order, stored to *offset (device f32); blocks of 256 of absmax - offset on the signed dynamic map);
+ * 0: the raw absmax (*offset is still the mean). workspace: device, >= 4 * N * (K/64) bytes. */
+int haff_nf4_quantize_f16(const void* W, long ldw, int N, int K, int double_quant, const int* row_map, void* packed, float* absmax,
+                          float* offset, void* workspace, long workspace_bytes, void* stream);
+/* f16 out row row_map[n] (NULL: n; row stride ldo, 16-B aligned) = f16_rn(NF4[code] * absmax) of stored row n */
+int haff_nf4_dequant_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out, long ldo, void* stream);
+/* haff_gemm_f16 with NF4 weights for M <= 64 (decode steps, [SEG] rows, lm_head on the last rows): C = epi(A . dequant(W)^T), same
+ * epilogue contract (bias, act, resid may alias C, row_map, out_f32, swiglu on [gate x16 | up x16] rows). Weight-streaming kernel,
+ * fixed summation order (bitwise repeatable). M > 64: -2; K % 64, lda, misalignment, SwiGLU with N % 32 or resid: -1. */
+int haff_gemm_nf4_f16(const void* A, long lda, const void* Wq, const float* absmax, void* C, long ldc, const float* bias,
+                      const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
+                      void* stream);
 /* Decode-sized product (M <= 16; with ssq_in: M <= 8, ssq_n <= 512, ssq_in 16-B aligned; K % 128 == 0) that carries Llama's RMSNorm between products without a norm kernel
  * (transformers LlamaDecoderLayer as reached from 2Haff/model/llava/model/language_model/llava_llama.py:93-102:
  * input_layernorm -> q/k/v_proj, post_attention_layernorm -> gate/up_proj). ssq_in != NULL: row m of A . W^T is scaled by
