@@ -51,6 +51,11 @@ _PROTOS = {
     "haff_nf4_dequant_f16": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p],
     "haff_gemm_nf4_f16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
                           c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_int8_quantize_weight_f16": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "haff_int8_quantize_act_f16": [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
+                                   c_void_p, c_void_p, c_void_p],
+    "haff_gemm_int8_f16": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long,
+                           c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "haff_gemm_stream_cap": [c_void_p, c_int],
     "haff_decode_chain_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p],

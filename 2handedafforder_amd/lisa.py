@@ -49,7 +49,8 @@ def _check_fp16_weights(sd, device):
 
 class LisaMI355:
     def __init__(self, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", sam_chunk=8, fp32_tail=True, fp32_stream=False,
-                 neck_f32=False, load_in_4bit=False, bnb_4bit_use_double_quant=True, bnb_4bit_quant_type="nf4", nf4_lm_head=True):
+                 neck_f32=False, load_in_4bit=False, bnb_4bit_use_double_quant=True, bnb_4bit_quant_type="nf4", nf4_lm_head=True,
+                 load_in_8bit=False, llm_int8_threshold=6.0, llm_int8_has_fp16_weight=False, int8_lm_head=True):
         # load_in_4bit: the reference's bitsandbytes 4-bit load (inference.py:133-146): the fp16 mode with the Llama projections,
         # mm_projector, text_hidden_fcs and (nf4_lm_head) lm_head quantised to NF4 (quant.py). Refused combinations are ValueErrors
         if load_in_4bit:
@@ -58,6 +59,18 @@ class LisaMI355:
                                  f"pass dtype=torch.float16, not {dtype}")
             if bnb_4bit_quant_type != "nf4":
                 raise ValueError(f"load_in_4bit: bnb_4bit_quant_type={bnb_4bit_quant_type!r} is not supported (only 'nf4')")
+        # load_in_8bit: the reference's bitsandbytes 8-bit load (inference.py:147-156): the fp16 mode with the same Linears as LLM.int8
+        # (quant.py) on the int8 matrix cores
+        if load_in_8bit:
+            if load_in_4bit:
+                raise ValueError("load_in_4bit and load_in_8bit are exclusive (the reference's CLIs take one or the other)")
+            if dtype != torch.float16:
+                raise ValueError("load_in_8bit: the reference's 8-bit mode computes in float16 (torch_dtype=torch.half); "
+                                 f"pass dtype=torch.float16, not {dtype}")
+            if llm_int8_has_fp16_weight:
+                raise ValueError("load_in_8bit: llm_int8_has_fp16_weight=True (the 8-bit training layout) is not supported")
+            if not llm_int8_threshold >= 0:
+                raise ValueError(f"load_in_8bit: llm_int8_threshold must be >= 0 (got {llm_int8_threshold})")
         if not torch.cuda.is_available():
             raise RuntimeError("LisaMI355 needs an MI355X (HIP device); there is no CPU fallback for the hot path")
         from .lib import load_library
@@ -123,8 +136,11 @@ class LisaMI355:
         self.sam_decoder = SamPromptDecoderHip(sd, cfg.sam, tail, dev)
         self.clip = ClipTowerHip(sd, cfg.clip, dtype, dev)
         self.load_in_4bit = bool(load_in_4bit)
+        self.load_in_8bit = bool(load_in_8bit)
+        self.llm_int8_threshold = float(llm_int8_threshold)
         self.llm = LlamaHip(sd, cfg.llm, dtype, dev, nf4=self.load_in_4bit, nf4_double_quant=bnb_4bit_use_double_quant,
-                            nf4_lm_head=nf4_lm_head)
+                            nf4_lm_head=nf4_lm_head, int8=self.load_in_8bit, int8_threshold=self.llm_int8_threshold,
+                            int8_lm_head=int8_lm_head)
         # fp32 residual streams in the bf16 mode: True / "sam" / "llm" — the ViT-H and / or Llama hidden-state
         # stream kept in fp32 between the bf16 MFMA products (2.8x closer to the reference on the image embedding at depth 32)
         self.sam_encoder.fp32_stream = fp32_stream in (True, "sam", "both")
@@ -136,6 +152,10 @@ class LisaMI355:
             if self.load_in_4bit:
                 from . import quant
                 return quant.round_trip(sd[name], dev, bnb_4bit_use_double_quant).to(dt).contiguous()
+            if self.load_in_8bit:
+                # 8-bit mode: int8 products (ops.linear_int8), one segment per frame's rows (encode_images, seg_embeddings)
+                from . import quant
+                return quant.quantize_int8([(sd[name], None)], dev)
             return sd[name].to(dev, dt).contiguous()
         self.w_proj = lin_w("model.mm_projector.weight", dtype)
         self.b_proj = _f32(sd["model.mm_projector.bias"], dev)
@@ -152,6 +172,13 @@ class LisaMI355:
         images_clip = images_clip.to(self.device)
 
         def fn(x):
+            if self.load_in_8bit:
+                # the projector's call in the reference is one frame's 256 patch rows: one segment each (cls rows dropped first)
+                n = self.cfg.clip.n_patches
+                h = self.clip.hidden(x)
+                rows = h.view(B, n + 1, -1)[:, 1:].reshape(B * n, -1)
+                q = ops.int8_quantize_act(rows, self.llm_int8_threshold, n)
+                return (ops.linear_int8(q, self.w_proj.cb, self.w_proj.scb, bias=self.b_proj).view(B, n, -1),)
             return (self.clip.project(self.clip.hidden(x), B, self.w_proj, self.b_proj),)
         if not self.decode_graphs or B > 4:
             return fn(images_clip)[0]
@@ -189,7 +216,7 @@ class LisaMI355:
         cache = self._persistent_cache(B, T + max_new_tokens)
         st = cache["book"]
         keep = None
-        if needed_hidden_only and self.prune_last_layer:
+        if needed_hidden_only and self.prune_last_layer and not self.load_in_8bit:
             # evaluate() reads two kinds of prefill rows only: each row's last real position (the first token's logits) and the
             # positions in front of a [SEG] that is part of the PROMPT (LISA.py:457-465 gathers the state that precedes the token);
             # the last Llama layer skips o_proj / MLP / norm for every other row (LlamaHip.forward, keep_rows)
@@ -199,7 +226,8 @@ class LisaMI355:
             # id position j + 1 holds [SEG] -> seg_embeddings reads hidden row j + 255 (the reference's fixed 255-row shift, wherever
             # the <image> sentinel sits: LISA.py:459-463)
             keep = torch.unique(torch.cat([b_last, pb * T + pt + (n_img - 1)]))
-        prefill = self.llm.forward(x, cache, keep_rows=keep)   # causal: a row's real positions never see its padding
+        i8 = {"valid": t_rows.to(torch.int32)} if self.load_in_8bit else {}
+        prefill = self.llm.forward(x, cache, keep_rows=keep, **i8)   # causal: a row's real positions never see its padding
         if after_prefill is not None:                    # work the caller wants enqueued (elsewhere) behind the prefill
             after_prefill()
         hidden, out_ids = st["hidden"], st["out_ids"]    # persistent [B, tmax, H] / [B, tmax]: the decode graph writes into them
@@ -397,6 +425,23 @@ class LisaMI355:
         b_idx, t_idx = mask.nonzero(as_tuple=True)
         if b_idx.numel() == 0:
             return torch.empty((0, self.cfg.out_dim), dtype=self.tail_dtype, device=self.device), b_idx, counts
+        if self.load_in_8bit:
+            # text_hidden_fcs run over every row of each frame (LISA.py:470), one segment per frame's valid rows; the [SEG] rows'
+            # f16 outputs are then widened to fp32 for the tail
+            B, Th, H = hidden.shape
+            x = hidden.reshape(B * Th, H).contiguous()
+            # each frame's own rows (the reference generates one frame per call and stops at its EOS): output_ids is left-aligned per
+            # row, real prompt then the generated tokens, pad behind a finished row's EOS — its ids up to the last non-pad one, of
+            # which the image sentinel stands for 256 hidden rows and the last token has none
+            ids_real = output_ids != self.cfg.pad_token_id
+            pos = torch.arange(output_ids.shape[1], device=output_ids.device)
+            n_ids = torch.where(ids_real, pos[None, :] + 1, torch.zeros_like(pos)[None, :]).amax(1)
+            valid = (n_ids + N_IMG_PAD - 1).clamp(max=Th).to(torch.int32)
+            q = ops.int8_quantize_act(x, self.llm_int8_threshold, Th, valid)
+            h = ops.linear_int8(q, self.fc0[0].cb, self.fc0[0].scb, bias=self.fc0[1], act=ops.ACT_RELU)
+            q = ops.int8_quantize_act(h, self.llm_int8_threshold, Th, valid)
+            y = ops.linear_int8(q, self.fc2[0].cb, self.fc2[0].scb, bias=self.fc2[1])
+            return y.view(B, Th, -1)[b_idx, t_idx].to(self.tail_dtype).contiguous(), b_idx, counts
         rows = hidden[b_idx, t_idx].to(self.tail_dtype).contiguous()
         h = ops.linear(rows, self.fc0[0], bias=self.fc0[1], act=ops.ACT_RELU)
         return ops.linear(h, self.fc2[0], bias=self.fc2[1]), b_idx, counts

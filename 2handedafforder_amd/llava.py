@@ -97,7 +97,8 @@ class ClipTowerHip:
 
 
 class LlamaHip:
-    def __init__(self, sd, cfg, dtype, device, nf4=False, nf4_double_quant=True, nf4_lm_head=True):
+    def __init__(self, sd, cfg, dtype, device, nf4=False, nf4_double_quant=True, nf4_lm_head=True, int8=False, int8_threshold=6.0,
+                 int8_lm_head=True):
         l = self.cfg = cfg
         self.dtype, self.device = dtype, device
         dev = device
@@ -114,7 +115,15 @@ class LlamaHip:
         if self.nf4:
             assert dtype == torch.float16
             self._load_nf4(sd, nf4_double_quant, nf4_lm_head)
-        for i in range(0 if self.nf4 else l.layers):
+        # load_in_8bit (quant.py, LLM.int8): the seven projections (and lm_head unless int8_lm_head=False) are quant.Int8Weight; every
+        # product quantises its input rows with the outlier decomposition and runs on the int8 matrix cores (ops.linear_int8). The
+        # outlier columns are per frame and sticky across a frame's decode steps: masks beside the KV cache (new_cache, "i8")
+        self.int8, self.int8_threshold = bool(int8), float(int8_threshold)
+        self._i8_masks = None
+        if self.int8:
+            assert dtype == torch.float16 and not self.nf4
+            self._load_int8(sd, int8_lm_head)
+        for i in range(0 if (self.nf4 or self.int8) else l.layers):
             L = f"model.layers.{i}"
             wqkv = torch.cat([sd[f"{L}.self_attn.{n}_proj.weight"] for n in ("q", "k", "v")], 0)
             wg, wu = sd[L + ".mlp.gate_proj.weight"], sd[L + ".mlp.up_proj.weight"]
@@ -129,12 +138,13 @@ class LlamaHip:
                 "wd": sd[L + ".mlp.down_proj.weight"].to(dev, dtype).contiguous()})
             del wqkv, wgu
         self.norm = _f32(sd["model.norm.weight"], dev)
-        if not (self.nf4 and nf4_lm_head):
+        if not ((self.nf4 and nf4_lm_head) or (self.int8 and int8_lm_head)):
             self.lm_head = sd["lm_head.weight"].to(dev, dtype).contiguous()
         # Decode steps of <= 8 rows (round 5; <= 4 before) carry RMSNorm between the products (ops.linear_rms): no norm kernels, the q/k/v and gate/up
         # weights get a second copy with the norm weight folded in (built on first use; +9 GB at 7B, +18 GB at 13B of 288)
         # (off with NF4 weights: folding gamma into them would change the quantised values)
-        self.carry_rms = dtype in (torch.bfloat16, torch.float16) and self.hd == 128 and l.hidden % 128 == 0 and l.ffn % 128 == 0 and not self.nf4
+        self.carry_rms = dtype in (torch.bfloat16, torch.float16) and self.hd == 128 and l.hidden % 128 == 0 and l.ffn % 128 == 0 and not self.nf4 \
+            and not self.int8
         self.carry_rms_max_rows = 8   # the consumer side of haff_gemm_bf16_rms gathers the partials of <= 8 rows
         self._folded = None
         # Round 6: the whole <= 8-row decode step as ONE launch (ops.decode_chain, csrc/decode_chain.hip): the five stages of every
@@ -144,7 +154,7 @@ class LlamaHip:
         self._cs = None
         # Prefill-sized batches (>= 1024 rows: where the 8-wave tile runs anyway): RoPE and the KV-cache append ride in the q|k|v projection's epilogue
         # (ops.qkv_rope): the weights get a second, row-permuted copy on first use (+3.2 GB at 7B, +6.3 GB at 13B of 288)
-        self.fused_qkv_rope = True    # ("force": any prefill; False: haff_gemm_bf16 + haff_rope_cache)
+        self.fused_qkv_rope = not self.int8    # ("force": any prefill; False: haff_gemm_bf16 + haff_rope_cache)
         self._wqkv_rope = None
         # fp32 RESIDUAL STREAM (bf16 mode; round 5): the hidden-state stream lives in HBM as fp32 — o_proj /
         # down_proj add their fp32 accumulators to it and write fp32, RMSNorm reads it and rounds the NORMALISED row to bf16 once
@@ -172,6 +182,27 @@ class LlamaHip:
         self._scratch_rows = max(3 * H, 2 * F, H)
         self._rope_map = quant.rope_row_map(3 * H, dev) if (3 * H) % 256 == 0 else None
 
+    def _load_int8(self, sd, lm_head):
+        from . import quant
+        l, dev = self.cfg, self.device
+        g_rows, u_rows = quant.swiglu_rows(l.ffn)
+        q = lambda parts: quant.quantize_int8(parts, dev)   # noqa: E731
+        for i in range(l.layers):
+            L = f"model.layers.{i}"
+            self.layers.append({
+                "n1": _f32(sd[L + ".input_layernorm.weight"], dev),
+                "wqkv": q([(sd[f"{L}.self_attn.{n}_proj.weight"], None) for n in ("q", "k", "v")]),
+                "wo": q([(sd[L + ".self_attn.o_proj.weight"], None)]),
+                "n2": _f32(sd[L + ".post_attention_layernorm.weight"], dev),
+                "wgu": q([(sd[L + ".mlp.gate_proj.weight"], g_rows), (sd[L + ".mlp.up_proj.weight"], u_rows)]),
+                "wd": q([(sd[L + ".mlp.down_proj.weight"], None)])})
+        if lm_head:
+            self.lm_head = q([(sd["lm_head.weight"], None)])
+
+    def _i8_slot(self, li, j):
+        """Sticky-mask slot of a Linear input: layer li's q|k|v (0), o (1), gate|up (2), down (3) inputs; lm_head: li = None."""
+        return len(self.layers) * 4 if li is None else 4 * li + j
+
     def _deq(self, w, rope=False):
         N, K = w.shape
         if self._scratch is None or self._scratch.numel() < N * K:
@@ -179,10 +210,17 @@ class LlamaHip:
             self._scratch = torch.empty((n,), dtype=torch.float16, device=self.device)
         return w.dequant(row_map=self._rope_map if rope else None, out=self._scratch[:N * K].view(N, K))
 
-    def _lin(self, x, w, **kw):
-        """ops.linear on a weight of this model: f16 (or bf16 / f32), or NF4 — streamed for <= 64 rows, else dequantised first."""
-        if not self.nf4 or isinstance(w, torch.Tensor):
+    def _lin(self, x, w, slot=None, seg_rows=None, valid=None, **kw):
+        """ops.linear on a weight of this model: f16 (or bf16 / f32), NF4 — streamed for <= 64 rows, else dequantised first — or
+        LLM.int8: the rows quantised in segments of seg_rows (one frame each; valid rows per frame) against the sticky masks of slot."""
+        if isinstance(w, torch.Tensor):
             return ops.linear(x, w, **kw)
+        if self.int8:
+            masks = None
+            if self._i8_masks is not None and slot is not None and self.int8_threshold > 0:
+                masks = self._i8_masks[slot]
+            q = ops.int8_quantize_act(x, self.int8_threshold, seg_rows, valid, masks)
+            return ops.linear_int8(q, w.cb, w.scb, **kw)
         if x.shape[0] <= 64:
             return ops.linear_nf4(x, w.packed, w.absmax, **kw)
         return ops.linear(x, self._deq(w), **kw)
@@ -203,6 +241,15 @@ class LlamaHip:
 
     def new_cache(self, B, tmax):
         H = self.cfg.hidden
+        c = self._new_cache(B, tmax)
+        if self.int8:
+            # LLM.int8 sticky outlier-column masks per (Linear input, frame): uint32 words as int32 [B, K/32], 4 per layer + lm_head
+            z = lambda k: torch.zeros((B, k // 32), dtype=torch.int32, device=self.device)   # noqa: E731
+            c["i8"] = [z(self.cfg.ffn if j == 3 else H) for _ in self.layers for j in range(4)] + [z(H)]
+        return c
+
+    def _new_cache(self, B, tmax):
+        H = self.cfg.hidden
         return {"k": [torch.empty((B, tmax, H), dtype=self.dtype, device=self.device) for _ in self.layers],
                 "v": [torch.empty((B, tmax, H), dtype=self.dtype, device=self.device) for _ in self.layers],
                 "len": 0, "tmax": tmax,
@@ -210,13 +257,15 @@ class LlamaHip:
                 "pos": torch.zeros((B,), dtype=torch.int32, device=self.device),
                 "nk": torch.ones((B,), dtype=torch.int32, device=self.device)}
 
-    def forward(self, x, cache, keep_rows=None):
+    def forward(self, x, cache, keep_rows=None, valid=None):
         """x [B,T,H] embeddings of the next T positions; appends to the cache; returns post-norm hidden [B,T,H].
         keep_rows (round 6; int64 [n] flat row indices b * T + t, or None = all): the rows whose FINAL hidden state the caller will
         read. Every position still runs through every layer's attention inputs (its K / V are what later tokens attend to), but in
         the LAST layer only these rows take o_proj, the MLP and the final norm — nothing downstream of the last layer's K / V
         depends on the other rows (llava_llama.py:93-105 returns them, LISA.py:443-485 never looks at them); their rows of the
-        result are zero. 75 % of the last layer's linear FLOPs: 0.9 % of the step at 64 frames."""
+        result are zero. 75 % of the last layer's linear FLOPs: 0.9 % of the step at 64 frames.
+        valid (int32 [B] device, LLM.int8 only): real rows per frame (right padding): a prefill from position 0 resets the frames'
+        sticky masks and sets them from these rows (the outlier columns of lm_head's input too: the reference's lm_head sees every row)."""
         l = self.cfg
         B, T, H = x.shape
         nh, hd = l.heads, self.hd
@@ -230,6 +279,14 @@ class LlamaHip:
             x = x.float()
         fused = self.fused_qkv_rope and T > 1 and \
             ops.qkv_rope_supported(B * T, nh, hd, H, self.dtype, 1 if self.fused_qkv_rope == "force" else 1024)
+        i8 = {}
+        if self.int8:
+            assert keep_rows is None, "LLM.int8: every row of the last layer is an input of lm_head / text_hidden_fcs (prune_last_layer off)"
+            self._i8_masks = cache["i8"]
+            if pos0 == 0:
+                for m in cache["i8"]:
+                    m.zero_()
+            i8 = {"seg_rows": T, "valid": valid}
         if fused and self._wqkv_rope is None and not self.nf4:
             self._wqkv_rope = [ops.rope_permute_rows(L["wqkv"]) for L in self.layers]
         for li, L in enumerate(self.layers):
@@ -240,7 +297,7 @@ class LlamaHip:
                 wr = self._deq(L["wqkv"], rope=True) if self.nf4 else self._wqkv_rope[li]
                 q = ops.qkv_rope(h, wr, kc, vc, cs, B, T, nh, hd, pos0).view(B, T, nh, hd).permute(0, 2, 1, 3)
             else:
-                qkv = self._lin(h, L["wqkv"])
+                qkv = self._lin(h, L["wqkv"], slot=4 * li, **i8)
                 ops.rope_cache(qkv, kc, vc, cs, B, T, nh, nh, hd, pos0)
                 q = qkv.view(B, T, 3, nh, hd)[:, :, 0].permute(0, 2, 1, 3)
             k = kc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)[:, :, :tk]
@@ -249,12 +306,15 @@ class LlamaHip:
             a2 = a.view(B * T, H)
             if keep_rows is not None and li == len(self.layers) - 1:
                 a2, x = a2.index_select(0, keep_rows), x.index_select(0, keep_rows)   # (row gathers: the products below see n rows)
-            x = self._lin(a2, L["wo"], resid=x, out=x)
+            x = self._lin(a2, L["wo"], resid=x, out=x, slot=4 * li + 1, **i8)
             h = ops.rmsnorm(x, L["n2"], l.rms_eps, out_dtype=nd)
-            g = self._lin(h, L["wgu"], swiglu=True)
-            x = self._lin(g, L["wd"], resid=x, out=x)
+            g = self._lin(h, L["wgu"], swiglu=True, slot=4 * li + 2, **i8)
+            x = self._lin(g, L["wd"], resid=x, out=x, slot=4 * li + 3, **i8)
         cache["len"] = pos0 + T
         y = ops.rmsnorm(x, self.norm, l.rms_eps, out_dtype=nd)
+        if self.int8 and not isinstance(self.lm_head, torch.Tensor) and self.int8_threshold > 0:
+            # lm_head's outlier columns: every valid row of the final hidden state (the codes are not needed here)
+            ops.int8_quantize_act(y, self.int8_threshold, T, valid, cache["i8"][self._i8_slot(None, 0)])
         if keep_rows is not None:
             full = torch.zeros((B * T, H), dtype=y.dtype, device=y.device)
             full.index_copy_(0, keep_rows, y)
@@ -281,9 +341,13 @@ class LlamaHip:
             x = x.float()
         elif self.carry_rms and B <= self.carry_rms_max_rows:
             return self._decode_rows_carry(x, cache, cs, nk)
+        i8 = {}
+        if self.int8:
+            self._i8_masks = cache["i8"]
+            i8 = {"seg_rows": 1}     # one row per frame: its sticky masks
         for li, L in enumerate(self.layers):
             h = ops.rmsnorm(x, L["n1"], l.rms_eps, out_dtype=nd)
-            qkv = self._lin(h, L["wqkv"])
+            qkv = self._lin(h, L["wqkv"], slot=4 * li, **i8)
             kc, vc = cache["k"][li], cache["v"][li]
             if self.dtype in (torch.bfloat16, torch.float16) and hd == 128:
                 # RoPE of q and the new k, the cache append and the attention over the row's pos+1 keys in ONE launch
@@ -294,10 +358,10 @@ class LlamaHip:
                 k = kc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)
                 v = vc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)
                 a = ops.attention_decode_rows(q, k, v, hd ** -0.5, nk)
-            x = self._lin(a.view(B, H), L["wo"], resid=x, out=x)
+            x = self._lin(a.view(B, H), L["wo"], resid=x, out=x, slot=4 * li + 1, **i8)
             h = ops.rmsnorm(x, L["n2"], l.rms_eps, out_dtype=nd)
-            g = self._lin(h, L["wgu"], swiglu=True)
-            x = self._lin(g, L["wd"], resid=x, out=x)
+            g = self._lin(h, L["wgu"], swiglu=True, slot=4 * li + 2, **i8)
+            x = self._lin(g, L["wd"], resid=x, out=x, slot=4 * li + 3, **i8)
         return ops.rmsnorm(x, self.norm, l.rms_eps, out_dtype=nd).view(B, 1, H)
 
     def fold_norm_weights(self):
@@ -351,4 +415,6 @@ class LlamaHip:
 
     def next_token_logits(self, hidden_last):
         """hidden_last [B,H] -> fp32 logits [B,V] (lm_head, no bias; llava_llama.py:105)."""
+        if self.int8:   # one row per frame, against the frame's sticky lm_head masks (set by the prefill / decode steps)
+            return self._lin(hidden_last, self.lm_head, out_dtype=torch.float32, slot=self._i8_slot(None, 0), seg_rows=1)
         return self._lin(hidden_last, self.lm_head, out_dtype=torch.float32)

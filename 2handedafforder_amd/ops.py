@@ -344,6 +344,100 @@ def linear_nf4(x, packed, absmax, bias=None, act=ACT_NONE, resid=None, row_map=N
     return out
 
 
+def int8_quantize_weight(w, row_map=None, cb=None, scb=None):
+    """LLM.int8 codes of an f16 weight [N, K] on the device (haff_int8_quantize_weight_f16; arithmetic: quant.py): returns
+    (CB int8 [R, K], SCB f32 [R]). row_map (int32 [N]): source row n goes to row row_map[n] of the given cb / scb (R rows);
+    None: R = N, new tensors unless given."""
+    lib = load_library()
+    _req(w, "w")
+    assert w.dtype == torch.float16 and w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    if K % 64:
+        raise ValueError(f"int8 needs K % 64 == 0 (K = {K})")
+    if cb is None:
+        assert row_map is None
+        cb = torch.empty((N, K), dtype=torch.int8, device=w.device)
+        scb = torch.empty((N,), dtype=torch.float32, device=w.device)
+    assert cb.dtype == torch.int8 and cb.is_contiguous() and cb.shape[1] == K
+    assert scb.dtype == torch.float32 and scb.is_contiguous() and scb.numel() == cb.shape[0]
+    if row_map is not None:
+        assert row_map.dtype == torch.int32 and row_map.numel() == N
+    else:
+        assert cb.shape[0] == N
+    check(lib.haff_int8_quantize_weight_f16(w.data_ptr(), w.stride(0), N, K, _p(row_map), cb.data_ptr(), scb.data_ptr(), _stream()),
+          "haff_int8_quantize_weight_f16")
+    return cb, scb
+
+
+class Int8Rows:
+    """The quantised activation rows of one int8 product: x (the f16 rows, for the outlier values), CA int8 [M, K], SCA f32 [M],
+    cols int32 [S, K] / ncols int32 [S] (each segment's outlier columns, ascending), seg_rows."""
+
+    def __init__(self, x, ca, sca, cols, ncols, seg_rows):
+        self.x, self.ca, self.sca, self.cols, self.ncols, self.seg_rows = x, ca, sca, cols, ncols, seg_rows
+
+def int8_quantize_act(x, threshold, seg_rows=None, valid=None, masks=None):
+    """Row quantisation of f16 x [M, K] with the outlier decomposition (haff_int8_quantize_act_f16): segments of seg_rows rows (None:
+    one segment), valid (int32 [S] device, or None: every row) = the rows of each segment whose outliers count, masks (uint32-as-int32
+    [S, K/32] device; ORed into, so pass zeros for a fresh call or a frame's sticky masks; None: a zeroed scratch). -> Int8Rows."""
+    lib = load_library()
+    _req(x, "x")
+    assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+    M, K = x.shape
+    seg_rows = M if seg_rows is None else int(seg_rows)
+    S = (M + seg_rows - 1) // seg_rows
+    if K % 64:
+        raise ValueError(f"int8 needs K % 64 == 0 (K = {K})")
+    if threshold < 0:
+        raise ValueError(f"llm_int8_threshold must be >= 0 (got {threshold})")
+    dev = x.device
+    if masks is None and threshold > 0:
+        masks = torch.zeros((S, K // 32), dtype=torch.int32, device=dev)
+    if masks is not None:
+        assert masks.dtype == torch.int32 and masks.is_contiguous() and masks.shape == (S, K // 32)
+    if valid is not None:
+        assert valid.dtype == torch.int32 and valid.numel() == S
+    ca = torch.empty((M, K), dtype=torch.int8, device=dev)
+    sca = torch.empty((M,), dtype=torch.float32, device=dev)
+    cols = torch.empty((S, K), dtype=torch.int32, device=dev)
+    ncols = torch.empty((S,), dtype=torch.int32, device=dev)
+    check(lib.haff_int8_quantize_act_f16(x.data_ptr(), x.stride(0), M, K, float(threshold), seg_rows, _p(valid), _p(masks),
+                                         ca.data_ptr(), K, sca.data_ptr(), cols.data_ptr(), ncols.data_ptr(), _stream()),
+          "haff_int8_quantize_act_f16")
+    return Int8Rows(x, ca, sca, cols, ncols, seg_rows)
+
+
+INT8_AUTO, INT8_SKINNY, INT8_TILED = 0, 1, 2
+
+
+def linear_int8(q, cb, scb, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, out_dtype=None, swiglu=False, form=INT8_AUTO):
+    """linear() with LLM.int8 weights (haff_gemm_int8_f16): q = int8_quantize_act(...) of the input rows, cb int8 [N, K], scb f32 [N];
+    same epilogue contract as linear(), applied to the f16 product Y. form: INT8_AUTO (by M), INT8_SKINNY (M <= 64), INT8_TILED."""
+    lib = load_library()
+    x = q.x
+    M, K = x.shape
+    N = cb.shape[0]
+    assert cb.dtype == torch.int8 and cb.is_contiguous() and cb.shape[1] == K and scb.numel() == N
+    n_out = N // 2 if swiglu else N
+    if out_dtype is None:
+        out_dtype = x.dtype
+    if out is None:
+        out = torch.empty((M, n_out), dtype=out_dtype, device=x.device)
+    assert out.stride(1) == 1 and out.shape[1] == n_out and out.dtype in (torch.float16, torch.float32)
+    if resid is not None:
+        assert resid.dtype == out.dtype and resid.stride(1) == 1
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == N
+    if row_map is not None:
+        assert row_map.dtype == torch.int32 and row_map.numel() == M
+    rc = lib.haff_gemm_int8_f16(x.data_ptr(), x.stride(0), q.ca.data_ptr(), q.ca.stride(0), q.sca.data_ptr(), cb.data_ptr(),
+                                scb.data_ptr(), q.cols.data_ptr(), q.ncols.data_ptr(), q.seg_rows, out.data_ptr(), out.stride(0),
+                                _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
+                                1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, int(form), _stream())
+    check(rc, "haff_gemm_int8_f16")
+    return out
+
+
 def linear_heads_supported(M, N, K, d, heads, dtype):
     """Shapes haff_gemm_bf16_heads serves: whole 256 x 256 tiles of the 8-wave kernel, N = parts * heads * d."""
     return (dtype in (torch.bfloat16, torch.float16) and M % 256 == 0 and N % 256 == 0 and K % 64 == 0 and d % 8 == 0 and N % (heads * d) == 0

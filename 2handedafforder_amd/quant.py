@@ -134,3 +134,127 @@ def round_trip(w, device, double_quant=True):
     """f16 dequant(quantize(w)): the values of an NF4 Linear whose product keeps its 16/32-bit path (mm_projector,
     text_hidden_fcs)."""
     return quantize([(w, None)], device, double_quant).dequant()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# LLM.int8: the reference's `load_in_8bit=True` (2Haff/inference.py:147-156; chat.py / app.py the same)
+# ---------------------------------------------------------------------------------------------------------------------------------
+# LLM.int8 language-model weights (bitsandbytes 0.41.1 `BitsAndBytesConfig(load_in_8bit=True, llm_int8_skip_modules=
+# ["visual_model"])` under transformers 4.31.0: llm_int8_threshold 6.0, llm_int8_has_fp16_weight False), RESTATED — bitsandbytes is not
+# a dependency, and the steps below are what this project computes (README, "What stays unpinned": the constant C and whether the row
+# absmax skips outlier elements or whole columns).
+#
+# Module selection: that of the 4-bit load (`nf4_linear`; `int8_lm_head=False` keeps lm_head fp16).
+#
+# Weights (Int8Params.cuda -> double_quant(W), threshold 0), per output row n:
+#   SCB[n] = fp32 max |W[n, :]|;  CB[n, k] = rint(f32(W[n, k]) * (127.0f / SCB[n]))  (one fp32 division per row, then one fp32 multiply
+#   per weight, rint = round half to even); SCB 0: every code 0.
+# Every call of a converted Linear (MatMul8bitLt.forward) on fp16 rows A [M, K], threshold t:
+#   1. outlier elements: |a| >= t (t = 0: none);
+#   2. SCA[m] = fp32 max |a| over row m's NON-OUTLIER elements (0 if there are none);
+#   3. CA[m, k] = rint(a * (127.0f / SCA[m])), 0 for an outlier element; SCA[m] = 0: every code 0 (bitsandbytes would compute 0 * inf);
+#   4. idx = the sorted columns holding an outlier in ANY row of the call; CA[:, idx] = 0 in every row;
+#   5. subA = A[:, idx] (fp16), subB = f16((f32(CB[:, idx]) * SCB[:, None]) / 127.0f) (a division, not a reciprocal multiply);
+#   6. Y = f16(f32(CA . CB^T) * C * SCA[m] * SCB[n] + bias[n]), left to right, each operation rounded to fp32 (no contraction);
+#      C = 6.200012e-05f; the int32 accumulation is exact (|acc| <= 127^2 * 11008 < 2^31);
+#   7. if idx is not empty: Y = f16(f32(Y) + f32(f16(subA . subB^T))), the outlier product a fixed-order fp32 sum over ascending columns
+#      (f16 x f16 is exact in fp32, so fma and multiply-then-add agree).
+# Whose rows form "the call": the reference generates with use_cache=False (LISA.py:115), one frame per call, recomputing the whole
+# prefix for every token. A SEGMENT here is one frame's valid rows; idx is per segment, never over a batch, never over padding rows.
+# KV-cached decoding keeps per-(frame, Linear input) STICKY column masks — the prefill sets them from the frame's rows, every decode step
+# ORs its row's outliers in before quantising — so the newest row is quantised exactly as the reference's last row. Deviation left:
+# when a decode step adds a column the reference would requantise the earlier rows too; their cached K / V keep the old values.
+
+
+def int8_quantize_weight_cpu(w):
+    """(CB int8 [N, K], SCB f32 [N]) of a weight (any float dtype; rounded to fp16 first, as the reference loads it)."""
+    w = w.to(torch.float16).float()
+    scb = w.abs().amax(1)
+    s = torch.where(scb > 0, torch.tensor(127.0, dtype=torch.float32) / scb, torch.zeros_like(scb))
+    return torch.round(w * s[:, None]).to(torch.int8), scb
+
+
+def int8_quantize_rows_cpu(a, threshold, seg_rows=None, valid=None, masks=None):
+    """Steps 1-4 on fp16 rows a [M, K]: -> (CA int8 [M, K], SCA f32 [M], cols bool [S, K]). Segments of seg_rows rows (None: one),
+    valid[s] of them counting (None: all); masks (bool [S, K]) are ORed into in place (the sticky masks) when given."""
+    a = a.to(torch.float16).float()
+    M, K = a.shape
+    seg_rows = M if seg_rows is None else seg_rows
+    S = (M + seg_rows - 1) // seg_rows
+    out = (a.abs() >= threshold) if threshold > 0 else torch.zeros_like(a, dtype=torch.bool)
+    sca = torch.where(out, torch.zeros_like(a), a.abs()).amax(1)
+    seg = torch.arange(M) // seg_rows
+    ok = torch.ones(M, dtype=torch.bool) if valid is None else (torch.arange(M) - seg * seg_rows) < torch.as_tensor(valid)[seg]
+    cols = torch.zeros((S, K), dtype=torch.bool) if masks is None else masks
+    for s in range(S):
+        rows = (seg == s) & ok
+        cols[s] |= out[rows].any(0)
+    sc = torch.where(sca > 0, torch.tensor(127.0, dtype=torch.float32) / sca, torch.zeros_like(sca))
+    ca = torch.round(a * sc[:, None])
+    ca = torch.where(out | cols[seg], torch.zeros_like(ca), ca)
+    return ca.to(torch.int8), sca, cols
+
+
+INT8_C = 6.200012e-05
+
+
+def int8_linear_cpu(a, cb, scb, ca, sca, cols, seg_rows=None, bias=None):
+    """Steps 5-7: the f16 Y [M, N] of a converted Linear from the quantised rows (int8_quantize_rows_cpu) and weights."""
+    a = a.to(torch.float16).float()
+    M = a.shape[0]
+    seg_rows = M if seg_rows is None else seg_rows
+    acc = (ca.long() @ cb.long().t()).float()
+    c = torch.tensor(INT8_C, dtype=torch.float32)
+    t = acc * c
+    t = t * sca[:, None]
+    t = t * scb[None, :]
+    if bias is not None:
+        t = t + bias.float()[None, :]
+    y = t.half().float()
+    seg = torch.arange(M) // seg_rows
+    for s in range(cols.shape[0]):
+        idx = cols[s].nonzero().flatten()
+        rows = (seg == s).nonzero().flatten()
+        if idx.numel() == 0 or rows.numel() == 0:
+            continue
+        sub_b = ((cb[:, idx].float() * scb[:, None]) / 127.0).half().float()      # [N, n]
+        sub_a = a[rows][:, idx]                                                   # [r, n]
+        o = torch.zeros((rows.numel(), cb.shape[0]), dtype=torch.float32)
+        for j in range(idx.numel()):                                              # fixed order: ascending columns
+            o = o + sub_a[:, j:j + 1] * sub_b[None, :, j]
+        y[rows] = (y[rows] + o.half().float()).half().float()
+    return y.half()
+
+
+class Int8Weight:
+    """An LLM.int8 weight on the device: CB int8 [N, K], SCB f32 [N] (no fp16 copy is kept)."""
+
+    def __init__(self, cb, scb):
+        self.cb, self.scb = cb, scb
+        self.shape = tuple(cb.shape)
+
+    @property
+    def nbytes(self):
+        return self.cb.numel() + self.scb.numel() * 4
+
+
+def quantize_int8(parts, device):
+    """One Int8Weight from source weights parts = [(w, rows)] (rows: int tensor of destination rows, or None: stacked in order). Row
+    quantisation is row-local, so the q|k|v concatenation and the SwiGLU interleave are row reorders of CB / SCB."""
+    K = parts[0][0].shape[1]
+    R = sum(w.shape[0] for w, _ in parts)
+    cb = torch.empty((R, K), dtype=torch.int8, device=device)
+    scb = torch.empty((R,), dtype=torch.float32, device=device)
+    r0 = 0
+    for w, rows in parts:
+        n = w.shape[0]
+        if rows is None:
+            rows = torch.arange(r0, r0 + n)
+        w16 = w.to(device=device, dtype=torch.float16).contiguous()
+        ops.int8_quantize_weight(w16, row_map=rows.to(device=device, dtype=torch.int32), cb=cb, scb=scb)
+        del w16
+        r0 += n
+    return Int8Weight(cb, scb)
+
+
+int8_linear = nf4_linear   # the same module selection

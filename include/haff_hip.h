@@ -98,6 +98,26 @@ int haff_nf4_dequant_f16(const void* packed, const float* absmax, int N, int K, 
 int haff_gemm_nf4_f16(const void* A, long lda, const void* Wq, const float* absmax, void* C, long ldc, const float* bias,
                       const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
                       void* stream);
+/* LLM.int8 language-model weights of the fp16 mode (load_in_8bit; csrc/gemm_int8.hip, arithmetic restated in quant.py). K % 64 == 0.
+ * haff_int8_quantize_weight_f16: f16 W [N][K] (row stride ldw, 16-B aligned) -> CB int8 [.][K] = rint(w * (127 / SCB)) and
+ * SCB f32 = max |W[n][:]| (0: all-zero codes), source row n written to row row_map[n] (NULL: n). CB 16-B aligned. */
+int haff_int8_quantize_weight_f16(const void* W, long ldw, int N, int K, const int* row_map, void* CB, float* SCB, void* stream);
+/* Row quantisation of f16 A [M][K] with outlier decomposition. Rows [s * seg_rows, (s + 1) * seg_rows) form segment s (a frame);
+ * its first seg_valid[s] rows (NULL: all) OR their outlier columns (|a| >= threshold; threshold 0: none) into masks[s] (uint32
+ * [S][K/32], bit c % 32 of word c / 32; never cleared here: zeroed by the caller for a fresh call, kept for sticky decode masks).
+ * SCA[m] = max |a| over row m's non-outlier elements; CA[m] (int8, row stride ldca % 16 == 0) = rint(a * (127 / SCA[m])), 0 on
+ * the columns of its segment's mask and on its own outliers (SCA 0: all zero); cols[s][0 .. ncols[s]) (int32 [S][K]) = the
+ * segment's columns, ascending. masks may be NULL with threshold 0. */
+int haff_int8_quantize_act_f16(const void* A, long lda, int M, int K, float threshold, int seg_rows, const int* seg_valid,
+                               unsigned* masks, void* CA, long ldca, float* SCA, int* cols, int* ncols, void* stream);
+/* The int8 product: Y = f16(f32(CA . CB^T) * 6.200012e-05f * SCA[m] * SCB[n] + bias[n]) (left to right, not contracted), then for a
+ * row whose segment (m / seg_rows) has columns: Y = f16(Y + f16(sum over its columns c, ascending, in fp32, of A[m][c] *
+ * f16(CB[n][c] * SCB[n] / 127))). Then haff_gemm_f16's epilogue on Y: act, resid (may alias C), row_map, out_f32, swiglu on
+ * [gate x16 | up x16] rows. cols / ncols NULL: no outlier term (A may then be NULL). form 0: by M (<= 64 weight-streaming,
+ * else tiled), 1: weight-streaming (M > 64: -2), 2: tiled. Every form gives the same bits for a row. */
+int haff_gemm_int8_f16(const void* A, long lda, const void* CA, long ldca, const float* SCA, const void* CB, const float* SCB,
+                       const int* cols, const int* ncols, int seg_rows, void* C, long ldc, const float* bias, const void* resid, long ldr,
+                       const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu, int form, void* stream);
 /* Decode-sized product (M <= 16; with ssq_in: M <= 8, ssq_n <= 512, ssq_in 16-B aligned; K % 128 == 0) that carries Llama's RMSNorm between products without a norm kernel
  * (transformers LlamaDecoderLayer as reached from 2Haff/model/llava/model/language_model/llava_llama.py:93-102:
  * input_layernorm -> q/k/v_proj, post_attention_layernorm -> gate/up_proj). ssq_in != NULL: row m of A . W^T is scaled by
