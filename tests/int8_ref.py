@@ -84,3 +84,64 @@ def linear(a, w_cb, w_scb, threshold, seg_rows=None, valid=None, masks=None, bia
     """One converted Linear on fp16 rows a: quantise the rows, then the product -> f16 [M, N]."""
     ca, sca, masks = quantize_rows(a, threshold, seg_rows, valid, masks)
     return product(a, ca, sca, w_cb, w_scb, masks, seg_rows, bias)
+
+
+ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU, ACT_SILU = 0, 1, 2, 3, 4
+EXACT_ACTS = (ACT_NONE, ACT_RELU)   # the epilogues below that are bit-exact; the others use the device's erff / __expf / rcpf
+
+
+def _erf(x):
+    import math
+    return np.vectorize(math.erf, otypes=[np.float64])(x)
+
+
+def _act(v, act):
+    """act of fp32 values v: ACT_NONE / ACT_RELU exactly in fp32, the others in float64 (the exact function of the fp32 input)."""
+    if act == ACT_NONE:
+        return v
+    if act == ACT_RELU:
+        return np.maximum(v, np.float32(0))
+    x = v.astype(np.float64)
+    if act == ACT_GELU:
+        return 0.5 * x * (1.0 + _erf(x * 0.7071067811865476))
+    if act == ACT_QUICK_GELU:
+        return x / (1.0 + np.exp(-1.702 * x))
+    if act == ACT_SILU:
+        return x / (1.0 + np.exp(-x))
+    raise ValueError(f"unknown act {act}")
+
+
+def swiglu_split(y):
+    """(gate, up) columns of a [.., N] product whose weight rows are interleaved [gate x16 | up x16] -> two [.., N/2]."""
+    t = np.asarray(y).reshape(*np.shape(y)[:-1], -1, 2, 16)
+    return t[..., 0, :].reshape(*np.shape(y)[:-1], -1), t[..., 1, :].reshape(*np.shape(y)[:-1], -1)
+
+
+def epilogue(y, act=ACT_NONE, resid=None, out_f32=False, row_map=None, swiglu=False, out=None):
+    """The int8 product's epilogue (gemm_int8.hip i8_epilogue) on the f16 Y that product() returns: act (or SwiGLU of the interleaved
+    gate / up columns) of the f16-valued Y in fp32, + resid (indexed like the output) in fp32, stored as f16 (round to nearest even)
+    or fp32, row m to output row row_map[m] (-1: not written). out: the output's contents before the call (rows the map does not
+    write keep them; None: zeros of [M, n_out]). Returns the new output (float16 or float32).
+
+    ACT_NONE / ACT_RELU without SwiGLU are exact restatements. GELU, quick-GELU, SiLU and SwiGLU are evaluated in float64 from the
+    same fp32 inputs, then rounded once to fp32: the device's erff / __expf / rcpf differ from them by a few fp32 ulps."""
+    y = np.asarray(y).astype(np.float32)
+    if swiglu:
+        g, u = swiglu_split(y)
+        g64 = g.astype(np.float64)
+        v = (g64 / (1.0 + np.exp(-g64)) * u.astype(np.float64)).astype(np.float32)
+    else:
+        v = np.asarray(_act(y, act)).astype(np.float32)
+    M, n_out = v.shape
+    odt = np.float32 if out_f32 else np.float16
+    res = np.zeros((M, n_out), dtype=odt) if out is None else np.array(out, dtype=odt)
+    rows = np.arange(M) if row_map is None else np.asarray(row_map)
+    for m in range(M):
+        r = int(rows[m])
+        if r < 0:
+            continue
+        t = v[m]
+        if resid is not None:
+            t = (t + np.asarray(resid, dtype=np.float32)[r]).astype(np.float32)
+        res[r] = t.astype(odt)
+    return res

@@ -57,3 +57,38 @@ def dequant(packed, absmax):
     N = packed.shape[0]
     codes = torch.stack([packed >> 4, packed & 15], dim=2).reshape(N, -1).long()
     return (NF4[codes].reshape(N, -1, 64) * absmax[:, :, None]).reshape(N, -1).half()
+
+
+# The tolerance of the NF4 product against product() below: C_ACC * (sum_k |x w| + |bias|), plus the output's rounding.
+# haff_gemm_nf4_f16 multiplies f16 x by f16 weights (exact in fp32) and accumulates in fp32: each of its 8 waves chains two
+# v_mfma_f32_16x16x32_f16 per 64-block of its K range, then the 8 partial sums are added in wave order and the bias added. At the
+# largest K the model runs (13824: 216 blocks, 27 per wave) that is 54 MFMAs, 7 adds and the bias: counting two roundings per MFMA
+# (its internal sum, then the add into the accumulator) and each rounding as a whole fp32 ulp (2^-23, which holds for a
+# truncating adder as much as for round to nearest), the error is below (2 * 54 + 8) * 2^-23 = 1.38e-5 of sum |x w| + |bias|.
+# C_ACC = 2^-16 (1.53e-5) is that bound rounded up to a power of two. tests/test_nf4_cpu.py shows that it still rejects one
+# dropped 64-block, a neighbouring block's absmax, a row shift inside a weight tile and a wrong row of an activation tile.
+C_ACC = 2.0 ** -16
+
+
+def product(x16, packed, absmax, bias=None):
+    """float64 [M, N] = x16 [M, K] (f16 values) @ dequant(packed, absmax).T (+ bias): the NF4 product without any rounding but the
+    weights' own f16_rn(NF4[code] * absmax)."""
+    w = dequant(packed, absmax).double()
+    y = x16.double() @ w.T
+    return y if bias is None else y + bias.double()[None, :]
+
+
+def magnitude(x, wdeq, bias=None):
+    """float64 [M, N] = sum_k |x w| (+ |bias|): the scale of the accumulation error."""
+    m = x.double().abs() @ wdeq.double().abs().T
+    return m if bias is None else m + bias.double().abs()[None, :]
+
+
+def tol(x, wdeq, bias, out_dtype, ref=None):
+    """float64 [M, N]: how far the NF4 product (f16 x [M, K], dequantised weights [N, K], fp32 bias or None) may lie from product():
+    C_ACC * magnitude, plus one ulp of the output format at |ref| (ref: the reference output values; None: no output rounding)."""
+    t = C_ACC * magnitude(x, wdeq, bias)
+    if ref is not None:
+        r = ref.double().abs()
+        t = t + (r.clamp_min(2.0 ** -14) * 2.0 ** -10 if out_dtype == torch.float16 else r * 2.0 ** -23)
+    return t

@@ -112,6 +112,39 @@ def test_outlier_product_by_hand(R):
     assert y[0, 0] == expect0 and abs(float(y[0, 0]) - (8 * 0.5 - 1)) < 0.05   # (0.5 is stored as 64 / 127)
 
 
+
+def test_epilogue_by_hand():
+    """int8_ref.epilogue: act on the f16 Y in fp32, + resid in fp32, one rounding to f16 (or none for fp32 out), the row map."""
+    R = sys.modules["int8_ref"]
+    y = np.array([[1.5, -2.0, 65504.0], [0.0009765625, -0.5, 3.0]], dtype=np.float16)
+    assert np.array_equal(R.epilogue(y), y)
+    assert R.epilogue(y, R.ACT_RELU).tolist() == [[1.5, 0.0, 65504.0], [0.0009765625, 0.0, 3.0]]
+    # 2049 + 1 = 2050 in fp32 then f16 (spacing 2 above 2048): exact; 2048 + 1 in fp32 is 2049 -> ties to even 2048 in f16
+    r = np.array([[2049.0, 1.0, -65504.0], [2048.0, 0.5, 1.0]], dtype=np.float16)
+    y2 = np.array([[1.0, 1.0, 0.0], [1.0, 0.5, 0.0]], dtype=np.float16)
+    assert R.epilogue(y2, resid=r).tolist() == [[2048.0, 2.0, -65504.0], [2048.0, 1.0, 1.0]]
+    # fp32 out keeps 2048 + 1 and the overflow of an f16 sum
+    assert R.epilogue(y2, resid=r.astype(np.float32), out_f32=True).tolist() == [[2049.0, 2.0, -65504.0], [2049.0, 1.0, 1.0]]
+    with np.errstate(over="ignore"):
+        assert np.isinf(R.epilogue(np.array([[65504.0]], np.float16), resid=np.array([[32.0]], np.float16))[0, 0])
+    # the row map sends row 0 to output row 2, drops row 1, and the residual is read at the output row
+    out = np.full((3, 3), 7.0, dtype=np.float16)
+    res = np.arange(9, dtype=np.float16).reshape(3, 3)
+    got = R.epilogue(y, resid=res, row_map=[2, -1], out=out)
+    assert got.tolist() == [[7.0] * 3, [7.0] * 3, [7.5, 5.0, 65504.0]]
+    # the transcendental acts are the exact functions of their fp32 input, rounded once
+    x = np.array([[-3.0, -1.0, 0.0, 0.5, 2.0]], dtype=np.float16)
+    assert np.allclose(R.epilogue(x, R.ACT_SILU, out_f32=True), x / (1 + np.exp(-x.astype(np.float64))), rtol=1e-7)
+    assert np.allclose(R.epilogue(x, R.ACT_GELU, out_f32=True)[0], [-0.0040496940948904, -0.15865525393145707, 0.0, 0.34573123063700656,
+                                                                 1.9544997361036416], rtol=1e-7)
+    assert np.allclose(R.epilogue(x, R.ACT_QUICK_GELU, out_f32=True), x / (1 + np.exp(-1.702 * x.astype(np.float64))), rtol=1e-7)
+    # SwiGLU: output column 16 j + i = silu(Y[32 j + i]) * Y[32 j + 16 + i]
+    y3 = np.zeros((1, 64), dtype=np.float16)
+    y3[0, 3], y3[0, 19], y3[0, 32], y3[0, 48] = 2.0, 3.0, -1.0, 4.0
+    s = R.epilogue(y3, swiglu=True, out_f32=True)
+    assert s.shape == (1, 32) and np.count_nonzero(s) == 2
+    assert np.isclose(s[0, 3], 2 / (1 + np.exp(-2.0)) * 3, rtol=1e-7) and np.isclose(s[0, 16], -1 / (1 + np.exp(1.0)) * 4, rtol=1e-7)
+
 @pytest.mark.parametrize("thr", [6.0, 1.5, 0.0])
 def test_quant_module_agrees_with_restatement(thr):
     R = sys.modules["int8_ref"]

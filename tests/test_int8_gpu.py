@@ -323,11 +323,13 @@ def test_load_in_8bit_matches_int8_oracle(dev, cfg_name):
         assert stats["int8"]["int8"][1] <= 1e-3, stats
 
 
-def test_full_width_7b_layer_against_oracle(dev):
+def _full_width_layer_against_oracle(dev, width):
+    """One Llama layer at 7B / 13B width, 2 frames x 16 rows (M = 32: the weight-streaming form's MT = 2, two weight tiles per
+    workgroup for q|k|v), against the oracle with int8_ref Linears: the mean relative error at most half the fp16 model's."""
     from haff import config as hcfg
     from haff.llava import LlamaHip
     from oracle import lisa_oracle as O
-    lc = hcfg.haff_7b().llm
+    lc = (hcfg.haff_7b() if width == "7B" else hcfg.haff_13b()).llm
     lc.layers = 1
     H, F = lc.hidden, lc.ffn
     g = torch.Generator().manual_seed(9)
@@ -352,8 +354,16 @@ def test_full_width_7b_layer_against_oracle(dev):
         got = m.forward(x.half().to(dev), cache, **kw).float().cpu()
         errs[name] = ((got - ref).abs().mean() / ref.abs().mean()).item()
         del m
-    print(f"7B-width layer vs int8 oracle: mean rel err int8 {errs['int8']:.3e}, fp16 {errs['fp16']:.3e}")
+    print(f"{width}-width layer vs int8 oracle: mean rel err int8 {errs['int8']:.3e}, fp16 {errs['fp16']:.3e}")
     assert errs["int8"] <= 0.5 * errs["fp16"]
+
+
+def test_full_width_7b_layer_against_oracle(dev):
+    _full_width_layer_against_oracle(dev, "7B")
+
+
+def test_full_width_13b_layer_against_oracle(dev):
+    _full_width_layer_against_oracle(dev, "13B")
 
 
 @pytest.mark.parametrize("B", [1, 4])

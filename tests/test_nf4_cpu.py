@@ -73,6 +73,57 @@ def test_double_quant_restatement():
     assert torch.isfinite(a1).all()
 
 
+def test_product_restatement_by_hand():
+    """nf4_ref.product: NF4[code] * absmax rounded to f16 once, then an exact float64 dot product and the bias."""
+    codes = torch.arange(64) % 16
+    packed = ((codes[0::2] << 4) | codes[1::2]).to(torch.uint8)[None, :]
+    absmax = torch.tensor([[0.1]])
+    w = (R.NF4[codes] * torch.tensor(0.1, dtype=torch.float32)).half().double()
+    x = torch.linspace(-2, 2, 64).half()
+    y = R.product(x[None, :], packed, absmax, torch.tensor([0.25]))
+    assert y.dtype == torch.float64 and y.item() == (x.double() * w).sum().item() + 0.25
+    assert R.magnitude(x[None, :], w[None, :], torch.tensor([-0.25])).item() == (x.double() * w).abs().sum().item() + 0.25
+    # the tolerance: C_ACC of the magnitude, plus one f16 ulp (at 2048: 2) or one fp32 ulp of the reference
+    t16 = R.tol(x[None, :], w[None, :], None, torch.float16, torch.tensor([[2048.0]], dtype=torch.float64))
+    t32 = R.tol(x[None, :], w[None, :], None, torch.float32, torch.tensor([[2048.0]], dtype=torch.float64))
+    base = R.C_ACC * (x.double() * w).abs().sum().item()
+    assert abs(t16.item() - (base + 2.0)) < 1e-12 and abs(t32.item() - (base + 2.0 ** -12)) < 1e-12
+    assert 1e-5 <= R.C_ACC <= 4e-5
+
+
+def test_tolerance_rejects_kernel_mistakes_at_7b_shape():
+    """The GPU comparisons (tests/test_quant_variants_gpu.py) can fail: at K = 4096, one 16-row activation tile and 16 weight
+    tiles, nf4_ref.tol with the f16 output term rejects each of the mistakes a tile kernel makes, in most of the outputs it changes."""
+    g = torch.Generator().manual_seed(5)
+    M, N, K = 16, 256, 4096
+    w = (torch.randn(N, K, generator=g) * 0.02).half()
+    x = torch.randn(M, K, generator=g).half()
+    bias = torch.randn(N, generator=g) * 0.1
+    packed, absmax, _ = R.quantize(w)
+    wd = R.dequant(packed, absmax)
+    ref = R.product(x, packed, absmax, bias)
+    tol = R.tol(x, wd, bias, torch.float16, ref)
+    assert ((ref.half().double() - ref).abs() <= tol).all()           # the f16 rounding of the exact result passes
+    j = 17
+    n = torch.arange(N)
+    shifted = 16 * (n // 16) + (n % 16 + 1) % 16
+    a_nb = absmax.clone()
+    a_nb[:, j] = absmax[:, j + 1]
+    m_row = ref.clone()
+    m_row[15] = ref[14]
+    mutations = {
+        "one 64-block dropped": ref - x[:, 64 * j:64 * j + 64].double() @ wd[:, 64 * j:64 * j + 64].double().T,
+        "a neighbouring block's absmax": R.product(x, packed, a_nb, bias),
+        "weight rows shifted by one in their 16-row tile": R.product(x, packed[shifted], absmax[shifted], bias[shifted]),
+        "the last row of the M tile from the row before": m_row,
+    }
+    for name, mut in mutations.items():
+        d = (mut - ref).abs()
+        changed = d > 0
+        rejected = (d > tol) & changed
+        assert rejected.sum() >= 0.8 * changed.sum(), (name, int(rejected.sum()), int(changed.sum()))
+
+
 def test_product_tables_equal_the_restatement():
     from haff import quant
     assert _bits(quant.nf4_table()) == NF4_BITS
