@@ -25,6 +25,16 @@ def _pad8(n):
     return (n + 7) // 8 * 8
 
 
+HALF = (torch.bfloat16, torch.float16)   # the 16-bit training dtypes: bf16 (throughput mode) and fp16 (the --precision fp16 mode)
+
+
+def _fn16(lib, name, dtype):
+    """The entry point of a 16-bit training kernel for dtype: the bf16 one, or its *_f16 sibling (same arguments) for fp16."""
+    if dtype == torch.float16:
+        return getattr(lib, name.replace("_bf16", "_f16") if "_bf16" in name else name + "_f16")
+    return getattr(lib, name)
+
+
 def scale_dev(a, alpha, per_row=False):
     """a * alpha with alpha a DEVICE fp32 scalar (or one value per row of the 2-D a): the multiply runs in fp32 inside the kernel —
     a torch multiply would first round the 0-dim upstream gradient to a's dtype (bf16)."""
@@ -77,8 +87,9 @@ def bgemm(a, w, out=None, out_dtype=None):
     if out is None:
         out = torch.empty((Zo, Zi, M, N), dtype=out_dtype, device=a.device)
     assert out.stride(3) == 1
-    if a.dtype == torch.bfloat16:
-        rc = lib.haff_gemm_bf16_batched(a.data_ptr(), a.stride(2), a.stride(0), a.stride(1), w.data_ptr(), w.stride(2),
+    if a.dtype in HALF:
+        assert w.dtype == a.dtype
+        rc = _fn16(lib, "haff_gemm_bf16_batched", a.dtype)(a.data_ptr(), a.stride(2), a.stride(0), a.stride(1), w.data_ptr(), w.stride(2),
                                         w.stride(0), w.stride(1), out.data_ptr(), out.stride(2), out.stride(0),
                                         out.stride(1), Zo, Zi, M, N, K, 1 if out.dtype == torch.float32 else 0, _s())
     else:
@@ -91,14 +102,14 @@ def bgemm(a, w, out=None, out_dtype=None):
 
 
 def gemm_tn_supported(a, b):
-    return (a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0]
+    return (a.dtype in HALF and b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0]
             and a.stride(1) == 1 and b.stride(1) == 1 and a.shape[1] % 8 == 0 and b.shape[1] % 8 == 0 and a.stride(0) % 8 == 0
             and b.stride(0) % 8 == 0 and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0)
 
 
 def gemm_tn(a, b, out_dtype=None):
-    """a [M, N1], b [M, N2] (bf16, row strides free) -> a^T @ b [N1, N2]: the contraction runs over the ROWS, no transposed copy of
-    either operand (haff_gemm_tn_bf16)."""
+    """a [M, N1], b [M, N2] (bf16 or fp16, row strides free) -> a^T @ b [N1, N2]: the contraction runs over the ROWS, no transposed copy
+    of either operand (haff_gemm_tn_bf16 / _f16)."""
     lib = load_library()
     assert gemm_tn_supported(a, b)
     M, N1 = a.shape
@@ -107,7 +118,7 @@ def gemm_tn(a, b, out_dtype=None):
     n_ws = lib.haff_gemm_tn_workspace_elems(M, N1, N2)
     assert n_ws > 0
     ws = torch.empty((n_ws,), dtype=torch.float32, device=a.device)
-    check(lib.haff_gemm_tn_bf16(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), M, N1, N2, ws.data_ptr(), n_ws, out.data_ptr(),
+    check(_fn16(lib, "haff_gemm_tn_bf16", a.dtype)(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), M, N1, N2, ws.data_ptr(), n_ws, out.data_ptr(),
                                 1 if out.dtype == torch.float32 else 0, _s()), "haff_gemm_tn_bf16")
     return out
 
@@ -475,9 +486,9 @@ class AttentionFn(Function):
 
 
 class FlashAttentionFn(Function):
-    """The same op without probabilities in HBM (d == 128, bf16: the Llama self-attention of the fine-tune step): forward =
-    haff_attention_lse_bf16 (flash kernel + per-row log-sum-exp), backward = haff_attention_bwd_bf16 (recomputes P per 64 x 64
-    block; dq / dk / dv in one launch, no transposes, no atomics)."""
+    """The same op without probabilities in HBM (d == 128, bf16 or fp16: the Llama self-attention of the fine-tune step): forward =
+    haff_attention_lse_bf16 / _f16 (flash kernel + per-row log-sum-exp), backward = haff_attention_bwd_bf16 / _f16 (recomputes P per
+    64 x 64 block; dq / dk / dv in one launch, no transposes, no atomics)."""
 
     @staticmethod
     def forward(ctx, q, k, v, H, scale_, causal):
@@ -488,7 +499,7 @@ class FlashAttentionFn(Function):
         d = HD // H
         out = torch.empty_like(q)
         lse = torch.empty((B, H, Nq), dtype=torch.float32, device=q.device)
-        check(lib.haff_attention_lse_bf16(q.data_ptr(), Nq * HD, d, HD, k.data_ptr(), Nk * HD, d, HD, v.data_ptr(), Nk * HD, d, HD,
+        check(_fn16(lib, "haff_attention_lse_bf16", q.dtype)(q.data_ptr(), Nq * HD, d, HD, k.data_ptr(), Nk * HD, d, HD, v.data_ptr(), Nk * HD, d, HD,
                                           out.data_ptr(), Nq * HD, d, HD, B, H, Nq, Nk, d, float(scale_), 1 if causal else 0,
                                           Nk - Nq, lse.data_ptr(), _s()), "haff_attention_lse_bf16")
         ctx.save_for_backward(q, k, v, out, lse)
@@ -507,7 +518,7 @@ class FlashAttentionFn(Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         n_ws = B * H * (Nq + 4 + ((Nq + 63) // 64) * 64 * d)
         ws = torch.empty((n_ws,), dtype=torch.float32, device=q.device)
-        check(lib.haff_attention_bwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), do.data_ptr(), lse.data_ptr(),
+        check(_fn16(lib, "haff_attention_bwd_bf16", q.dtype)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), do.data_ptr(), lse.data_ptr(),
                                           dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), n_ws, HD, B, H, Nq, Nk, d,
                                           scale_, 1 if causal else 0, Nk - Nq, _s()), "haff_attention_bwd_bf16")
         return dq, dk, dv, None, None, None
@@ -518,7 +529,7 @@ FLASH_TRAINING_ATTENTION = True   # False: every attention of the fine-tune step
 
 def attention(q, k, v, H, scale_, causal):
     """softmax(scale * q k^T [+ causal]) v for token-major q [B,Nq,H*d], k / v [B,Nk,H*d] under autograd."""
-    if (FLASH_TRAINING_ATTENTION and q.dtype == torch.bfloat16 and q.shape[2] // H == 128 and (not causal or k.shape[1] >= q.shape[1])
+    if (FLASH_TRAINING_ATTENTION and q.dtype in HALF and q.shape[2] // H == 128 and (not causal or k.shape[1] >= q.shape[1])
             and (q.shape[2] % 8) == 0):
         return FlashAttentionFn.apply(q, k, v, H, scale_, causal)
     return AttentionFn.apply(q, k, v, H, scale_, causal)
@@ -533,7 +544,7 @@ class LoraQKVRopeFn(Function):
     keep holds the mask VALUES: 0 / 1/(1-p) as torch's dropout writes them, or 0 / 1 with the 1/(1-p) folded into s (what
     train_model passes: one Bernoulli launch for the mask, and x * keep is then exact in bf16).
 
-    bf16, head dim 128, rank <= 8 (csrc/lora.hip). The rank activations are carried TRANSPOSED ([16][M]: they come out of the
+    bf16 or fp16 (the *_f16 entry points), head dim 128, rank <= 8 (csrc/lora.hip). The rank activations are carried TRANSPOSED ([16][M]: they come out of the
     weight-streaming product with the roles swapped, A2 as its 16 "activation rows" and the token rows as its "weights"), the
     rank-8 updates ride in one pass over q|k|v together with RoPE, and backward needs neither transposed copies of its
     operands nor autograd's slice adjoints: d(qkv) is assembled in one pass, dA / dB are contractions over the rows."""
@@ -574,7 +585,7 @@ class LoraQKVRopeFn(Function):
         else:
             ops.linear(a2, xd, out=tT[:, :M])
         q, k, v = (torch.empty((M, H), dtype=x.dtype, device=dev) for _ in range(3))
-        check(lib.haff_lora_qkv_rope_fwd(qkv.data_ptr(), qkv.stride(0), tT.data_ptr(), Mp, b2[0].data_ptr(), b2[1].data_ptr(), 8,
+        check(_fn16(lib, "haff_lora_qkv_rope_fwd", x.dtype)(qkv.data_ptr(), qkv.stride(0), tT.data_ptr(), Mp, b2[0].data_ptr(), b2[1].data_ptr(), 8,
                                          cos_sin.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), H, M, H, d, int(T),
                                          float(scale_), _s()), "haff_lora_qkv_rope_fwd")
         none = torch.empty(0, device=dev)
@@ -598,7 +609,7 @@ class LoraQKVRopeFn(Function):
         Mp = tT.shape[1]
         dq, dk, dv = dq.contiguous(), dk.contiguous(), dv.contiguous()
         dqkv = torch.empty((M, 3 * H), dtype=dt_, device=dev)
-        check(lib.haff_lora_qkv_rope_bwd(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), H, cos_sin.data_ptr(), dqkv.data_ptr(), 3 * H,
+        check(_fn16(lib, "haff_lora_qkv_rope_bwd", dt_)(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), H, cos_sin.data_ptr(), dqkv.data_ptr(), 3 * H,
                                          M, H, d, T, _s()), "haff_lora_qkv_rope_bwd")
         # dt^T [16][M] = B^T . d(q|v)^T: the weight-streaming product again, the gradient rows as its "weights"
         b2t = b2.transpose(1, 2).contiguous()   # [2][8][H]
@@ -610,7 +621,7 @@ class LoraQKVRopeFn(Function):
             n_ws = lib.haff_lora_tn_workspace_elems(M, R, n)
             assert n_ws > 0
             ws = torch.empty((n_ws,), dtype=torch.float32, device=dev)
-            check(lib.haff_lora_tn(sT.data_ptr(), Mp, R, big.data_ptr(), big.stride(0), M, n, ws.data_ptr(), ws.numel(),
+            check(_fn16(lib, "haff_lora_tn", dt_)(sT.data_ptr(), Mp, R, big.data_ptr(), big.stride(0), M, n, ws.data_ptr(), ws.numel(),
                                    out.data_ptr(), out.stride(0), 1 if out.dtype == torch.float32 else 0, 1 if transposed else 0,
                                    j_valid, scale_, _s()), "haff_lora_tn")
             return out
@@ -627,17 +638,17 @@ class LoraQKVRopeFn(Function):
         if ctx.needs_input_grad[0]:
             dx = ops.linear(dqkv, wqkv_t)
             if two:   # dx += s * (keep_q o (dt_q . Aq) + keep_v o (dt_v . Av)) in one pass
-                check(lib.haff_lora_dx2(dtT.data_ptr(), Mp, a2.data_ptr(), K, keep.data_ptr(), keep_v.data_ptr(), K, dx.data_ptr(),
+                check(_fn16(lib, "haff_lora_dx2", dt_)(dtT.data_ptr(), Mp, a2.data_ptr(), K, keep.data_ptr(), keep_v.data_ptr(), K, dx.data_ptr(),
                                         dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx2")
             else:
-                check(lib.haff_lora_dx(dtT.data_ptr(), Mp, a2.data_ptr(), K, keep.data_ptr() if keep.numel() else 0, K, dx.data_ptr(),
+                check(_fn16(lib, "haff_lora_dx", dt_)(dtT.data_ptr(), Mp, a2.data_ptr(), K, keep.data_ptr() if keep.numel() else 0, K, dx.data_ptr(),
                                        dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx")
         return dx, None, None, da2[0:r], dbq, da2[8:8 + r], dbv, None, None, None, None, None
 
 
 def lora_qkv_rope_supported(x, wqkv, aq, heads):
     H = wqkv.shape[0] // 3
-    return (x.dtype == torch.bfloat16 and H % heads == 0 and H // heads == 128 and aq.shape[0] <= 8 and x.shape[1] % 128 == 0
+    return (x.dtype in HALF and wqkv.dtype == x.dtype and H % heads == 0 and H // heads == 128 and aq.shape[0] <= 8 and x.shape[1] % 128 == 0
             and x.shape[0] >= 16)
 
 
@@ -722,8 +733,11 @@ class CrossEntropyFn(Function):
         n_valid = max(int(n_valid), 1)
         row_loss = torch.empty((R,), dtype=torch.float32, device=logits.device)
         dlogits = torch.empty_like(logits)
+        # fp16: the kernel writes softmax - onehot unscaled and the 1 / n_valid joins the upstream (loss-scaled) gradient in backward:
+        # softmax / n_valid itself would fall below fp16's subnormals for a 32003-word vocabulary before the loss scale reaches it
+        ctx.post = n_valid if logits.dtype == torch.float16 else None
         check(lib.haff_cross_entropy(logits.data_ptr(), logits.stride(0), labels.data_ptr(), row_loss.data_ptr(), dlogits.data_ptr(),
-                                     R, V, 1.0 / n_valid, _dt(logits), _s()), "haff_cross_entropy")
+                                     R, V, 1.0 if ctx.post else 1.0 / n_valid, _dt(logits), _s()), "haff_cross_entropy")
         ctx.save_for_backward(dlogits)
         # sum of R floats / n_valid: reduction of a tiny vector (torch sum as plumbing of a scalar)
         return (row_loss.sum() / n_valid).to(torch.float32)
@@ -731,6 +745,8 @@ class CrossEntropyFn(Function):
     @staticmethod
     def backward(ctx, g):
         (dlogits,) = ctx.saved_tensors
+        if ctx.post:
+            g = g.to(torch.float32) / ctx.post
         return scale_dev(dlogits, g), None, None   # the upstream scalar stays on the device AND in fp32 (no read-back, no bf16 rounding)
 
 
@@ -817,7 +833,7 @@ resize_bilinear = BilinearFn.apply
 
 
 class CastFn(Function):
-    """dtype change (bf16 <-> f32) — a copy, kept as a Function so gradients come back in the source dtype."""
+    """dtype change (bf16 / fp16 <-> f32) — a copy, kept as a Function so gradients come back in the source dtype."""
 
     @staticmethod
     def forward(ctx, x, dtype):

@@ -1326,6 +1326,17 @@ extern "C" int haff_attention_lse_bf16(const void* q, long q_sb, long q_sh, long
   return attention_bf16_impl(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq, Nk, d,
                              scale, causal, q_pos0, nullptr, nullptr, 0, nullptr, stream, lse);
 }
+// fp16 instance of haff_attention_lse_bf16 (fp16 fine-tuning: the forward half of the f16 flash pair with haff_attention_bwd_f16)
+extern "C" int haff_attention_lse_f16(const void* q, long q_sb, long q_sh, long q_st,
+                                      const void* k, long k_sb, long k_sh, long k_st,
+                                      const void* v, long v_sb, long v_sh, long v_st,
+                                      void* o, long o_sb, long o_sh, long o_st,
+                                      int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
+                                      float* lse, void* stream) {
+  if (!lse) return HAFF_ERR_BAD_ARG;
+  return attention_bf16_impl<true>(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq,
+                                   Nk, d, scale, causal, q_pos0, nullptr, nullptr, 0, nullptr, stream, lse);
+}
 
 // SAM GLOBAL attention with the decomposed rel-pos bias computed inside the kernel (Attention.forward,
 // image_encoder.py:235-260, + add_decomposed_rel_pos :354-392 at q_size == k_size == S x S): replaces haff_relpos_tables_bf16 +

@@ -49,7 +49,10 @@ __device__ __forceinline__ bf16x8 frag_tr(const bf16_t* img, int stride, int k0,
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// F16: q / k / v / o / dout / dq / dk / dv are IEEE binary16 (f16 MFMA forms; P and dS rounded to fp16 as the forward rounds P)
+template <bool F16>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(BwdArgs p) {
+  using E = h16<F16>;
   extern __shared__ __attribute__((aligned(16))) unsigned char bsm[];
   bf16_t* sK = reinterpret_cast<bf16_t*>(bsm);
   bf16_t* sV = sK + BB * BSTR;
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(BwdArgs p) {
         unsigned o4[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          o4[e] = pack_bf16x2(__uint_as_float(w4[e] << 16) * sl2, __uint_as_float(w4[e] & 0xffff0000u) * sl2);
+          o4[e] = E::pack2(E::lo(w4[e]) * sl2, E::hi(w4[e]) * sl2);
         *reinterpret_cast<uint4*>(sQ + r * BSTR + col) = nq[ii];
         *reinterpret_cast<uint4*>(sQs + r * BSTR + col) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
         *reinterpret_cast<uint4*>(sdO + r * BSTR + col) = ndo[ii];
@@ -146,8 +149,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(BwdArgs p) {
         for (int qt = 0; qt < 4; ++qt) {
           const bf16x8 qf = *reinterpret_cast<const bf16x8*>(sQs + (16 * qt + fr) * BSTR + kd * 32 + fh * 8);
           const bf16x8 of = *reinterpret_cast<const bf16x8*>(sdO + (16 * qt + fr) * BSTR + kd * 32 + fh * 8);
-          sS[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, sS[qt], 0, 0, 0);
-          dP[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of, vf, dP[qt], 0, 0, 0);
+          sS[qt] = E::mfma16(qf, kf, sS[qt]);
+          dP[qt] = E::mfma16(of, vf, dP[qt]);
         }
       }
       // ---- P and dS: lane = key column 16 wave + fr, rows = queries 16 qt + 4 fh + r ----
@@ -172,22 +175,22 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(BwdArgs p) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         uint4 up, ud;
-        up.x = pack_bf16x2(pv[2 * ks][0], pv[2 * ks][1]);         up.y = pack_bf16x2(pv[2 * ks][2], pv[2 * ks][3]);
-        up.z = pack_bf16x2(pv[2 * ks + 1][0], pv[2 * ks + 1][1]); up.w = pack_bf16x2(pv[2 * ks + 1][2], pv[2 * ks + 1][3]);
-        ud.x = pack_bf16x2(dsv[2 * ks][0], dsv[2 * ks][1]);         ud.y = pack_bf16x2(dsv[2 * ks][2], dsv[2 * ks][3]);
-        ud.z = pack_bf16x2(dsv[2 * ks + 1][0], dsv[2 * ks + 1][1]); ud.w = pack_bf16x2(dsv[2 * ks + 1][2], dsv[2 * ks + 1][3]);
+        up.x = E::pack2(pv[2 * ks][0], pv[2 * ks][1]);         up.y = E::pack2(pv[2 * ks][2], pv[2 * ks][3]);
+        up.z = E::pack2(pv[2 * ks + 1][0], pv[2 * ks + 1][1]); up.w = E::pack2(pv[2 * ks + 1][2], pv[2 * ks + 1][3]);
+        ud.x = E::pack2(dsv[2 * ks][0], dsv[2 * ks][1]);         ud.y = E::pack2(dsv[2 * ks][2], dsv[2 * ks][3]);
+        ud.z = E::pack2(dsv[2 * ks + 1][0], dsv[2 * ks + 1][1]); ud.w = E::pack2(dsv[2 * ks + 1][2], dsv[2 * ks + 1][3]);
         const bf16x8 pB = __builtin_bit_cast(bf16x8, up), dB = __builtin_bit_cast(bf16x8, ud);
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) {
           const bf16x8 a_do = frag_tr(sdO, BSTR, 32 * ks, 16 * dt, fr, fh);
           const bf16x8 a_q = frag_tr(sQ, BSTR, 32 * ks, 16 * dt, fr, fh);
-          dVt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_do, pB, dVt[dt], 0, 0, 0);
-          dKt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_q, dB, dKt[dt], 0, 0, 0);
+          dVt[dt] = E::mfma16(a_do, pB, dVt[dt]);
+          dKt[dt] = E::mfma16(a_q, dB, dKt[dt]);
         }
       }
       // ---- dS^T -> LDS [key][q] (the lane's 4 consecutive queries of each tile: one 8-byte store) ----
 #pragma unroll
-      for (int qt = 0; qt < 4; ++qt) store4(sdS + (16 * wave + fr) * SSTR + 16 * qt + 4 * fh, dsv[qt]);
+      for (int qt = 0; qt < 4; ++qt) store4h<F16>(sdS + (16 * wave + fr) * SSTR + 16 * qt + 4 * fh, dsv[qt]);
       __syncthreads();
       // ---- dQ^T[d][q] (query tile = wave) = K^T[d][key] . dS^T[key][q], summed over this key block ----
       f32x4 dQt[8];
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(BwdArgs p) {
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) {
           const bf16x8 a_k = frag_tr(sK, BSTR, 32 * ks, 16 * dt, fr, fh);
-          dQt[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_k, bS, dQt[dt], 0, 0, 0);
+          dQt[dt] = E::mfma16(a_k, bS, dQt[dt]);
         }
       }
       {
@@ -230,8 +233,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(BwdArgs p) {
         for (int dt = 0; dt < 8; ++dt) {
           float a[4] = {dKt[dt][0], dKt[dt][1], dKt[dt][2], dKt[dt][3]};
           float c[4] = {dVt[dt][0], dVt[dt][1], dVt[dt][2], dVt[dt][3]};
-          store4(rk + 16 * dt, a);
-          store4(rv + 16 * dt, c);
+          store4h<F16>(rk + 16 * dt, a);
+          store4h<F16>(rv + 16 * dt, c);
         }
       }
     }
@@ -243,11 +246,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(BwdArgs p) {
     const int qq = c >> 4, col = (c & 15) * 8;
     float v[8];
     load8(acc_bh + (long)qq * BD + col, v);
-    store8(p.dq + qbase + (long)qq * p.ld + col, v);
+    store8h<F16>(p.dq + qbase + (long)qq * p.ld + col, v);
   }
 }
 
 // delta[b][h][q] = sum_c dO[b][q][h][c] * O[b][q][h][c]: one 16-lane group per (b, q, h) row
+template <bool F16>
 __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const bf16_t* o, const bf16_t* dout, float* delta, long ld, int B,
                                                              int H, int Nq) {
   const long row = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;
@@ -262,8 +266,8 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const bf16_t* o, co
     b = bq / Nq;
     const long off = (b * Nq + q) * ld + h * BD + c * 8;
     float a[8], d[8];
-    load8(o + off, a);
-    load8(dout + off, d);
+    load8h<F16>(o + off, a);
+    load8h<F16>(dout + off, d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += a[e] * d[e];
   }
@@ -279,10 +283,10 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const bf16_t* o, co
 // dq, dk, dv of out = softmax(scale * q k^T [causal: key j visible to query i iff j <= i + q_pos0]) v, bf16, d == 128.
 // q / dout / o / dq: [B][Nq][ld], k / v / dk / dv: [B][Nk][ld] token-major with head h at columns h*128 (ld = H*128 for the
 // fused projections); lse f32 [B][H][Nq] from haff_attention_lse_bf16; workspace f32, >= B*H*(Nq + 128*roundup(Nq, 64)) values.
-extern "C" int haff_attention_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                                       const float* lse, void* dq, void* dk, void* dv, float* workspace, long workspace_elems,
-                                       long ld, int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
-                                       void* stream) {
+template <bool F16>
+static int attention_bwd_impl(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq,
+                              void* dk, void* dv, float* workspace, long workspace_elems, long ld, int B, int H, int Nq, int Nk, int d,
+                              float scale, int causal, int q_pos0, void* stream) {
   if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || !q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !workspace)
     return HAFF_ERR_BAD_ARG;
   if (d != BD) return HAFF_ERR_UNSUPPORTED;
@@ -298,14 +302,30 @@ extern "C" int haff_attention_bwd_bf16(const void* q, const void* k, const void*
   if (dq_acc + (long)B * H * nqp * BD > workspace + workspace_elems) return HAFF_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long rows = (long)B * Nq * H;
-  hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, s,
+  hipLaunchKernelGGL((attn_bwd_delta_kernel<F16>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const bf16_t*>(o), reinterpret_cast<const bf16_t*>(dout), delta, ld, B, H, Nq);
   BwdArgs p{reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const bf16_t*>(v),
             reinterpret_cast<const bf16_t*>(dout), lse, delta, reinterpret_cast<bf16_t*>(dq), reinterpret_cast<bf16_t*>(dk),
             reinterpret_cast<bf16_t*>(dv), dq_acc, ld, B, H, Nq, Nk, scale, causal, q_pos0};
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_LDS) !=
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<F16>), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_LDS) !=
       hipSuccess)
     return HAFF_ERR_LAUNCH;
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * H), dim3(256), BWD_LDS, s, p);
+  hipLaunchKernelGGL((attn_bwd_kernel<F16>), dim3(B * H), dim3(256), BWD_LDS, s, p);
   return haff_check_launch();
+}
+
+extern "C" int haff_attention_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                       const float* lse, void* dq, void* dk, void* dv, float* workspace, long workspace_elems,
+                                       long ld, int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
+                                       void* stream) {
+  return attention_bwd_impl<false>(q, k, v, o, dout, lse, dq, dk, dv, workspace, workspace_elems, ld, B, H, Nq, Nk, d, scale, causal,
+                                   q_pos0, stream);
+}
+// fp16 instance (fp16 fine-tuning; lse from haff_attention_lse_f16): every 16-bit operand and result IEEE binary16, same contract
+extern "C" int haff_attention_bwd_f16(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                                      const float* lse, void* dq, void* dk, void* dv, float* workspace, long workspace_elems,
+                                      long ld, int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
+                                      void* stream) {
+  return attention_bwd_impl<true>(q, k, v, o, dout, lse, dq, dk, dv, workspace, workspace_elems, ld, B, H, Nq, Nk, d, scale, causal,
+                                  q_pos0, stream);
 }

@@ -2074,13 +2074,24 @@ extern "C" int haff_gemm_f16_heads(const void* A, long lda, const void* W, long 
 
 // Batched C_z = A_z . W_z^T (no epilogue): z = zo * nb_inner + zi, operand offsets zo * s?o + zi * s?i (elements).
 // Used by the training path for attention-shaped products over (batch, head) (scores, P.V and their gradients).
-extern "C" int haff_gemm_bf16_batched(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo,
-                                      long sWi, void* C, long ldc, long sCo, long sCi, int nb_outer, int nb_inner,
-                                      int M, int N, int K, int out_f32, void* stream) {
+template <bool F16>
+static int gemm_batched_impl(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo, long sWi, void* C,
+                             long ldc, long sCo, long sCi, int nb_outer, int nb_inner, int M, int N, int K, int out_f32, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || nb_outer <= 0 || nb_inner <= 0) return HAFF_ERR_BAD_ARG;
   if ((K & 7) || (lda & 7) || (ldw & 7) || (sAo & 7) || (sAi & 7) || (sWo & 7) || (sWi & 7)) return HAFF_ERR_BAD_ARG;
   if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return HAFF_ERR_BAD_ARG;
   GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), ldw, C, ldc,
              nullptr, nullptr, 0, nullptr, nullptr, 8, nullptr, nullptr, M, N, K, 0, out_f32, 0, nb_inner, sAo, sAi, sWo, sWi, sCo, sCi};
-  return launch_gemm<128, 128, 2, 2>(p, reinterpret_cast<hipStream_t>(stream), nb_outer * nb_inner);
+  return launch_gemm<128, 128, 2, 2, F16>(p, reinterpret_cast<hipStream_t>(stream), nb_outer * nb_inner);
+}
+extern "C" int haff_gemm_bf16_batched(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo,
+                                      long sWi, void* C, long ldc, long sCo, long sCi, int nb_outer, int nb_inner,
+                                      int M, int N, int K, int out_f32, void* stream) {
+  return gemm_batched_impl<false>(A, lda, sAo, sAi, W, ldw, sWo, sWi, C, ldc, sCo, sCi, nb_outer, nb_inner, M, N, K, out_f32, stream);
+}
+// fp16 instance (fp16 fine-tuning): A, W and a 16-bit C are IEEE binary16; same arguments and contract
+extern "C" int haff_gemm_f16_batched(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo,
+                                     long sWi, void* C, long ldc, long sCo, long sCi, int nb_outer, int nb_inner,
+                                     int M, int N, int K, int out_f32, void* stream) {
+  return gemm_batched_impl<true>(A, lda, sAo, sAi, W, ldw, sWo, sWi, C, ldc, sCo, sCi, nb_outer, nb_inner, M, N, K, out_f32, stream);
 }

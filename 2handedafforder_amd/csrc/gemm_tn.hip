@@ -37,6 +37,8 @@ struct TnArgs {
   float* part;           // [splits][N1][N2]
 };
 
+// F16: A and B are IEEE binary16 (v_mfma_f32_16x16x32_f16; the transposing LDS read moves 16-bit payloads either way)
+template <bool F16>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs p) {
   __shared__ __attribute__((aligned(16))) bf16_t sA[TR * TSTR];
   __shared__ __attribute__((aligned(16))) bf16_t sB[TR * TSTR];
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs p) {
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[b], fa[a], acc[a][b], 0, 0, 0);
+        for (int b = 0; b < 4; ++b) acc[a][b] = h16<F16>::mfma16(fb[b], fa[a], acc[a][b]);
     }
   }
   float* dst = p.part + (long)blockIdx.z * p.N1 * p.N2;
@@ -142,10 +144,9 @@ extern "C" int haff_gemm_tn_workspace_elems(long M, int N1, int N2) {
   return n > 0x7fffffffL ? HAFF_ERR_UNSUPPORTED : (int)n;
 }
 
-// out [N1][N2] (contiguous; bf16 or f32) = A^T . B with A [M][lda] (N1 columns), B [M][ldb] (N2 columns), both bf16.
-// N1, N2, lda, ldb multiples of 8 and 16-byte aligned bases (anything else: HAFF_ERR_UNSUPPORTED, the caller transposes).
-extern "C" int haff_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
-                                 long workspace_elems, void* out, int out_f32, void* stream) {
+template <bool F16>
+static int gemm_tn_impl(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
+                        long workspace_elems, void* out, int out_f32, void* stream) {
   if (M <= 0 || N1 <= 0 || N2 <= 0 || !A || !B || !workspace || !out || lda < N1 || ldb < N2) return HAFF_ERR_BAD_ARG;
   if ((N1 & 7) || (N2 & 7) || (lda & 7) || (ldb & 7) || (reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15) ||
       (reinterpret_cast<uintptr_t>(out) & 15))
@@ -157,11 +158,24 @@ extern "C" int haff_gemm_tn_bf16(const void* A, long lda, const void* B, long ld
   if (workspace_elems < (long)splits * n) return HAFF_ERR_BAD_ARG;
   TnArgs p{(const bf16_t*)A, (const bf16_t*)B, lda, ldb, M, N1, N2, rps, workspace};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(gemm_tn_kernel, dim3((N1 + TT - 1) / TT, (N2 + TT - 1) / TT, splits), dim3(256), 0, s, p);
+  hipLaunchKernelGGL((gemm_tn_kernel<F16>), dim3((N1 + TT - 1) / TT, (N2 + TT - 1) / TT, splits), dim3(256), 0, s, p);
   long g = (n / 4 + 255) / 256;
   if (g > 4096) g = 4096;
   if (g < 1) g = 1;
   if (out_f32) hipLaunchKernelGGL((gemm_tn_reduce_kernel<float>), dim3((unsigned)g), dim3(256), 0, s, workspace, splits, n, (float*)out);
+  else if (F16) hipLaunchKernelGGL((gemm_tn_reduce_kernel<f16_t>), dim3((unsigned)g), dim3(256), 0, s, workspace, splits, n, (f16_t*)out);
   else hipLaunchKernelGGL((gemm_tn_reduce_kernel<bf16_t>), dim3((unsigned)g), dim3(256), 0, s, workspace, splits, n, (bf16_t*)out);
   return hipGetLastError() == hipSuccess ? HAFF_OK : HAFF_ERR_LAUNCH;
+}
+
+// out [N1][N2] (contiguous; bf16 or f32) = A^T . B with A [M][lda] (N1 columns), B [M][ldb] (N2 columns), both bf16.
+// N1, N2, lda, ldb multiples of 8 and 16-byte aligned bases (anything else: HAFF_ERR_UNSUPPORTED, the caller transposes).
+extern "C" int haff_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
+                                 long workspace_elems, void* out, int out_f32, void* stream) {
+  return gemm_tn_impl<false>(A, lda, B, ldb, M, N1, N2, workspace, workspace_elems, out, out_f32, stream);
+}
+// fp16 instance (fp16 fine-tuning): A, B and a 16-bit out are IEEE binary16; same arguments and contract
+extern "C" int haff_gemm_tn_f16(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
+                                long workspace_elems, void* out, int out_f32, void* stream) {
+  return gemm_tn_impl<true>(A, lda, B, ldb, M, N1, N2, workspace, workspace_elems, out, out_f32, stream);
 }

@@ -15,7 +15,8 @@
 //   * dt^T = B^T.dq^T is again the swapped weight-streaming product; lora_dx_kernel adds s.keep.(dt.A2) into the d(x) the
 //     frozen product's adjoint wrote; lora_tn_kernel is the one contraction over ROWS (dA = dt^T.x, dB = dq^T.t): rank rows
 //     in SGPRs, the big operand streamed once, per-row-block partials summed in index order (no atomics, deterministic).
-// bf16 storage, fp32 arithmetic, head dim 128, rank <= 8 per adapter.
+// bf16 or f16 storage (every kernel is one template, F16 = the fp16 fine-tune's instance: the *_f16 entry points), fp32
+// arithmetic, head dim 128, rank <= 8 per adapter.
 #include "haff_common.h"
 
 namespace {
@@ -48,7 +49,9 @@ struct LoraFwdArgs {
 // 8 * (i / 4) + 4 * h + i % 4), so that lane (fr, fh) ends up with row fr, columns 8fh .. 8fh+7 of the group: 16-byte
 // loads and stores, 64 contiguous bytes per row and instruction (the natural operand order leaves 4 columns per lane:
 // 8-byte accesses in 32-byte runs, which held this kernel at 2.4 TB/s)
+template <bool F16>
 __global__ __launch_bounds__(256, 3) void lora_qkv_rope_fwd_kernel(LoraFwdArgs p) {
+  using E = h16<F16>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, fh = lane >> 4;
   const int head = blockIdx.x;
@@ -76,18 +79,18 @@ __global__ __launch_bounds__(256, 3) void lora_qkv_rope_fwd_kernel(LoraFwdArgs p
 #pragma unroll
     for (int g = 0; g < 2; ++g) {   // column group g and its rotate-half partner g + 2
       float qa[8], qb[8], ka[8], kb[8], va[8], vb[8], co[8], si[8];
-      load8(src + 32 * g, qa); load8(src + 64 + 32 * g, qb);
-      load8(src + p.H + 32 * g, ka); load8(src + p.H + 64 + 32 * g, kb);
-      load8(src + 2 * (long)p.H + 32 * g, va); load8(src + 2 * (long)p.H + 64 + 32 * g, vb);
+      load8h<F16>(src + 32 * g, qa); load8h<F16>(src + 64 + 32 * g, qb);
+      load8h<F16>(src + p.H + 32 * g, ka); load8h<F16>(src + p.H + 64 + 32 * g, kb);
+      load8h<F16>(src + 2 * (long)p.H + 32 * g, va); load8h<F16>(src + 2 * (long)p.H + 64 + 32 * g, vb);
       load8(csr + 32 * g, co); load8(csr + 64 + 32 * g, si);
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       f32x4 dq0[2], dq1[2], dv0[2], dv1[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        dq0[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[g][h], tt, z, 0, 0, 0);
-        dq1[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[g + 2][h], tt, z, 0, 0, 0);
-        dv0[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bv[g][h], tt, z, 0, 0, 0);
-        dv1[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bv[g + 2][h], tt, z, 0, 0, 0);
+        dq0[h] = E::mfma16(bq[g][h], tt, z);
+        dq1[h] = E::mfma16(bq[g + 2][h], tt, z);
+        dv0[h] = E::mfma16(bv[g][h], tt, z);
+        dv1[h] = E::mfma16(bv[g + 2][h], tt, z);
       }
       float q1[8], q2[8], k1[8], k2[8];
 #pragma unroll
@@ -101,15 +104,16 @@ __global__ __launch_bounds__(256, 3) void lora_qkv_rope_fwd_kernel(LoraFwdArgs p
         vb[e] += p.scale * dv1[e >> 2][e & 3];
       }
       if (valid) {
-        store8(q_o + 32 * g, q1); store8(q_o + 64 + 32 * g, q2);
-        store8(k_o + 32 * g, k1); store8(k_o + 64 + 32 * g, k2);
-        store8(v_o + 32 * g, va); store8(v_o + 64 + 32 * g, vb);
+        store8h<F16>(q_o + 32 * g, q1); store8h<F16>(q_o + 64 + 32 * g, q2);
+        store8h<F16>(k_o + 32 * g, k1); store8h<F16>(k_o + 64 + 32 * g, k2);
+        store8h<F16>(v_o + 32 * g, va); store8h<F16>(v_o + 64 + 32 * g, vb);
       }
     }
   }
 }
 
 // d(qkv) [M][3H] = [rope^T dq | rope^T dk | dv]: thread = (row, head, 8 low columns + their partners)
+template <bool F16>
 __global__ __launch_bounds__(256) void lora_qkv_rope_bwd_kernel(const bf16_t* dq, const bf16_t* dk, const bf16_t* dv, long ld_in,
                                                               const float* cs, bf16_t* dqkv, long ld_out, long M, int H, int T) {
   const int nh = H / HD;
@@ -124,18 +128,18 @@ __global__ __launch_bounds__(256) void lora_qkv_rope_bwd_kernel(const bf16_t* dq
     load8(cs + (long)pos * HD + 8 * ch, co);
     load8(cs + (long)pos * HD + 64 + 8 * ch, si);
     float a[8], b[8], x1[8], x2[8];
-    load8(dq + row * ld_in + col, a);
-    load8(dq + row * ld_in + col + 64, b);
+    load8h<F16>(dq + row * ld_in + col, a);
+    load8h<F16>(dq + row * ld_in + col + 64, b);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { x1[e] = a[e] * co[e] + b[e] * si[e]; x2[e] = b[e] * co[e] - a[e] * si[e]; }
-    store8(dqkv + row * ld_out + col, x1);
-    store8(dqkv + row * ld_out + col + 64, x2);
-    load8(dk + row * ld_in + col, a);
-    load8(dk + row * ld_in + col + 64, b);
+    store8h<F16>(dqkv + row * ld_out + col, x1);
+    store8h<F16>(dqkv + row * ld_out + col + 64, x2);
+    load8h<F16>(dk + row * ld_in + col, a);
+    load8h<F16>(dk + row * ld_in + col + 64, b);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { x1[e] = a[e] * co[e] + b[e] * si[e]; x2[e] = b[e] * co[e] - a[e] * si[e]; }
-    store8(dqkv + row * ld_out + H + col, x1);
-    store8(dqkv + row * ld_out + H + col + 64, x2);
+    store8h<F16>(dqkv + row * ld_out + H + col, x1);
+    store8h<F16>(dqkv + row * ld_out + H + col + 64, x2);
     *reinterpret_cast<uint4*>(dqkv + row * ld_out + 2 * (long)H + col) = *reinterpret_cast<const uint4*>(dv + row * ld_in + col);
     *reinterpret_cast<uint4*>(dqkv + row * ld_out + 2 * (long)H + col + 64) = *reinterpret_cast<const uint4*>(dv + row * ld_in + col + 64);
   }
@@ -150,7 +154,9 @@ struct LoraDxArgs {
   long M; int K; int accumulate; float scale;
   const bf16_t* keep_v;   // two masks (haff_lora_dx2): `keep` gates the q adapter's ranks (rows 0-7 of A2), keep_v the v adapter's (8-15)
 };
+template <bool F16>
 __global__ __launch_bounds__(256) void lora_dx_kernel(LoraDxArgs p) {   // column operands permuted as in the forward kernel
+  using E = h16<F16>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, fh = lane >> 4;
   const long c0 = (long)blockIdx.x * 128;
@@ -178,27 +184,27 @@ __global__ __launch_bounds__(256) void lora_dx_kernel(LoraDxArgs p) {   // colum
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       float old[8], kp[8], kv[8];
-      if (p.accumulate) load8(dst + 32 * g, old);
-      if (kpr) load8(kpr + 32 * g, kp);
-      if (kvr) load8(kvr + 32 * g, kv);
+      if (p.accumulate) load8h<F16>(dst + 32 * g, old);
+      if (kpr) load8h<F16>(kpr + 32 * g, kp);
+      if (kvr) load8h<F16>(kvr + 32 * g, kv);
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       f32x4 d[2];
       float v[8];
       if (kvr) {   // (wave-uniform) two masks: the q adapter's ranks sit in the fh = 0 lanes of the A fragment, the v adapter's in fh = 1
         const bf16x8 zf = zero_frag();
         f32x4 dv[2];
-        d[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh == 0 ? af[g][0] : zf, tt, z, 0, 0, 0);
-        d[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh == 0 ? af[g][1] : zf, tt, z, 0, 0, 0);
-        dv[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh == 1 ? af[g][0] : zf, tt, z, 0, 0, 0);
-        dv[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh == 1 ? af[g][1] : zf, tt, z, 0, 0, 0);
+        d[0] = E::mfma16(fh == 0 ? af[g][0] : zf, tt, z);
+        d[1] = E::mfma16(fh == 0 ? af[g][1] : zf, tt, z);
+        dv[0] = E::mfma16(fh == 1 ? af[g][0] : zf, tt, z);
+        dv[1] = E::mfma16(fh == 1 ? af[g][1] : zf, tt, z);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           v[e] = p.scale * (d[e >> 2][e & 3] * kp[e] + dv[e >> 2][e & 3] * kv[e]);
           if (p.accumulate) v[e] += old[e];
         }
       } else {
-        d[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[g][0], tt, z, 0, 0, 0);
-        d[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[g][1], tt, z, 0, 0, 0);
+        d[0] = E::mfma16(af[g][0], tt, z);
+        d[1] = E::mfma16(af[g][1], tt, z);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           v[e] = p.scale * d[e >> 2][e & 3];
@@ -206,7 +212,7 @@ __global__ __launch_bounds__(256) void lora_dx_kernel(LoraDxArgs p) {   // colum
           if (p.accumulate) v[e] += old[e];
         }
       }
-      if (valid) store8(dst + 32 * g, v);
+      if (valid) store8h<F16>(dst + 32 * g, v);
     }
   }
 }
@@ -214,9 +220,10 @@ __global__ __launch_bounds__(256) void lora_dx_kernel(LoraDxArgs p) {   // colum
 // part[rb][j][n] = sum over the row block's rows m of sT[j][m] * big[m][n]: workgroup = 128 columns (2 per lane) x one row
 // block; its 4 waves take 8-row groups in turn (the R x 8 rank values of a group are wave-uniform: scalar loads), and meet in
 // LDS in wave order
-template <int R>
+template <int R, bool F16>
 __global__ __launch_bounds__(256) void lora_tn_kernel(const bf16_t* sT, long lds, const bf16_t* big, long ldb, long M, int N,
                                                       int rows_per_block, float* part) {
+  using E = h16<F16>;
   __shared__ float red[4][R][128];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -251,10 +258,10 @@ __global__ __launch_bounds__(256) void lora_tn_kernel(const bf16_t* sT, long lds
       const unsigned sw[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const unsigned h = (i & 1) ? (sw[i >> 1] & 0xffff0000u) : (sw[i >> 1] << 16);
-        const float sv = (m0 + i < r_hi) ? __uint_as_float(h) : 0.f;
-        acc[j][0] = fmaf(sv, __uint_as_float(bw[i] << 16), acc[j][0]);
-        acc[j][1] = fmaf(sv, __uint_as_float(bw[i] & 0xffff0000u), acc[j][1]);
+        const float h = (i & 1) ? E::hi(sw[i >> 1]) : E::lo(sw[i >> 1]);
+        const float sv = (m0 + i < r_hi) ? h : 0.f;
+        acc[j][0] = fmaf(sv, E::lo(bw[i]), acc[j][0]);
+        acc[j][1] = fmaf(sv, E::hi(bw[i]), acc[j][1]);
       }
     }
     if (more) {
@@ -297,9 +304,10 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 }  // namespace
 
-extern "C" int haff_lora_qkv_rope_fwd(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
-                                      int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M,
-                                      int H, int d, int T, float scale, void* stream) {
+template <bool F16>
+static int lora_qkv_rope_fwd_impl(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, int ldb,
+                                  const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int d, int T,
+                                  float scale, void* stream) {
   if (M <= 0 || T <= 0 || H <= 0 || !qkv || !tT || !Bq || !Bv || !cos_sin || !q_out || !k_out || !v_out) return HAFF_ERR_BAD_ARG;
   if (d != HD || H % HD || ldb != 8) return HAFF_ERR_UNSUPPORTED;
   if (ld_qkv < 3L * H || ldo < H || ldt < M || (ld_qkv & 7) || (ldo & 7)) return HAFF_ERR_BAD_ARG;
@@ -311,12 +319,13 @@ extern "C" int haff_lora_qkv_rope_fwd(const void* qkv, long ld_qkv, const void* 
   const int nh = H / HD;
   const long cap = (2048 + nh - 1) / nh;   // ~2048 workgroups: 8 per CU
   if (gy > cap) gy = cap;
-  hipLaunchKernelGGL(lora_qkv_rope_fwd_kernel, dim3(nh, (unsigned)gy), dim3(256), 0, HS(stream), p);
+  hipLaunchKernelGGL((lora_qkv_rope_fwd_kernel<F16>), dim3(nh, (unsigned)gy), dim3(256), 0, HS(stream), p);
   return check_launch();
 }
 
-extern "C" int haff_lora_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, long ld_in, const float* cos_sin, void* dqkv,
-                                      long ld_out, long M, int H, int d, int T, void* stream) {
+template <bool F16>
+static int lora_qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv, long ld_in, const float* cos_sin, void* dqkv,
+                                  long ld_out, long M, int H, int d, int T, void* stream) {
   if (M <= 0 || T <= 0 || H <= 0 || !dq || !dk || !dv || !cos_sin || !dqkv) return HAFF_ERR_BAD_ARG;
   if (d != HD || H % HD) return HAFF_ERR_UNSUPPORTED;
   if (ld_in < H || ld_out < 3L * H || (ld_in & 7) || (ld_out & 7)) return HAFF_ERR_BAD_ARG;
@@ -324,11 +333,12 @@ extern "C" int haff_lora_qkv_rope_bwd(const void* dq, const void* dk, const void
   const long total = M * (H / HD) * 8;
   long g = (total + 255) / 256;
   if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(lora_qkv_rope_bwd_kernel, dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)dq, (const bf16_t*)dk,
+  hipLaunchKernelGGL((lora_qkv_rope_bwd_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)dq, (const bf16_t*)dk,
                      (const bf16_t*)dv, ld_in, cos_sin, (bf16_t*)dqkv, ld_out, M, H, T);
   return check_launch();
 }
 
+template <bool F16>
 static int lora_dx_launch(const void* dtT, long ldt, const void* A2, long lda, const void* keep, const void* keep_v, long ldk, void* dx,
                           long ldx, int accumulate, long M, int K, float scale, void* stream) {
   if (M <= 0 || K <= 0 || !dtT || !A2 || !dx || (keep_v && !keep)) return HAFF_ERR_BAD_ARG;
@@ -342,21 +352,8 @@ static int lora_dx_launch(const void* dtT, long ldt, const void* A2, long lda, c
   const int gx = K / 128;
   const long cap = (2048 + gx - 1) / gx;
   if (gy > cap) gy = cap;
-  hipLaunchKernelGGL(lora_dx_kernel, dim3(gx, (unsigned)gy), dim3(256), 0, HS(stream), p);
+  hipLaunchKernelGGL((lora_dx_kernel<F16>), dim3(gx, (unsigned)gy), dim3(256), 0, HS(stream), p);
   return check_launch();
-}
-
-extern "C" int haff_lora_dx(const void* dtT, long ldt, const void* A2, long lda, const void* keep, long ldk, void* dx, long ldx,
-                            int accumulate, long M, int K, float scale, void* stream) {
-  return lora_dx_launch(dtT, ldt, A2, lda, keep, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
-}
-
-// haff_lora_dx with TWO dropout masks (peft: one lora_dropout module per adapted Linear, 2Haff/train_ds.py:218-230):
-//   dx (+)= scale * ( keep_q o (dt[0:8]^T . A2[0:8]) + keep_v o (dt[8:16]^T . A2[8:16]) ),   both masks bf16 [M][ldk] of values.
-extern "C" int haff_lora_dx2(const void* dtT, long ldt, const void* A2, long lda, const void* keep_q, const void* keep_v, long ldk,
-                             void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
-  if (!keep_q || !keep_v) return HAFF_ERR_BAD_ARG;
-  return lora_dx_launch(dtT, ldt, A2, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream);
 }
 
 // rows per block of haff_lora_tn (multiple of 64): ~16 row blocks
@@ -368,13 +365,10 @@ static long lora_tn_ws(long M, int R, int N) {
   const long rpb = lora_tn_rows_per_block(M);
   return ((M + rpb - 1) / rpb) * (long)R * N;
 }
-extern "C" int haff_lora_tn_workspace_elems(long M, int R, int N) {   // f32 values haff_lora_tn wants; < 0: does not fit an int
-  const long n = (M > 0 && R > 0 && N > 0) ? lora_tn_ws(M, R, N) : -1;
-  return n > 0x7fffffffL ? HAFF_ERR_UNSUPPORTED : (int)n;
-}
-extern "C" int haff_lora_tn(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace,
-                            long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale,
-                            void* stream) {
+
+template <bool F16>
+static int lora_tn_impl(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace, long workspace_elems,
+                        void* out, long ldo, int out_f32, int transposed, int j_valid, float scale, void* stream) {
   if (M <= 0 || N <= 0 || !sT || !big || !workspace || !out || j_valid <= 0 || j_valid > R) return HAFF_ERR_BAD_ARG;
   if (R != 8 && R != 16) return HAFF_ERR_UNSUPPORTED;
   if ((lds & 7) || lds < (M + 15) / 16 * 16 || !al16(sT) || (N & 1) || (ldb & 1) || ldb < N || (reinterpret_cast<uintptr_t>(big) & 3))
@@ -385,15 +379,76 @@ extern "C" int haff_lora_tn(const void* sT, long lds, int R, const void* big, lo
   const int nrb = (int)((M + rpb - 1) / rpb);
   const dim3 g((N + 127) / 128, nrb), b(256);
   if (R == 8)
-    hipLaunchKernelGGL((lora_tn_kernel<8>), g, b, 0, HS(stream), (const bf16_t*)sT, lds, (const bf16_t*)big, ldb, M, N, (int)rpb, workspace);
+    hipLaunchKernelGGL((lora_tn_kernel<8, F16>), g, b, 0, HS(stream), (const bf16_t*)sT, lds, (const bf16_t*)big, ldb, M, N, (int)rpb, workspace);
   else
-    hipLaunchKernelGGL((lora_tn_kernel<16>), g, b, 0, HS(stream), (const bf16_t*)sT, lds, (const bf16_t*)big, ldb, M, N, (int)rpb, workspace);
+    hipLaunchKernelGGL((lora_tn_kernel<16, F16>), g, b, 0, HS(stream), (const bf16_t*)sT, lds, (const bf16_t*)big, ldb, M, N, (int)rpb, workspace);
   const long total = (long)j_valid * N;
   long gr = (total + 255) / 256;
   if (gr > 4096) gr = 4096;
   if (out_f32)
     hipLaunchKernelGGL((lora_tn_reduce_kernel<float>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (float*)out, ldo, transposed, j_valid, scale);
+  else if (F16)
+    hipLaunchKernelGGL((lora_tn_reduce_kernel<f16_t>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (f16_t*)out, ldo, transposed, j_valid, scale);
   else
     hipLaunchKernelGGL((lora_tn_reduce_kernel<bf16_t>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (bf16_t*)out, ldo, transposed, j_valid, scale);
   return check_launch();
+}
+
+extern "C" int haff_lora_qkv_rope_fwd(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
+                                      int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M,
+                                      int H, int d, int T, float scale, void* stream) {
+  return lora_qkv_rope_fwd_impl<false>(qkv, ld_qkv, tT, ldt, Bq, Bv, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale, stream);
+}
+
+extern "C" int haff_lora_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, long ld_in, const float* cos_sin, void* dqkv,
+                                      long ld_out, long M, int H, int d, int T, void* stream) {
+  return lora_qkv_rope_bwd_impl<false>(dq, dk, dv, ld_in, cos_sin, dqkv, ld_out, M, H, d, T, stream);
+}
+
+extern "C" int haff_lora_dx(const void* dtT, long ldt, const void* A2, long lda, const void* keep, long ldk, void* dx, long ldx,
+                            int accumulate, long M, int K, float scale, void* stream) {
+  return lora_dx_launch<false>(dtT, ldt, A2, lda, keep, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
+}
+
+// haff_lora_dx with TWO dropout masks (peft: one lora_dropout module per adapted Linear, 2Haff/train_ds.py:218-230):
+//   dx (+)= scale * ( keep_q o (dt[0:8]^T . A2[0:8]) + keep_v o (dt[8:16]^T . A2[8:16]) ),   both masks bf16 [M][ldk] of values.
+extern "C" int haff_lora_dx2(const void* dtT, long ldt, const void* A2, long lda, const void* keep_q, const void* keep_v, long ldk,
+                             void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
+  if (!keep_q || !keep_v) return HAFF_ERR_BAD_ARG;
+  return lora_dx_launch<false>(dtT, ldt, A2, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream);
+}
+
+extern "C" int haff_lora_tn_workspace_elems(long M, int R, int N) {   // f32 values haff_lora_tn wants; < 0: does not fit an int
+  const long n = (M > 0 && R > 0 && N > 0) ? lora_tn_ws(M, R, N) : -1;
+  return n > 0x7fffffffL ? HAFF_ERR_UNSUPPORTED : (int)n;
+}
+extern "C" int haff_lora_tn(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace,
+                            long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale,
+                            void* stream) {
+  return lora_tn_impl<false>(sT, lds, R, big, ldb, M, N, workspace, workspace_elems, out, ldo, out_f32, transposed, j_valid, scale, stream);
+}
+
+// ---- fp16 instances (fp16 fine-tuning): every 16-bit operand, mask and result IEEE binary16; same arguments and contracts ----
+extern "C" int haff_lora_qkv_rope_fwd_f16(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
+                                          int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M,
+                                          int H, int d, int T, float scale, void* stream) {
+  return lora_qkv_rope_fwd_impl<true>(qkv, ld_qkv, tT, ldt, Bq, Bv, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale, stream);
+}
+extern "C" int haff_lora_qkv_rope_bwd_f16(const void* dq, const void* dk, const void* dv, long ld_in, const float* cos_sin, void* dqkv,
+                                          long ld_out, long M, int H, int d, int T, void* stream) {
+  return lora_qkv_rope_bwd_impl<true>(dq, dk, dv, ld_in, cos_sin, dqkv, ld_out, M, H, d, T, stream);
+}
+extern "C" int haff_lora_dx_f16(const void* dtT, long ldt, const void* A2, long lda, const void* keep, long ldk, void* dx, long ldx,
+                                int accumulate, long M, int K, float scale, void* stream) {
+  return lora_dx_launch<true>(dtT, ldt, A2, lda, keep, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
+}
+extern "C" int haff_lora_dx2_f16(const void* dtT, long ldt, const void* A2, long lda, const void* keep_q, const void* keep_v, long ldk,
+                                 void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
+  if (!keep_q || !keep_v) return HAFF_ERR_BAD_ARG;
+  return lora_dx_launch<true>(dtT, ldt, A2, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream);
+}
+extern "C" int haff_lora_tn_f16(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace,
+                                long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale,
+                                void* stream) {
+  return lora_tn_impl<true>(sT, lds, R, big, ldb, M, N, workspace, workspace_elems, out, ldo, out_f32, transposed, j_valid, scale, stream);
 }

@@ -4,6 +4,8 @@
 // batched entry points); everything here is the HBM-bound remainder: transposes, activation / norm / softmax /
 // RoPE adjoints, fused cross-entropy, mask losses, bilinear adjoint, embedding scatter-add, AdamW.
 // All kernels are templated on the storage type (bf16 / f32) and compute in fp32.
+#include <type_traits>
+
 #include "haff_common.h"
 
 namespace {
@@ -103,8 +105,9 @@ __global__ void mul_kernel(const T* a, const T* b, T* out, long n) {
     elem<T>::st(out + i, elem<T>::ld(a + i) * elem<T>::ld(b + i));
 }
 
-// bf16 forms with 16-byte accesses: a thread owns 8 consecutive outputs (half a 16-column group)
-__global__ void swiglu_fwd_vec_kernel(const bf16_t* gu, bf16_t* y, long M, int F) {
+// 16-bit forms (T = bf16_t / f16_t) with 16-byte accesses: a thread owns 8 consecutive outputs (half a 16-column group)
+template <typename T>
+__global__ void swiglu_fwd_vec_kernel(const T* gu, T* y, long M, int F) {
   const long n8 = M * F / 8;
   const int f8 = F >> 3;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
@@ -119,7 +122,8 @@ __global__ void swiglu_fwd_vec_kernel(const bf16_t* gu, bf16_t* y, long M, int F
     store8(y + m * F + j, o);
   }
 }
-__global__ void swiglu_bwd_vec_kernel(const bf16_t* gu, const bf16_t* dy, bf16_t* dgu, long M, int F) {
+template <typename T>
+__global__ void swiglu_bwd_vec_kernel(const T* gu, const T* dy, T* dgu, long M, int F) {
   const long n8 = M * F / 8;
   const int f8 = F >> 3;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
@@ -181,18 +185,22 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const T* x, const T* dy, 
   }
 }
 
-// the same for bf16 rows of C = 512 * NV elements (Llama hidden sizes): the row and its gradient live in registers as 16-byte
+// the two halves of a dword of 16-bit values as fp32 (T = bf16_t / f16_t)
+template <typename T> __device__ __forceinline__ float lo16(unsigned w) { return h16<std::is_same<T, f16_t>::value>::lo(w); }
+template <typename T> __device__ __forceinline__ float hi16(unsigned w) { return h16<std::is_same<T, f16_t>::value>::hi(w); }
+
+// the same for 16-bit rows (T = bf16_t / f16_t) of C = 512 * NV elements (Llama hidden sizes): the row and its gradient live in registers as 16-byte
 // loads — ONE pass over HBM; the generic kernel above walks the row four times with 2-byte loads (74 us for 2808 x 4096
 // against 15 us of traffic at the HBM rate: 2.6 % of the fine-tune step)
-template <bool RMS, int NV>
-__global__ __launch_bounds__(256) void norm_bwd_vec_kernel(const bf16_t* x, const bf16_t* dy, const float* w, bf16_t* dx, float* dyx,
-                                                          int rows, float eps, const bf16_t* add) {
+template <typename T, bool RMS, int NV>
+__global__ __launch_bounds__(256) void norm_bwd_vec_kernel(const T* x, const T* dy, const float* w, T* dx, float* dyx,
+                                                          int rows, float eps, const T* add) {
   constexpr int C = 512 * NV;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const bf16_t* xr = x + (long)row * C;
-  const bf16_t* dr = dy + (long)row * C;
+  const T* xr = x + (long)row * C;
+  const T* dr = dy + (long)row * C;
   uint4 xv[NV], dv[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -202,7 +210,7 @@ __global__ __launch_bounds__(256) void norm_bwd_vec_kernel(const bf16_t* x, cons
   auto unpack = [](const uint4& r, float (&v)[8]) {
     const unsigned u[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(u[e] << 16); v[2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u); }
+    for (int e = 0; e < 4; ++e) { v[2 * e] = lo16<T>(u[e]); v[2 * e + 1] = hi16<T>(u[e]); }
   };
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -279,7 +287,8 @@ __global__ void colsum_kernel(const T* x, float* out, long R, int C, long rows_p
 // LDS in index order and group 0 adds the block's sums to out. At most 64 blocks of 16 waves: with one block per 256 rows
 // the 65 536 x 256 image-token bias gradients of the mask decoders spent their time in 256 atomics per output address
 // (38 us, 0.9 TB/s); the 2-byte one-column-per-thread walk above ran them at 0.7 TB/s
-__global__ __launch_bounds__(1024) void colsum_vec_kernel(const bf16_t* x, float* out, long R, int C, long rows_per_block) {
+template <typename T>
+__global__ __launch_bounds__(1024) void colsum_vec_kernel(const T* x, float* out, long R, int C, long rows_per_block) {
   __shared__ float red[1024][9];
   const int cpr = C >> 3, rpp = 1024 / cpr;
   const int ch = threadIdx.x % cpr, rg = threadIdx.x / cpr;
@@ -295,7 +304,7 @@ __global__ __launch_bounds__(1024) void colsum_vec_kernel(const bf16_t* x, float
     for (int u = 0; u < 8; ++u) {
       const unsigned w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { acc[2 * e] += __uint_as_float(w[e] << 16); acc[2 * e + 1] += __uint_as_float(w[e] & 0xffff0000u); }
+      for (int e = 0; e < 4; ++e) { acc[2 * e] += lo16<T>(w[e]); acc[2 * e + 1] += hi16<T>(w[e]); }
     }
   }
   for (; r < r1; r += rpp) {
@@ -633,9 +642,12 @@ __global__ void sumsq_kernel(const T* g, float* out, long n) {
 }
 // AdamW (torch semantics; train_ds.py:352-360: lr 3e-4 default, betas (0.9,0.95), wd 0): fp32 master + moments,
 // gradient scaled by gscale (clipping / accumulation average), optional low-precision copy of the parameter.
+// norm (device fp32 scalar, may be null): the global gradient norm; when it is not finite (an inf / NaN gradient element: the fp16
+// mode's overflow) the step is skipped — master, moments and the copy keep every bit (DeepSpeed's fp16 optimizer skips the step)
 template <typename TG, typename TP>
 __global__ void adamw_kernel(float* master, float* m, float* v, const TG* g, TP* param_lp, long n, float lr, float b1, float b2,
-                             float eps, float wd, float bc1, float bc2, float gscale, const float* gscale_dev) {
+                             float eps, float wd, float bc1, float bc2, float gscale, const float* gscale_dev, const float* norm) {
+  if (norm && !isfinite(*norm)) return;
   if (gscale_dev) gscale *= *gscale_dev;   // the clip coefficient straight from the device (no host read of the gradient norm)
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float gr = elem<TG>::ld(g + i) * gscale;
@@ -653,61 +665,67 @@ __global__ void adamw_kernel(float* master, float* m, float* v, const TG* g, TP*
 }  // namespace
 
 #define HS(s) reinterpret_cast<hipStream_t>(s)
-#define DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
-  do { if ((dtype) == 0) { CALL_BF16; } else { CALL_F32; } } while (0)
+// storage-type dispatch: T = the element type of dtype code 0 (bf16), 1 (f32) or 3 (f16); any other code is refused before a
+// launch (code 2 is the norms' mixed form, which none of these kernels has)
+#define DISPATCH_T(dtype, ...) \
+  do { \
+    switch (dtype) { \
+      case 0: { using T = bf16_t; __VA_ARGS__; } break; \
+      case 1: { using T = float; __VA_ARGS__; } break; \
+      case 3: { using T = f16_t; __VA_ARGS__; } break; \
+      default: return HAFF_ERR_BAD_ARG; \
+    } \
+  } while (0)
 
 extern "C" int haff_transpose(const void* in, long ld_in, long s_in_o, long s_in_i, void* out, int R, int C, int Rp, int Cp,
                               int nb_outer, int nb_inner, int dtype, void* stream) {
   if (R <= 0 || C <= 0 || Rp < R || Cp < C || nb_outer <= 0 || nb_inner <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g((Cp + 31) / 32, (Rp + 31) / 32, nb_outer * nb_inner), b(32, 8);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL((transpose_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)in, ld_in, s_in_o, s_in_i, (bf16_t*)out, R, C, Rp, Cp, nb_inner),
-             hipLaunchKernelGGL((transpose_kernel<float>), g, b, 0, HS(stream), (const float*)in, ld_in, s_in_o, s_in_i, (float*)out, R, C, Rp, Cp, nb_inner));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((transpose_kernel<T>), g, b, 0, HS(stream), (const T*)in, ld_in, s_in_o, s_in_i, (T*)out, R, C, Rp, Cp, nb_inner));
   return haff_check_launch();
 }
 
 extern "C" int haff_act_fwd(const void* x, void* y, long n, int act, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((act_fwd_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)x, (bf16_t*)y, n, act),
-             hipLaunchKernelGGL((act_fwd_kernel<float>), g, b, 0, HS(stream), (const float*)x, (float*)y, n, act));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((act_fwd_kernel<T>), g, b, 0, HS(stream), (const T*)x, (T*)y, n, act));
   return haff_check_launch();
 }
 extern "C" int haff_act_bwd(const void* x, const void* dy, void* dx, long n, int act, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((act_bwd_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, n, act),
-             hipLaunchKernelGGL((act_bwd_kernel<float>), g, b, 0, HS(stream), (const float*)x, (const float*)dy, (float*)dx, n, act));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((act_bwd_kernel<T>), g, b, 0, HS(stream), (const T*)x, (const T*)dy, (T*)dx, n, act));
   return haff_check_launch();
 }
 extern "C" int haff_swiglu_fwd(const void* gu, void* y, long M, int F, int dtype, void* stream) {
   if (M <= 0 || F <= 0 || (F & 15)) return HAFF_ERR_BAD_ARG;
-  if (dtype == 0 && ((reinterpret_cast<uintptr_t>(gu) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
-    hipLaunchKernelGGL(swiglu_fwd_vec_kernel, dim3(grid_for(M * F / 8, 256)), dim3(256), 0, HS(stream), (const bf16_t*)gu, (bf16_t*)y, M, F);
+  if ((dtype == 0 || dtype == 3) && ((reinterpret_cast<uintptr_t>(gu) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
+    const dim3 g(grid_for(M * F / 8, 256)), b(256);
+    if (dtype == 0) hipLaunchKernelGGL((swiglu_fwd_vec_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)gu, (bf16_t*)y, M, F);
+    else hipLaunchKernelGGL((swiglu_fwd_vec_kernel<f16_t>), g, b, 0, HS(stream), (const f16_t*)gu, (f16_t*)y, M, F);
     return haff_check_launch();
   }
   dim3 g(grid_for(M * F, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_fwd_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)gu, (bf16_t*)y, M, F),
-             hipLaunchKernelGGL((swiglu_fwd_kernel<float>), g, b, 0, HS(stream), (const float*)gu, (float*)y, M, F));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_fwd_kernel<T>), g, b, 0, HS(stream), (const T*)gu, (T*)y, M, F));
   return haff_check_launch();
 }
 extern "C" int haff_swiglu_bwd(const void* gu, const void* dy, void* dgu, long M, int F, int dtype, void* stream) {
   if (M <= 0 || F <= 0 || (F & 15)) return HAFF_ERR_BAD_ARG;
-  if (dtype == 0 && ((reinterpret_cast<uintptr_t>(gu) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dgu)) & 15) == 0) {
-    hipLaunchKernelGGL(swiglu_bwd_vec_kernel, dim3(grid_for(M * F / 8, 256)), dim3(256), 0, HS(stream), (const bf16_t*)gu, (const bf16_t*)dy, (bf16_t*)dgu, M, F);
+  if ((dtype == 0 || dtype == 3) && ((reinterpret_cast<uintptr_t>(gu) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dgu)) & 15) == 0) {
+    const dim3 g(grid_for(M * F / 8, 256)), b(256);
+    if (dtype == 0) hipLaunchKernelGGL((swiglu_bwd_vec_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)gu, (const bf16_t*)dy, (bf16_t*)dgu, M, F);
+    else hipLaunchKernelGGL((swiglu_bwd_vec_kernel<f16_t>), g, b, 0, HS(stream), (const f16_t*)gu, (const f16_t*)dy, (f16_t*)dgu, M, F);
     return haff_check_launch();
   }
   dim3 g(grid_for(M * F, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_bwd_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)gu, (const bf16_t*)dy, (bf16_t*)dgu, M, F),
-             hipLaunchKernelGGL((swiglu_bwd_kernel<float>), g, b, 0, HS(stream), (const float*)gu, (const float*)dy, (float*)dgu, M, F));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_bwd_kernel<T>), g, b, 0, HS(stream), (const T*)gu, (const T*)dy, (T*)dgu, M, F));
   return haff_check_launch();
 }
 // out = alpha*a + beta*b (b may be null)
 extern "C" int haff_axpby(const void* a, const void* b, void* out, long n, float alpha, float beta, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), blk(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((axpby_kernel<bf16_t>), g, blk, 0, HS(stream), (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n, alpha, beta),
-             hipLaunchKernelGGL((axpby_kernel<float>), g, blk, 0, HS(stream), (const float*)a, (const float*)b, (float*)out, n, alpha, beta));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((axpby_kernel<T>), g, blk, 0, HS(stream), (const T*)a, (const T*)b, (T*)out, n, alpha, beta));
   return haff_check_launch();
 }
 // out = a * alpha with alpha an fp32 scalar (alpha_stride = 0) or one fp32 value per row (alpha_stride = 1) in DEVICE memory: the
@@ -718,16 +736,14 @@ extern "C" int haff_scale_dev(const void* a, void* out, long rows, long cols, co
                               void* stream) {
   if (rows <= 0 || cols <= 0 || !alpha || (alpha_stride != 0 && alpha_stride != 1)) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(rows * cols, 256)), blk(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((scale_dev_kernel<bf16_t>), g, blk, 0, HS(stream), (const bf16_t*)a, (bf16_t*)out, rows, cols, alpha, alpha_stride),
-             hipLaunchKernelGGL((scale_dev_kernel<float>), g, blk, 0, HS(stream), (const float*)a, (float*)out, rows, cols, alpha, alpha_stride));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((scale_dev_kernel<T>), g, blk, 0, HS(stream), (const T*)a, (T*)out, rows, cols, alpha, alpha_stride));
   return haff_check_launch();
 }
 // out = a * b elementwise (LoRA dropout mask, peft lora_dropout, train_ds.py:224)
 extern "C" int haff_mul(const void* a, const void* b, void* out, long n, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), blk(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((mul_kernel<bf16_t>), g, blk, 0, HS(stream), (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n),
-             hipLaunchKernelGGL((mul_kernel<float>), g, blk, 0, HS(stream), (const float*)a, (const float*)b, (float*)out, n));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((mul_kernel<T>), g, blk, 0, HS(stream), (const T*)a, (const T*)b, (T*)out, n));
   return haff_check_launch();
 }
 // rms != 0: RMSNorm adjoint (dx only). dyx (f32 [rows][C], may be null) receives dy*xhat for the weight gradient.
@@ -737,20 +753,21 @@ static int norm_bwd_launch(const void* x, const void* dy, const float* w, const 
   dim3 g((rows + 3) / 4), b(256);
   const bool al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) |
                     reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dyx) | reinterpret_cast<uintptr_t>(add)) & 15) == 0;
-  if (dtype == 0 && al && (C == 4096 || C == 5120)) {   // Llama 7B / 13B rows: one pass, the row in registers
-#define HAFF_NBV(R_, NV_) hipLaunchKernelGGL((norm_bwd_vec_kernel<R_, NV_>), g, b, 0, HS(stream), (const bf16_t*)x, (const bf16_t*)dy, w, (bf16_t*)dx, dyx, rows, eps, (const bf16_t*)add)
-    if (C == 4096) { if (rms) HAFF_NBV(true, 8); else HAFF_NBV(false, 8); }
-    else { if (rms) HAFF_NBV(true, 10); else HAFF_NBV(false, 10); }
+  if ((dtype == 0 || dtype == 3) && al && (C == 4096 || C == 5120)) {   // Llama 7B / 13B rows: one pass, the row in registers
+#define HAFF_NBV(T_, R_, NV_) hipLaunchKernelGGL((norm_bwd_vec_kernel<T_, R_, NV_>), g, b, 0, HS(stream), (const T_*)x, (const T_*)dy, w, (T_*)dx, dyx, rows, eps, (const T_*)add)
+    if (dtype == 0) {
+      if (C == 4096) { if (rms) HAFF_NBV(bf16_t, true, 8); else HAFF_NBV(bf16_t, false, 8); }
+      else { if (rms) HAFF_NBV(bf16_t, true, 10); else HAFF_NBV(bf16_t, false, 10); }
+    } else {
+      if (C == 4096) { if (rms) HAFF_NBV(f16_t, true, 8); else HAFF_NBV(f16_t, false, 8); }
+      else { if (rms) HAFF_NBV(f16_t, true, 10); else HAFF_NBV(f16_t, false, 10); }
+    }
 #undef HAFF_NBV
     return haff_check_launch();
   }
-  if (dtype == 0) {
-    if (rms) hipLaunchKernelGGL((norm_bwd_kernel<bf16_t, true>), g, b, 0, HS(stream), (const bf16_t*)x, (const bf16_t*)dy, w, (bf16_t*)dx, dyx, rows, C, eps, (const bf16_t*)add);
-    else hipLaunchKernelGGL((norm_bwd_kernel<bf16_t, false>), g, b, 0, HS(stream), (const bf16_t*)x, (const bf16_t*)dy, w, (bf16_t*)dx, dyx, rows, C, eps, (const bf16_t*)add);
-  } else {
-    if (rms) hipLaunchKernelGGL((norm_bwd_kernel<float, true>), g, b, 0, HS(stream), (const float*)x, (const float*)dy, w, (float*)dx, dyx, rows, C, eps, (const float*)add);
-    else hipLaunchKernelGGL((norm_bwd_kernel<float, false>), g, b, 0, HS(stream), (const float*)x, (const float*)dy, w, (float*)dx, dyx, rows, C, eps, (const float*)add);
-  }
+  DISPATCH_T(dtype,
+             if (rms) hipLaunchKernelGGL((norm_bwd_kernel<T, true>), g, b, 0, HS(stream), (const T*)x, (const T*)dy, w, (T*)dx, dyx, rows, C, eps, (const T*)add);
+             else hipLaunchKernelGGL((norm_bwd_kernel<T, false>), g, b, 0, HS(stream), (const T*)x, (const T*)dy, w, (T*)dx, dyx, rows, C, eps, (const T*)add));
   return haff_check_launch();
 }
 
@@ -770,33 +787,32 @@ extern "C" int haff_norm_bwd_add(const void* x, const void* dy, const float* w, 
 }
 extern "C" int haff_colsum(const void* x, float* out, long R, int C, int dtype, void* stream) {
   if (R <= 0 || C <= 0) return HAFF_ERR_BAD_ARG;
-  if (dtype == 0 && (C & 7) == 0 && C >= 8 && C <= 2048 && ((C >> 3) & ((C >> 3) - 1)) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-      R >= 1024) {
+  if ((dtype == 0 || dtype == 3) && (C & 7) == 0 && C >= 8 && C <= 2048 && ((C >> 3) & ((C >> 3) - 1)) == 0 &&
+      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && R >= 1024) {
     const long rpp = 1024 / (C >> 3);
     long rpb_v = ((R + 63) / 64 + 8 * rpp - 1) / (8 * rpp) * (8 * rpp);   // <= 64 blocks, whole 8-row steps
-    hipLaunchKernelGGL(colsum_vec_kernel, dim3((unsigned)((R + rpb_v - 1) / rpb_v)), dim3(1024), 0, HS(stream), (const bf16_t*)x, out, R, C, rpb_v);
+    const dim3 g((unsigned)((R + rpb_v - 1) / rpb_v)), b(1024);
+    if (dtype == 0) hipLaunchKernelGGL((colsum_vec_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)x, out, R, C, rpb_v);
+    else hipLaunchKernelGGL((colsum_vec_kernel<f16_t>), g, b, 0, HS(stream), (const f16_t*)x, out, R, C, rpb_v);
     return haff_check_launch();
   }
   const long rpb = 256;
   dim3 g((C + 63) / 64, (unsigned)((R + rpb - 1) / rpb)), b(64);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)x, out, R, C, rpb),
-             hipLaunchKernelGGL((colsum_kernel<float>), g, b, 0, HS(stream), (const float*)x, out, R, C, rpb));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<T>), g, b, 0, HS(stream), (const T*)x, out, R, C, rpb));
   return haff_check_launch();
 }
 extern "C" int haff_softmax_fwd(const float* s, long ld, void* p, long ldp, long rows, int Nq, int Nk, float scale, int causal,
                                 int q_pos0, int dtype, void* stream) {
   if (rows <= 0 || Nk <= 0 || ldp < Nk || ld < Nk) return HAFF_ERR_BAD_ARG;
   dim3 g((unsigned)((rows + 3) / 4)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_fwd_kernel<bf16_t>), g, b, 0, HS(stream), s, ld, (bf16_t*)p, ldp, rows, Nq, Nk, scale, causal, q_pos0),
-             hipLaunchKernelGGL((softmax_fwd_kernel<float>), g, b, 0, HS(stream), s, ld, (float*)p, ldp, rows, Nq, Nk, scale, causal, q_pos0));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_fwd_kernel<T>), g, b, 0, HS(stream), s, ld, (T*)p, ldp, rows, Nq, Nk, scale, causal, q_pos0));
   return haff_check_launch();
 }
 extern "C" int haff_softmax_bwd(const void* p, long ldp, const float* dp, long ld, void* ds, long rows, int Nk, float scale,
                                 int dtype, void* stream) {
   if (rows <= 0 || Nk <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g((unsigned)((rows + 3) / 4)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_bwd_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)p, ldp, dp, ld, (bf16_t*)ds, rows, Nk, scale),
-             hipLaunchKernelGGL((softmax_bwd_kernel<float>), g, b, 0, HS(stream), (const float*)p, ldp, dp, ld, (float*)ds, rows, Nk, scale));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_bwd_kernel<T>), g, b, 0, HS(stream), (const T*)p, ldp, dp, ld, (T*)ds, rows, Nk, scale));
   return haff_check_launch();
 }
 extern "C" int haff_rope(const void* x, long ldx, void* y, long ldy, const float* cos_sin, long rows, int Tlen, int H, int d,
@@ -804,16 +820,14 @@ extern "C" int haff_rope(const void* x, long ldx, void* y, long ldy, const float
   if (rows <= 0 || (d & 1)) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(rows * H * (d / 2), 256)), b(256);
   const float sign = adjoint ? -1.f : 1.f;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((rope_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)x, ldx, (bf16_t*)y, ldy, cos_sin, rows, Tlen, H, d, pos0, sign),
-             hipLaunchKernelGGL((rope_kernel<float>), g, b, 0, HS(stream), (const float*)x, ldx, (float*)y, ldy, cos_sin, rows, Tlen, H, d, pos0, sign));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((rope_kernel<T>), g, b, 0, HS(stream), (const T*)x, ldx, (T*)y, ldy, cos_sin, rows, Tlen, H, d, pos0, sign));
   return haff_check_launch();
 }
 extern "C" int haff_cross_entropy(const void* logits, long ld, const long* labels, float* row_loss, void* dlogits, long rows,
                                   int V, float gscale, int dtype, void* stream) {
   if (rows <= 0 || V <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g((unsigned)rows), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((cross_entropy_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)logits, ld, labels, row_loss, (bf16_t*)dlogits, V, gscale),
-             hipLaunchKernelGGL((cross_entropy_kernel<float>), g, b, 0, HS(stream), (const float*)logits, ld, labels, row_loss, (float*)dlogits, V, gscale));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((cross_entropy_kernel<T>), g, b, 0, HS(stream), (const T*)logits, ld, labels, row_loss, (T*)dlogits, V, gscale));
   return haff_check_launch();
 }
 extern "C" int haff_mask_loss_stats(const float* x, const float* t, float* stats, int n_samples, long n, float wgt, void* stream) {
@@ -845,8 +859,7 @@ extern "C" int haff_resize_bilinear_bwd(const float* dout, float* din, int N, in
 extern "C" int haff_scatter_add_rows(const long* ids, const void* dx, float* dE, long rows, int C, int dtype, void* stream) {
   if (rows <= 0 || C <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(rows * C, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((scatter_add_rows_kernel<bf16_t>), g, b, 0, HS(stream), ids, (const bf16_t*)dx, dE, rows, C),
-             hipLaunchKernelGGL((scatter_add_rows_kernel<float>), g, b, 0, HS(stream), ids, (const float*)dx, dE, rows, C));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((scatter_add_rows_kernel<T>), g, b, 0, HS(stream), ids, (const T*)dx, dE, rows, C));
   return haff_check_launch();
 }
 // ---- ordered (atomic-free, bitwise repeatable) forms; partial buffers are caller-provided DEVICE fp32 ----
@@ -862,8 +875,7 @@ extern "C" int haff_sumsq_partials(const void* g, float* partials, long n, int d
   if (n <= 0 || !partials || !n_parts) return HAFF_ERR_BAD_ARG;
   const int nb = grid_for(n, 256) > 1024 ? 1024 : grid_for(n, 256);
   *n_parts = nb;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((sumsq_partials_kernel<bf16_t>), dim3(nb), dim3(256), 0, HS(stream), (const bf16_t*)g, partials, n),
-             hipLaunchKernelGGL((sumsq_partials_kernel<float>), dim3(nb), dim3(256), 0, HS(stream), (const float*)g, partials, n));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((sumsq_partials_kernel<T>), dim3(nb), dim3(256), 0, HS(stream), (const T*)g, partials, n));
   return haff_check_launch();
 }
 // partials: >= n_samples * 256 * 4 floats, laid out [sample][part][4]; *n_parts = parts per sample
@@ -886,41 +898,43 @@ extern "C" int haff_colsum_partials(const void* x, float* partials, long R, int 
   const int parts = haff_colsum_parts(R);
   const long rpb = (R + parts - 1) / parts;
   dim3 g((C + 63) / 64, parts), b(64);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_partials_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)x, partials, R, C, rpb),
-             hipLaunchKernelGGL((colsum_partials_kernel<float>), g, b, 0, HS(stream), (const float*)x, partials, R, C, rpb));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_partials_kernel<T>), g, b, 0, HS(stream), (const T*)x, partials, R, C, rpb));
   return haff_check_launch();
 }
 // sorted_ids / order: a STABLE ascending sort of the rows' ids and the permutation that produced it (DEVICE int64 [rows])
 extern "C" int haff_scatter_add_rows_sorted(const long* sorted_ids, const long* order, const void* dx, float* dE, long rows, int C,
                                             int dtype, void* stream) {
   if (rows <= 0 || C <= 0 || !sorted_ids || !order) return HAFF_ERR_BAD_ARG;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((scatter_add_rows_sorted_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, HS(stream), sorted_ids, order, (const bf16_t*)dx, dE, rows, C),
-             hipLaunchKernelGGL((scatter_add_rows_sorted_kernel<float>), dim3((unsigned)rows), dim3(256), 0, HS(stream), sorted_ids, order, (const float*)dx, dE, rows, C));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((scatter_add_rows_sorted_kernel<T>), dim3((unsigned)rows), dim3(256), 0, HS(stream), sorted_ids, order, (const T*)dx, dE, rows, C));
   return haff_check_launch();
 }
 extern "C" int haff_sumsq(const void* g, float* out, long n, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 gr(grid_for(n, 256) > 1024 ? 1024 : grid_for(n, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((sumsq_kernel<bf16_t>), gr, b, 0, HS(stream), (const bf16_t*)g, out, n),
-             hipLaunchKernelGGL((sumsq_kernel<float>), gr, b, 0, HS(stream), (const float*)g, out, n));
+  DISPATCH_T(dtype, hipLaunchKernelGGL((sumsq_kernel<T>), gr, b, 0, HS(stream), (const T*)g, out, n));
   return haff_check_launch();
 }
-// g_dtype: gradient storage (0 bf16 / 1 f32); lp_dtype: -1 none, 0 bf16 copy of the updated parameter
+// g_dtype: gradient storage (0 bf16 / 1 f32 / 3 f16); lp_dtype: -1 none, 0 bf16 / 3 f16 copy of the updated parameter
 static int adamw_launch(float* master, float* m, float* v, const void* g, void* param_lp, long n, float lr, float beta1,
-                               float beta2, float eps, float wd, int step, float gscale, const float* gscale_dev, int g_dtype, int lp_dtype, void* stream) {
+                               float beta2, float eps, float wd, int step, float gscale, const float* gscale_dev, const float* norm,
+                               int g_dtype, int lp_dtype, void* stream) {
   if (n <= 0 || step <= 0) return HAFF_ERR_BAD_ARG;
+  if (lp_dtype != -1 && lp_dtype != 0 && lp_dtype != 3) return HAFF_ERR_BAD_ARG;
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   dim3 gr(grid_for(n, 256)), b(256);
-  if (g_dtype == 0)
-    hipLaunchKernelGGL((adamw_kernel<bf16_t, bf16_t>), gr, b, 0, HS(stream), master, m, v, (const bf16_t*)g, lp_dtype == 0 ? (bf16_t*)param_lp : nullptr, n, lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gscale_dev);
-  else
-    hipLaunchKernelGGL((adamw_kernel<float, bf16_t>), gr, b, 0, HS(stream), master, m, v, (const float*)g, lp_dtype == 0 ? (bf16_t*)param_lp : nullptr, n, lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gscale_dev);
+  // the copy's type is a template parameter: an f16 copy is f16_rn(master), a bf16 one bf16_rn(master) (lp_dtype -1: no copy)
+#define HAFF_ADAMW(TP_) \
+  DISPATCH_T(g_dtype, hipLaunchKernelGGL((adamw_kernel<T, TP_>), gr, b, 0, HS(stream), master, m, v, (const T*)g, \
+                                         lp_dtype == -1 ? nullptr : (TP_*)param_lp, n, lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gscale_dev, norm))
+  if (lp_dtype == 3) HAFF_ADAMW(f16_t);
+  else HAFF_ADAMW(bf16_t);
+#undef HAFF_ADAMW
   return haff_check_launch();
 }
 
 extern "C" int haff_adamw_step(float* master, float* m, float* v, const void* g, void* param_lp, long n, float lr, float beta1,
                                float beta2, float eps, float wd, int step, float gscale, int g_dtype, int lp_dtype, void* stream) {
-  return adamw_launch(master, m, v, g, param_lp, n, lr, beta1, beta2, eps, wd, step, gscale, nullptr, g_dtype, lp_dtype, stream);
+  return adamw_launch(master, m, v, g, param_lp, n, lr, beta1, beta2, eps, wd, step, gscale, nullptr, nullptr, g_dtype, lp_dtype, stream);
 }
 // the same with the gradient scale multiplied by a device scalar (the clip coefficient min(1, 1 / (norm + 1e-6)) computed on the
 // device: the optimizer launches are then queued behind backward without the host waiting for the norm)
@@ -928,7 +942,16 @@ extern "C" int haff_adamw_step_dev(float* master, float* m, float* v, const void
                                    float beta2, float eps, float wd, int step, float gscale, const float* gscale_dev, int g_dtype,
                                    int lp_dtype, void* stream) {
   if (!gscale_dev) return HAFF_ERR_BAD_ARG;
-  return adamw_launch(master, m, v, g, param_lp, n, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, g_dtype, lp_dtype, stream);
+  return adamw_launch(master, m, v, g, param_lp, n, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, nullptr, g_dtype, lp_dtype, stream);
+}
+// haff_adamw_step_dev that skips the update when the device gradient norm `norm` (fp32 scalar, the one the clip coefficient came
+// from) is not finite: the fp16 mode's overflow check (with f16 gradients the sum of squares cannot overflow fp32, so a non-finite
+// norm means an inf / NaN element). gscale_dev may be null here.
+extern "C" int haff_adamw_step_skip(float* master, float* m, float* v, const void* g, void* param_lp, long n, float lr, float beta1,
+                                    float beta2, float eps, float wd, int step, float gscale, const float* gscale_dev, const float* norm,
+                                    int g_dtype, int lp_dtype, void* stream) {
+  if (!norm) return HAFF_ERR_BAD_ARG;
+  return adamw_launch(master, m, v, g, param_lp, n, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, norm, g_dtype, lp_dtype, stream);
 }
 
 // z, t f32 [rows][C<=8]; probs (may be null) = softmax(z); loss f32[rows]; dz (may be null) = d loss / d z

@@ -113,7 +113,13 @@ _PROTOS = {
                                 c_void_p, c_void_p],
     "haff_attention_bwd_bf16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p],
+    "haff_attention_lse_f16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
+                               c_void_p, c_long, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int,
+                               c_void_p, c_void_p],
+    "haff_attention_bwd_f16": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p],
     "haff_gemm_tn_workspace_elems": [c_long, c_int, c_int],
+    "haff_gemm_tn_f16": [c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p],
     "haff_gemm_tn_bf16": [c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_int, c_void_p],
     "haff_lora_qkv_rope_fwd": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_long, c_long, c_int, c_int, c_int, c_float, c_void_p],
@@ -124,6 +130,16 @@ _PROTOS = {
     "haff_lora_tn_workspace_elems": [c_long, c_int, c_int],
     "haff_lora_tn": [c_void_p, c_long, c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int,
                      c_int, c_float, c_void_p],
+    "haff_lora_qkv_rope_fwd_f16": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_long, c_long, c_int, c_int, c_int, c_float, c_void_p],
+    "haff_lora_qkv_rope_bwd_f16": [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int,
+                                   c_void_p],
+    "haff_lora_dx_f16": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_int, c_float,
+                         c_void_p],
+    "haff_lora_dx2_f16": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_int,
+                          c_float, c_void_p],
+    "haff_lora_tn_f16": [c_void_p, c_long, c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int,
+                         c_int, c_float, c_void_p],
     "haff_global_attention_bf16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
@@ -157,6 +173,8 @@ _PROTOS = {
     # ---- training path (csrc/train.hip + batched GEMMs) ----
     "haff_gemm_bf16_batched": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long,
                                c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_gemm_f16_batched": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long,
+                              c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "haff_gemm_f32_batched": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long,
                               c_long, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "haff_transpose": [c_void_p, c_long, c_long, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
@@ -189,6 +207,8 @@ _PROTOS = {
     "haff_sumsq": [c_void_p, c_void_p, c_long, c_int, c_void_p],
     "haff_adamw_step_dev": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_float,
                             c_int, c_float, c_void_p, c_int, c_int, c_void_p],
+    "haff_adamw_step_skip": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_float,
+                             c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "haff_adamw_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_float,
                         c_int, c_float, c_int, c_int, c_void_p],
 }

@@ -263,6 +263,14 @@ def validate(model, dataset, tokenizer, args, rank, world, device):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+PRECISIONS = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
+
+
+def precision_dtype(precision):
+    """--precision -> the trainer's dtype (train_ds.py:365-370 of the reference: bf16, fp16 with dynamic loss scaling, or fp32)."""
+    return PRECISIONS[precision]
+
+
 def main(argv):
     args = parse_args(argv)
     hprompt.set_default_conversation(args.conv_type)      # train_ds.py:188-190
@@ -271,7 +279,7 @@ def main(argv):
         raise SystemExit("train_ds.py needs MI355X devices: the fine-tune path has no CPU fallback")
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
-    dtype = torch.bfloat16 if args.precision == "bf16" else torch.float32
+    dtype = precision_dtype(args.precision)
     if args.synthetic:
         cfg = {"tiny": hcfg.tiny, "mid": hcfg.mid, "7b": hcfg.haff_7b, "13b": hcfg.haff_13b}[args.synthetic]()
         tokenizer = checkpoint.ByteTokenizer(cfg)
@@ -311,6 +319,8 @@ def main(argv):
     reducer = T.GradBucketReducer(model.named_parameters())   # p.grad become views into flat per-dtype buckets
     opt = T.BucketAdamW(reducer, model.named_parameters())    # fp32 master / moments per bucket, one fused launch each
     states = opt.states
+    # fp16: dynamic loss scaling with DeepSpeed's defaults (the reference's config enables fp16 and states nothing else)
+    scaler = T.DynamicLossScaler() if dtype == torch.float16 else None
     ckpt_dir = os.path.join(args.log_base_dir, args.exp_name, "ckpt_model")
     global_step, best_score, start_epoch = 0, 0.0, args.start_epoch
     resume = args.resume or (ckpt_dir if args.auto_resume and os.path.exists(os.path.join(ckpt_dir, "latest.pt")) else "")
@@ -320,6 +330,8 @@ def main(argv):
         for k, st in blob["optim"].items():
             states[k].master.copy_(st["master"]); states[k].m.copy_(st["m"]); states[k].v.copy_(st["v"]); states[k].step = st["step"]
         opt.refresh_lp()
+        if scaler is not None and "loss_scaler" in blob:
+            scaler.load_state_dict(blob["loss_scaler"])
         global_step, best_score = blob["global_step"], blob["best_score"]
         start_epoch = global_step // args.steps_per_epoch
         if rank == 0:
@@ -371,17 +383,38 @@ def main(argv):
                 # gradients accumulate into the bucket views across the micro-steps; on the last one each bucket's
                 # all-reduce (RCCL) is issued as soon as its last gradient lands, under the rest of backward
                 reducer.begin(sync=micro == args.grad_accumulation_steps - 1)
-                out["loss"].backward()
+                if scaler is not None:   # fp16: the f32 loss times the current scale, so small f16 gradients stay representable
+                    (out["loss"] * scaler.loss_scale).backward()
+                else:
+                    out["loss"].backward()
                 loss_acc += torch.stack([out[k].detach().float().reshape(()) for k in keys[1:]])   # no host sync
                 n_acc += 1
             reducer.finish()
             grads = reducer.grads()
             gscale = 1.0 / args.grad_accumulation_steps
-            # gradient_clipping: 1.0 — the coefficient min(1, 1 / (norm + 1e-6)) is computed and consumed on the device (the
-            # optimizer launches queue up behind backward; no host read of the norm)
-            clip = T.clip_coef_device(T.grad_norm(grads) * gscale, 1.0)
-            lr = T.warmup_decay_lr(global_step, total_steps, args.lr)
-            opt.step(lr=lr, betas=(args.beta1, args.beta2), eps=1e-8, wd=0.0, gscale=gscale, gscale_dev=clip)
+            if scaler is not None:
+                gscale /= scaler.loss_scale
+            # gradient_clipping: 1.0 — the coefficient min(1, 1 / (norm + 1e-6)) of the UNSCALED norm is computed and consumed on
+            # the device (the optimizer launches queue up behind backward; no host read of the norm)
+            norm = T.grad_norm(grads)
+            clip = T.clip_coef_device(norm * gscale, 1.0)
+            # the schedule counts the steps that were taken (DeepSpeed does not step its lr_scheduler on a skipped step); global_step
+            # counts every optimizer step, skipped ones included (the engine's global_steps: data position, epochs, print cadence)
+            lr = T.warmup_decay_lr(global_step - (scaler.skipped_steps if scaler is not None else 0), total_steps, args.lr)
+            # fp16: the kernels skip the update when the norm is not finite (an inf / NaN gradient: the scale overflowed f16). The
+            # buckets were all-reduced before the norm, so every rank sees the same norm and skips the same step: no extra collective
+            opt.step(lr=lr, betas=(args.beta1, args.beta2), eps=1e-8, wd=0.0, gscale=gscale, gscale_dev=clip,
+                     skip_norm=norm if scaler is not None else None)
+            skipped = False
+            if scaler is not None:
+                # the one host read of the step (DeepSpeed reads its overflow flag once per step too): decides the step count, the
+                # schedule and the scale. A skipped step is not counted: neither Adam's step nor the LR schedule advance
+                scale_used = scaler.loss_scale
+                skipped = scaler.update_scale(not bool(torch.isfinite(norm).item()))
+                if skipped:
+                    opt.unstep()
+                    if rank == 0:
+                        print(f"[fp16] gradient overflow: step skipped, loss scale {scale_used:g} -> {scaler.loss_scale:g}", flush=True)
             global_step += 1
             meters[0].update(time.time() - end)
             end = time.time()
@@ -392,7 +425,10 @@ def main(argv):
                 n_acc = 0
                 all_reduce_meters(meters, device)
                 if rank == 0:
-                    print(progress_line(epoch, step + 1, args.steps_per_epoch, meters[:6]), flush=True)
+                    line = progress_line(epoch, step + 1, args.steps_per_epoch, meters[:6])
+                    if scaler is not None:
+                        line += f"\tLossScale {scaler.loss_scale:g}" + ("\tskipped" if skipped else "")
+                    print(line, flush=True)
                 for m in meters:
                     m.reset()
         if not args.no_eval:
@@ -408,9 +444,11 @@ def main(argv):
                 torch.distributed.barrier()
             if rank == 0:  # parameters and optimizer state are replicated: rank 0 writes the only copy
                 os.makedirs(ckpt_dir, exist_ok=True)
-                torch.save({"params": model.state_dict(), "global_step": global_step, "best_score": best_score, "epoch": epoch,
-                            "optim": {k: {"master": s.master, "m": s.m, "v": s.v, "step": s.step} for k, s in states.items()}},
-                           os.path.join(ckpt_dir, "latest.pt"))
+                blob = {"params": model.state_dict(), "global_step": global_step, "best_score": best_score, "epoch": epoch,
+                        "optim": {k: {"master": s.master, "m": s.m, "v": s.v, "step": s.step} for k, s in states.items()}}
+                if scaler is not None:
+                    blob["loss_scaler"] = scaler.state_dict()
+                torch.save(blob, os.path.join(ckpt_dir, "latest.pt"))
                 print(f"saved checkpoint to {ckpt_dir} (global_step{global_step})")
     if world > 1:
         torch.distributed.barrier()

@@ -31,7 +31,14 @@ class LisaTrainable:
     def __init__(self, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", lora_r=8, lora_alpha=16, lora_dropout=0.05,
                  ce_loss_weight=1.0, dice_loss_weight=0.5, bce_loss_weight=2.0, seed=0, lora_init_b_zero=True):
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
-        self.base = LisaMI355(cfg, state_dict, dtype=dtype, device=device, fp32_tail=False)  # training is bf16 end to end, as the reference's
+        # bf16: training is bf16 end to end, as the reference's. fp16 (--precision fp16): the frozen CLIP / ViT-H / Llama stacks run
+        # on the fp16 inference mode's kernels with its own settings (weights over 65504 refused by name; the ViT-H neck in f32, so
+        # the image embedding leaves it in f32); the trainable decoders below run in fp16 on f16_rn of that embedding
+        self.base = LisaMI355(cfg, state_dict, dtype=dtype, device=device, fp32_tail=dtype == torch.float16)
+        # the frozen decoder constants in the trainer's dtype (the bf16 base keeps them in bf16: the same tensors)
+        dec = self.base.sam_decoder
+        self.key_pe = dec.key_pe if dec.key_pe.dtype == dtype else dec.key_pe.to(dtype).contiguous()
+        self.no_mask = dec.no_mask if dec.no_mask.dtype == dtype else dec.no_mask.to(dtype).contiguous()
         self.lora_r, self.lora_scale, self.lora_dropout = lora_r, lora_alpha / lora_r, lora_dropout
         # peft draws one dropout mask per adapted Linear: q_proj's and v_proj's adapters see independently dropped inputs (the
         # reference's semantics; default since round 5). False: ONE mask per layer for both adapters (rounds 3-4: same marginal
@@ -178,7 +185,7 @@ class LisaTrainable:
         Pn, N, C = src.shape
         g = self.cfg.sam.grid
         nt = 6
-        key_pe = self.base.sam_decoder.key_pe
+        key_pe = self.key_pe
         out_tok = torch.cat([P[D + ".iou_token.weight"], P[D + ".mask_tokens.weight"]], dim=0)
         tokens = torch.cat([out_tok.unsqueeze(0).expand(Pn, -1, -1), text.view(Pn, 1, C)], dim=1).reshape(Pn * nt, C)
         queries, keys = tokens, src.reshape(Pn * N, C)
@@ -298,8 +305,10 @@ class LisaTrainable:
             cur.wait_stream(sam_stream)
             emb.record_stream(cur)
         with torch.no_grad():
+            if emb.dtype != self.dtype:   # fp16: the f32 neck's output rounded once (the reference's x.to(dtype), image_encoder.py:118-124)
+                emb = emb.to(self.dtype)
             src = emb.index_select(0, frame_idx).reshape(Pn * N, C)
-            src = ops.add_bcast(src, base.sam_decoder.no_mask, mod=1).view(Pn, N, C)
+            src = ops.add_bcast(src, self.no_mask, mod=1).view(Pn, N, C)
         lo_l, tax_logits = self._decoder("left", src, pred, True)
         lo_r, _ = self._decoder("right", src, pred, False)
         S = cfg.sam.img_size

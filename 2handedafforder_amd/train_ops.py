@@ -20,16 +20,27 @@ class AdamWState:
         self.step = 0
 
 
-def adamw_step(state, grad, lr, betas=(0.9, 0.95), eps=1e-8, wd=0.0, gscale=1.0, param_lp=None, gscale_dev=None):
-    """One fused AdamW update (torch.optim.AdamW semantics); optionally refreshes a bf16 copy of the parameter.
-    gscale_dev: device fp32 scalar multiplied into gscale inside the kernel (clip_coef_device: no host read of the norm)."""
+_LP_DT = {torch.bfloat16: 0, torch.float16: 3}   # the kernel's code of a 16-bit parameter copy (bf16_rn / f16_rn of the master)
+
+
+def adamw_step(state, grad, lr, betas=(0.9, 0.95), eps=1e-8, wd=0.0, gscale=1.0, param_lp=None, gscale_dev=None, skip_norm=None):
+    """One fused AdamW update (torch.optim.AdamW semantics); optionally refreshes a bf16 / fp16 copy of the parameter.
+    gscale_dev: device fp32 scalar multiplied into gscale inside the kernel (clip_coef_device: no host read of the norm).
+    skip_norm: device fp32 gradient norm; the kernel leaves every bit of the state and the copy alone when it is not finite (the
+    fp16 mode's overflow). The host does not know the outcome: the caller undoes `state.step += 1` after reading the norm."""
     lib = load_library()
     state.step += 1
     grad = grad.contiguous()
     lp_ptr, lp_dt = 0, -1
-    if param_lp is not None and param_lp.dtype == torch.bfloat16:
-        lp_ptr, lp_dt = param_lp.data_ptr(), 0
-    if gscale_dev is not None:
+    if param_lp is not None and param_lp.dtype in _LP_DT:
+        lp_ptr, lp_dt = param_lp.data_ptr(), _LP_DT[param_lp.dtype]
+    if skip_norm is not None:
+        assert skip_norm.dtype == torch.float32 and skip_norm.numel() == 1
+        check(lib.haff_adamw_step_skip(state.master.data_ptr(), state.m.data_ptr(), state.v.data_ptr(), grad.data_ptr(), lp_ptr,
+                                       state.master.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(wd),
+                                       state.step, float(gscale), 0 if gscale_dev is None else gscale_dev.data_ptr(),
+                                       skip_norm.data_ptr(), _dt(grad), lp_dt, _s()), "haff_adamw_step_skip")
+    elif gscale_dev is not None:
         assert gscale_dev.dtype == torch.float32 and gscale_dev.numel() == 1
         check(lib.haff_adamw_step_dev(state.master.data_ptr(), state.m.data_ptr(), state.v.data_ptr(), grad.data_ptr(), lp_ptr,
                                       state.master.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(wd),
@@ -272,15 +283,90 @@ class BucketAdamW:
             if b["lp"] is not None:
                 b["lp"].copy_(b["master"])
 
-    def step(self, lr, betas=(0.9, 0.95), eps=1e-8, wd=0.0, gscale=1.0, gscale_dev=None):
+    def step(self, lr, betas=(0.9, 0.95), eps=1e-8, wd=0.0, gscale=1.0, gscale_dev=None, skip_norm=None):
+        """skip_norm (device fp32 gradient norm, fp16 mode): every bucket's update is skipped on the device when it is not finite.
+        The step count advances here; the caller reads the norm once and calls unstep() on an overflow (the skipped step then
+        does not count: DeepSpeed's fp16 optimizer neither steps Adam nor the LR scheduler on an overflow)."""
         lib = load_library()
         self.step_count += 1
         for b in self.buckets:
             g = b["grad"]
-            lp_ptr, lp_dt = (b["lp"].data_ptr(), 0) if b["lp"] is not None else (0, -1)
+            lp_ptr, lp_dt = (b["lp"].data_ptr(), _LP_DT[b["lp"].dtype]) if b["lp"] is not None else (0, -1)
             args = (b["master"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), g.data_ptr(), lp_ptr, g.numel(), float(lr),
                     float(betas[0]), float(betas[1]), float(eps), float(wd), self.step_count, float(gscale))
-            if gscale_dev is not None:
+            if skip_norm is not None:
+                check(lib.haff_adamw_step_skip(*args, 0 if gscale_dev is None else gscale_dev.data_ptr(), skip_norm.data_ptr(), _dt(g),
+                                               lp_dt, _s()), "haff_adamw_step_skip")
+            elif gscale_dev is not None:
                 check(lib.haff_adamw_step_dev(*args, gscale_dev.data_ptr(), _dt(g), lp_dt, _s()), "haff_adamw_step_dev")
             else:
                 check(lib.haff_adamw_step(*args, _dt(g), lp_dt, _s()), "haff_adamw_step")
+
+    def unstep(self):
+        """The last step() was skipped on the device (non-finite gradient norm): its step number is handed to the next one."""
+        self.step_count -= 1
+
+
+class DynamicLossScaler:
+    """fp16 dynamic loss scaling as the reference's engine runs it: its DeepSpeed config says only "fp16": {"enabled": true}
+    (train_ds.py:365-370), so DeepSpeed's defaults apply — restated here (DeepSpeed is not a dependency):
+
+      initial scale 2**initial_scale_power (16), loss_scale_window 1000, scale factor 2, hysteresis 2 with consecutive_hysteresis
+      off, min_loss_scale 1;
+      overflow:     if the remaining hysteresis is 1, the scale halves (not below min_scale); otherwise the hysteresis drops by one;
+                    last_overflow_iter = iter; an overflow at the minimum scale raises (raise_error_at_min_scale);
+      no overflow:  when (iter - last_overflow_iter) % window == 0 the scale doubles and the hysteresis is reset;
+      iter advances on every update, skipped steps included.
+
+    The scaled loss is scale * loss; gradients are unscaled inside the optimizer step (gscale / scale)."""
+
+    def __init__(self, init_scale=2.0 ** 16, scale_factor=2.0, scale_window=1000, hysteresis=2, min_scale=1.0,
+                 consecutive_hysteresis=False, raise_error_at_min_scale=True):
+        self.cur_scale = float(init_scale)
+        self.scale_factor = float(scale_factor)
+        self.scale_window = int(scale_window)
+        self.delayed_shift = int(hysteresis)
+        self.cur_hysteresis = int(hysteresis)
+        self.min_scale = float(min_scale)
+        self.consecutive_hysteresis = bool(consecutive_hysteresis)
+        self.raise_error_at_min_scale = bool(raise_error_at_min_scale)
+        self.cur_iter = 0
+        self.last_overflow_iter = -1
+        self.skipped_steps = 0
+
+    @property
+    def loss_scale(self):
+        return self.cur_scale
+
+    def update_scale(self, overflow):
+        """One optimizer step's outcome. Returns True when the step was skipped (overflow)."""
+        if overflow:
+            if self.delayed_shift == 1 or self.cur_hysteresis == 1:
+                if self.cur_scale == self.min_scale and self.raise_error_at_min_scale:
+                    raise RuntimeError("fp16 loss scaling: gradient overflow at the minimum loss scale "
+                                       f"({self.min_scale:g}); the gradients are not finite at any scale")
+                self.cur_scale = max(self.cur_scale / self.scale_factor, self.min_scale)
+            else:
+                self.cur_hysteresis -= 1
+            self.last_overflow_iter = self.cur_iter
+            self.skipped_steps += 1
+        else:
+            if self.consecutive_hysteresis:
+                self.cur_hysteresis = self.delayed_shift
+            if (self.cur_iter - self.last_overflow_iter) % self.scale_window == 0:
+                if not self.consecutive_hysteresis:
+                    self.cur_hysteresis = self.delayed_shift
+                self.cur_scale *= self.scale_factor
+        self.cur_iter += 1
+        return bool(overflow)
+
+    def state_dict(self):
+        return {"cur_scale": self.cur_scale, "cur_hysteresis": self.cur_hysteresis, "last_overflow_iter": self.last_overflow_iter,
+                "cur_iter": self.cur_iter, "skipped_steps": self.skipped_steps}
+
+    def load_state_dict(self, sd):
+        self.cur_scale = float(sd["cur_scale"])
+        self.cur_hysteresis = int(sd["cur_hysteresis"])
+        self.last_overflow_iter = int(sd["last_overflow_iter"])
+        self.cur_iter = int(sd["cur_iter"])
+        self.skipped_steps = int(sd["skipped_steps"])

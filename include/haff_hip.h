@@ -284,6 +284,13 @@ int haff_attention_lse_bf16(const void* q, long q_sb, long q_sh, long q_st, cons
 int haff_attention_bwd_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                             void* dq, void* dk, void* dv, float* workspace, long workspace_elems, long ld, int B, int H, int Nq,
                             int Nk, int d, float scale, int causal, int q_pos0, void* stream);
+/* fp16 fine-tuning: the same pair on IEEE binary16 operands (f16 MFMA, fp32 accumulation and statistics) */
+int haff_attention_lse_f16(const void* q, long q_sb, long q_sh, long q_st, const void* k, long k_sb, long k_sh, long k_st,
+                           const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb, long o_sh, long o_st, int B, int H,
+                           int Nq, int Nk, int d, float scale, int causal, int q_pos0, float* lse, void* stream);
+int haff_attention_bwd_f16(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                           void* dq, void* dk, void* dv, float* workspace, long workspace_elems, long ld, int B, int H, int Nq,
+                           int Nk, int d, float scale, int causal, int q_pos0, void* stream);
 
 /* TN product of the fine-tune step: out [N1][N2] = A^T . B, A [M][lda] (N1 columns), B [M][ldb] (N2 columns), bf16, contraction
  * over the M rows — the weight gradient dW = dY^T . X of a trainable Linear (torch.nn.Linear under autograd: text_hidden_fcs and
@@ -294,6 +301,9 @@ int haff_attention_bwd_bf16(const void* q, const void* k, const void* v, const v
 int haff_gemm_tn_workspace_elems(long M, int N1, int N2);
 int haff_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
                       long workspace_elems, void* out, int out_f32, void* stream);
+/* fp16 fine-tuning: A, B and a 16-bit out IEEE binary16 */
+int haff_gemm_tn_f16(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
+                     long workspace_elems, void* out, int out_f32, void* stream);
 
 /* rank-r adapter path of the fine-tune step (peft LoRA on q_proj / v_proj: 2Haff/train_ds.py:192-230; RoPE of the adapted
  * projections: llava_llama.py -> transformers LlamaAttention). bf16, head dim d == 128, rank <= 8 per adapter; see csrc/lora.hip.
@@ -320,6 +330,18 @@ int haff_lora_dx2(const void* dtT, long ldt, const void* A2, long lda, const voi
 int haff_lora_tn_workspace_elems(long M, int R, int N);
 int haff_lora_tn(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace,
                  long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale, void* stream);
+/* fp16 fine-tuning: the same five entry points on IEEE binary16 operands, masks and results (haff_lora_tn_workspace_elems serves both) */
+int haff_lora_qkv_rope_fwd_f16(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, int ldb,
+                               const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int d, int T,
+                               float scale, void* stream);
+int haff_lora_qkv_rope_bwd_f16(const void* dq, const void* dk, const void* dv, long ld_in, const float* cos_sin, void* dqkv,
+                               long ld_out, long M, int H, int d, int T, void* stream);
+int haff_lora_dx_f16(const void* dtT, long ldt, const void* A2, long lda, const void* keep, long ldk, void* dx, long ldx,
+                     int accumulate, long M, int K, float scale, void* stream);
+int haff_lora_dx2_f16(const void* dtT, long ldt, const void* A2, long lda, const void* keep_q, const void* keep_v, long ldk, void* dx,
+                      long ldx, int accumulate, long M, int K, float scale, void* stream);
+int haff_lora_tn_f16(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace,
+                     long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale, void* stream);
 
 /* fused SAM WINDOW attention with the decomposed rel-pos bias computed in the kernel (one pass over HBM; replaces
  * haff_relpos_tables_bf16 + haff_attention_bf16 for the 28 windowed ViT-H blocks): Attention.forward
@@ -456,6 +478,10 @@ int haff_gate_threshold_masks(const float* logits, void* planes, long total, lon
 int haff_gemm_bf16_batched(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo, long sWi,
                            void* C, long ldc, long sCo, long sCi, int nb_outer, int nb_inner, int M, int N, int K,
                            int out_f32, void* stream);
+/* fp16 fine-tuning: A, W and a 16-bit C IEEE binary16 */
+int haff_gemm_f16_batched(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo, long sWi,
+                          void* C, long ldc, long sCo, long sCi, int nb_outer, int nb_inner, int M, int N, int K,
+                          int out_f32, void* stream);
 int haff_gemm_f32_batched(const float* A, long lda, long sAo, long sAi, const float* W, long ldw, long sWo, long sWi,
                           float* C, long ldc, long sCo, long sCi, int nb_outer, int nb_inner, int M, int N, int K,
                           void* stream);
@@ -529,13 +555,19 @@ int haff_resize_bilinear_bwd(const float* dout, float* din, int N, int Hs, int W
 int haff_scatter_add_rows(const long* ids, const void* dx, float* dE, long rows, int C, int dtype, void* stream);
 /* out += sum(g^2) (gradient-norm clipping, train_ds.py:370) */
 int haff_sumsq(const void* g, float* out, long n, int dtype, void* stream);
-/* fused AdamW on fp32 master weights (+ optional bf16 copy), torch semantics, gradient pre-scaled by gscale */
+/* fused AdamW on fp32 master weights (+ optional 16-bit copy), torch semantics, gradient pre-scaled by gscale.
+ * g_dtype: 0 bf16 / 1 f32 / 3 f16 gradients; lp_dtype: -1 no copy, 0 bf16 copy, 3 f16 copy (= f16_rn(master)); other codes -1 */
 int haff_adamw_step(float* master, float* m, float* v, const void* g, void* param_lp, long n, float lr, float beta1,
                     float beta2, float eps, float wd, int step, float gscale, int g_dtype, int lp_dtype, void* stream);
 /* the same, the gradient scale multiplied by *gscale_dev (device f32: the clip coefficient computed on the device) */
 int haff_adamw_step_dev(float* master, float* m, float* v, const void* g, void* param_lp, long n, float lr, float beta1,
                         float beta2, float eps, float wd, int step, float gscale, const float* gscale_dev, int g_dtype,
                         int lp_dtype, void* stream);
+/* the fp16 mode's step: as haff_adamw_step_dev (gscale_dev may be null), skipped when the device gradient norm *norm is not finite
+ * (an inf / NaN gradient element: loss-scale overflow) — master, m, v and the copy then keep every bit */
+int haff_adamw_step_skip(float* master, float* m, float* v, const void* g, void* param_lp, long n, float lr, float beta1,
+                         float beta2, float eps, float wd, int step, float gscale, const float* gscale_dev, const float* norm,
+                         int g_dtype, int lp_dtype, void* stream);
 
 #ifdef __cplusplus
 }
