@@ -9,8 +9,11 @@ decode -> [SEG] -> SAM ViT-H encoder -> left/right mask decoders -> postprocess)
 frames already resident in HBM. Default workload = BASELINE.json configs[2]: 2HandedAfforder-7B, 64 x 1024^2
 uint8 NHWC frames, 32-token prompts (L=36, T=291), 8 forced answer tokens with [SEG], bf16. Frames are
 independent units: for N>1 every rank processes its own batch (weak scaling, no data-path collective).
-One JSON line on rank 0: metric/value (+ roofline of the dominant kernel, + cpu_baseline = the CPU oracle
-timed on a bounded, depth-reduced sample and extrapolated by layer counts).
+One JSON line on rank 0: metric/value and the contract's keys. A plain run does nothing else: it sets up, warms up,
+times the K steps, writes --dump-outputs and prints the line (roofline and cpu_baseline null, no parity object).
+--full adds everything beside the headline, each in passes of its own after the timed steps: the roofline of the
+dominant kernel (a metered single-stream step), batch-1 latency and decode rate, the CPU oracle's baseline, and
+the parity objects against the oracle with their gate (exit code 3).
 """
 import argparse
 import json
@@ -902,6 +905,30 @@ def cpu_train_baseline(cfg, n_ids, mask_hw, threads):
             "seconds_per_sample_full_depth_extrapolated": t_full, "loss_of_the_reduced_model": loss}
 
 
+def train_gemm_roofline(model, step, ms_per_step, b):
+    """--full, --mode train: the roofline object of the line, from one metered step after the timed steps (and one untimed
+    step before it), both single-stream."""
+    # per-launch event timing needs ONE HIP stream: with the frozen SAM encoder on its side stream the main stream's products
+    # were timed while they waited for CUs the encoder's persistent tiles held (round 4's by_shape listed the CLIP products at
+    # M = 2056 at 52 ... 211 TFLOP/s for that reason: single-stream they run at what the inference line shows)
+    overlap_prev, model.overlap_sam = model.overlap_sam, False
+    step()
+    torch.cuda.synchronize()
+    with GemmMeter() as meter:
+        step()
+    torch.cuda.synchronize()
+    model.overlap_sam = overlap_prev
+    n_launch, gemm_ms, gemm_fl, gemm_bytes = meter.summary()
+    achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12
+    return {"bound": "mfma", "kernel": "gemm_bf16_kernel (every haff_gemm_bf16 launch with M > 64 of the step: forward, dX and dW products)",
+            "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS,
+            "traffic": None, "launches_per_step": n_launch, "avg_launch_us": 1e3 * gemm_ms / max(n_launch, 1),
+            "flops_per_launch_avg": gemm_fl / max(n_launch, 1), "algorithmic_bytes_per_launch_avg": gemm_bytes / max(n_launch, 1),
+            "gemm_share_of_step": gemm_ms / ms_per_step,
+            "executed_gemm_flop_per_sample": meter.total_gemm_flop() / b,
+            "by_shape": meter.shape_summary(top=24)}
+
+
 def train_main(args):
     """--mode train: BASELINE.json configs[3] — LoRA fine-tune (train_ds.py path), bf16, 8 synthetic 2HANDS samples per GPU per
     step (global batch 64 on 8 GPUs), 96-id conversations (351 expanded tokens), 1024^2 masks. A step = forward + backward of
@@ -949,26 +976,17 @@ def train_main(args):
     ms_per_step = 1e3 * elapsed / args.steps
     sps = world * b * args.steps / elapsed
     n_ranks = rccl_ranks(device)
-    # how long the host needs to ENQUEUE one step on an idle GPU (no read-back waits on device work then): the step is GPU-bound
-    # while this stays below ms_per_step
-    torch.cuda.synchronize()
-    t_host = time.time()
-    step()
-    host_enqueue_ms = 1e3 * (time.time() - t_host)
-    torch.cuda.synchronize()
-    if rank == 0:
-        # per-launch event timing needs ONE HIP stream: with the frozen SAM encoder on its side stream the main stream's products
-        # were timed while they waited for CUs the encoder's persistent tiles held (round 4's by_shape listed the CLIP products at
-        # M = 2056 at 52 ... 211 TFLOP/s for that reason: single-stream they run at what the inference line shows)
-        overlap_prev, model.overlap_sam = model.overlap_sam, False
+    host_enqueue_ms = None
+    if args.full:
+        # how long the host needs to ENQUEUE one step on an idle GPU (no read-back waits on device work then): the step is
+        # GPU-bound while this stays below ms_per_step
+        torch.cuda.synchronize()
+        t_host = time.time()
         step()
+        host_enqueue_ms = 1e3 * (time.time() - t_host)
         torch.cuda.synchronize()
-        with GemmMeter() as meter:
-            step()
-        torch.cuda.synchronize()
-        model.overlap_sam = overlap_prev
-        n_launch, gemm_ms, gemm_fl, gemm_bytes = meter.summary()
-        achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12
+    if rank == 0:
+        roofline = train_gemm_roofline(model, step, ms_per_step, b) if args.full else None
         n_train = sum(p.numel() for _, p in named)
         line = {"metric": "LoRA fine-tune samples/sec (train_ds.py path), bf16", "value": sps, "unit": "samples/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
@@ -981,18 +999,12 @@ def train_main(args):
                            "parallelism": "sample-sharded DDP x%d (all-reduce of %.2f GB of bf16/fp32 gradients per step in %d buckets)" %
                                           (world, sum(f.numel() * f.element_size() for f in reducer.grads()) / 1e9, len(reducer.buckets))},
                 "samples_per_s_per_gpu": sps / world, "rccl_ranks": n_ranks,
-                "host_enqueue_ms_per_step": host_enqueue_ms,
                 "loss_first_last": [float(losses[0]), float(losses[-1])],
-                "roofline": {"bound": "mfma", "kernel": "gemm_bf16_kernel (every haff_gemm_bf16 launch with M > 64 of the step: forward, dX and dW products)",
-                             "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS,
-                             "traffic": None, "launches_per_step": n_launch, "avg_launch_us": 1e3 * gemm_ms / max(n_launch, 1),
-                             "flops_per_launch_avg": gemm_fl / max(n_launch, 1), "algorithmic_bytes_per_launch_avg": gemm_bytes / max(n_launch, 1),
-                             "gemm_share_of_step": gemm_ms / ms_per_step,
-                             "executed_gemm_flop_per_sample": meter.total_gemm_flop() / b,
-                             "by_shape": meter.shape_summary(top=24)},
-                "cpu_baseline": None,
+                "roofline": roofline, "cpu_baseline": None,
                 "peak_hbm_gb": torch.cuda.max_memory_allocated() / 2 ** 30}
-        if world == 1 and not args.no_cpu_baseline:
+        if host_enqueue_ms is not None:
+            line["host_enqueue_ms_per_step"] = host_enqueue_ms
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_train_baseline(cfg, args.train_ids, (args.train_mask, args.train_mask), min(len(os.sched_getaffinity(0)), 32))
         emit(line)
     if world > 1:
@@ -1058,6 +1070,89 @@ def rccl_ranks(device):
     return n
 
 
+def gemm_roofline(model, step, cfg, args, fps, world, ms_per_step, f32_mode):
+    """--full: the roofline object of the line, from one metered step in single-stream, graphs-off mode after the timed
+    steps (and one untimed step in that mode before it)."""
+    B = args.batch
+    flops_frame = SURVEY_FLOPS.get(cfg.name) or hflops.frame_flops(cfg, args.text_tokens, args.n_gen)["total"]
+    prev = (model.overlap_streams, model.decode_graphs)
+    model.overlap_streams = False  # per-launch event timing needs a single HIP stream
+    model.decode_graphs = False    # ... and every GEMM launch to go through the metered wrapper (no graph replays)
+    step()                         # one untimed step in this (eager, single-stream) mode: its first pass allocates the eager
+    torch.cuda.synchronize()       # decode loop's buffers / workspaces inside what would be metered launches (seen once: frac 0.39)
+    with GemmMeter() as meter:
+        step()
+    model.overlap_streams, model.decode_graphs = prev
+    n_launch, gemm_ms, gemm_fl, gemm_bytes = meter.summary()
+    ws_n, ws_ms, ws_bytes = meter.stream_summary()
+    f32_n, f32_ms, f32_fl = meter.f32_summary()
+    # FLOPs the step actually executed: every GEMM launch as issued (the padded window rows SURVEY's 10.01 TFLOP counts
+    # are skipped by the kernels) + the attention / rel-pos terms of flops.py
+    s_ = cfg.sam
+    attn_fl = 0.0
+    for i in range(s_.depth):
+        glob = i in s_.global_idx
+        ntok, n_seq = (s_.grid ** 2, 1) if glob else (s_.window ** 2, ((s_.grid + s_.window - 1) // s_.window) ** 2)
+        attn_fl += 2.0 * 2 * n_seq * ntok * ntok * s_.embed_dim + 2.0 * n_seq * ntok * 2 * (s_.grid if glob else s_.window) * s_.embed_dim
+    n_clip = cfg.clip.n_patches + 1
+    n_clip_layers = cfg.clip.layers + 1 + cfg.clip.select_layer if cfg.clip.select_layer < 0 else cfg.clip.select_layer
+    attn_fl += n_clip_layers * 2.0 * 2 * n_clip * n_clip * cfg.clip.hidden
+    T_all = 4 + args.text_tokens + cfg.clip.n_patches - 1 + args.n_gen - 1
+    attn_fl += 2.0 * cfg.llm.layers * cfg.llm.hidden * sum(t + 1 for t in range(T_all))
+    executed_frame = meter.total_gemm_flop() / B + attn_fl
+    # HBM traffic of the dominant kernel cannot be sampled from inside this process: it comes from the two
+    # rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of THIS command, summarised by tools/pmc_traffic.py into
+    # profiles/ (FETCH_SIZE doubled on gfx950: see that tool). null when no summary matches.
+    traffic, traffic_src = None, None
+    pmc_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "pmc_gemm_traffic.json")
+    if os.path.exists(pmc_path):
+        with open(pmc_path) as fh:
+            pmc = json.load(fh)
+        from haff import lib as hlib
+        if pmc.get("config") == cfg.name and pmc.get("batch") == B and pmc.get("library_source_sha16") == hlib.source_hash():
+            traffic = pmc["hbm_bytes_per_launch"]
+            traffic_src = "profiles/pmc_gemm_traffic.json (%s)" % pmc.get("collected", "")
+        else:   # collected on another tree / workload: not this run's traffic
+            traffic_src = "profiles/pmc_gemm_traffic.json does not match this tree (config %s, batch %s, csrc sha %s vs %s): null" % (
+                pmc.get("config"), pmc.get("batch"), pmc.get("library_source_sha16"), hlib.source_hash())
+    if f32_mode:   # the parity mode: every product is gemm_f32_kernel (f32-input MFMA, 157.3 TFLOP/s dense)
+        n_launch, gemm_ms, gemm_fl = f32_n, f32_ms, f32_fl
+        gemm_bytes, traffic, traffic_src = 0.0, None, None
+    peak = 157.3 if f32_mode else PEAK_BF16_TFLOPS
+    achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12
+    roofline = {
+        "bound": "mfma", "kernel": "gemm_f32_kernel (haff_gemm_f32: v_mfma_f32_16x16x4_f32 tiles; every product of the fp32 parity mode)" if f32_mode else
+                                   "gemm_bf16_kernel (haff_gemm_bf16 with M > 64: the 256x256 / 128x128 MFMA tiles, all epilogue variants)",
+        "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+        "traffic": traffic, "traffic_source": traffic_src,
+        "algorithmic_bytes_per_launch_avg": gemm_bytes / n_launch,
+        "launches_per_step": n_launch, "avg_launch_us": 1e3 * gemm_ms / n_launch,
+        "flops_per_launch_avg": gemm_fl / n_launch, "gemm_share_of_step": gemm_ms / ms_per_step,
+        # the same launches split by what their epilogue carries besides bias / activation / residual (round 3 moved the
+        # LayerNorm fold, the LayerNorm statistics of the output rows, RoPE + KV-cache append INTO these launches: the work
+        # left other kernels, the FLOPs did not change, so `frac` pays for it)
+        "by_epilogue": {k: {"launches_per_step": n, "achieved": fl / (ms * 1e-3) / 1e12 if ms > 0 else None,
+                            "share_of_step": ms / ms_per_step} for k, (n, ms, fl) in sorted(meter.fused_summary().items())},
+        "by_shape": meter.shape_summary(),
+        "weight_streaming_gemm": {"kernel": "haff_gemm_bf16 launches with M <= 64 (KV-cached decode steps, [SEG] MLP): gemm_skinny_kernel, or the split-K 128x128 tile path for wide / deep weights at 33..64 rows",
+                                  "bound": "hbm", "launches_per_step": ws_n, "share_of_step": ws_ms / ms_per_step,
+                                  "achieved": (ws_bytes / (ws_ms * 1e-3) / 1e9) if ws_ms > 0 else None, "peak": 8000.0,
+                                  "unit": "GB/s", "algorithmic_bytes": "2*N*K (the weight matrix, read once)"},
+        "fp32_decoder_tail_gemm": {"kernel": "gemm_f32_kernel (v_mfma_f32_16x16x4_f32; text_hidden_fcs + both mask decoders)",
+                                   "launches_per_step": f32_n, "share_of_step": f32_ms / ms_per_step,
+                                   "achieved": (f32_fl / (f32_ms * 1e-3) / 1e12) if f32_ms > 0 else None, "peak": 157.3,
+                                   "unit": "TFLOP/s"},
+        "whole_path": {"flops_per_frame": flops_frame, "flops_per_frame_source": "SURVEY.md 8(d) (counts the padded window rows)",
+                       "achieved": fps / world * flops_frame / 1e12,
+                       "frac": fps / world * flops_frame / 1e12 / peak,
+                       "executed_flops_per_frame": executed_frame,
+                       "executed_note": "every GEMM launch as issued (padded window rows skipped) + attention / rel-pos terms",
+                       "executed_achieved": fps / world * executed_frame / 1e12,
+                       "executed_frac": fps / world * executed_frame / 1e12 / peak},
+    }
+    return roofline
+
+
 def main(argv=None):
     exit_code = 0
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -1093,10 +1188,14 @@ def main(argv=None):
     ap.add_argument("--decode-chain", default="auto", choices=["auto", "on"], help="on: the chained decode launch even beside a capped encoder (A/B)")
     ap.add_argument("--no-decode-chain", action="store_true",
                     help="decode steps of <= 8 rows: five launches per Llama layer instead of the one chained launch per step (csrc/decode_chain.hip; A/B)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-full-frame", action="store_true", help="cpu_baseline: skip the one real end-to-end CPU frame (~31 GB host RAM, ~1 min)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the tiny-config HIP-vs-oracle parity object")
-    ap.add_argument("--no-b1", action="store_true", help="skip the batch=1 latency line (configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything beside the headline: roofline (a metered step), batch-1 "
+                         "latency, CPU baseline, parity against the oracle with its gate (exit code 3). Off: the run times the steps, "
+                         "writes --dump-outputs and prints the line, nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-cpu-full-frame", action="store_true", help="--full: cpu_baseline without the one real end-to-end CPU frame (~31 GB host RAM, ~1 min)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the HIP-vs-oracle parity objects")
+    ap.add_argument("--no-b1", action="store_true", help="--full: skip the batch=1 latency line (configs[1])")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"],
                     help="numeric mode of the timed model: bf16 (bf16 MFMA stacks + fp32 decoder tail: the headline) or f32 (the "
                          "parity mode, f32-input MFMA everywhere: what IoU >= 0.999 / logits within 1e-3 is measured in)")
@@ -1107,10 +1206,10 @@ def main(argv=None):
     ap.add_argument("--unfused-fp32-stream", action="store_true",
                     help="--fp32-stream sam/both: round 5's unfused form (LayerNorm kernels on the fp32 stream) instead of the fused epilogue (A/B)")
     ap.add_argument("--no-full-frame-parity", action="store_true",
-                    help="parity: skip the one full-depth frame against the oracle on shared weights (~31 GB host RAM, ~1 min of CPU)")
+                    help="--full: parity without the one full-depth frame against the oracle on shared weights (~31 GB host RAM, ~1 min of CPU)")
     ap.add_argument("--attribution", action="store_true",
-                    help="full-frame parity: add the oracle's per-stack bf16-points passes (~45 s of CPU; off by default since round 6: "
-                         "the default run is the driver's bench, tools/full_frame_parity.py is where attribution lives)")
+                    help="--full, full-frame parity: add the oracle's per-stack bf16-points passes (~45 s of CPU; off by default since "
+                         "round 6: tools/full_frame_parity.py is where attribution lives)")
     ap.add_argument("--no-attribution", action="store_true", help="(default since round 6; kept for old command lines)")
     ap.add_argument("--mode", default="infer", choices=["infer", "train"],
                     help="infer: BASELINE configs[2] (the headline metric); train: configs[3], one LoRA fine-tune step per step")
@@ -1217,84 +1316,8 @@ def main(argv=None):
     n_ranks = rccl_ranks(device)   # one real all-reduce over the group the timing fence used: the rank count that actually ran
 
     if rank == 0:
-        flops_frame = SURVEY_FLOPS.get(cfg.name) or hflops.frame_flops(cfg, args.text_tokens, args.n_gen)["total"]
-        prev = (model.overlap_streams, model.decode_graphs)
-        model.overlap_streams = False  # per-launch event timing needs a single HIP stream
-        model.decode_graphs = False    # ... and every GEMM launch to go through the metered wrapper (no graph replays)
-        step()                         # one untimed step in this (eager, single-stream) mode: its first pass allocates the eager
-        torch.cuda.synchronize()       # decode loop's buffers / workspaces inside what would be metered launches (seen once: frac 0.39)
-        with GemmMeter() as meter:
-            step()
-        model.overlap_streams, model.decode_graphs = prev
-        n_launch, gemm_ms, gemm_fl, gemm_bytes = meter.summary()
-        ws_n, ws_ms, ws_bytes = meter.stream_summary()
-        f32_n, f32_ms, f32_fl = meter.f32_summary()
-        # FLOPs the step actually executed: every GEMM launch as issued (the padded window rows SURVEY's 10.01 TFLOP counts
-        # are skipped by the kernels) + the attention / rel-pos terms of flops.py
-        parts = hflops.frame_flops(cfg, args.text_tokens, args.n_gen)
-        s_ = cfg.sam
-        attn_fl = 0.0
-        for i in range(s_.depth):
-            glob = i in s_.global_idx
-            ntok, n_seq = (s_.grid ** 2, 1) if glob else (s_.window ** 2, ((s_.grid + s_.window - 1) // s_.window) ** 2)
-            attn_fl += 2.0 * 2 * n_seq * ntok * ntok * s_.embed_dim + 2.0 * n_seq * ntok * 2 * (s_.grid if glob else s_.window) * s_.embed_dim
-        n_clip = cfg.clip.n_patches + 1
-        n_clip_layers = cfg.clip.layers + 1 + cfg.clip.select_layer if cfg.clip.select_layer < 0 else cfg.clip.select_layer
-        attn_fl += n_clip_layers * 2.0 * 2 * n_clip * n_clip * cfg.clip.hidden
-        T_all = 4 + args.text_tokens + cfg.clip.n_patches - 1 + args.n_gen - 1
-        attn_fl += 2.0 * cfg.llm.layers * cfg.llm.hidden * sum(t + 1 for t in range(T_all))
-        executed_frame = meter.total_gemm_flop() / B + attn_fl
-        # HBM traffic of the dominant kernel cannot be sampled from inside this process: it comes from the two
-        # rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of THIS command, summarised by tools/pmc_traffic.py into
-        # profiles/ (FETCH_SIZE doubled on gfx950 as MI355X_MICROARCH.md prescribes). null when no summary matches.
-        traffic, traffic_src = None, None
-        pmc_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "pmc_gemm_traffic.json")
-        if os.path.exists(pmc_path):
-            with open(pmc_path) as fh:
-                pmc = json.load(fh)
-            from haff import lib as hlib
-            if pmc.get("config") == cfg.name and pmc.get("batch") == B and pmc.get("library_source_sha16") == hlib.source_hash():
-                traffic = pmc["hbm_bytes_per_launch"]
-                traffic_src = "profiles/pmc_gemm_traffic.json (%s)" % pmc.get("collected", "")
-            else:   # collected on another tree / workload: not this run's traffic
-                traffic_src = "profiles/pmc_gemm_traffic.json does not match this tree (config %s, batch %s, csrc sha %s vs %s): null" % (
-                    pmc.get("config"), pmc.get("batch"), pmc.get("library_source_sha16"), hlib.source_hash())
         f32_mode = run_dtype == torch.float32
-        if f32_mode:   # the parity mode: every product is gemm_f32_kernel (f32-input MFMA, 157.3 TFLOP/s dense)
-            n_launch, gemm_ms, gemm_fl = f32_n, f32_ms, f32_fl
-            gemm_bytes, traffic, traffic_src = 0.0, None, None
-        peak = 157.3 if f32_mode else PEAK_BF16_TFLOPS
-        achieved = gemm_fl / (gemm_ms * 1e-3) / 1e12
-        roofline = {
-            "bound": "mfma", "kernel": "gemm_f32_kernel (haff_gemm_f32: v_mfma_f32_16x16x4_f32 tiles; every product of the fp32 parity mode)" if f32_mode else
-                                       "gemm_bf16_kernel (haff_gemm_bf16 with M > 64: the 256x256 / 128x128 MFMA tiles, all epilogue variants)",
-            "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-            "traffic": traffic, "traffic_source": traffic_src,
-            "algorithmic_bytes_per_launch_avg": gemm_bytes / n_launch,
-            "launches_per_step": n_launch, "avg_launch_us": 1e3 * gemm_ms / n_launch,
-            "flops_per_launch_avg": gemm_fl / n_launch, "gemm_share_of_step": gemm_ms / ms_per_step,
-            # the same launches split by what their epilogue carries besides bias / activation / residual (round 3 moved the
-            # LayerNorm fold, the LayerNorm statistics of the output rows, RoPE + KV-cache append INTO these launches: the work
-            # left other kernels, the FLOPs did not change, so `frac` pays for it)
-            "by_epilogue": {k: {"launches_per_step": n, "achieved": fl / (ms * 1e-3) / 1e12 if ms > 0 else None,
-                                "share_of_step": ms / ms_per_step} for k, (n, ms, fl) in sorted(meter.fused_summary().items())},
-            "by_shape": meter.shape_summary(),
-            "weight_streaming_gemm": {"kernel": "haff_gemm_bf16 launches with M <= 64 (KV-cached decode steps, [SEG] MLP): gemm_skinny_kernel, or the split-K 128x128 tile path for wide / deep weights at 33..64 rows",
-                                      "bound": "hbm", "launches_per_step": ws_n, "share_of_step": ws_ms / ms_per_step,
-                                      "achieved": (ws_bytes / (ws_ms * 1e-3) / 1e9) if ws_ms > 0 else None, "peak": 8000.0,
-                                      "unit": "GB/s", "algorithmic_bytes": "2*N*K (the weight matrix, read once)"},
-            "fp32_decoder_tail_gemm": {"kernel": "gemm_f32_kernel (v_mfma_f32_16x16x4_f32; text_hidden_fcs + both mask decoders)",
-                                       "launches_per_step": f32_n, "share_of_step": f32_ms / ms_per_step,
-                                       "achieved": (f32_fl / (f32_ms * 1e-3) / 1e12) if f32_ms > 0 else None, "peak": 157.3,
-                                       "unit": "TFLOP/s"},
-            "whole_path": {"flops_per_frame": flops_frame, "flops_per_frame_source": "SURVEY.md 8(d) (counts the padded window rows)",
-                           "achieved": fps / world * flops_frame / 1e12,
-                           "frac": fps / world * flops_frame / 1e12 / peak,
-                           "executed_flops_per_frame": executed_frame,
-                           "executed_note": "every GEMM launch as issued (padded window rows skipped) + attention / rel-pos terms",
-                           "executed_achieved": fps / world * executed_frame / 1e12,
-                           "executed_frac": fps / world * executed_frame / 1e12 / peak},
-        }
+        roofline = gemm_roofline(model, step, cfg, args, fps, world, ms_per_step, f32_mode) if args.full else None
         T_exp = 4 + args.text_tokens + cfg.clip.n_patches - 1
         line = base_line(fps, world, args.steps, args.warmup, ms_per_step,
                          "BASELINE.json %s: %s, %d x %dx%d uint8 NHWC frames/step/GPU, %d-token prompt (T=%d), %d forced "
@@ -1320,7 +1343,7 @@ def main(argv=None):
         # sanity of the produced masks (finite, right shapes)
         ok = all(m.shape == (1, S, S) and bool(torch.isfinite(m).all()) for m in out[1] + out[2])
         line["outputs_finite"] = ok
-        if not args.no_b1:
+        if args.full and not args.no_b1:
             for _ in range(2):
                 step(1)
             torch.cuda.synchronize()
@@ -1353,14 +1376,14 @@ def main(argv=None):
                                           "note": "a read-only streaming kernel reaches 6.25 TB/s on this part (tools/probes/lds_dma_bw.hip)"}
         threads = min(len(os.sched_getaffinity(0)), 32)
         full_parity = None
-        if world == 1 and not args.no_parity and not args.no_full_frame_parity and cfg.name in SURVEY_FLOPS:
+        if args.full and world == 1 and not args.no_parity and not args.no_full_frame_parity and cfg.name in SURVEY_FLOPS:
             # ONE full-depth frame through the HIP path (both numeric modes) and the oracle on shared weights: the parity object's
             # full_frame entry AND cpu_baseline's one real frame (the oracle's exact pass is the timed CPU frame)
             del model
             model = None
             torch.cuda.empty_cache()
             full_parity = parity_full_frame(cfg, device, threads, args.text_tokens, args.n_gen, attribution=args.attribution)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, args.text_tokens, args.n_gen, threads)
             if not args.no_cpu_full_frame:
                 # one REAL frame beside the sample: the full-frame parity's oracle pass when that ran, else a pass of its own
@@ -1381,7 +1404,7 @@ def main(argv=None):
                     cb["sample"] = full["what"] + " - ONE measured end-to-end frame (the `extrapolation` object is the per-layer estimate beside it)"
         else:
             line["cpu_baseline"] = None
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             del model
             line["parity"] = parity_vs_oracle(device)
             # which entry of the parity objects belongs to the number this line prints (the compact line quotes that one)

@@ -66,7 +66,7 @@ def main():
            "hbm_bytes_per_launch": g["fetch_bytes_per_launch"] + g["write_bytes_per_launch"],
            "fetch_bytes_per_launch": g["fetch_bytes_per_launch"], "write_bytes_per_launch": g["write_bytes_per_launch"],
            "collected": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python3 bench.py --batch %d --steps 1 "
-                        "--warmup 1 --no-cpu-baseline --no-b1; FETCH_SIZE x2 (gfx950)" % batch,
+                        "--warmup 1 --full --no-cpu-baseline --no-b1; FETCH_SIZE x2 (gfx950)" % batch,
            "other_kernels": {k: v for k, v in sorted(table.items(), key=lambda kv: -kv[1]["fetch_bytes_per_launch"] * kv[1]["launches"])[:10]
                              if k != "gemm_bf16_kernel"}}
     fi, wi = per_instance(fpath, "FETCH_SIZE"), per_instance(wpath, "WRITE_SIZE")
