@@ -659,6 +659,284 @@ def lora_qkv_rope(x, wqkv, wqkv_t, aq, bq, av, bv, cos_sin, T, heads, scale_, ke
     return LoraQKVRopeFn.apply(x, wqkv, wqkv_t, aq, bq, av, bv, cos_sin, T, heads, scale_, keep)
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# LoRA on every Llama projection (--lora_target_modules): the k adapter inside the fused q|k|v node, o_proj / down_proj as a
+# Linear with a residual epilogue plus its rank-8 update, gate|up with both updates and SwiGLU in one pass (csrc/lora.hip).
+# Rank <= 8 per adapter; the rank activations travel transposed ([8 per adapter][Mp]) as in LoraQKVRopeFn.
+# ------------------------------------------------------------------------------------------------------------------
+def _lora_tn(lib, dt_, sT, R, big, M, n, out, transposed, j_valid, scale_):
+    """out = scale * sT[:, :M] . big (the contraction over rows of csrc/lora.hip; sT [R][Mp] with zero padding)."""
+    n_ws = lib.haff_lora_tn_workspace_elems(M, R, n)
+    assert n_ws > 0
+    ws = torch.empty((n_ws,), dtype=torch.float32, device=big.device)
+    check(_fn16(lib, "haff_lora_tn", dt_)(sT.data_ptr(), sT.stride(0), R, big.data_ptr(), big.stride(0), M, n, ws.data_ptr(), ws.numel(),
+                                          out.data_ptr(), out.stride(0), 1 if out.dtype == torch.float32 else 0, 1 if transposed else 0,
+                                          j_valid, scale_, _s()), "haff_lora_tn")
+    return out
+
+
+def _rank_rows(M, rows, dtype, dev):
+    """[rows][Mp] for transposed rank activations: Mp = roundup(M, 16), the pad columns zero (finite for the row contractions)."""
+    Mp = (M + 15) // 16 * 16
+    return (torch.empty if Mp == M else torch.zeros)((rows, Mp), dtype=dtype, device=dev)
+
+
+def _masks(keep, n):
+    """keep: None, one mask for every adapter, or one per adapter -> a list of n (mask or None)."""
+    if isinstance(keep, (tuple, list)):
+        assert len(keep) == n
+        return list(keep)
+    return [keep] * n
+
+
+class LoraQKV3RopeFn(Function):
+    """LoraQKVRopeFn with a k adapter: q = rope(x Wq^T + s (xd_q Aq^T) Bq^T), k = rope(x Wk^T + s (xd_k Ak^T) Bk^T),
+    v = x Wv^T + s (xd_v Av^T) Bv^T. Any of the three adapters may be None (not a target): its rank rows are zero and it gets no
+    gradient. keep: None, one mask for all, or a triple (q, v, k) of 0 / 1 mask values (1/(1-p) folded into s)."""
+
+    @staticmethod
+    def forward(ctx, x, wqkv, wqkv_t, aq, bq, av, bv, ak, bk, cos_sin, T, heads, scale_, keep):
+        lib = load_library()
+        M, K = x.shape
+        H = wqkv.shape[0] // 3
+        d = H // heads
+        dev = x.device
+        x = x.contiguous()
+        qkv = ops.linear(x, wqkv)
+        pairs = [(aq, bq), (av, bv), (ak, bk)]                # t^T rank rows 0-7, 8-15, 16-23
+        on = [a is not None for a, _ in pairs]
+        r = next(a.shape[0] for a, _ in pairs if a is not None)
+        a3 = torch.zeros((24, K), dtype=x.dtype, device=dev)
+        b3 = torch.zeros((3, H, 8), dtype=x.dtype, device=dev)
+        for i, (a, b) in enumerate(pairs):
+            if on[i]:
+                a3[8 * i:8 * i + r] = a
+                b3[i, :, :r] = b
+        masks = _masks(keep, 3)
+        xds = [x if m is None else _mul(x, m) for m in masks] if isinstance(keep, (tuple, list)) else None
+        Mp = (M + 15) // 16 * 16
+        tT = torch.zeros((24, Mp), dtype=x.dtype, device=dev)
+        if xds is not None:   # each adapter's rank rows from ITS dropped input
+            for i in range(3):
+                if on[i]:
+                    ops.linear(a3[8 * i:8 * i + 8], xds[i], out=tT[8 * i:8 * i + 8, :M])
+        else:
+            xd = x if keep is None else _mul(x, keep)
+            xds = [xd] * 3
+            ops.linear(a3, xd, out=tT[:, :M])
+        q, k, v = (torch.empty((M, H), dtype=x.dtype, device=dev) for _ in range(3))
+        check(_fn16(lib, "haff_lora_qkv3_rope_fwd", x.dtype)(qkv.data_ptr(), qkv.stride(0), tT.data_ptr(), Mp, b3[0].data_ptr(),
+                                                             b3[1].data_ptr(), b3[2].data_ptr(), 8, cos_sin.data_ptr(), q.data_ptr(),
+                                                             k.data_ptr(), v.data_ptr(), H, M, H, d, int(T), float(scale_), _s()),
+              "haff_lora_qkv3_rope_fwd")
+        none = torch.empty(0, device=dev)
+        ctx.save_for_backward(wqkv_t, a3, b3, tT, cos_sin, *xds, *[none if m is None else m for m in masks])
+        ctx.cfg = (int(T), heads, float(scale_), r, on, isinstance(keep, (tuple, list)), keep is not None)
+        return q, k, v
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        lib = load_library()
+        wqkv_t, a3, b3, tT, cos_sin, *rest = ctx.saved_tensors
+        xds, masks = rest[0:3], rest[3:6]
+        T, heads, scale_, r, on, per_adapter, masked = ctx.cfg
+        M, K = xds[0].shape
+        H = b3.shape[1]
+        d = H // heads
+        dev, dt_ = xds[0].device, xds[0].dtype
+        Mp = tT.shape[1]
+        dq, dk, dv = dq.contiguous(), dk.contiguous(), dv.contiguous()
+        dqkv = torch.empty((M, 3 * H), dtype=dt_, device=dev)
+        check(_fn16(lib, "haff_lora_qkv_rope_bwd", dt_)(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), H, cos_sin.data_ptr(), dqkv.data_ptr(),
+                                                        3 * H, M, H, d, T, _s()), "haff_lora_qkv_rope_bwd")
+        cols = [dqkv[:, :H], dqkv[:, 2 * H:], dqkv[:, H:2 * H]]   # q, v, k: the adapters' order in t^T
+        b3t = b3.transpose(1, 2).contiguous()                      # [3][8][H]
+        dtT = torch.zeros((24, Mp), dtype=dt_, device=dev)
+        grads = [None] * 6
+        for i in range(3):
+            if not on[i]:
+                continue
+            ops.linear(b3t[i], cols[i], out=dtT[8 * i:8 * i + 8, :M])
+            grads[2 * i + 1] = _lora_tn(lib, dt_, tT[8 * i:8 * i + 8], 8, cols[i], M, H, torch.empty((H, r), dtype=dt_, device=dev), True, r,
+                                        scale_)
+            grads[2 * i] = _lora_tn(lib, dt_, dtT[8 * i:8 * i + 8], 8, xds[i], M, K, torch.empty((r, K), dtype=dt_, device=dev), False, r,
+                                    scale_)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.linear(dqkv, wqkv_t)
+            kq = masks[0].data_ptr() if masked else 0
+            kv = masks[1].data_ptr() if per_adapter else 0
+            kk = masks[2].data_ptr() if per_adapter else 0
+            check(_fn16(lib, "haff_lora_dx3", dt_)(dtT.data_ptr(), Mp, a3.data_ptr(), K, kq, kv, kk, K, dx.data_ptr(), dx.stride(0), 1, M, K,
+                                                   scale_, _s()), "haff_lora_dx3")
+        gq_a, gq_b, gv_a, gv_b, gk_a, gk_b = grads
+        return dx, None, None, gq_a, gq_b, gv_a, gv_b, gk_a, gk_b, None, None, None, None, None
+
+
+def lora_qkv3_rope(x, wqkv, wqkv_t, aq, bq, av, bv, ak, bk, cos_sin, T, heads, scale_, keep=None):
+    return LoraQKV3RopeFn.apply(x, wqkv, wqkv_t, aq, bq, av, bv, ak, bk, cos_sin, T, heads, scale_, keep)
+
+
+def _pad_rank(t, rows_major):
+    """An adapter operand padded to rank 8: A [r][K] -> [8][K] (rows_major) or B [N][r] -> [N][8]; zeros beyond r."""
+    r = t.shape[0] if rows_major else t.shape[1]
+    if r == 8:
+        return t.contiguous()
+    out = torch.zeros(((8, t.shape[1]) if rows_major else (t.shape[0], 8)), dtype=t.dtype, device=t.device)
+    if rows_major:
+        out[:r] = t
+    else:
+        out[:, :r] = t
+    return out
+
+
+class LoraLinearFn(Function):
+    """An adapted Llama Linear with a residual epilogue (o_proj, down_proj): y = x W^T + resid + s ((x o keep) A^T) B^T.
+    The frozen product carries the residual as today; one haff_lora_out pass adds the rank-8 update to its rows."""
+
+    @staticmethod
+    def forward(ctx, x, w, w_t, resid, a, b, scale_, keep):
+        lib = load_library()
+        M, K = x.shape
+        N = w.shape[0]
+        r = a.shape[0]
+        x = x.contiguous()
+        y = ops.linear(x, w, resid=resid)
+        xd = x if keep is None else _mul(x, keep)
+        a8, b8 = _pad_rank(a, True), _pad_rank(b, False)
+        tT = _rank_rows(M, 8, x.dtype, x.device)
+        ops.linear(a8, xd, out=tT[:, :M])
+        check(_fn16(lib, "haff_lora_out", x.dtype)(tT.data_ptr(), tT.stride(0), b8.data_ptr(), y.data_ptr(), y.stride(0), M, N,
+                                                   float(scale_), _s()), "haff_lora_out")
+        ctx.save_for_backward(xd, w_t, a8, b8, tT, keep if keep is not None else torch.empty(0, device=x.device))
+        ctx.cfg = (float(scale_), r, resid is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = load_library()
+        xd, w_t, a8, b8, tT, keep = ctx.saved_tensors
+        scale_, r, has_resid = ctx.cfg
+        M, K = xd.shape
+        N = b8.shape[0]
+        dev, dt_ = xd.device, xd.dtype
+        dy = dy.contiguous()
+        # haff_lora_dx reads 16 rank rows (two adapter slots) of dt^T and A: this adapter's in rows 0-7, rows 8-15 zero
+        dtT = torch.zeros((16, tT.shape[1]), dtype=dt_, device=dev)
+        ops.linear(b8.t().contiguous(), dy, out=dtT[0:8, :M])
+        db = _lora_tn(lib, dt_, tT, 8, dy, M, N, torch.empty((N, r), dtype=dt_, device=dev), True, r, scale_)
+        da = _lora_tn(lib, dt_, dtT[0:8], 8, xd, M, K, torch.empty((r, K), dtype=dt_, device=dev), False, r, scale_)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.linear(dy, w_t)
+            a16 = torch.cat([a8, torch.zeros_like(a8)], 0)
+            check(_fn16(lib, "haff_lora_dx", dt_)(dtT.data_ptr(), dtT.stride(0), a16.data_ptr(), K, keep.data_ptr() if keep.numel() else 0, K,
+                                                  dx.data_ptr(), dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx")
+        return dx, None, None, (dy if has_resid else None), da, db, None, None
+
+
+def lora_linear(x, w, w_t, resid, a, b, scale_, keep=None):
+    return LoraLinearFn.apply(x, w, w_t, resid, a, b, scale_, keep)
+
+
+class LoraGateUpSwigluFn(Function):
+    """The adapted gate | up product with SwiGLU: gu' = x Wgu^T + s ((x o keep_g) Ag^T) Bg^T (gate columns) and
+    + s ((x o keep_u) Au^T) Bu^T (up columns) in the interleaved [gate x16 | up x16] layout, y = silu(g') * u'. Either adapter may
+    be None. keep: None, one mask for both, or a pair (gate, up). gu' stays for the SwiGLU adjoint, as SwigluFn keeps gu."""
+
+    @staticmethod
+    def forward(ctx, x, wgu, wgu_t, ag, bg, au, bu, scale_, keep):
+        lib = load_library()
+        M, K = x.shape
+        F = wgu.shape[0] // 2
+        dev = x.device
+        x = x.contiguous()
+        gu = ops.linear(x, wgu)
+        on = [ag is not None, au is not None]
+        r = ag.shape[0] if on[0] else au.shape[0]
+        a2 = torch.zeros((16, K), dtype=x.dtype, device=dev)
+        bgp = torch.zeros((F, 8), dtype=x.dtype, device=dev)
+        bup = torch.zeros((F, 8), dtype=x.dtype, device=dev)
+        if on[0]:
+            a2[0:r] = ag
+            bgp[:, :r] = bg
+        if on[1]:
+            a2[8:8 + r] = au
+            bup[:, :r] = bu
+        tT = _rank_rows(M, 16, x.dtype, dev)
+        if isinstance(keep, (tuple, list)):
+            xds = [_mul(x, keep[0]), _mul(x, keep[1])]
+            for i in range(2):
+                if on[i]:
+                    ops.linear(a2[8 * i:8 * i + 8], xds[i], out=tT[8 * i:8 * i + 8, :M])
+                else:
+                    tT[8 * i:8 * i + 8].zero_()
+        else:
+            xd = x if keep is None else _mul(x, keep)
+            xds = [xd, xd]
+            ops.linear(a2, xd, out=tT[:, :M])
+        y = torch.empty((M, F), dtype=x.dtype, device=dev)
+        check(_fn16(lib, "haff_lora_gu_swiglu", x.dtype)(tT.data_ptr(), tT.stride(0), bgp.data_ptr(), bup.data_ptr(), gu.data_ptr(),
+                                                         gu.stride(0), y.data_ptr(), F, M, F, float(scale_), _s()), "haff_lora_gu_swiglu")
+        masks = _masks(keep, 2)
+        none = torch.empty(0, device=dev)
+        ctx.save_for_backward(gu, wgu_t, a2, bgp, bup, tT, xds[0], xds[1], *[none if m is None else m for m in masks])
+        ctx.cfg = (float(scale_), r, on, isinstance(keep, (tuple, list)), keep is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = load_library()
+        gu, wgu_t, a2, bgp, bup, tT, xg, xu, kg, ku = ctx.saved_tensors
+        scale_, r, on, per_adapter, masked = ctx.cfg
+        M, K = xg.shape
+        F = bgp.shape[0]
+        dev, dt_ = xg.device, xg.dtype
+        dy = dy.contiguous()
+        dgu = torch.empty_like(gu)
+        check(lib.haff_swiglu_bwd(gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(), M, F, _dt(gu), _s()), "haff_swiglu_bwd")
+        # dt^T [16][M] = Bblk^T . dgu'^T in one weight-streaming launch: Bblk^T [16][2F] holds Bg^T on the gate columns (rows 0-7)
+        # and Bu^T on the up columns (rows 8-15), zeros elsewhere
+        blk = torch.zeros((16, F // 16, 2, 16), dtype=dt_, device=dev)
+        blk[0:8, :, 0, :] = bgp.t().reshape(8, F // 16, 16)
+        blk[8:16, :, 1, :] = bup.t().reshape(8, F // 16, 16)
+        dtT = _rank_rows(M, 16, dt_, dev)
+        ops.linear(blk.view(16, 2 * F), dgu, out=dtT[:, :M])
+        dag = dbg = dau = dbu = None
+        db_all = _lora_tn(lib, dt_, tT, 16, dgu, M, 2 * F, torch.empty((2 * F, 16), dtype=dt_, device=dev), True, 16, scale_)
+        db_all = db_all.view(F // 16, 2, 16, 16)
+        if on[0]:
+            dbg = db_all[:, 0, :, 0:r].reshape(F, r)
+            dag = _lora_tn(lib, dt_, dtT[0:8], 8, xg, M, K, torch.empty((r, K), dtype=dt_, device=dev), False, r, scale_)
+        if on[1]:
+            dbu = db_all[:, 1, :, 8:8 + r].reshape(F, r)
+            dau = _lora_tn(lib, dt_, dtT[8:16], 8, xu, M, K, torch.empty((r, K), dtype=dt_, device=dev), False, r, scale_)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.linear(dgu, wgu_t)
+            if per_adapter:
+                check(_fn16(lib, "haff_lora_dx2", dt_)(dtT.data_ptr(), dtT.stride(0), a2.data_ptr(), K, kg.data_ptr(), ku.data_ptr(), K,
+                                                       dx.data_ptr(), dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx2")
+            else:
+                check(_fn16(lib, "haff_lora_dx", dt_)(dtT.data_ptr(), dtT.stride(0), a2.data_ptr(), K, kg.data_ptr() if masked else 0, K,
+                                                      dx.data_ptr(), dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx")
+        return dx, None, None, dag, dbg, dau, dbu, None, None
+
+
+def lora_gate_up_swiglu(x, wgu, wgu_t, ag, bg, au, bu, scale_, keep=None):
+    return LoraGateUpSwigluFn.apply(x, wgu, wgu_t, ag, bg, au, bu, scale_, keep)
+
+
+def lora_fused_supported(x, w, a):
+    """The fused adapter nodes' shapes: 16-bit operands, K % 128 == 0 (haff_lora_dx), N % 16 == 0, rank <= 8, M >= 16."""
+    return (x.dtype in HALF and w.dtype == x.dtype and x.shape[1] % 128 == 0 and w.shape[0] % 16 == 0 and a.shape[0] <= 8
+            and x.shape[0] >= 16)
+
+
+FUSED_LORA_OUT = True      # False: o_proj / down_proj adapters as LinearFn / scale / add nodes (A/B, tests)
+FUSED_LORA_GATE_UP = True  # False: gate / up adapters as LinearFn nodes added into gu before SwigluFn (A/B, tests)
+
+
 class BgemmFn(Function):
     """c[z] = a[z] @ b[z].T for a [Z,M,K], b [Z,N,K]."""
 

@@ -15,6 +15,9 @@
 //   * dt^T = B^T.dq^T is again the swapped weight-streaming product; lora_dx_kernel adds s.keep.(dt.A2) into the d(x) the
 //     frozen product's adjoint wrote; lora_tn_kernel is the one contraction over ROWS (dA = dt^T.x, dB = dq^T.t): rank rows
 //     in SGPRs, the big operand streamed once, per-row-block partials summed in index order (no atomics, deterministic).
+// LoRA on the other projections (--lora_target_modules): the q|k|v kernel with a third (k) adapter, t^T [24][M]; lora_out_kernel
+// adds an adapted Linear's update into the frozen product's rows (o_proj, down_proj, residual already in); lora_gu_swiglu_kernel
+// adds the gate and up updates into the interleaved gate|up product and applies SwiGLU in the same pass.
 // bf16 or f16 storage (every kernel is one template, F16 = the fp16 fine-tune's instance: the *_f16 entry points), fp32
 // arithmetic, head dim 128, rank <= 8 per adapter.
 #include "haff_common.h"
@@ -25,10 +28,11 @@ constexpr int HD = 128;   // head dim (Llama 7B / 13B)
 
 __device__ __forceinline__ bf16x8 zero_frag() { return bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
 
-// the 16 x 32 operand tile of t (rows = activation rows row0.., k = adapter index 0..15, 16..31 empty) out of t^T [16][ldt]
-__device__ __forceinline__ bf16x8 load_t_frag(const bf16_t* tT, long ldt, long row, int fh) {
+// the 16 x 32 operand tile of t (rows = activation rows row0.., k = adapter rank index 0..8na-1, the rest empty) out of
+// t^T [8na][ldt]: na = 2 adapters (q, v) or 3 (q, v, k)
+__device__ __forceinline__ bf16x8 load_t_frag(const bf16_t* tT, long ldt, long row, int fh, int na) {
   bf16x8 f = zero_frag();
-  if (fh < 2) {
+  if (fh < na) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) f[i] = (short)tT[(long)(8 * fh + i) * ldt + row];
   }
@@ -42,6 +46,7 @@ struct LoraFwdArgs {
   const float* cs;
   bf16_t *qo, *ko, *vo; long ldo;
   long M; int H, T; float scale;
+  const bf16_t* Bk;   // NA = 3 (haff_lora_qkv3_rope_fwd): the k adapter's B, its ranks at t^T rows 16-23
 };
 
 // one wave = one head x 16-row tiles. The head's 128 columns are four groups of 32 (groups 2, 3 = the rotate-half partners of
@@ -49,14 +54,14 @@ struct LoraFwdArgs {
 // 8 * (i / 4) + 4 * h + i % 4), so that lane (fr, fh) ends up with row fr, columns 8fh .. 8fh+7 of the group: 16-byte
 // loads and stores, 64 contiguous bytes per row and instruction (the natural operand order leaves 4 columns per lane:
 // 8-byte accesses in 32-byte runs, which held this kernel at 2.4 TB/s)
-template <bool F16>
+template <bool F16, int NA>
 __global__ __launch_bounds__(256, 3) void lora_qkv_rope_fwd_kernel(LoraFwdArgs p) {
   using E = h16<F16>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, fh = lane >> 4;
   const int head = blockIdx.x;
   const long n_rt = (p.M + 15) / 16;
-  bf16x8 bq[4][2], bv[4][2];
+  bf16x8 bq[4][2], bv[4][2], bk[4][2];
 #pragma unroll
   for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -64,13 +69,14 @@ __global__ __launch_bounds__(256, 3) void lora_qkv_rope_fwd_kernel(LoraFwdArgs p
       const long col = (long)head * HD + 32 * g + 8 * (fr >> 2) + 4 * h + (fr & 3);
       bq[g][h] = fh == 0 ? *reinterpret_cast<const bf16x8*>(p.Bq + col * p.ldb) : zero_frag();
       bv[g][h] = fh == 1 ? *reinterpret_cast<const bf16x8*>(p.Bv + col * p.ldb) : zero_frag();
+      bk[g][h] = (NA == 3 && fh == 2) ? *reinterpret_cast<const bf16x8*>(p.Bk + col * p.ldb) : zero_frag();
     }
   for (long rt = (long)blockIdx.y * 4 + wave; rt < n_rt; rt += (long)gridDim.y * 4) {
     const long row = rt * 16 + fr;
     const bool valid = row < p.M;
     const long rc = valid ? row : p.M - 1;
     const int pos = (int)(rc % p.T);
-    const bf16x8 tt = load_t_frag(p.tT, p.ldt, rc, fh);
+    const bf16x8 tt = load_t_frag(p.tT, p.ldt, rc, fh, NA);
     const bf16_t* src = p.qkv + rc * p.ld_qkv + (long)head * HD + 8 * fh;
     bf16_t* q_o = p.qo + rc * p.ldo + (long)head * HD + 8 * fh;
     bf16_t* k_o = p.ko + rc * p.ldo + (long)head * HD + 8 * fh;
@@ -91,6 +97,19 @@ __global__ __launch_bounds__(256, 3) void lora_qkv_rope_fwd_kernel(LoraFwdArgs p
         dq1[h] = E::mfma16(bq[g + 2][h], tt, z);
         dv0[h] = E::mfma16(bv[g][h], tt, z);
         dv1[h] = E::mfma16(bv[g + 2][h], tt, z);
+      }
+      if constexpr (NA == 3) {   // the k adapter's update lands on k BEFORE its rotation, as q's does
+        f32x4 dk0[2], dk1[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          dk0[h] = E::mfma16(bk[g][h], tt, z);
+          dk1[h] = E::mfma16(bk[g + 2][h], tt, z);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          ka[e] += p.scale * dk0[e >> 2][e & 3];
+          kb[e] += p.scale * dk1[e >> 2][e & 3];
+        }
       }
       float q1[8], q2[8], k1[8], k2[8];
 #pragma unroll
@@ -153,6 +172,8 @@ struct LoraDxArgs {
   bf16_t* dx; long ldx;
   long M; int K; int accumulate; float scale;
   const bf16_t* keep_v;   // two masks (haff_lora_dx2): `keep` gates the q adapter's ranks (rows 0-7 of A2), keep_v the v adapter's (8-15)
+  const bf16_t* keep_k;   // three masks (haff_lora_dx3): keep_k gates the k adapter's ranks (rows 16-23 of A3)
+  int na;                 // adapters (8 rank rows each) in dt^T / A: 2, or 3 (haff_lora_dx3)
 };
 template <bool F16>
 __global__ __launch_bounds__(256) void lora_dx_kernel(LoraDxArgs p) {   // column operands permuted as in the forward kernel
@@ -167,7 +188,7 @@ __global__ __launch_bounds__(256) void lora_dx_kernel(LoraDxArgs p) {   // colum
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       af[g][h] = zero_frag();
-      if (fh < 2) {
+      if (fh < p.na) {
         const long col = c0 + 32 * g + 8 * (fr >> 2) + 4 * h + (fr & 3);
 #pragma unroll
         for (int i = 0; i < 8; ++i) af[g][h][i] = (short)p.A2[(long)(8 * fh + i) * p.lda + col];
@@ -177,29 +198,36 @@ __global__ __launch_bounds__(256) void lora_dx_kernel(LoraDxArgs p) {   // colum
     const long row = rt * 16 + fr;
     const bool valid = row < p.M;
     const long rc = valid ? row : p.M - 1;
-    const bf16x8 tt = load_t_frag(p.dtT, p.ldt, rc, fh);
+    const bf16x8 tt = load_t_frag(p.dtT, p.ldt, rc, fh, p.na);
     bf16_t* dst = p.dx + rc * p.ldx + c0 + 8 * fh;
     const bf16_t* kpr = p.keep ? p.keep + rc * p.ldk + c0 + 8 * fh : nullptr;
     const bf16_t* kvr = p.keep_v ? p.keep_v + rc * p.ldk + c0 + 8 * fh : nullptr;
+    const bf16_t* kkr = p.keep_k ? p.keep_k + rc * p.ldk + c0 + 8 * fh : nullptr;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      float old[8], kp[8], kv[8];
+      float old[8], kp[8], kv[8], kk[8];
       if (p.accumulate) load8h<F16>(dst + 32 * g, old);
       if (kpr) load8h<F16>(kpr + 32 * g, kp);
       if (kvr) load8h<F16>(kvr + 32 * g, kv);
+      if (kkr) load8h<F16>(kkr + 32 * g, kk);
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       f32x4 d[2];
       float v[8];
       if (kvr) {   // (wave-uniform) two masks: the q adapter's ranks sit in the fh = 0 lanes of the A fragment, the v adapter's in fh = 1
         const bf16x8 zf = zero_frag();
-        f32x4 dv[2];
+        f32x4 dv[2], dk[2];
         d[0] = E::mfma16(fh == 0 ? af[g][0] : zf, tt, z);
         d[1] = E::mfma16(fh == 0 ? af[g][1] : zf, tt, z);
         dv[0] = E::mfma16(fh == 1 ? af[g][0] : zf, tt, z);
         dv[1] = E::mfma16(fh == 1 ? af[g][1] : zf, tt, z);
+        if (kkr) {   // (wave-uniform) the third mask: the k adapter's ranks in the fh = 2 lanes
+          dk[0] = E::mfma16(fh == 2 ? af[g][0] : zf, tt, z);
+          dk[1] = E::mfma16(fh == 2 ? af[g][1] : zf, tt, z);
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           v[e] = p.scale * (d[e >> 2][e & 3] * kp[e] + dv[e >> 2][e & 3] * kv[e]);
+          if (kkr) v[e] += p.scale * (dk[e >> 2][e & 3] * kk[e]);
           if (p.accumulate) v[e] += old[e];
         }
       } else {
@@ -298,28 +326,129 @@ __global__ void lora_tn_reduce_kernel(const float* part, int nrb, int R, int N, 
   }
 }
 
+// An adapted Linear's rank-8 update added into the frozen product's output, which already holds its residual epilogue
+// (o_proj, down_proj):  y[m][n] += scale * sum_j t[m][j] * B[n][j],  t^T [8][ldt] (ldt % 4 == 0, columns past M finite).
+// Thread = 4 rows x 8 columns: B's 8 x 8 block stays in registers, the 4 rows' rank values come in as one 8-byte load per rank
+// (the same address in every lane of a wave whose lanes walk the columns), y is read and written once with 16-byte accesses.
+template <bool F16>
+__global__ __launch_bounds__(256) void lora_out_kernel(const bf16_t* tT, long ldt, const bf16_t* B, bf16_t* y, long ldy, long M, int N,
+                                                       float scale) {
+  using E = h16<F16>;
+  const int n8 = N >> 3;
+  const long total = (M + 3) / 4 * n8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long m0 = (i / n8) * 4;
+    const long c = (i - (m0 / 4) * n8) * 8;
+    float b[8][8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) load8h<F16>(B + (c + e) * 8, b[e]);
+    float t[4][8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint2 w = *reinterpret_cast<const uint2*>(tT + (long)j * ldt + m0);
+      t[0][j] = E::lo(w.x); t[1][j] = E::hi(w.x); t[2][j] = E::lo(w.y); t[3][j] = E::hi(w.y);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (m0 + r >= M) break;
+      bf16_t* dst = y + (m0 + r) * ldy + c;
+      float o[8];
+      load8h<F16>(dst, o);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc = fmaf(t[r][j], b[e][j], acc);
+        o[e] += scale * acc;
+      }
+      store8h<F16>(dst, o);
+    }
+  }
+}
+
+// gate | up with SwiGLU: gu [M][2F] in the interleaved [gate x16 | up x16] column layout of the frozen product. The gate
+// adapter's ranks are t^T rows 0-7 (Bg [F][8]), the up adapter's rows 8-15 (Bu [F][8]); output f's gate column takes Bg row f,
+// its up column Bu row f (a block-structured B over the interleaved rows: each column sees one adapter's 8 ranks only).
+//   gu[m][.] += scale * update (IN PLACE: the SwiGLU adjoint's operand),  y[m][f] = silu(g') * u'
+// Thread = 4 rows x 8 outputs (8 gate + 8 up columns of one 16-column half group).
+template <bool F16>
+__global__ __launch_bounds__(256) void lora_gu_swiglu_kernel(const bf16_t* tT, long ldt, const bf16_t* Bg, const bf16_t* Bu, bf16_t* gu,
+                                                             long ldg, bf16_t* y, long ldy, long M, int F, float scale) {
+  using E = h16<F16>;
+  const int f8 = F >> 3;
+  const long total = (M + 3) / 4 * f8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long m0 = (i / f8) * 4;
+    const long f = (i - (m0 / 4) * f8) * 8;
+    const long base = (f >> 4) * 32 + (f & 15);
+    float bg[8][8], bu[8][8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      load8h<F16>(Bg + (f + e) * 8, bg[e]);
+      load8h<F16>(Bu + (f + e) * 8, bu[e]);
+    }
+    float tg[4][8], tu[4][8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint2 w = *reinterpret_cast<const uint2*>(tT + (long)j * ldt + m0);
+      const uint2 v = *reinterpret_cast<const uint2*>(tT + (long)(8 + j) * ldt + m0);
+      tg[0][j] = E::lo(w.x); tg[1][j] = E::hi(w.x); tg[2][j] = E::lo(w.y); tg[3][j] = E::hi(w.y);
+      tu[0][j] = E::lo(v.x); tu[1][j] = E::hi(v.x); tu[2][j] = E::lo(v.y); tu[3][j] = E::hi(v.y);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (m0 + r >= M) break;
+      bf16_t* g_p = gu + (m0 + r) * ldg + base;
+      float g[8], u[8], o[8];
+      load8h<F16>(g_p, g);
+      load8h<F16>(g_p + 16, u);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float ag = 0.f, au = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          ag = fmaf(tg[r][j], bg[e][j], ag);
+          au = fmaf(tu[r][j], bu[e][j], au);
+        }
+        g[e] += scale * ag;
+        u[e] += scale * au;
+      }
+      store8h<F16>(g_p, g);
+      store8h<F16>(g_p + 16, u);
+      // silu of the values as STORED (rounded to 16 bits): the adjoint reads gu' back, so forward and backward see one g', u'
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float gs = E::to_f32(E::from_f32(g[e])), us = E::to_f32(E::from_f32(u[e]));
+        o[e] = gs / (1.0f + expf(-gs)) * us;
+      }
+      store8h<F16>(y + (m0 + r) * ldy + f, o);
+    }
+  }
+}
+
 inline hipStream_t HS(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int check_launch() { return hipGetLastError() == hipSuccess ? HAFF_OK : HAFF_ERR_LAUNCH; }
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
-template <bool F16>
-static int lora_qkv_rope_fwd_impl(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, int ldb,
-                                  const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int d, int T,
-                                  float scale, void* stream) {
+template <bool F16, int NA>
+static int lora_qkv_rope_fwd_impl(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, const void* Bk,
+                                  int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int d,
+                                  int T, float scale, void* stream) {
   if (M <= 0 || T <= 0 || H <= 0 || !qkv || !tT || !Bq || !Bv || !cos_sin || !q_out || !k_out || !v_out) return HAFF_ERR_BAD_ARG;
+  if (NA == 3 && (!Bk || !al16(Bk))) return HAFF_ERR_BAD_ARG;
   if (d != HD || H % HD || ldb != 8) return HAFF_ERR_UNSUPPORTED;
   if (ld_qkv < 3L * H || ldo < H || ldt < M || (ld_qkv & 7) || (ldo & 7)) return HAFF_ERR_BAD_ARG;
   if (!al16(qkv) || !al16(Bq) || !al16(Bv) || !al16(cos_sin) || !al16(q_out) || !al16(k_out) || !al16(v_out)) return HAFF_ERR_BAD_ARG;
   LoraFwdArgs p{(const bf16_t*)qkv, ld_qkv, (const bf16_t*)tT, ldt, (const bf16_t*)Bq, (const bf16_t*)Bv, ldb, cos_sin,
-                (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, ldo, M, H, T, scale};
+                (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, ldo, M, H, T, scale, (const bf16_t*)Bk};
   const long n_rt = (M + 15) / 16;
   long gy = (n_rt + 3) / 4;
   const int nh = H / HD;
   const long cap = (2048 + nh - 1) / nh;   // ~2048 workgroups: 8 per CU
   if (gy > cap) gy = cap;
-  hipLaunchKernelGGL((lora_qkv_rope_fwd_kernel<F16>), dim3(nh, (unsigned)gy), dim3(256), 0, HS(stream), p);
+  hipLaunchKernelGGL((lora_qkv_rope_fwd_kernel<F16, NA>), dim3(nh, (unsigned)gy), dim3(256), 0, HS(stream), p);
   return check_launch();
 }
 
@@ -340,13 +469,14 @@ static int lora_qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv
 
 template <bool F16>
 static int lora_dx_launch(const void* dtT, long ldt, const void* A2, long lda, const void* keep, const void* keep_v, long ldk, void* dx,
-                          long ldx, int accumulate, long M, int K, float scale, void* stream) {
-  if (M <= 0 || K <= 0 || !dtT || !A2 || !dx || (keep_v && !keep)) return HAFF_ERR_BAD_ARG;
+                          long ldx, int accumulate, long M, int K, float scale, void* stream, int na = 2, const void* keep_k = nullptr) {
+  if (M <= 0 || K <= 0 || !dtT || !A2 || !dx || (keep_v && !keep) || (keep_k && !keep_v)) return HAFF_ERR_BAD_ARG;
+  if (keep_k && !al16(keep_k)) return HAFF_ERR_BAD_ARG;
   if (K % 128) return HAFF_ERR_UNSUPPORTED;
   if (ldt < M || lda < K || ldx < K || (ldx & 7) || (keep && (ldk < K || (ldk & 7)))) return HAFF_ERR_BAD_ARG;
   if (!al16(dx) || (keep && !al16(keep)) || (keep_v && !al16(keep_v))) return HAFF_ERR_BAD_ARG;
   LoraDxArgs p{(const bf16_t*)dtT, ldt, (const bf16_t*)A2, lda, (const bf16_t*)keep, ldk, (bf16_t*)dx, ldx, M, K, accumulate, scale,
-               (const bf16_t*)keep_v};
+               (const bf16_t*)keep_v, (const bf16_t*)keep_k, na};
   const long n_rt = (M + 15) / 16;
   long gy = (n_rt + 3) / 4;
   const int gx = K / 128;
@@ -397,7 +527,8 @@ static int lora_tn_impl(const void* sT, long lds, int R, const void* big, long l
 extern "C" int haff_lora_qkv_rope_fwd(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
                                       int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M,
                                       int H, int d, int T, float scale, void* stream) {
-  return lora_qkv_rope_fwd_impl<false>(qkv, ld_qkv, tT, ldt, Bq, Bv, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale, stream);
+  return lora_qkv_rope_fwd_impl<false, 2>(qkv, ld_qkv, tT, ldt, Bq, Bv, nullptr, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale,
+                                          stream);
 }
 
 extern "C" int haff_lora_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, long ld_in, const float* cos_sin, void* dqkv,
@@ -432,7 +563,8 @@ extern "C" int haff_lora_tn(const void* sT, long lds, int R, const void* big, lo
 extern "C" int haff_lora_qkv_rope_fwd_f16(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
                                           int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M,
                                           int H, int d, int T, float scale, void* stream) {
-  return lora_qkv_rope_fwd_impl<true>(qkv, ld_qkv, tT, ldt, Bq, Bv, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale, stream);
+  return lora_qkv_rope_fwd_impl<true, 2>(qkv, ld_qkv, tT, ldt, Bq, Bv, nullptr, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale,
+                                         stream);
 }
 extern "C" int haff_lora_qkv_rope_bwd_f16(const void* dq, const void* dk, const void* dv, long ld_in, const float* cos_sin, void* dqkv,
                                           long ld_out, long M, int H, int d, int T, void* stream) {
@@ -451,4 +583,71 @@ extern "C" int haff_lora_tn_f16(const void* sT, long lds, int R, const void* big
                                 long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale,
                                 void* stream) {
   return lora_tn_impl<true>(sT, lds, R, big, ldb, M, N, workspace, workspace_elems, out, ldo, out_f32, transposed, j_valid, scale, stream);
+}
+
+// ---- all-projection LoRA (--lora_target_modules): a k adapter in the fused q|k|v node, and the adapted o / down / gate|up ----
+
+template <bool F16>
+static int lora_out_impl(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream) {
+  if (M <= 0 || N <= 0 || !tT || !B || !y) return HAFF_ERR_BAD_ARG;
+  if (N % 8) return HAFF_ERR_UNSUPPORTED;
+  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || (reinterpret_cast<uintptr_t>(tT) & 7) || ldy < N || (ldy & 7) || !al16(y) || !al16(B))
+    return HAFF_ERR_BAD_ARG;
+  const long total = (M + 3) / 4 * (N / 8);
+  long g = (total + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL((lora_out_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)tT, ldt, (const bf16_t*)B, (bf16_t*)y,
+                     ldy, M, N, scale);
+  return check_launch();
+}
+
+template <bool F16>
+static int lora_gu_swiglu_impl(const void* tT, long ldt, const void* Bg, const void* Bu, void* gu, long ldg, void* y, long ldy, long M, int F,
+                               float scale, void* stream) {
+  if (M <= 0 || F <= 0 || !tT || !Bg || !Bu || !gu || !y) return HAFF_ERR_BAD_ARG;
+  if (F % 16) return HAFF_ERR_UNSUPPORTED;
+  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || (reinterpret_cast<uintptr_t>(tT) & 7) || ldg < 2L * F || (ldg & 7) || ldy < F || (ldy & 7))
+    return HAFF_ERR_BAD_ARG;
+  if (!al16(Bg) || !al16(Bu) || !al16(gu) || !al16(y)) return HAFF_ERR_BAD_ARG;
+  const long total = (M + 3) / 4 * (F / 8);
+  long g = (total + 255) / 256;
+  if (g > 8192) g = 8192;
+  hipLaunchKernelGGL((lora_gu_swiglu_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)tT, ldt, (const bf16_t*)Bg,
+                     (const bf16_t*)Bu, (bf16_t*)gu, ldg, (bf16_t*)y, ldy, M, F, scale);
+  return check_launch();
+}
+
+extern "C" int haff_lora_qkv3_rope_fwd(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, const void* Bk,
+                                       int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int d,
+                                       int T, float scale, void* stream) {
+  return lora_qkv_rope_fwd_impl<false, 3>(qkv, ld_qkv, tT, ldt, Bq, Bv, Bk, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale, stream);
+}
+extern "C" int haff_lora_dx3(const void* dtT, long ldt, const void* A3, long lda, const void* keep_q, const void* keep_v, const void* keep_k,
+                             long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
+  if (keep_v && !keep_k) return HAFF_ERR_BAD_ARG;   // no mask, one shared mask (keep_q), or three
+  return lora_dx_launch<false>(dtT, ldt, A3, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream, 3, keep_k);
+}
+extern "C" int haff_lora_out(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream) {
+  return lora_out_impl<false>(tT, ldt, B, y, ldy, M, N, scale, stream);
+}
+extern "C" int haff_lora_gu_swiglu(const void* tT, long ldt, const void* Bg, const void* Bu, void* gu, long ldg, void* y, long ldy, long M,
+                                   int F, float scale, void* stream) {
+  return lora_gu_swiglu_impl<false>(tT, ldt, Bg, Bu, gu, ldg, y, ldy, M, F, scale, stream);
+}
+extern "C" int haff_lora_qkv3_rope_fwd_f16(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
+                                           const void* Bk, int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo,
+                                           long M, int H, int d, int T, float scale, void* stream) {
+  return lora_qkv_rope_fwd_impl<true, 3>(qkv, ld_qkv, tT, ldt, Bq, Bv, Bk, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, d, T, scale, stream);
+}
+extern "C" int haff_lora_dx3_f16(const void* dtT, long ldt, const void* A3, long lda, const void* keep_q, const void* keep_v,
+                                 const void* keep_k, long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
+  if (keep_v && !keep_k) return HAFF_ERR_BAD_ARG;
+  return lora_dx_launch<true>(dtT, ldt, A3, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream, 3, keep_k);
+}
+extern "C" int haff_lora_out_f16(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream) {
+  return lora_out_impl<true>(tT, ldt, B, y, ldy, M, N, scale, stream);
+}
+extern "C" int haff_lora_gu_swiglu_f16(const void* tT, long ldt, const void* Bg, const void* Bu, void* gu, long ldg, void* y, long ldy,
+                                       long M, int F, float scale, void* stream) {
+  return lora_gu_swiglu_impl<true>(tT, ldt, Bg, Bu, gu, ldg, y, ldy, M, F, scale, stream);
 }

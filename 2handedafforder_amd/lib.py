@@ -140,6 +140,19 @@ _PROTOS = {
                           c_float, c_void_p],
     "haff_lora_tn_f16": [c_void_p, c_long, c_int, c_void_p, c_long, c_long, c_int, c_void_p, c_long, c_void_p, c_long, c_int, c_int,
                          c_int, c_float, c_void_p],
+    "haff_lora_qkv3_rope_fwd": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_long, c_long, c_int, c_int, c_int, c_float, c_void_p],
+    "haff_lora_dx3": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_long, c_int,
+                      c_float, c_void_p],
+    "haff_lora_out": [c_void_p, c_long, c_void_p, c_void_p, c_long, c_long, c_int, c_float, c_void_p],
+    "haff_lora_gu_swiglu": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_float, c_void_p],
+    "haff_lora_qkv3_rope_fwd_f16": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_float, c_void_p],
+    "haff_lora_dx3_f16": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_long,
+                          c_int, c_float, c_void_p],
+    "haff_lora_out_f16": [c_void_p, c_long, c_void_p, c_void_p, c_long, c_long, c_int, c_float, c_void_p],
+    "haff_lora_gu_swiglu_f16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_float,
+                                c_void_p],
     "haff_global_attention_bf16": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long,
                                    c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],

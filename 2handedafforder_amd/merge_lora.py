@@ -1,8 +1,8 @@
 """Fold a fine-tune checkpoint back into a plain HF-style checkpoint — the step between train_ds.py and inference.py.
 
 Mirrors `2Haff/merge_lora_weights_and_save_hf_model.py:91-155`: rebuild the LoRA model, load the trained tensors,
-`merge_and_unload()` (peft: W += (alpha / r) * B @ A on every adapted Linear, here q_proj and v_proj of each Llama layer,
-train_ds.py:192-230), drop every `vision_tower` key (the CLIP tower is loaded separately, clip_encoder.py:21-29) and
+`merge_and_unload()` (peft: W += (alpha / r) * B @ A on every adapted Linear: each `<module>.lora_A` / `.lora_B` pair the
+checkpoint holds, whichever of q/k/v/o/gate/up/down_proj --lora_target_modules selected, train_ds.py:192-230), drop every `vision_tower` key (the CLIP tower is loaded separately, clip_encoder.py:21-29) and
 `save_pretrained` (sharded weights + an index json + config.json). The trained tensors are the ones
 `train_model.LisaTrainable.state_dict()` holds: the LoRA pairs plus the fully trained `embed_tokens`, `lm_head`,
 `text_hidden_fcs` and both mask decoders (train_ds.py:233-244).

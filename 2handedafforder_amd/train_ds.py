@@ -309,12 +309,13 @@ def main(argv):
                                         seed=args.seed, cfg=cfg)
     model = LisaTrainable(cfg, sd, dtype=dtype, device=device, lora_r=args.lora_r, lora_alpha=args.lora_alpha,
                           lora_dropout=args.lora_dropout, ce_loss_weight=args.ce_loss_weight,
-                          dice_loss_weight=args.dice_loss_weight, bce_loss_weight=args.bce_loss_weight, seed=args.seed)
+                          dice_loss_weight=args.dice_loss_weight, bce_loss_weight=args.bce_loss_weight, seed=args.seed,
+                          lora_target_modules=args.lora_target_modules)
     del sd
     n_lora = sum(p.numel() for k, p in model.named_parameters() if "lora_" in k)
     n_train = sum(p.numel() for p in model.parameters())
     if rank == 0:
-        print(f"trainable params: {n_train:,d} (LoRA {n_lora:,d}) | world_size {world} | micro-batch {args.batch_size} "
+        print(f"trainable params: {n_train:,d} (LoRA {n_lora:,d} in {len(model.lora_modules)} adapters) | world_size {world} | micro-batch {args.batch_size} "
               f"x accum {args.grad_accumulation_steps}")
     reducer = T.GradBucketReducer(model.named_parameters())   # p.grad become views into flat per-dtype buckets
     opt = T.BucketAdamW(reducer, model.named_parameters())    # fp32 master / moments per bucket, one fused launch each

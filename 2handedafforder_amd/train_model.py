@@ -4,9 +4,9 @@
 (2Haff/utils/dataset.py:152-169) and returns what `LISAForCausalLM.forward(**kwargs)` -> `model_forward` returns
 (2Haff/model/LISA.py:170-430): the dict {loss, ce_loss, taxonomy_ce_loss, mask_bce_loss, mask_dice_loss, mask_loss},
 or with inference=True {pred_masks_left, pred_masks_right, pred_taxonomies, gt_masks_left, gt_masks_right,
-gt_taxonomies}. Trainable set = train_ds.py:192-244: LoRA (r, alpha, dropout) on q_proj/v_proj of every Llama layer +
-embed_tokens, lm_head, text_hidden_fcs, mask_decoder_left/right. SAM encoder, CLIP tower, projector and the Llama
-base weights are frozen; base weights keep a resident transposed copy for the dX products (288 GB of HBM: +13.5 GB
+gt_taxonomies}. Trainable set = train_ds.py:192-244: LoRA (r, alpha, dropout) on the Llama projections that
+--lora_target_modules selects (default q_proj, v_proj; lora_targets) + embed_tokens, lm_head, text_hidden_fcs,
+mask_decoder_left/right. SAM encoder, CLIP tower, projector and the Llama base weights are frozen; base weights keep a resident transposed copy for the dX products (288 GB of HBM: +13.5 GB
 for 7B is cheaper than re-transposing, and no activation checkpointing is needed either).
 Every op is an autograd.Function over HIP kernels (autograd.py).
 """
@@ -27,9 +27,59 @@ def _pad8(n):
     return (n + 7) // 8 * 8
 
 
+# the adaptable Linears of one Llama layer, in the order the adapter initialisation draws them
+LORA_PROJ = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+# find_linear_layers (train_ds.py:195-214) skips every Linear whose name contains one of these
+LORA_SKIP = ("visual_model", "vision_tower", "mm_projector", "text_hidden_fcs")
+
+
+def _proj_module(i, n):
+    return f"model.layers.{i}.{'self_attn' if n in LORA_PROJ[:4] else 'mlp'}.{n}"
+
+
+def lora_targets(cfg, spec="q_proj,v_proj"):
+    """The Llama Linears a --lora_target_modules spec adapts (find_linear_layers, train_ds.py:195-214): a Linear is adapted when
+    any comma-separated target is a substring of its full module name; names holding LORA_SKIP are skipped. Returns the
+    module names layer by layer, each layer in LORA_PROJ order. A target that matches no Linear, or one that matches a Linear
+    outside the seven projections (lm_head: fully trained already; LoRA on it is not built), raises ValueError."""
+    targets = [t.strip() for t in spec.split(",")] if isinstance(spec, str) else [str(t).strip() for t in spec]
+    if not targets:
+        raise ValueError("lora_target_modules is empty")
+    proj = [_proj_module(i, n) for i in range(cfg.llm.layers) for n in LORA_PROJ]
+    others = ["lm_head"]   # the only Linear of the language model outside the layers' projections
+    for t in targets:
+        if not any(t in name for name in proj + others if not any(s in name for s in LORA_SKIP)):
+            raise ValueError(f"Target modules {{'{t}'}} not found in the base model. Please check the target modules and try again.")
+        bad = [name for name in others if t in name]
+        if bad:
+            raise ValueError(f"lora_target_modules: '{t}' selects {', '.join(bad)}; LoRA is built on the Llama projections only "
+                             f"({', '.join(LORA_PROJ)})")
+    return [name for name in proj if any(t in name for t in targets)]
+
+
+def init_lora(cfg, targets, r, seed=0, init_b_zero=True):
+    """Adapter tensors (fp32, CPU) for the modules of lora_targets, as peft initialises them: A [r, in_features] ~
+    kaiming_uniform(a=sqrt(5)) = U(-1/sqrt(in_features), 1/sqrt(in_features)), B [out_features, r] = 0. One generator drawn in
+    lora_targets' order (layer by layer, q k v o gate up down): the default q_proj, v_proj draws what earlier versions drew.
+    init_b_zero=False (tests): B ~ U(-0.05, 0.05) from the same generator, right after its A."""
+    H, F = cfg.llm.hidden, cfg.llm.ffn
+    dims = {"q_proj": (H, H), "k_proj": (H, H), "v_proj": (H, H), "o_proj": (H, H), "gate_proj": (H, F), "up_proj": (H, F),
+            "down_proj": (F, H)}   # (in_features, out_features)
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    out = OrderedDict()
+    for k in targets:
+        fin, fout = dims[k.rsplit(".", 1)[1]]
+        a = (torch.rand((r, fin), generator=g) * 2 - 1) * (1.0 / math.sqrt(fin))
+        b = torch.zeros((fout, r)) if init_b_zero else (torch.rand((fout, r), generator=g) * 2 - 1) * 0.05
+        out[k + ".lora_A"] = a
+        out[k + ".lora_B"] = b
+    return out
+
+
 class LisaTrainable:
     def __init__(self, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", lora_r=8, lora_alpha=16, lora_dropout=0.05,
-                 ce_loss_weight=1.0, dice_loss_weight=0.5, bce_loss_weight=2.0, seed=0, lora_init_b_zero=True):
+                 ce_loss_weight=1.0, dice_loss_weight=0.5, bce_loss_weight=2.0, seed=0, lora_init_b_zero=True,
+                 lora_target_modules="q_proj,v_proj"):
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         # bf16: training is bf16 end to end, as the reference's. fp16 (--precision fp16): the frozen CLIP / ViT-H / Llama stacks run
         # on the fp16 inference mode's kernels with its own settings (weights over 65504 refused by name; the ViT-H neck in f32, so
@@ -39,7 +89,10 @@ class LisaTrainable:
         dec = self.base.sam_decoder
         self.key_pe = dec.key_pe if dec.key_pe.dtype == dtype else dec.key_pe.to(dtype).contiguous()
         self.no_mask = dec.no_mask if dec.no_mask.dtype == dtype else dec.no_mask.to(dtype).contiguous()
-        self.lora_r, self.lora_scale, self.lora_dropout = lora_r, lora_alpha / lora_r, lora_dropout
+        # lora_r = 0: no adapters (train_ds.py:193, `if lora_r > 0:`); the rest of the trainable set is unchanged
+        self.lora_r, self.lora_scale, self.lora_dropout = lora_r, (lora_alpha / lora_r if lora_r > 0 else 0.0), lora_dropout
+        self.lora_modules = lora_targets(cfg, lora_target_modules) if lora_r > 0 else []
+        self._adapted = set(self.lora_modules)
         # peft draws one dropout mask per adapted Linear: q_proj's and v_proj's adapters see independently dropped inputs (the
         # reference's semantics; default since round 5). False: ONE mask per layer for both adapters (rounds 3-4: same marginal
         # distribution, one mask launch / one rank product / one dx pass less per layer: +1.6 % samples/s)
@@ -64,17 +117,9 @@ class LisaTrainable:
             if k.startswith(V + ".mask_decoder_left.") or k.startswith(V + ".mask_decoder_right."):
                 is_vec = t.dim() == 1  # biases and norm gains/offsets are consumed as fp32 vectors by the kernels
                 add(k, t, keep_f32=is_vec)
-        # LoRA adapters (peft: A ~ kaiming_uniform(a=sqrt(5)), B = 0)
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        H = cfg.llm.hidden
-        for i in range(cfg.llm.layers):
-            for n in ("q_proj", "v_proj"):
-                k = f"model.layers.{i}.self_attn.{n}"
-                bound = 1.0 / math.sqrt(H)
-                a = (torch.rand((lora_r, H), generator=g) * 2 - 1) * bound
-                b = torch.zeros((H, lora_r)) if lora_init_b_zero else (torch.rand((H, lora_r), generator=g) * 2 - 1) * 0.05
-                add(k + ".lora_A", a)
-                add(k + ".lora_B", b)
+        # LoRA adapters (peft: A ~ kaiming_uniform(a=sqrt(5)), B = 0) on the resolved targets
+        for k, t in init_lora(cfg, self.lora_modules, lora_r, seed, lora_init_b_zero).items():
+            add(k, t)
         # frozen Llama base: resident transposed copies for dX = dY . W
         self.wt = []
         for L in self.base.llm.layers:
@@ -102,13 +147,49 @@ class LisaTrainable:
         return OrderedDict((k, v.detach().clone()) for k, v in self.params.items())
 
     def load_state_dict(self, sd):
+        have = {k for k in self.params if ".lora_" in k}
+        got = {k for k in sd if ".lora_" in k}
+        if have != got:   # a checkpoint of other --lora_target_modules / --lora_r: name the difference, not a bare KeyError
+            missing, extra = sorted(have - got), sorted(got - have)
+            raise ValueError(f"checkpoint LoRA adapters do not match this model's ({len(self.lora_modules)} adapted modules): "
+                             f"missing keys {missing[:4]}{' ...' if len(missing) > 4 else ''} ({len(missing)}), "
+                             f"extra keys {extra[:4]}{' ...' if len(extra) > 4 else ''} ({len(extra)})")
         with torch.no_grad():
             for k, v in sd.items():
                 self.params[k].copy_(v.to(self.params[k].dtype))
 
     # -- Llama with LoRA ---------------------------------------------------------------------------------------------
+    def _lora(self, i, n):
+        """(A, B) of layer i's projection n when it is a LoRA target, else (None, None)."""
+        k = _proj_module(i, n)
+        if k not in self._adapted:
+            return None, None
+        return self.params[k + ".lora_A"], self.params[k + ".lora_B"]
+
+    def _fused_keep(self, h, n, drop):
+        """Dropout masks of the fused nodes as 0 / 1 values (their 1/(1-p) folded into the adapter scale) for n adapters on the
+        input h: None (no dropout), n independent masks from one Bernoulli launch (peft: one lora_dropout module per adapted
+        Linear), or one shared mask (independent_lora_dropout False)."""
+        if drop <= 0:
+            return None
+        k = n if self.independent_lora_dropout else 1
+        masks = torch.empty((k,) + tuple(h.shape), dtype=h.dtype, device=h.device).bernoulli_(1.0 - drop)
+        return tuple(masks[j] for j in range(n)) if k == n and n > 1 else masks[0]
+
+    def _delta(self, x, a, b, drop, shared):
+        """The generic composition of one adapter: s * ((x o keep) A^T) B^T as LinearFn / scale nodes (keep values 0 or 1/(1-p)).
+        shared: a one-element list holding the input's mask when the adapters of one input share it."""
+        xd = x
+        if drop > 0:
+            if not self.independent_lora_dropout and shared:
+                xd = shared[0]
+            else:
+                xd = DropoutMul.apply(x, (torch.rand(x.shape, device=x.device) >= drop).to(x.dtype) / (1 - drop))
+                shared.append(xd)
+        return A.scale(A.linear(A.linear(xd, a), _pad_k(b)), self.lora_scale)
+
     def _llm(self, x, B, T):
-        """x [B*T, H] embeddings -> post-norm hidden [B*T, H] (LlamaModel.forward with peft LoRA on q/v)."""
+        """x [B*T, H] embeddings -> post-norm hidden [B*T, H] (LlamaModel.forward with peft LoRA on the target projections)."""
         l = self.cfg.llm
         llm = self.base.llm
         H, nh, hd = l.hidden, l.heads, llm.hd
@@ -123,7 +204,10 @@ class LisaTrainable:
                 h = A.rmsnorm(x, L["n1"], l.rms_eps)
             pre = f"model.layers.{i}.self_attn."
             drop = self.lora_dropout if self.training else 0.0
-            if A.FUSED_LORA_QKV and A.lora_qkv_rope_supported(h, L["wqkv"], P[pre + "q_proj.lora_A"], nh):
+            (aq, bq), (ak, bk), (av, bv) = self._lora(i, "q_proj"), self._lora(i, "k_proj"), self._lora(i, "v_proj")
+            a_any = next((t for t in (aq, av, ak) if t is not None), None)
+            qv_only = aq is not None and av is not None and ak is None
+            if qv_only and A.FUSED_LORA_QKV and A.lora_qkv_rope_supported(h, L["wqkv"], P[pre + "q_proj.lora_A"], nh):
                 # one node: q|k|v product, both rank-r updates, RoPE (csrc/lora.hip); the dropout mask as 0 / 1 values from one
                 # Bernoulli launch, its 1/(1-p) folded into the adapter scale
                 keep = None
@@ -134,29 +218,56 @@ class LisaTrainable:
                 q, k, v = A.lora_qkv_rope(h, L["wqkv"], wt["wqkv"], P[pre + "q_proj.lora_A"], P[pre + "q_proj.lora_B"],
                                           P[pre + "v_proj.lora_A"], P[pre + "v_proj.lora_B"], cs, T, nh,
                                           self.lora_scale / (1.0 - drop), keep)
+            elif a_any is not None and A.FUSED_LORA_QKV and A.lora_qkv_rope_supported(h, L["wqkv"], a_any, nh):
+                # any other q / k / v subset: the three-adapter node (rank rows q 0-7, v 8-15, k 16-23; absent adapters zero)
+                q, k, v = A.lora_qkv3_rope(h, L["wqkv"], wt["wqkv"], aq, bq, av, bv, ak, bk, cs, T, nh,
+                                           self.lora_scale / (1.0 - drop), self._fused_keep(h, 3, drop))
             else:
                 qkv = A.linear(h, L["wqkv"], None, None, wt["wqkv"])
-                hl = hv = h
-                if drop > 0:
-                    draw = lambda: (torch.rand(h.shape, device=h.device) >= drop).to(h.dtype) / (1 - drop)   # noqa: E731
-                    hl = DropoutMul.apply(h, draw())
-                    hv = DropoutMul.apply(h, draw()) if self.independent_lora_dropout else hl
-                dq = A.linear(A.linear(hl, P[pre + "q_proj.lora_A"]), _pad_k(P[pre + "q_proj.lora_B"]))
-                dv = A.linear(A.linear(hv, P[pre + "v_proj.lora_A"]), _pad_k(P[pre + "v_proj.lora_B"]))
-                q = A.add(qkv[:, :H], A.scale(dq, self.lora_scale))
-                k = qkv[:, H:2 * H]
-                v = A.add(qkv[:, 2 * H:], A.scale(dv, self.lora_scale))
+                q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
+                shared = []
+                if aq is not None:
+                    q = A.add(q, self._delta(h, aq, bq, drop, shared))
+                if av is not None:
+                    v = A.add(v, self._delta(h, av, bv, drop, shared))
+                if ak is not None:
+                    k = A.add(k, self._delta(h, ak, bk, drop, shared))
+                if av is None:
+                    v = v.contiguous()
                 q = A.rope(q, cs, T, nh, hd)
                 k = A.rope(k, cs, T, nh, hd)
             a = A.attention(q.view(B, T, H), k.view(B, T, H), v.view(B, T, H), nh, hd ** -0.5, True)
-            x = A.linear(a.view(B * T, H), L["wo"], None, x, wt["wo"])
+            x = self._adapted_out(a.view(B * T, H), L["wo"], wt["wo"], x, self._lora(i, "o_proj"), drop)
             if A.FUSED_RESID_NORM:
                 x, h = A.resid_rmsnorm(x, L["n2"], l.rms_eps)
             else:
                 h = A.rmsnorm(x, L["n2"], l.rms_eps)
-            gu = A.linear(h, L["wgu"], None, None, wt["wgu"])
-            x = A.linear(A.swiglu(gu), L["wd"], None, x, wt["wd"])
+            (ag, bg), (au, bu) = self._lora(i, "gate_proj"), self._lora(i, "up_proj")
+            a_gu = ag if ag is not None else au
+            if a_gu is None:
+                y = A.swiglu(A.linear(h, L["wgu"], None, None, wt["wgu"]))
+            elif A.FUSED_LORA_GATE_UP and A.lora_fused_supported(h, L["wgu"], a_gu):
+                y = A.lora_gate_up_swiglu(h, L["wgu"], wt["wgu"], ag, bg, au, bu, self.lora_scale / (1.0 - drop),
+                                          self._fused_keep(h, 2, drop))
+            else:   # the updates added into gu in its interleaved [gate x16 | up x16] layout, then SwiGLU
+                gu = A.linear(h, L["wgu"], None, None, wt["wgu"])
+                M, F = h.shape[0], gu.shape[1] // 2
+                shared = []
+                dg = self._delta(h, ag, bg, drop, shared) if ag is not None else torch.zeros((M, F), dtype=gu.dtype, device=gu.device)
+                du = self._delta(h, au, bu, drop, shared) if au is not None else torch.zeros((M, F), dtype=gu.dtype, device=gu.device)
+                d = torch.cat([dg.view(M, F // 16, 1, 16), du.view(M, F // 16, 1, 16)], dim=2).reshape(M, 2 * F)
+                y = A.swiglu(A.add(gu, d))
+            x = self._adapted_out(y, L["wd"], wt["wd"], x, self._lora(i, "down_proj"), drop)
         return A.rmsnorm(x, llm.norm, l.rms_eps)
+
+    def _adapted_out(self, a, w, w_t, resid, lora, drop):
+        """resid + a W^T (+ the adapter's update when the projection is a target): o_proj and down_proj."""
+        la, lb = lora
+        if la is None:
+            return A.linear(a, w, None, resid, w_t)
+        if A.FUSED_LORA_OUT and A.lora_fused_supported(a, w, la):
+            return A.lora_linear(a, w, w_t, resid, la, lb, self.lora_scale / (1.0 - drop), self._fused_keep(a, 1, drop))
+        return A.add(A.linear(a, w, None, resid, w_t), self._delta(a, la, lb, drop, []))
 
     # -- one mask decoder (MaskDecoder.predict_masks, mask_decoder.py:122-170; TwoWayTransformer, transformer.py) -------
     def _attn(self, pfx, q_in, k_in, v_in, Pn, nq, nk, heads=8):

@@ -342,6 +342,32 @@ int haff_lora_dx2_f16(const void* dtT, long ldt, const void* A2, long lda, const
                       long ldx, int accumulate, long M, int K, float scale, void* stream);
 int haff_lora_tn_f16(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace,
                      long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale, void* stream);
+/* LoRA on every Llama projection (--lora_target_modules). Rank <= 8 per adapter, B operands [rows][8] (unused rank columns zero).
+ * haff_lora_qkv3_rope_fwd: haff_lora_qkv_rope_fwd with a k adapter: tT [24][ldt], rows 16..23 the k adapter's ranks;
+ *                          k_out = rope(qkv[:, H:2H] + scale * t_k.Bk^T).
+ * haff_lora_dx3:           dx (+)= scale * sum over the three adapters of keep_a o (dt_a . A_a), dtT / A3 [24][.] in the same
+ *                          order (q, v, k); masks: none, keep_q alone (one mask for all three), or all three.
+ * haff_lora_out:           y [M][N] += scale * t.B^T, tT [8][ldt] (ldt % 4 == 0, ldt >= roundup(M, 4), padding finite), B [N][8]:
+ *                          an adapted Linear's update on the frozen product's output (o_proj / down_proj, residual included).
+ * haff_lora_gu_swiglu:     gu [M][2F] (interleaved [gate x16 | up x16]) += scale * update IN PLACE, the gate columns from
+ *                          t^T rows 0..7 and Bg [F][8], the up columns from rows 8..15 and Bu [F][8]; y [M][F] = silu(g') * u'
+ *                          of the stored (rounded) g', u'. */
+int haff_lora_qkv3_rope_fwd(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, const void* Bk,
+                            int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int d,
+                            int T, float scale, void* stream);
+int haff_lora_dx3(const void* dtT, long ldt, const void* A3, long lda, const void* keep_q, const void* keep_v, const void* keep_k,
+                  long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream);
+int haff_lora_out(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream);
+int haff_lora_gu_swiglu(const void* tT, long ldt, const void* Bg, const void* Bu, void* gu, long ldg, void* y, long ldy, long M,
+                        int F, float scale, void* stream);
+int haff_lora_qkv3_rope_fwd_f16(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
+                                const void* Bk, int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo,
+                                long M, int H, int d, int T, float scale, void* stream);
+int haff_lora_dx3_f16(const void* dtT, long ldt, const void* A3, long lda, const void* keep_q, const void* keep_v,
+                      const void* keep_k, long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream);
+int haff_lora_out_f16(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream);
+int haff_lora_gu_swiglu_f16(const void* tT, long ldt, const void* Bg, const void* Bu, void* gu, long ldg, void* y, long ldy,
+                            long M, int F, float scale, void* stream);
 
 /* fused SAM WINDOW attention with the decomposed rel-pos bias computed in the kernel (one pass over HBM; replaces
  * haff_relpos_tables_bf16 + haff_attention_bf16 for the 28 windowed ViT-H blocks): Attention.forward
