@@ -932,6 +932,45 @@ def gate_threshold_masks(x, logit_ths, on_value=255, taxonomy=None, blank_class=
     return buf[:, :total].reshape((n_th,) + tuple(x.shape))
 
 
+def robot_heatmap(logits, jet):
+    """fp32 [n, H, W] mask logits -> uint8 [n, H, W, 3] RGB: robot_demo.py's create_heatmap per plane (min-max to 0..255, truncate,
+    JET through the device table jet uint8 [256, 3], the bit-exact 5x5 sigma-1 Gaussian blur)."""
+    lib = load_library()
+    _req(logits, "logits")
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 3
+    assert jet.dtype == torch.uint8 and jet.is_cuda and jet.shape == (256, 3) and jet.is_contiguous()
+    n, H, W = logits.shape
+    ws = torch.empty((n * 512,), dtype=torch.float32, device=logits.device)
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=logits.device)
+    rc = lib.haff_robot_heatmap(logits.data_ptr(), n, H, W, jet.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream())
+    check(rc, "haff_robot_heatmap")
+    return out
+
+
+def robot_mask(logits, th, margins, mask=None, on_value=255, out=None):
+    """fp32 [H0, W0] -> uint8 [H0 + top + bottom, W0 + left + right]: (logits > th) pasted at (left, top), ANDed with the lowest bit
+    of mask (uint8 of the padded size, or None), times on_value. margins = (left, top, right, bottom); a mask of another size is
+    refused by the library, as cv2.bitwise_and raises. out: a contiguous uint8 plane of the padded size to write into."""
+    lib = load_library()
+    _req(logits, "logits")
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+    left, top, right, bottom = (int(v) for v in margins)
+    H0, W0 = logits.shape
+    mh = mw = 0
+    if mask is not None:
+        _req(mask, "mask")
+        assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 2
+        mh, mw = mask.shape
+    shape = (max(H0 + top + bottom, 0), max(W0 + left + right, 0))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=logits.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape and out.device == logits.device
+    rc = lib.haff_robot_mask(logits.data_ptr(), H0, W0, left, top, right, bottom, float(th), _p(mask), mh, mw, int(on_value),
+                             out.data_ptr(), _stream())
+    check(rc, "haff_robot_mask")
+    return out
+
+
 def resample_u8(frames, out_hw, axis, bounds, coeffs):
     """One axis of Pillow's antialiased resampling on uint8 NHWC frames [B,H,W,3]; bounds/coeffs = device int32 tables."""
     lib = load_library()

@@ -80,3 +80,49 @@ def chat_plane(mask_logits, taxonomy, side, on_value=100):
     if k == (1 if side == "left" else 0):
         return torch.zeros(mask_logits.shape[-2:], dtype=torch.uint8, device=mask_logits.device)
     return ops.gate_threshold_masks(mask_logits.contiguous(), [0.0], on_value, None, 1 if side == "left" else 0)[0]
+
+
+# ---- robot_demo.py (2Haff/robot_demo.py:57-73,266-327): the heat map and the padded, ANDed mask of each written hand ----
+
+def _octave_jet(x):
+    """GNU Octave's jet.m at x in [0, 1] (exact fractions): what OpenCV's COLORMAP_JET tabulates (colormap.cpp, class Jet)."""
+    from fractions import Fraction as F
+    r = 4 * x - F(3, 2) if F(3, 8) <= x < F(5, 8) else (1 if F(5, 8) <= x < F(7, 8) else (F(9, 2) - 4 * x if x >= F(7, 8) else 0))
+    g = 4 * x - F(1, 2) if F(1, 8) <= x < F(3, 8) else (1 if F(3, 8) <= x < F(5, 8) else (F(7, 2) - 4 * x if F(5, 8) <= x < F(7, 8) else 0))
+    b = 4 * x + F(1, 2) if x < F(1, 8) else (1 if x < F(3, 8) else (F(5, 2) - 4 * x if x < F(5, 8) else 0))
+    return r, g, b
+
+
+def jet_table():
+    """cv2.COLORMAP_JET as uint8 [256, 3] in RGB order (what cv2.imwrite of applyColorMap's BGR result holds on disk): Octave's jet
+    sampled at i/255, times 255, rounded half to even (convertTo's cvRound). Restated: cv2 is not installed, so the table is not
+    pinned against OpenCV's own float constants."""
+    import numpy as np
+    from fractions import Fraction
+    return np.array([[round(255 * c) for c in _octave_jet(Fraction(i, 255))] for i in range(256)], dtype=np.uint8)
+
+
+_JET_DEVICE = {}
+
+
+def robot_planes(logits, th, margins, and_masks, on_value=255):
+    """The outputs of one robot_demo.py request for the hands it writes, on the device (haff_robot_heatmap, haff_robot_mask).
+    logits fp32 [n, H0, W0]: pred_masks_<hand>[i][0] of each written hand. th: --th, a LOGIT threshold. margins: (left, top, right,
+    bottom). and_masks: n uint8 device tensors [H0 + top + bottom, W0 + left + right], the mask each hand is ANDed with.
+    Returns (heat uint8 [n, H0, W0, 3] RGB = aff_<hand>_heat.png, masks uint8 [n, H1, W1] of 0 / on_value = aff_<hand>.png)."""
+    import math
+    logits = logits.float().contiguous()
+    key = str(logits.device)
+    if key not in _JET_DEVICE:
+        _JET_DEVICE[key] = torch.from_numpy(jet_table()).to(logits.device)
+    heat = ops.robot_heatmap(logits, _JET_DEVICE[key])
+    # `pred_mask[pred_mask > th] = 1; pred_mask[pred_mask <= th] = 0` runs in place (:277-278): for th >= 1 the second line also
+    # clears the ones the first one wrote, so no pixel survives
+    t = float(th) if th < 1 else math.inf
+    n, H0, W0 = logits.shape
+    left, top, right, bottom = margins
+    Ho, Wo = max(H0 + top + bottom, 0), max(W0 + left + right, 0)
+    buf = torch.empty((n, (Ho * Wo + 3) // 4 * 4), dtype=torch.uint8, device=logits.device)   # 4-B aligned planes
+    for k in range(n):
+        ops.robot_mask(logits[k], t, margins, and_masks[k], on_value, out=buf[k, :Ho * Wo].view(Ho, Wo))
+    return heat, buf[:, :Ho * Wo].view(n, Ho, Wo)

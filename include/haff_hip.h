@@ -495,6 +495,19 @@ int haff_threshold_masks(const float* in, void* out, long total, float logit_th,
 int haff_gate_threshold_masks(const float* logits, void* planes, long total, long plane_stride,
                               const float* thresholds_host, int n_th, int on_value, const float* taxonomy, int blank_class,
                               void* stream);
+/* ---- the robot loop's per-request outputs (2Haff/robot_demo.py:57-73,266-327; csrc/robot_post.hip) ----
+ * create_heatmap of n f32 logit planes [n][H][W] (4-B aligned; 16-B aligned with W % 4 == 0 takes the float4 path) -> out u8
+ * [n][H][W][3] in RGB order: min-max normalisation to 0..255 as cv2.normalize (scale and shift in double, fmaf in float),
+ * truncation, JET through jet_rgb (u8 [256][3]), the 5x5 sigma-1 Gaussian blur of OpenCV's bit-exact 8-bit path
+ * (BORDER_REFLECT_101). workspace: workspace_floats >= n * 512 floats of scratch for the per-plane min / max partials (no
+ * atomics: deterministic). */
+int haff_robot_heatmap(const float* logits, int n, int H, int W, const void* jet_rgb, float* workspace, long workspace_floats,
+                       void* out, void* stream);
+/* logits f32 [H0][W0] -> out u8 [H0+top+bottom][W0+left+right] (4-B aligned): (logits > th) pasted at (left, top) (negative
+ * margins crop, as PIL's paste), ANDed with the lowest bit of mask (u8 [mask_h][mask_w], 4-B aligned, or NULL = no AND), times
+ * on_value. -1 when mask's size is not the padded size (cv2.bitwise_and raises) or the padded size is empty. */
+int haff_robot_mask(const float* logits, int H0, int W0, int left, int top, int right, int bottom, float th, const void* mask,
+                    int mask_h, int mask_w, int on_value, void* out, void* stream);
 
 
 /* ==== training path (LoRA fine-tune: train_ds.py:489-622 driving model_forward, LISA.py:175-430) ==================
