@@ -186,7 +186,7 @@ class LisaTrainable:
             else:
                 xd = DropoutMul.apply(x, (torch.rand(x.shape, device=x.device) >= drop).to(x.dtype) / (1 - drop))
                 shared.append(xd)
-        return A.scale(A.linear(A.linear(xd, a), _pad_k(b)), self.lora_scale)
+        return lora_delta(xd, a, b, self.lora_scale)
 
     def _llm(self, x, B, T):
         """x [B*T, H] embeddings -> post-norm hidden [B*T, H] (LlamaModel.forward with peft LoRA on the target projections)."""
@@ -467,6 +467,19 @@ def _pad_k(w):
     if r % 8 == 0:
         return w
     return torch.nn.functional.pad(w, (0, _pad8(r) - r))
+
+
+def _pad_rows(w):
+    """LoRA A is [r, K]: zero rows up to _pad8(r), so that x A^T has the padded B's K columns (the zeros meet zeros)."""
+    r = w.shape[0]
+    if r % 8 == 0:
+        return w
+    return torch.nn.functional.pad(w, (0, 0, 0, _pad8(r) - r))
+
+
+def lora_delta(xd, a, b, scale_):
+    """The generic composition of one adapter on its (dropped) input: scale * (xd A^T) B^T as LinearFn / ScaleFn nodes, any rank."""
+    return A.scale(A.linear(A.linear(xd, _pad_rows(a)), _pad_k(b)), scale_)
 
 
 class DropoutMul(torch.autograd.Function):

@@ -291,6 +291,23 @@ def test_f16_gemm_skinny(dev, M, N, K):
         assert torch.equal(out.cpu(), exact.float().to(out.dtype)), out_f32
 
 
+@pytest.mark.parametrize("M", [8, 16])
+@pytest.mark.parametrize("N", [351, 2808])
+@pytest.mark.parametrize("K", [22016, 27648])
+def test_f16_gemm_skinny_rank_products(dev, M, N, K):
+    """The f16 LoRA nodes' rank products (8 / 16 rank rows over K = 2F at 7B / 13B) into a strided [rows][roundup(N, 16)] view:
+    exact integer operands, so the f16 (and f32) result EQUALS the exact sum rounded once; the pad columns stay untouched."""
+    ops = _ops()
+    a, w = _ints((M, K), 130 + M), _ints((N, K), 131)
+    exact = a @ w.T
+    ld = (N + 15) // 16 * 16
+    for odt in (F16, torch.float32):
+        buf = torch.full((M, ld), 3.0, dtype=odt, device=dev)
+        ops.linear(_h(a, dev), _h(w, dev), out=buf[:, :N])
+        assert torch.equal(buf[:, :N].cpu(), exact.float().to(odt)), odt
+        assert (buf[:, N:] == 3.0).all()
+
+
 @pytest.mark.parametrize("M,N,K", [(64, 22016, 4096), (40, 16384, 4096), (288, 22016, 4096), (100, 2048, 4096)])
 def test_f16_gemm_split_k_swiglu(dev, M, N, K):
     """SwiGLU through the split-K tile path's skinny_reduce_kernel<true> (and the skinny kernel where the shape keeps it):

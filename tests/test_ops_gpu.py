@@ -321,6 +321,33 @@ def test_gemm_skinny(dev, M, N, K):
         _close(got, F.silu(x[:M].float() @ wg.float().T) * (x[:M].float() @ wu.float().T), 1.2e-2, "skinny swiglu")
 
 
+@pytest.mark.parametrize("M", [8, 16])
+@pytest.mark.parametrize("N", [351, 2808])
+@pytest.mark.parametrize("K", [22016, 27648])
+def test_gemm_skinny_rank_products(dev, M, N, K):
+    """The LoRA nodes' rank products on the weight-streaming kernel: 8 / 16 rank rows against M activation rows over K = 2F
+    (gate|up's dt^T = Bblk^T . dgu'^T at 7B / 13B), written into a strided [rows][roundup(N, 16)] view as the nodes do; fp64
+    reference, within one bf16 ulp (f32 out: 1e-6 of the sum of |terms|) plus the fp32 sum's own rounding."""
+    ops = _ops()
+    x = _rand((M, K), dev, torch.bfloat16, 30)
+    w = _rand((N, K), dev, torch.bfloat16, 31)
+    ref = x.double() @ w.double().T
+    mag = x.double().abs() @ w.double().abs().T
+    ld = (N + 15) // 16 * 16
+    for odt in (torch.bfloat16, torch.float32):
+        buf = torch.full((M, ld), 3.0, dtype=odt, device=dev)
+        ops.linear(x, w, out=buf[:, :N])
+        got = buf[:, :N].double()
+        assert torch.isfinite(got).all()
+        if odt == torch.float32:
+            bound = 1e-6 * mag
+        else:
+            bound = torch.pow(2.0, torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126))) - 7) + 1e-6 * mag
+        worst = ((got - ref).abs() / bound).max().item()
+        assert worst <= 1.0, (odt, worst)
+        assert (buf[:, N:] == 3.0).all()   # the pad columns of the strided rows untouched
+
+
 @pytest.mark.parametrize("M,N,K", [(700, 512, 1280), (5, 1003, 256), (16, 320, 1280), (40, 320, 1280), (300, 384, 128), (4096, 2560, 1280)])
 @pytest.mark.parametrize("rms", [False, True])
 def test_gemm_folded_norm(dev, M, N, K, rms):
