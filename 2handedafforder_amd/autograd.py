@@ -176,16 +176,67 @@ def axpby(a, b, alpha, beta):
 TN_WEIGHT_GRADIENTS = True   # False: dW through haff_transpose + the NT product (A/B, tests)
 
 
+class FrozenWeight:
+    """A frozen Linear weight as the nodes below take it in place of the tensors (w, w_t): w() is W [N, K] for the forward product,
+    w_t() is W^T [K, N] (or [K, roundup(N, 8)] with zero pad columns) for dX = dY . W. Here both are resident tensors: the bf16 /
+    fp32 / fp16 trainers, which get back the very tensors they passed in.
+
+    The contract a node keeps, so that Nf4FrozenWeight can stand in: what w() / w_t() return is used AT ONCE, on the stream it was
+    asked for on, and is never put in ctx.save_for_backward. The node keeps the FrozenWeight itself (ctx.frozen) and asks again in
+    backward, immediately before the dX product."""
+
+    def __init__(self, w, w_t=None):
+        self._w, self._wt = w, w_t
+        self.shape, self.dtype, self.device = tuple(w.shape), w.dtype, w.device
+
+    def w(self):
+        return self._w
+
+    def w_t(self):
+        if self._wt is None:
+            self._wt = transpose(self._w, Rp=_pad8(self.shape[0]))[0]
+        return self._wt
+
+
+class Nf4FrozenWeight(FrozenWeight):
+    """A frozen NF4 Linear (quant.Nf4Weight: packed codes + absmax, the only resident form). Every w() / w_t() dequantises into the
+    scratch buffer of its shape — ONE [N, K] and ONE [K, roundup(N, 8)] f16 buffer per distinct projection shape, shared by all
+    layers (scratch: {("w" | "w_t", (N, K)): tensor}). The tensor handed out holds another layer's weights after the next call on
+    the same shape, and the kernels write it through ctypes, behind autograd's version counters: hence FrozenWeight's contract."""
+
+    def __init__(self, q, scratch):
+        self.q, self._scratch = q, scratch
+        self.shape, self.dtype, self.device = tuple(q.shape), torch.float16, q.packed.device
+
+    def w(self):
+        return self.q.dequant(out=self._scratch["w", self.shape])
+
+    def w_t(self):
+        return self.q.dequant_t(out=self._scratch["w_t", self.shape])
+
+
+def frozen(w, w_t=None):
+    """The FrozenWeight of a node's (w, w_t) arguments: w itself when it is one already, else the two resident tensors."""
+    return w if isinstance(w, FrozenWeight) else FrozenWeight(w, w_t)
+
+
 class LinearFn(Function):
-    """y = x @ w.T + bias (+ resid). w_t: optional precomputed w.T (frozen weights keep one resident)."""
+    """y = x @ w.T + bias (+ resid). w_t: optional precomputed w.T (frozen weights keep one resident). w may be a FrozenWeight
+    (the trainer's frozen Llama projections): no dW, W^T from w.w_t() in backward."""
 
     @staticmethod
     def forward(ctx, x, w, bias, resid, w_t):
         x2 = x if x.stride(1) == 1 else x.contiguous()
-        y = ops.linear(x2, w, bias=bias, resid=resid)
-        ctx.save_for_backward(x2, w, w_t if w_t is not None else torch.empty(0, device=x.device))
+        ctx.frozen = w if isinstance(w, FrozenWeight) else None
         ctx.has_bias = bias is not None
         ctx.has_resid = resid is not None
+        if ctx.frozen is not None:
+            y = ops.linear(x2, w.w(), bias=bias, resid=resid)
+            none = torch.empty(0, device=x.device)
+            ctx.save_for_backward(x2, none, none)
+            return y
+        y = ops.linear(x2, w, bias=bias, resid=resid)
+        ctx.save_for_backward(x2, w, w_t if w_t is not None else torch.empty(0, device=x.device))
         return y
 
     @staticmethod
@@ -194,9 +245,11 @@ class LinearFn(Function):
         dy = dy.contiguous()
         dx = dw = db = dres = None
         M, K = x.shape
-        N = w.shape[0]
+        N = w.shape[0] if ctx.frozen is None else ctx.frozen.shape[0]
         if ctx.needs_input_grad[0]:
-            if w_t.numel() == 0:
+            if ctx.frozen is not None:
+                w_t = ctx.frozen.w_t()
+            elif w_t.numel() == 0:
                 w_t = transpose(w, Rp=_pad8(N))[0]  # [K, Np]
             dyk = dy
             if w_t.shape[1] != N:  # K-dim of this product is N: pad dy's columns with zeros
@@ -553,12 +606,13 @@ class LoraQKVRopeFn(Function):
     def forward(ctx, x, wqkv, wqkv_t, aq, bq, av, bv, cos_sin, T, heads, scale_, keep):
         lib = load_library()
         M, K = x.shape
-        H = wqkv.shape[0] // 3
+        fw = ctx.frozen = frozen(wqkv, wqkv_t)
+        H = fw.shape[0] // 3
         d = H // heads
         r = aq.shape[0]
         dev = x.device
         x = x.contiguous()
-        qkv = ops.linear(x, wqkv)
+        qkv = ops.linear(x, fw.w())
         # keep: None, ONE mask for both adapters (rounds 3-4), or a pair (keep_q, keep_v) — peft gives each adapted Linear its own
         # lora_dropout module (train_ds.py:218-230), i.e. q_proj's and v_proj's adapters see independently dropped inputs
         two = isinstance(keep, (tuple, list))
@@ -590,16 +644,16 @@ class LoraQKVRopeFn(Function):
                                          float(scale_), _s()), "haff_lora_qkv_rope_fwd")
         none = torch.empty(0, device=dev)
         if two:
-            ctx.save_for_backward(xd, wqkv_t, a2, b2, tT, cos_sin, keep_q, xdv, keep_v)
+            ctx.save_for_backward(xd, a2, b2, tT, cos_sin, keep_q, xdv, keep_v)
         else:
-            ctx.save_for_backward(xd, wqkv_t, a2, b2, tT, cos_sin, keep if keep is not None else none, none, none)
+            ctx.save_for_backward(xd, a2, b2, tT, cos_sin, keep if keep is not None else none, none, none)
         ctx.cfg = (int(T), heads, float(scale_), r)
         return q, k, v
 
     @staticmethod
     def backward(ctx, dq, dk, dv):
         lib = load_library()
-        xd, wqkv_t, a2, b2, tT, cos_sin, keep, xdv, keep_v = ctx.saved_tensors
+        xd, a2, b2, tT, cos_sin, keep, xdv, keep_v = ctx.saved_tensors
         two = xdv.numel() > 0
         T, heads, scale_, r = ctx.cfg
         M, K = xd.shape
@@ -636,7 +690,7 @@ class LoraQKVRopeFn(Function):
             da2 = tn(dtT, 16, xd, K, torch.empty((16, K), dtype=dt_, device=dev), False, 16)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = ops.linear(dqkv, wqkv_t)
+            dx = ops.linear(dqkv, ctx.frozen.w_t())
             if two:   # dx += s * (keep_q o (dt_q . Aq) + keep_v o (dt_v . Av)) in one pass
                 check(_fn16(lib, "haff_lora_dx2", dt_)(dtT.data_ptr(), Mp, a2.data_ptr(), K, keep.data_ptr(), keep_v.data_ptr(), K, dx.data_ptr(),
                                         dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx2")
@@ -698,11 +752,12 @@ class LoraQKV3RopeFn(Function):
     def forward(ctx, x, wqkv, wqkv_t, aq, bq, av, bv, ak, bk, cos_sin, T, heads, scale_, keep):
         lib = load_library()
         M, K = x.shape
-        H = wqkv.shape[0] // 3
+        fw = ctx.frozen = frozen(wqkv, wqkv_t)
+        H = fw.shape[0] // 3
         d = H // heads
         dev = x.device
         x = x.contiguous()
-        qkv = ops.linear(x, wqkv)
+        qkv = ops.linear(x, fw.w())
         pairs = [(aq, bq), (av, bv), (ak, bk)]                # t^T rank rows 0-7, 8-15, 16-23
         on = [a is not None for a, _ in pairs]
         r = next(a.shape[0] for a, _ in pairs if a is not None)
@@ -730,14 +785,14 @@ class LoraQKV3RopeFn(Function):
                                                              k.data_ptr(), v.data_ptr(), H, M, H, d, int(T), float(scale_), _s()),
               "haff_lora_qkv3_rope_fwd")
         none = torch.empty(0, device=dev)
-        ctx.save_for_backward(wqkv_t, a3, b3, tT, cos_sin, *xds, *[none if m is None else m for m in masks])
+        ctx.save_for_backward(a3, b3, tT, cos_sin, *xds, *[none if m is None else m for m in masks])
         ctx.cfg = (int(T), heads, float(scale_), r, on, isinstance(keep, (tuple, list)), keep is not None)
         return q, k, v
 
     @staticmethod
     def backward(ctx, dq, dk, dv):
         lib = load_library()
-        wqkv_t, a3, b3, tT, cos_sin, *rest = ctx.saved_tensors
+        a3, b3, tT, cos_sin, *rest = ctx.saved_tensors
         xds, masks = rest[0:3], rest[3:6]
         T, heads, scale_, r, on, per_adapter, masked = ctx.cfg
         M, K = xds[0].shape
@@ -763,7 +818,7 @@ class LoraQKV3RopeFn(Function):
                                     scale_)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = ops.linear(dqkv, wqkv_t)
+            dx = ops.linear(dqkv, ctx.frozen.w_t())
             kq = masks[0].data_ptr() if masked else 0
             kv = masks[1].data_ptr() if per_adapter else 0
             kk = masks[2].data_ptr() if per_adapter else 0
@@ -798,24 +853,25 @@ class LoraLinearFn(Function):
     def forward(ctx, x, w, w_t, resid, a, b, scale_, keep):
         lib = load_library()
         M, K = x.shape
-        N = w.shape[0]
+        fw = ctx.frozen = frozen(w, w_t)
+        N = fw.shape[0]
         r = a.shape[0]
         x = x.contiguous()
-        y = ops.linear(x, w, resid=resid)
+        y = ops.linear(x, fw.w(), resid=resid)
         xd = x if keep is None else _mul(x, keep)
         a8, b8 = _pad_rank(a, True), _pad_rank(b, False)
         tT = _rank_rows(M, 8, x.dtype, x.device)
         ops.linear(a8, xd, out=tT[:, :M])
         check(_fn16(lib, "haff_lora_out", x.dtype)(tT.data_ptr(), tT.stride(0), b8.data_ptr(), y.data_ptr(), y.stride(0), M, N,
                                                    float(scale_), _s()), "haff_lora_out")
-        ctx.save_for_backward(xd, w_t, a8, b8, tT, keep if keep is not None else torch.empty(0, device=x.device))
+        ctx.save_for_backward(xd, a8, b8, tT, keep if keep is not None else torch.empty(0, device=x.device))
         ctx.cfg = (float(scale_), r, resid is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = load_library()
-        xd, w_t, a8, b8, tT, keep = ctx.saved_tensors
+        xd, a8, b8, tT, keep = ctx.saved_tensors
         scale_, r, has_resid = ctx.cfg
         M, K = xd.shape
         N = b8.shape[0]
@@ -828,7 +884,7 @@ class LoraLinearFn(Function):
         da = _lora_tn(lib, dt_, dtT[0:8], 8, xd, M, K, torch.empty((r, K), dtype=dt_, device=dev), False, r, scale_)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = ops.linear(dy, w_t)
+            dx = ops.linear(dy, ctx.frozen.w_t())
             a16 = torch.cat([a8, torch.zeros_like(a8)], 0)
             check(_fn16(lib, "haff_lora_dx", dt_)(dtT.data_ptr(), dtT.stride(0), a16.data_ptr(), K, keep.data_ptr() if keep.numel() else 0, K,
                                                   dx.data_ptr(), dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx")
@@ -848,10 +904,11 @@ class LoraGateUpSwigluFn(Function):
     def forward(ctx, x, wgu, wgu_t, ag, bg, au, bu, scale_, keep):
         lib = load_library()
         M, K = x.shape
-        F = wgu.shape[0] // 2
+        fw = ctx.frozen = frozen(wgu, wgu_t)
+        F = fw.shape[0] // 2
         dev = x.device
         x = x.contiguous()
-        gu = ops.linear(x, wgu)
+        gu = ops.linear(x, fw.w())
         on = [ag is not None, au is not None]
         r = ag.shape[0] if on[0] else au.shape[0]
         a2 = torch.zeros((16, K), dtype=x.dtype, device=dev)
@@ -880,14 +937,14 @@ class LoraGateUpSwigluFn(Function):
                                                          gu.stride(0), y.data_ptr(), F, M, F, float(scale_), _s()), "haff_lora_gu_swiglu")
         masks = _masks(keep, 2)
         none = torch.empty(0, device=dev)
-        ctx.save_for_backward(gu, wgu_t, a2, bgp, bup, tT, xds[0], xds[1], *[none if m is None else m for m in masks])
+        ctx.save_for_backward(gu, a2, bgp, bup, tT, xds[0], xds[1], *[none if m is None else m for m in masks])
         ctx.cfg = (float(scale_), r, on, isinstance(keep, (tuple, list)), keep is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = load_library()
-        gu, wgu_t, a2, bgp, bup, tT, xg, xu, kg, ku = ctx.saved_tensors
+        gu, a2, bgp, bup, tT, xg, xu, kg, ku = ctx.saved_tensors
         scale_, r, on, per_adapter, masked = ctx.cfg
         M, K = xg.shape
         F = bgp.shape[0]
@@ -913,7 +970,7 @@ class LoraGateUpSwigluFn(Function):
             dau = _lora_tn(lib, dt_, dtT[8:16], 8, xu, M, K, torch.empty((r, K), dtype=dt_, device=dev), False, r, scale_)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = ops.linear(dgu, wgu_t)
+            dx = ops.linear(dgu, ctx.frozen.w_t())
             if per_adapter:
                 check(_fn16(lib, "haff_lora_dx2", dt_)(dtT.data_ptr(), dtT.stride(0), a2.data_ptr(), K, kg.data_ptr(), ku.data_ptr(), K,
                                                        dx.data_ptr(), dx.stride(0), 1, M, K, scale_, _s()), "haff_lora_dx2")

@@ -1,5 +1,6 @@
 // NF4 (4-bit NormalFloat) language-model weights for the fp16 inference mode: load-time quantisation, dequantisation and the
-// weight-streaming product of decode-sized M on the packed weights.
+// weight-streaming product of decode-sized M on the packed weights; and for NF4 fine-tuning (QLoRA), whose frozen products
+// dequantise row-major for the forward and TRANSPOSED (nf4_dequant_t_kernel) for the dX products.
 //
 // The format is the one bitsandbytes' `load_in_4bit=True, bnb_4bit_quant_type="nf4", bnb_4bit_use_double_quant=True` gives the
 // reference (2Haff/inference.py:133-146), restated in 2handedafforder_amd/quant.py, stored ROW-LOCAL so that row reorders of a
@@ -171,6 +172,93 @@ __global__ __launch_bounds__(256) void nf4_dequant_kernel(const unsigned char* _
   store8(reinterpret_cast<f16_t*>(out) + dst * ldo + 8 * g, v);
 }
 
+typedef float nf4_f2 __attribute__((ext_vector_type(2)));
+
+// The transposed dequantisation (NF4 fine-tuning: the f16 W^T of a dX product, written straight from the codes):
+//   out_t[k][map[n]] = f16_rn(NF4[code(n, k)] * absmax(n, k / 64)),   columns N .. roundup(N, 8) - 1 zero.
+// Pure data movement: N K / 2 code bytes and N K / 64 floats in, 2 K Np bytes out; the bound is HBM.
+// One workgroup = 64 stored rows x 256 k through a [256 k][64 n] f16 LDS image (32 KiB).
+//   fill: lane (row l / 8, piece l % 8) reads 16 B of codes (32 k of one row; 8 lanes = 128 contiguous bytes of the row) and the
+//     block absmax, looks each byte up in the LDS table of {NF4[hi], NF4[lo]} pairs, and writes 32 f16 down a column of the
+//     image. Piece p lands in image rows 32 p .. 32 p + 31 with its columns ROTATED by 8 p: at one step the wave's 64 lanes
+//     (8 rows x 8 pieces) then touch all 32 LDS banks instead of the four an unrotated 128-B image row would give them.
+//   drain: lane (k row l / 8, chunk l % 8) reads 8 consecutive columns (one ds_read_b128, the rotation keeps 8-column chunks
+//     whole) and stores 16 B; 8 lanes = 128 contiguous bytes of an output row.
+// A row_map is honoured per 8-column chunk: a chunk whose 8 stored rows go to 8 consecutive, 8-aligned columns (every chunk of
+// the RoPE permutation and of the [gate x16 | up x16] interleave) keeps its 16-B store; any other chunk stores element by element.
+constexpr int kT_N = 64, kT_K = 256;
+
+__global__ __launch_bounds__(256) void nf4_dequant_t_kernel(const unsigned char* __restrict__ packed, const float* __restrict__ absmax,
+                                                            int N, int K, const int* __restrict__ row_map, f16_t* out, long ldo) {
+  __shared__ __attribute__((aligned(16))) f16_t tile[kT_K * kT_N];
+  __shared__ nf4_f2 tab[256];
+  const int tid = threadIdx.x;
+  tab[tid] = nf4_f2{kNF4[tid >> 4], kNF4[tid & 15]};
+  const int k0 = blockIdx.x * kT_K, n0 = blockIdx.y * kT_N;
+  const int Np = (N + 7) & ~7;
+  __syncthreads();
+  {
+    const int p = tid & 7;                 // 32 k of the tile
+    const int kp = k0 + 32 * p;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int nl = (tid >> 3) + 32 * it;
+      const int n = n0 + nl;
+      if (kp >= K) continue;               // (the drain skips these image rows too)
+      uint4 w = make_uint4(0x77777777u, 0x77777777u, 0x77777777u, 0x77777777u);   // code 7 = 0.0: rows past N fill pad columns
+      float a = 0.f;
+      if (n < N) {
+        w = *reinterpret_cast<const uint4*>(packed + (long)n * (K >> 1) + (kp >> 1));
+        a = absmax[(long)n * (K >> 6) + (kp >> 6)];
+      }
+      const unsigned wd[4] = {w.x, w.y, w.z, w.w};
+      unsigned short* col = reinterpret_cast<unsigned short*>(tile) + (32 * p) * kT_N + ((nl + 8 * p) & (kT_N - 1));
+#pragma unroll
+      for (int b = 0; b < 16; ++b) {       // byte b: codes 2 b (high nibble) and 2 b + 1
+        const nf4_f2 t = tab[(wd[b >> 2] >> (8 * (b & 3))) & 255u];
+        // the product rounded to fp32 FIRST, then to f16 (a scalar (f16)(x * a) compiles to one mixed-precision multiply with a
+        // single rounding: one f16 ulp off wherever the fp32 product lands on an f16 tie)
+        const unsigned pk = pack_f16x2(__fmul_rn(t.x, a), __fmul_rn(t.y, a));
+        col[(2 * b) * kT_N] = (unsigned short)(pk & 0xffffu);
+        col[(2 * b + 1) * kT_N] = (unsigned short)(pk >> 16);
+      }
+    }
+  }
+  __syncthreads();
+  const int ch = tid & 7;
+  const int nc = n0 + 8 * ch;              // first stored row of this lane's chunk
+  if (nc >= Np) return;
+  int m[8];
+  bool whole = true;                       // one 16-B store per k row
+  if (row_map) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = nc + j < N ? row_map[nc + j] : -1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) whole = whole && m[j] == m[0] + j;
+    whole = whole && m[0] >= 0 && (m[0] & 7) == 0;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = nc + j;
+  }
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {         // image rows 32 it + tid / 8: piece it, rotation 8 it
+    const int kl = 32 * it + (tid >> 3);
+    const int k = k0 + kl;
+    if (k >= K) break;
+    const f16x8 v = *reinterpret_cast<const f16x8*>(tile + kl * kT_N + ((8 * ch + 8 * it) & (kT_N - 1)));
+    f16_t* dst = out + (long)k * ldo;
+    if (whole) {
+      *reinterpret_cast<f16x8*>(dst + m[0]) = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (nc + j < N) dst[m[j]] = v[j];
+        else if (nc + j < Np) dst[nc + j] = (f16_t)0.f;
+      }
+    }
+  }
+}
+
 struct Nf4Args {
   const bf16_t* A; long lda;
   const unsigned char* Wq; const float* absmax;
@@ -180,8 +268,6 @@ struct Nf4Args {
   const int* row_map;
   int M, N, K, act, out_f32;
 };
-
-typedef float nf4_f2 __attribute__((ext_vector_type(2)));
 
 // Activation 16-B fragments per 64-block per tile row of 16: two k-steps. Blocks per batch of loads (two register sets).
 template <int MT> constexpr int nf4_batch() { return MT == 1 ? 4 : (MT == 2 ? 2 : 1); }
@@ -379,6 +465,18 @@ extern "C" int haff_nf4_dequant_f16(const void* packed, const float* absmax, int
   const long thr = (long)N * (K >> 3);
   hipLaunchKernelGGL(nf4_dequant_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const unsigned char*>(packed), absmax, N, K, row_map, reinterpret_cast<bf16_t*>(out), ldo);
+  return haff_check_launch();
+}
+
+extern "C" int haff_nf4_dequant_t_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out_t, long ldo,
+                                      void* stream) {
+  if (N <= 0 || K <= 0 || (K & 63) || (ldo & 7) || ldo < ((N + 7) & ~7) || !packed || !absmax || !out_t) return HAFF_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(absmax) & 3) || (reinterpret_cast<uintptr_t>(out_t) & 15) ||
+      (reinterpret_cast<uintptr_t>(row_map) & 3))
+    return HAFF_ERR_BAD_ARG;
+  hipLaunchKernelGGL(nf4_dequant_t_kernel, dim3((unsigned)((K + kT_K - 1) / kT_K), (unsigned)((N + kT_N - 1) / kT_N)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const unsigned char*>(packed), absmax, N, K, row_map,
+                     reinterpret_cast<f16_t*>(out_t), ldo);
   return haff_check_launch();
 }
 

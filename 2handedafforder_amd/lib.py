@@ -49,6 +49,7 @@ _PROTOS = {
                              c_int, c_int, c_long, c_long, c_void_p],
     "haff_nf4_quantize_f16": [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "haff_nf4_dequant_f16": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p],
+    "haff_nf4_dequant_t_f16": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p],
     "haff_gemm_nf4_f16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
                           c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "haff_int8_quantize_weight_f16": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],

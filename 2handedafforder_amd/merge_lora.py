@@ -106,6 +106,9 @@ def main(argv=None):
     base = checkpoint.load_hf_dir(args.version)
     blob = torch.load(args.weight, map_location="cpu", weights_only=False)
     trained = blob["params"] if isinstance(blob, dict) and "params" in blob else blob
+    if isinstance(blob, dict) and blob.get("base_format") == "nf4":
+        print("checkpoint was trained on the NF4 base (--load_in_4bit): merging into the 16-bit weights of --version; the merged "
+              "model is meant to be loaded with load_in_4bit=True")
     if args.vision_pretrained:   # frozen SAM encoder / prompt encoder of the fine-tune run (the decoders come from `trained`)
         for k, v in checkpoint._load_file(args.vision_pretrained).items():
             if not k.startswith("mask_decoder."):

@@ -316,6 +316,26 @@ def nf4_dequant(packed, absmax, row_map=None, out=None):
     return out
 
 
+def nf4_dequant_t(packed, absmax, row_map=None, out=None):
+    """f16 [K, Np] = the TRANSPOSE of nf4_dequant's result (stored row n in column row_map[n], or n), Np = roundup(N, 8), the pad
+    columns zero: the layout autograd.transpose(w, Rp=_pad8(N)) gives a frozen weight's resident W^T (haff_nf4_dequant_t_f16).
+    out: f16 [K, >= Np] with unit inner stride; its columns from Np on are left alone."""
+    lib = load_library()
+    _req(packed, "packed")
+    N, K = packed.shape[0], packed.shape[1] * 2
+    Np = (N + 7) // 8 * 8
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and absmax.dtype == torch.float32 and absmax.is_contiguous()
+    assert absmax.shape == (N, K // 64)
+    if out is None:
+        out = torch.empty((K, Np), dtype=torch.float16, device=packed.device)
+    assert out.dtype == torch.float16 and out.stride(1) == 1 and out.shape[0] == K and out.shape[1] >= Np
+    if row_map is not None:
+        assert row_map.dtype == torch.int32 and row_map.numel() == N
+    check(lib.haff_nf4_dequant_t_f16(packed.data_ptr(), absmax.data_ptr(), N, K, _p(row_map), out.data_ptr(), out.stride(0), _stream()),
+          "haff_nf4_dequant_t_f16")
+    return out
+
+
 def linear_nf4(x, packed, absmax, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, out_dtype=None, swiglu=False):
     """linear() with NF4 weights (haff_gemm_nf4_f16): x f16 [M <= 64, K], packed uint8 [N, K/2], absmax f32 [N, K/64]; same
     epilogue contract as linear()."""

@@ -91,6 +91,10 @@ class Nf4Weight:
     def dequant(self, row_map=None, out=None):
         return ops.nf4_dequant(self.packed, self.absmax, row_map=row_map, out=out)
 
+    def dequant_t(self, row_map=None, out=None):
+        """The transpose of dequant() as f16 [K, roundup(N, 8)] (pad columns zero): W^T of a dX product, written from the codes."""
+        return ops.nf4_dequant_t(self.packed, self.absmax, row_map=row_map, out=out)
+
 
 def quantize(parts, device, double_quant=True):
     """One Nf4Weight from source weights quantised EACH ON ITS OWN (as the reference quantises each Linear): parts = [(w, rows)],

@@ -40,6 +40,9 @@ def parse_args(args):
     p.add_argument("--version", default="liuhaotian/llava-v1.5-13b")
     p.add_argument("--vis_save_path", default="./vis_output", type=str)
     p.add_argument("--precision", default="bf16", type=str, choices=["fp32", "bf16", "fp16"])
+    p.add_argument("--load_in_8bit", action="store_true", default=False)
+    p.add_argument("--load_in_4bit", action="store_true", default=False,
+                   help="QLoRA: train on the frozen NF4 base (the seven Llama projections and mm_projector; needs --precision fp16)")
     p.add_argument("--image_size", default=1024, type=int)
     p.add_argument("--model_max_length", default=575, type=int)
     p.add_argument("--lora_r", default=8, type=int)
@@ -273,6 +276,10 @@ def precision_dtype(precision):
 
 def main(argv):
     args = parse_args(argv)
+    if args.load_in_8bit:
+        raise SystemExit("--load_in_8bit: LLM.int8 is not built for training (inference only; --load_in_4bit trains on the NF4 base)")
+    if args.load_in_4bit and args.precision != "fp16":
+        raise SystemExit(f"--load_in_4bit requires --precision fp16 (NF4 fine-tuning computes in float16), not --precision {args.precision}")
     hprompt.set_default_conversation(args.conv_type)      # train_ds.py:188-190
     rank, world, local_rank = hdist.init_from_env()
     if not torch.cuda.is_available():
@@ -310,7 +317,7 @@ def main(argv):
     model = LisaTrainable(cfg, sd, dtype=dtype, device=device, lora_r=args.lora_r, lora_alpha=args.lora_alpha,
                           lora_dropout=args.lora_dropout, ce_loss_weight=args.ce_loss_weight,
                           dice_loss_weight=args.dice_loss_weight, bce_loss_weight=args.bce_loss_weight, seed=args.seed,
-                          lora_target_modules=args.lora_target_modules)
+                          lora_target_modules=args.lora_target_modules, load_in_4bit=args.load_in_4bit)
     del sd
     n_lora = sum(p.numel() for k, p in model.named_parameters() if "lora_" in k)
     n_train = sum(p.numel() for p in model.parameters())
@@ -327,6 +334,12 @@ def main(argv):
     resume = args.resume or (ckpt_dir if args.auto_resume and os.path.exists(os.path.join(ckpt_dir, "latest.pt")) else "")
     if resume:
         blob = torch.load(os.path.join(resume, "latest.pt"), map_location=device, weights_only=False)
+        # adapters fitted against one base do not continue on the other (a checkpoint from before the field existed: 16-bit base)
+        saved_fmt = blob.get("base_format")
+        if saved_fmt != model.base_format:
+            name = {"nf4": "NF4 (--load_in_4bit)", None: "16-bit"}
+            raise ValueError(f"checkpoint {resume} was trained on the {name.get(saved_fmt, saved_fmt)} base, this run uses the "
+                             f"{name[model.base_format]} base: {'pass' if saved_fmt == 'nf4' else 'drop'} --load_in_4bit to resume it")
         model.load_state_dict(blob["params"])
         for k, st in blob["optim"].items():
             states[k].master.copy_(st["master"]); states[k].m.copy_(st["m"]); states[k].v.copy_(st["v"]); states[k].step = st["step"]
@@ -446,6 +459,7 @@ def main(argv):
             if rank == 0:  # parameters and optimizer state are replicated: rank 0 writes the only copy
                 os.makedirs(ckpt_dir, exist_ok=True)
                 blob = {"params": model.state_dict(), "global_step": global_step, "best_score": best_score, "epoch": epoch,
+                        "base_format": model.base_format,   # "nf4" (--load_in_4bit) or None: the frozen base the adapters were fitted on
                         "optim": {k: {"master": s.master, "m": s.m, "v": s.v, "step": s.step} for k, s in states.items()}}
                 if scaler is not None:
                     blob["loss_scaler"] = scaler.state_dict()

@@ -7,7 +7,9 @@ or with inference=True {pred_masks_left, pred_masks_right, pred_taxonomies, gt_m
 gt_taxonomies}. Trainable set = train_ds.py:192-244: LoRA (r, alpha, dropout) on the Llama projections that
 --lora_target_modules selects (default q_proj, v_proj; lora_targets) + embed_tokens, lm_head, text_hidden_fcs,
 mask_decoder_left/right. SAM encoder, CLIP tower, projector and the Llama base weights are frozen; base weights keep a resident transposed copy for the dX products (288 GB of HBM: +13.5 GB
-for 7B is cheaper than re-transposing, and no activation checkpointing is needed either).
+for 7B is cheaper than re-transposing, and no activation checkpointing is needed either). load_in_4bit=True (QLoRA, fp16 compute)
+keeps the frozen projections as NF4 codes instead and dequantises each one into a shared scratch buffer at every use, forward and
+backward (autograd.Nf4FrozenWeight).
 Every op is an autograd.Function over HIP kernels (autograd.py).
 """
 import math
@@ -57,6 +59,13 @@ def lora_targets(cfg, spec="q_proj,v_proj"):
     return [name for name in proj if any(t in name for t in targets)]
 
 
+def nf4_frozen_linear(name):
+    """True for the weights LisaTrainable(load_in_4bit=True) holds in NF4: quant.nf4_linear's selection minus what the trainer trains
+    in full (lm_head, text_hidden_fcs), i.e. the seven projections of every Llama layer and mm_projector."""
+    from . import quant
+    return quant.nf4_linear(name, lm_head=False) and "text_hidden_fcs" not in name
+
+
 def init_lora(cfg, targets, r, seed=0, init_b_zero=True):
     """Adapter tensors (fp32, CPU) for the modules of lora_targets, as peft initialises them: A [r, in_features] ~
     kaiming_uniform(a=sqrt(5)) = U(-1/sqrt(in_features), 1/sqrt(in_features)), B [out_features, r] = 0. One generator drawn in
@@ -79,12 +88,31 @@ def init_lora(cfg, targets, r, seed=0, init_b_zero=True):
 class LisaTrainable:
     def __init__(self, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", lora_r=8, lora_alpha=16, lora_dropout=0.05,
                  ce_loss_weight=1.0, dice_loss_weight=0.5, bce_loss_weight=2.0, seed=0, lora_init_b_zero=True,
-                 lora_target_modules="q_proj,v_proj"):
+                 lora_target_modules="q_proj,v_proj", load_in_4bit=False, bnb_4bit_use_double_quant=True, bnb_4bit_quant_type="nf4"):
+        # load_in_4bit (the reference's train_ds.py:58 / QLoRA): LoRA on a frozen NF4 base. The seven projections of every Llama
+        # layer and mm_projector are NF4 (quant.nf4_linear's selection minus what this class trains: lm_head, embed_tokens,
+        # text_hidden_fcs and both mask decoders are trained in full and never quantised); compute is fp16, as the 4-bit inference
+        # mode's. Refused combinations are ValueErrors, raised before any device work
+        if load_in_4bit:
+            if dtype != torch.float16:
+                raise ValueError("load_in_4bit: NF4 fine-tuning computes in float16 (bnb_4bit_compute_dtype=torch.float16, --precision "
+                                 f"fp16); pass dtype=torch.float16, not {dtype}")
+            if bnb_4bit_quant_type != "nf4":
+                raise ValueError(f"load_in_4bit: bnb_4bit_quant_type={bnb_4bit_quant_type!r} is not supported (only 'nf4')")
+        self.load_in_4bit = bool(load_in_4bit)
+        self.base_format = "nf4" if self.load_in_4bit else None   # recorded in train_ds.py's latest.pt
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         # bf16: training is bf16 end to end, as the reference's. fp16 (--precision fp16): the frozen CLIP / ViT-H / Llama stacks run
         # on the fp16 inference mode's kernels with its own settings (weights over 65504 refused by name; the ViT-H neck in f32, so
         # the image embedding leaves it in f32); the trainable decoders below run in fp16 on f16_rn of that embedding
-        self.base = LisaMI355(cfg, state_dict, dtype=dtype, device=device, fp32_tail=dtype == torch.float16)
+        if self.load_in_4bit:
+            self.base = LisaMI355(cfg, state_dict, dtype=dtype, device=device, fp32_tail=True, load_in_4bit=True,
+                                  bnb_4bit_use_double_quant=bnb_4bit_use_double_quant, bnb_4bit_quant_type=bnb_4bit_quant_type,
+                                  nf4_lm_head=False)
+            # text_hidden_fcs is trained in full from the ORIGINAL weights (params below): no quantised copy of it is kept
+            self.base.fc0 = self.base.fc2 = None
+        else:
+            self.base = LisaMI355(cfg, state_dict, dtype=dtype, device=device, fp32_tail=dtype == torch.float16)
         # the frozen decoder constants in the trainer's dtype (the bf16 base keeps them in bf16: the same tensors)
         dec = self.base.sam_decoder
         self.key_pe = dec.key_pe if dec.key_pe.dtype == dtype else dec.key_pe.to(dtype).contiguous()
@@ -120,10 +148,24 @@ class LisaTrainable:
         # LoRA adapters (peft: A ~ kaiming_uniform(a=sqrt(5)), B = 0) on the resolved targets
         for k, t in init_lora(cfg, self.lora_modules, lora_r, seed, lora_init_b_zero).items():
             add(k, t)
-        # frozen Llama base: resident transposed copies for dX = dY . W
-        self.wt = []
-        for L in self.base.llm.layers:
-            self.wt.append({n: A.transpose(L[n])[0] for n in ("wqkv", "wo", "wgu", "wd")})
+        # frozen Llama base as A.FrozenWeight objects (what the Linear / LoRA nodes take): resident W and a resident transposed
+        # copy for dX = dY . W ...
+        names = ("wqkv", "wo", "wgu", "wd")
+        self.wt, self.nf4_scratch = [], {}
+        if not self.load_in_4bit:
+            for L in self.base.llm.layers:
+                self.wt.append({n: A.transpose(L[n])[0] for n in names})
+            self.frozen = [{n: A.FrozenWeight(L[n], wt[n]) for n in names} for L, wt in zip(self.base.llm.layers, self.wt)]
+        else:
+            # ... or, on the NF4 base, neither: each use dequantises the packed codes into an f16 scratch buffer, one [N, K] and one
+            # [K, roundup(N, 8)] per distinct projection shape, allocated here once and reused by every layer (A.Nf4FrozenWeight).
+            # The scratch buffers belong to the LLAMA stream only (the stream forward() is called on, which backward runs on too):
+            # the frozen SAM encoder's side stream never touches them, and nothing else may fill or read them on another stream.
+            for shape in sorted({tuple(L[n].shape) for L in self.base.llm.layers for n in names}):
+                N, K = shape
+                self.nf4_scratch["w", shape] = torch.empty((N, K), dtype=torch.float16, device=dev)
+                self.nf4_scratch["w_t", shape] = torch.empty((K, _pad8(N)), dtype=torch.float16, device=dev)
+            self.frozen = [{n: A.Nf4FrozenWeight(L[n], self.nf4_scratch) for n in names} for L in self.base.llm.layers]
 
     # -- parameter plumbing ------------------------------------------------------------------------------------------
     def parameters(self):
@@ -196,7 +238,7 @@ class LisaTrainable:
         cs = llm._cos_sin(T)
         P = self.params
         for i, L in enumerate(llm.layers):
-            wt = self.wt[i]
+            W = self.frozen[i]   # the four frozen products of the layer (resident W / W^T, or NF4 codes + shared scratch)
             # (x, norm(x)) as one node: the adjoint adds the residual branch's gradient of x inside the norm kernel
             if A.FUSED_RESID_NORM:
                 x, h = A.resid_rmsnorm(x, L["n1"], l.rms_eps)
@@ -207,7 +249,7 @@ class LisaTrainable:
             (aq, bq), (ak, bk), (av, bv) = self._lora(i, "q_proj"), self._lora(i, "k_proj"), self._lora(i, "v_proj")
             a_any = next((t for t in (aq, av, ak) if t is not None), None)
             qv_only = aq is not None and av is not None and ak is None
-            if qv_only and A.FUSED_LORA_QKV and A.lora_qkv_rope_supported(h, L["wqkv"], P[pre + "q_proj.lora_A"], nh):
+            if qv_only and A.FUSED_LORA_QKV and A.lora_qkv_rope_supported(h, W["wqkv"], P[pre + "q_proj.lora_A"], nh):
                 # one node: q|k|v product, both rank-r updates, RoPE (csrc/lora.hip); the dropout mask as 0 / 1 values from one
                 # Bernoulli launch, its 1/(1-p) folded into the adapter scale
                 keep = None
@@ -215,15 +257,15 @@ class LisaTrainable:
                     n_masks = 2 if self.independent_lora_dropout else 1   # (one Bernoulli launch either way)
                     masks = torch.empty((n_masks,) + tuple(h.shape), dtype=h.dtype, device=h.device).bernoulli_(1.0 - drop)
                     keep = (masks[0], masks[1]) if n_masks == 2 else masks[0]
-                q, k, v = A.lora_qkv_rope(h, L["wqkv"], wt["wqkv"], P[pre + "q_proj.lora_A"], P[pre + "q_proj.lora_B"],
+                q, k, v = A.lora_qkv_rope(h, W["wqkv"], None, P[pre + "q_proj.lora_A"], P[pre + "q_proj.lora_B"],
                                           P[pre + "v_proj.lora_A"], P[pre + "v_proj.lora_B"], cs, T, nh,
                                           self.lora_scale / (1.0 - drop), keep)
-            elif a_any is not None and A.FUSED_LORA_QKV and A.lora_qkv_rope_supported(h, L["wqkv"], a_any, nh):
+            elif a_any is not None and A.FUSED_LORA_QKV and A.lora_qkv_rope_supported(h, W["wqkv"], a_any, nh):
                 # any other q / k / v subset: the three-adapter node (rank rows q 0-7, v 8-15, k 16-23; absent adapters zero)
-                q, k, v = A.lora_qkv3_rope(h, L["wqkv"], wt["wqkv"], aq, bq, av, bv, ak, bk, cs, T, nh,
+                q, k, v = A.lora_qkv3_rope(h, W["wqkv"], None, aq, bq, av, bv, ak, bk, cs, T, nh,
                                            self.lora_scale / (1.0 - drop), self._fused_keep(h, 3, drop))
             else:
-                qkv = A.linear(h, L["wqkv"], None, None, wt["wqkv"])
+                qkv = A.linear(h, W["wqkv"])
                 q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
                 shared = []
                 if aq is not None:
@@ -237,7 +279,7 @@ class LisaTrainable:
                 q = A.rope(q, cs, T, nh, hd)
                 k = A.rope(k, cs, T, nh, hd)
             a = A.attention(q.view(B, T, H), k.view(B, T, H), v.view(B, T, H), nh, hd ** -0.5, True)
-            x = self._adapted_out(a.view(B * T, H), L["wo"], wt["wo"], x, self._lora(i, "o_proj"), drop)
+            x = self._adapted_out(a.view(B * T, H), W["wo"], x, self._lora(i, "o_proj"), drop)
             if A.FUSED_RESID_NORM:
                 x, h = A.resid_rmsnorm(x, L["n2"], l.rms_eps)
             else:
@@ -245,29 +287,29 @@ class LisaTrainable:
             (ag, bg), (au, bu) = self._lora(i, "gate_proj"), self._lora(i, "up_proj")
             a_gu = ag if ag is not None else au
             if a_gu is None:
-                y = A.swiglu(A.linear(h, L["wgu"], None, None, wt["wgu"]))
-            elif A.FUSED_LORA_GATE_UP and A.lora_fused_supported(h, L["wgu"], a_gu):
-                y = A.lora_gate_up_swiglu(h, L["wgu"], wt["wgu"], ag, bg, au, bu, self.lora_scale / (1.0 - drop),
+                y = A.swiglu(A.linear(h, W["wgu"]))
+            elif A.FUSED_LORA_GATE_UP and A.lora_fused_supported(h, W["wgu"], a_gu):
+                y = A.lora_gate_up_swiglu(h, W["wgu"], None, ag, bg, au, bu, self.lora_scale / (1.0 - drop),
                                           self._fused_keep(h, 2, drop))
             else:   # the updates added into gu in its interleaved [gate x16 | up x16] layout, then SwiGLU
-                gu = A.linear(h, L["wgu"], None, None, wt["wgu"])
+                gu = A.linear(h, W["wgu"])
                 M, F = h.shape[0], gu.shape[1] // 2
                 shared = []
                 dg = self._delta(h, ag, bg, drop, shared) if ag is not None else torch.zeros((M, F), dtype=gu.dtype, device=gu.device)
                 du = self._delta(h, au, bu, drop, shared) if au is not None else torch.zeros((M, F), dtype=gu.dtype, device=gu.device)
                 d = torch.cat([dg.view(M, F // 16, 1, 16), du.view(M, F // 16, 1, 16)], dim=2).reshape(M, 2 * F)
                 y = A.swiglu(A.add(gu, d))
-            x = self._adapted_out(y, L["wd"], wt["wd"], x, self._lora(i, "down_proj"), drop)
+            x = self._adapted_out(y, W["wd"], x, self._lora(i, "down_proj"), drop)
         return A.rmsnorm(x, llm.norm, l.rms_eps)
 
-    def _adapted_out(self, a, w, w_t, resid, lora, drop):
-        """resid + a W^T (+ the adapter's update when the projection is a target): o_proj and down_proj."""
+    def _adapted_out(self, a, w, resid, lora, drop):
+        """resid + a W^T (+ the adapter's update when the projection is a target): o_proj and down_proj. w: an A.FrozenWeight."""
         la, lb = lora
         if la is None:
-            return A.linear(a, w, None, resid, w_t)
+            return A.linear(a, w, None, resid)
         if A.FUSED_LORA_OUT and A.lora_fused_supported(a, w, la):
-            return A.lora_linear(a, w, w_t, resid, la, lb, self.lora_scale / (1.0 - drop), self._fused_keep(a, 1, drop))
-        return A.add(A.linear(a, w, None, resid, w_t), self._delta(a, la, lb, drop, []))
+            return A.lora_linear(a, w, None, resid, la, lb, self.lora_scale / (1.0 - drop), self._fused_keep(a, 1, drop))
+        return A.add(A.linear(a, w, None, resid), self._delta(a, la, lb, drop, []))
 
     # -- one mask decoder (MaskDecoder.predict_masks, mask_decoder.py:122-170; TwoWayTransformer, transformer.py) -------
     def _attn(self, pfx, q_in, k_in, v_in, Pn, nq, nk, heads=8):

@@ -92,6 +92,12 @@ int haff_nf4_quantize_f16(const void* W, long ldw, int N, int K, int double_quan
                           float* offset, void* workspace, long workspace_bytes, void* stream);
 /* f16 out row row_map[n] (NULL: n; row stride ldo, 16-B aligned) = f16_rn(NF4[code] * absmax) of stored row n */
 int haff_nf4_dequant_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out, long ldo, void* stream);
+/* The same values TRANSPOSED, for the dX products of NF4 fine-tuning: f16 out_t[k][row_map[n]] (NULL: n; K rows of stride ldo, 16-B
+ * aligned, ldo % 8 == 0, ldo >= roundup(N, 8)) = f16_rn(NF4[code(n, k)] * absmax(n, k / 64)); columns N .. roundup(N, 8) - 1 are
+ * zero-filled, columns from roundup(N, 8) on are not written. row_map: a permutation of 0 .. N - 1. packed 16-B aligned. K % 64,
+ * ldo, misalignment: -1. */
+int haff_nf4_dequant_t_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out_t, long ldo,
+                           void* stream);
 /* haff_gemm_f16 with NF4 weights for M <= 64 (decode steps, [SEG] rows, lm_head on the last rows): C = epi(A . dequant(W)^T), same
  * epilogue contract (bias, act, resid may alias C, row_map, out_f32, swiglu on [gate x16 | up x16] rows). Weight-streaming kernel,
  * fixed summation order (bitwise repeatable). M > 64: -2; K % 64, lda, misalignment, SwiGLU with N % 32 or resid: -1. */
