@@ -135,9 +135,19 @@ __global__ void rope_cache_kernel(T* qkv, long ld, T* kcache, T* vcache, const f
   }
 }
 
-// First maximum of each row (torch.argmax tie rule). One 1024-thread workgroup per row, 8 independent loads per thread
-// per trip: a 32 003-entry logit row is 4 trips (the 256-thread, one-load-per-trip form spent 38 us per decode step on
-// 125 dependent L2 round trips).
+// torch.argmax's order, shared by the three reduction stages below: a NaN is greater than every number, and among equals
+// (two NaNs are equals) the lower index wins. (best, bi) starts at (-inf, INT_MAX), which every real candidate replaces.
+__device__ __forceinline__ bool argmax_takes(float v, int i, float best, int bi) {
+  const bool gt = !(v <= best) && best == best;            // v > best, or v is the first NaN met
+  const bool eq = v == best || (v != v && best != best);
+  return gt || (eq && i < bi);
+}
+
+// First maximum of each row (torch.argmax: first index on ties, the first NaN when the row holds one). One 1024-thread
+// workgroup per row, 8 independent loads per thread per trip: a 32 003-entry logit row is 4 trips (the 256-thread,
+// one-load-per-trip form spent 38 us per decode step on 125 dependent L2 round trips). The id goes straight into the next
+// embedding gather (haff_decode_book), so it is always in [0, V): thread 0 always takes element 0, which beats the start
+// value, and the final write clamps.
 __global__ __launch_bounds__(1024) void argmax_rows_kernel(const float* x, long ld, long* out, int V) {
   __shared__ float sv[16];
   __shared__ int si[16];
@@ -151,21 +161,21 @@ __global__ __launch_bounds__(1024) void argmax_rows_kernel(const float* x, long 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int i = i0 + j * 1024;
-      if (i < V && (v[j] > best || (v[j] == best && i < bi))) { best = v[j]; bi = i; }
+      if (i < V && argmax_takes(v[j], i, best, bi)) { best = v[j]; bi = i; }
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    if (argmax_takes(ov, oi, best, bi)) { best = ov; bi = oi; }
   }
   if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 16; ++w)
-      if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-    out[blockIdx.x] = bi;
+      if (argmax_takes(sv[w], si[w], best, bi)) { best = sv[w]; bi = si[w]; }
+    out[blockIdx.x] = (unsigned)bi < (unsigned)V ? bi : 0;
   }
 }
 
@@ -238,7 +248,8 @@ inline int grid_for(long total, int block) {
 
 #define HAFF_STREAM(s) reinterpret_cast<hipStream_t>(s)
 
-// in_dtype/out_dtype: 0 = bf16, 1 = f32, 3 = f16 (dtype codes of include/haff_hip.h; below, too)
+// in_dtype/out_dtype: 0 = bf16, 1 = f32, 3 = f16 (dtype codes of include/haff_hip.h; below, too). Any other code is refused
+// with HAFF_ERR_BAD_ARG: no entry point treats "anything else" as f32.
 extern "C" int haff_patchify_nchw(const void* x, void* out, int B, int Cin, int Hin, int Win, int P, int gh, int gw,
                                   int Kp, int in_dtype, int out_dtype, void* stream) {
   if (B <= 0 || P <= 0 || gh * P > Hin || gw * P > Win || Kp < Cin * P * P) return HAFF_ERR_BAD_ARG;
@@ -273,9 +284,10 @@ extern "C" int haff_patchify_u8(const void* frames, void* out, int B, int Hf, in
   else if (out_dtype == 3)
     hipLaunchKernelGGL((patchify_u8_kernel<f16_t>), g, b, 0, s, (const unsigned char*)frames, (f16_t*)out, B, Hf, Wf, P, gh, gw, Kp,
                        mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  else
+  else if (out_dtype == 1)
     hipLaunchKernelGGL((patchify_u8_kernel<float>), g, b, 0, s, (const unsigned char*)frames, (float*)out, B, Hf, Wf, P, gh, gw, Kp,
                        mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
 
@@ -285,7 +297,8 @@ extern "C" int haff_im2col3x3(const void* x, void* out, int B, int H, int W, int
   dim3 g(grid_for(total, 256)), b(256);
   if (dtype == 0) hipLaunchKernelGGL((im2col3x3_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (const bf16_t*)x, (bf16_t*)out, B, H, W, C);
   else if (dtype == 3) hipLaunchKernelGGL((im2col3x3_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (const f16_t*)x, (f16_t*)out, B, H, W, C);
-  else hipLaunchKernelGGL((im2col3x3_kernel<float>), g, b, 0, HAFF_STREAM(stream), (const float*)x, (float*)out, B, H, W, C);
+  else if (dtype == 1) hipLaunchKernelGGL((im2col3x3_kernel<float>), g, b, 0, HAFF_STREAM(stream), (const float*)x, (float*)out, B, H, W, C);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
 
@@ -295,7 +308,8 @@ extern "C" int haff_embed_splice(const long* ids, const int* img_pos, const void
   dim3 g(B * (L + n_img - 1)), b(128);
   if (dtype == 0) hipLaunchKernelGGL((embed_splice_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const bf16_t*)embed, (const bf16_t*)img, (bf16_t*)out, L, n_img, Hd);
   else if (dtype == 3) hipLaunchKernelGGL((embed_splice_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const f16_t*)embed, (const f16_t*)img, (f16_t*)out, L, n_img, Hd);
-  else hipLaunchKernelGGL((embed_splice_kernel<float>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const float*)embed, (const float*)img, (float*)out, L, n_img, Hd);
+  else if (dtype == 1) hipLaunchKernelGGL((embed_splice_kernel<float>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const float*)embed, (const float*)img, (float*)out, L, n_img, Hd);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
 
@@ -306,7 +320,8 @@ extern "C" int haff_rope_cache(void* qkv, long ld, void* kcache, void* vcache, c
   dim3 g(grid_for(total, 256)), b(256);
   if (dtype == 0) hipLaunchKernelGGL((rope_cache_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (bf16_t*)qkv, ld, (bf16_t*)kcache, (bf16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
   else if (dtype == 3) hipLaunchKernelGGL((rope_cache_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (f16_t*)qkv, ld, (f16_t*)kcache, (f16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
-  else hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
+  else if (dtype == 1) hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
 
@@ -319,7 +334,8 @@ extern "C" int haff_rope_cache_rows(void* qkv, long ld, void* kcache, void* vcac
   dim3 g(grid_for(total, 256)), b(256);
   if (dtype == 0) hipLaunchKernelGGL((rope_cache_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (bf16_t*)qkv, ld, (bf16_t*)kcache, (bf16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
   else if (dtype == 3) hipLaunchKernelGGL((rope_cache_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (f16_t*)qkv, ld, (f16_t*)kcache, (f16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
-  else hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
+  else if (dtype == 1) hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
 
@@ -353,7 +369,8 @@ extern "C" int haff_add_bcast(const void* a, const void* b, void* out, long rows
   dim3 g(grid_for(rows * (C / 8), 256)), blk(256);
   if (dtype == 0) hipLaunchKernelGGL((add_bcast_kernel<bf16_t>), g, blk, 0, HAFF_STREAM(stream), (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, rows, C, mod);
   else if (dtype == 3) hipLaunchKernelGGL((add_bcast_kernel<f16_t>), g, blk, 0, HAFF_STREAM(stream), (const f16_t*)a, (const f16_t*)b, (f16_t*)out, rows, C, mod);
-  else hipLaunchKernelGGL((add_bcast_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)a, (const float*)b, (float*)out, rows, C, mod);
+  else if (dtype == 1) hipLaunchKernelGGL((add_bcast_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)a, (const float*)b, (float*)out, rows, C, mod);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
 
@@ -362,6 +379,7 @@ extern "C" int haff_softmax_rows(const void* x, float* out, int rows, int C, int
   dim3 g((rows + 63) / 64), blk(64);
   if (dtype == 0) hipLaunchKernelGGL((softmax_rows_kernel<bf16_t>), g, blk, 0, HAFF_STREAM(stream), (const bf16_t*)x, out, rows, C);
   else if (dtype == 3) hipLaunchKernelGGL((softmax_rows_kernel<f16_t>), g, blk, 0, HAFF_STREAM(stream), (const f16_t*)x, out, rows, C);
-  else hipLaunchKernelGGL((softmax_rows_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)x, out, rows, C);
+  else if (dtype == 1) hipLaunchKernelGGL((softmax_rows_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)x, out, rows, C);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }

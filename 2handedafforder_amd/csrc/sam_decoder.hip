@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void gate_threshold_kernel(GateArgs p) {
 
 }  // namespace
 
-// up1: [n_prompts*h*w][4*64] (dtype 0 bf16 / 1 f32), columns (dy*2+dx)*64+co, bias already added.
+// up1: [n_prompts*h*w][4*64] (dtype 0 bf16 / 1 f32 / 3 f16, any other code is refused), columns (dy*2+dx)*64+co, bias already added.
 // w2: fp32 [64][4*32] with column (dy2*2+dx2)*32+c2; b2 fp32 [32]; hyper fp32 [n_prompts][32];
 // out: fp32 [n_prompts][4h][4w] low-res mask logits.
 extern "C" int haff_upscale_mask(const void* up1, const float* ln_w, const float* ln_b, const float* w2,
@@ -165,7 +165,9 @@ extern "C" int haff_upscale_mask(const void* up1, const float* ln_w, const float
   dim3 g((unsigned)((total + 255) / 256)), b(256);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dtype == 0) hipLaunchKernelGGL((upscale_mask_kernel<bf16_t>), g, b, 0, s, (const bf16_t*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps);
-  else hipLaunchKernelGGL((upscale_mask_kernel<float>), g, b, 0, s, (const float*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps);
+  else if (dtype == 3) hipLaunchKernelGGL((upscale_mask_kernel<f16_t>), g, b, 0, s, (const f16_t*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps);
+  else if (dtype == 1) hipLaunchKernelGGL((upscale_mask_kernel<float>), g, b, 0, s, (const float*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps);
+  else return HAFF_ERR_BAD_ARG;
   return haff_check_launch();
 }
 

@@ -16,7 +16,8 @@
  *     fp32 accumulate, fp32 softmax/norm statistics); f32 = parity mode (every op in fp32, for the 1e-3 mask-logit criterion);
  *     f16 = the inference mode of the reference's `--precision fp16` (f16 MFMA, otherwise as bf16). Code 2 is the norms'
  *     "f32 x -> bf16 y". Entry points named *_bf16 take no dtype; those the fp16 path needs have *_f16 siblings with the
- *     same arguments and contracts (one kernel template, two instances).
+ *     same arguments and contracts (one kernel template, two instances). The data-movement entry points and
+ *     haff_upscale_mask return -1 for a code (or an in/out pair) they have no kernel for: none falls through to f32.
  *   - strides/leading dimensions are in ELEMENTS.
  *   - activation codes: 0 none, 1 GELU(erf), 2 quick-GELU (x*sigmoid(1.702x)), 3 ReLU, 4 SiLU.
  */
@@ -450,7 +451,8 @@ int haff_rope_cache(void* qkv, long ld, void* kcache, void* vcache, const float*
  * pos0_rows[b] + Tq <= Tmax is the caller's contract) — greedy decode of right-padded prompts of different lengths */
 int haff_rope_cache_rows(void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, int B, int Tq, int Hq,
                          int Hkv, int d, const int* pos0_rows, int Tmax, int dtype, void* stream);
-/* greedy token: first index of the row maximum (generate(num_beams=1), LISA.py:443-450) */
+/* greedy token: first index of the row maximum (generate(num_beams=1), LISA.py:443-450), in torch.argmax's order: a NaN
+ * is greater than every number, so a row that holds NaNs gives the index of its first NaN. out[r] is always in [0, V). */
 int haff_argmax_rows(const float* x, long ld, long* out, int rows, int V, void* stream);
 /* One generated token per row of the greedy decode loop, on the device (replaces the per-step host bookkeeping of
  * transformers' generate as used by LISA.py:443-450; sits inside the decode hipGraph). Row b, step s = steps[b]:
@@ -470,7 +472,7 @@ int haff_softmax_rows(const void* x, float* out, int rows, int C, int dtype, voi
  * haff_upscale_mask: LayerNorm2d(64) -> GELU -> ConvTranspose2d(64->32,k2,s2) -> GELU -> dot with the hypernetwork
  * vector of mask token 0 (mask_decoder.py:58-64,153-165,110-114). up1 [n*h*w][4*64] = output of the first
  * transposed conv as GEMM, columns (dy*2+dx)*64+co; w2 f32 [64][4*32] column (dy2*2+dx2)*32+c2; hyper f32 [n][32];
- * out f32 [n][4h][4w]. */
+ * out f32 [n][4h][4w]. dtype (of up1): 0 bf16, 1 f32, 3 f16. */
 int haff_upscale_mask(const void* up1, const float* ln_w, const float* ln_b, const float* w2, const float* b2,
                       const float* hyper, float* out, int n_prompts, int h, int w, float eps, int dtype, void* stream);
 /* F.interpolate(bilinear, align_corners=False) of the top-left [Hc][Wc] crop of in [N][Hs][Ws] -> out [N][Ho][Wo]
