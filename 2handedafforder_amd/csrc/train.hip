@@ -69,7 +69,9 @@ __global__ void swiglu_fwd_kernel(const T* gu, T* y, long M, int F) {
     const int j = (int)(i - m * F);
     const long base = m * 2 * F + (j >> 4) * 32 + (j & 15);
     const float g = elem<T>::ld(gu + base), u = elem<T>::ld(gu + base + 16);
-    elem<T>::st(y + i, g / (1.0f + expf(-g)) * u);
+    float o = g / (1.0f + expf(-g)) * u;
+    asm volatile("" : "+v"(o));   // rounded to fp32 before the store's conversion, as in the 16-byte form (preventive: see the adjoint)
+    elem<T>::st(y + i, o);
   }
 }
 template <typename T>
@@ -81,8 +83,12 @@ __global__ void swiglu_bwd_kernel(const T* gu, const T* dy, T* dgu, long M, int 
     const long base = m * 2 * F + (j >> 4) * 32 + (j & 15);
     const float g = elem<T>::ld(gu + base), u = elem<T>::ld(gu + base + 16), d = elem<T>::ld(dy + i);
     const float s = 1.0f / (1.0f + expf(-g));
-    elem<T>::st(dgu + base, d * u * s * (1.0f + g * (1.0f - s)));
-    elem<T>::st(dgu + base + 16, d * g * s);
+    float dg = d * u * s * (1.0f + g * (1.0f - s)), du = d * g * s;
+    // rounded to fp32 before the store's conversion, as in the 16-byte form: without this the last product and the f16
+    // conversion become one v_fma_mixlo_f16 (one rounding) and the two forms differ in the last bit of a few f16 results
+    asm volatile("" : "+v"(dg), "+v"(du));
+    elem<T>::st(dgu + base, dg);
+    elem<T>::st(dgu + base + 16, du);
   }
 }
 template <typename T>
@@ -105,7 +111,10 @@ __global__ void mul_kernel(const T* a, const T* b, T* out, long n) {
     elem<T>::st(out + i, elem<T>::ld(a + i) * elem<T>::ld(b + i));
 }
 
-// 16-bit forms (T = bf16_t / f16_t) with 16-byte accesses: a thread owns 8 consecutive outputs (half a 16-column group)
+// 16-bit forms (T = bf16_t / f16_t) with 16-byte accesses: a thread owns 8 consecutive outputs (half a 16-column group).
+// Both forms give the same bits (tests/test_train_edge_kernels_gpu.py): each result is rounded to fp32 and THEN converted by the
+// store. Here the results pass through the float arrays of store8 (packed conversions, which take fp32 operands); the scalar
+// kernels above hold theirs behind an empty asm so that the last product cannot be folded into the conversion.
 template <typename T>
 __global__ void swiglu_fwd_vec_kernel(const T* gu, T* y, long M, int F) {
   const long n8 = M * F / 8;
@@ -803,21 +812,21 @@ extern "C" int haff_colsum(const void* x, float* out, long R, int C, int dtype, 
 }
 extern "C" int haff_softmax_fwd(const float* s, long ld, void* p, long ldp, long rows, int Nq, int Nk, float scale, int causal,
                                 int q_pos0, int dtype, void* stream) {
-  if (rows <= 0 || Nk <= 0 || ldp < Nk || ld < Nk) return HAFF_ERR_BAD_ARG;
+  if (rows <= 0 || Nq <= 0 || Nk <= 0 || ldp < Nk || ld < Nk) return HAFF_ERR_BAD_ARG;   // the kernel takes row % Nq
   dim3 g((unsigned)((rows + 3) / 4)), b(256);
   DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_fwd_kernel<T>), g, b, 0, HS(stream), s, ld, (T*)p, ldp, rows, Nq, Nk, scale, causal, q_pos0));
   return haff_check_launch();
 }
 extern "C" int haff_softmax_bwd(const void* p, long ldp, const float* dp, long ld, void* ds, long rows, int Nk, float scale,
                                 int dtype, void* stream) {
-  if (rows <= 0 || Nk <= 0) return HAFF_ERR_BAD_ARG;
+  if (rows <= 0 || Nk <= 0 || ldp < Nk || ld < Nk) return HAFF_ERR_BAD_ARG;   // rows shorter than Nk would overlap
   dim3 g((unsigned)((rows + 3) / 4)), b(256);
   DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_bwd_kernel<T>), g, b, 0, HS(stream), (const T*)p, ldp, dp, ld, (T*)ds, rows, Nk, scale));
   return haff_check_launch();
 }
 extern "C" int haff_rope(const void* x, long ldx, void* y, long ldy, const float* cos_sin, long rows, int Tlen, int H, int d,
                          int pos0, int adjoint, int dtype, void* stream) {
-  if (rows <= 0 || (d & 1)) return HAFF_ERR_BAD_ARG;
+  if (rows <= 0 || Tlen <= 0 || H <= 0 || d <= 0 || (d & 1)) return HAFF_ERR_BAD_ARG;   // the kernel divides by each of them
   dim3 g(grid_for(rows * H * (d / 2), 256)), b(256);
   const float sign = adjoint ? -1.f : 1.f;
   DISPATCH_T(dtype, hipLaunchKernelGGL((rope_kernel<T>), g, b, 0, HS(stream), (const T*)x, ldx, (T*)y, ldy, cos_sin, rows, Tlen, H, d, pos0, sign));
@@ -825,7 +834,7 @@ extern "C" int haff_rope(const void* x, long ldx, void* y, long ldy, const float
 }
 extern "C" int haff_cross_entropy(const void* logits, long ld, const long* labels, float* row_loss, void* dlogits, long rows,
                                   int V, float gscale, int dtype, void* stream) {
-  if (rows <= 0 || V <= 0) return HAFF_ERR_BAD_ARG;
+  if (rows <= 0 || V <= 0 || ld < V) return HAFF_ERR_BAD_ARG;   // ld < V: a row's gradient would be written over the next row
   dim3 g((unsigned)rows), b(256);
   DISPATCH_T(dtype, hipLaunchKernelGGL((cross_entropy_kernel<T>), g, b, 0, HS(stream), (const T*)logits, ld, labels, row_loss, (T*)dlogits, V, gscale));
   return haff_check_launch();
@@ -852,7 +861,7 @@ extern "C" int haff_mask_loss_grad_dev(const float* x, const float* t, const flo
 }
 extern "C" int haff_resize_bilinear_bwd(const float* dout, float* din, int N, int Hs, int Ws, int Hc, int Wc, int Ho, int Wo,
                                         void* stream) {
-  if (N <= 0 || Hc <= 0 || Wc <= 0 || Hc > Hs || Wc > Ws) return HAFF_ERR_BAD_ARG;
+  if (N <= 0 || Hc <= 0 || Wc <= 0 || Hc > Hs || Wc > Ws || Ho <= 0 || Wo <= 0) return HAFF_ERR_BAD_ARG;   // the scales divide by Ho / Wo
   hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(grid_for((long)N * Hc * Wc, 256)), dim3(256), 0, HS(stream), dout, din, N, Hs, Ws, Hc, Wc, Ho, Wo);
   return haff_check_launch();
 }
