@@ -281,23 +281,26 @@ extern "C" int haff_rmsnorm(const void* x, long ldx, void* y, long ldy, const fl
 // {mean, rstd} from the per-wave partial sums haff_gemm_bf16_rowstats left: partials f32 [rows][slots][2] = {sum, sum of squares}
 // over 64 columns each, added in slot order (deterministic); C = the row length the sums cover.
 namespace {
-__global__ __launch_bounds__(256) void row_stats_finalize_kernel(const float* part, float* stats, int rows, int slots, float inv_c,
+__global__ __launch_bounds__(256) void row_stats_finalize_kernel(const float* part, float* stats, int rows, int slots, int C,
                                                                  float eps) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= rows) return;
   const float2* p = reinterpret_cast<const float2*>(part) + (long)r * slots;
   // E[x^2] - mean^2 cancels when |mean| >> std: the slot sums arrive as fp32 (each the sum of 64 fp32 products: ~5e-7
-  // relative), so the variance carries ~5e-7 * (mean / std)^2 whatever is done here — adding the slots and forming the
-  // difference in double at least contributes nothing more (fp32 here doubled it; the two-pass haff_row_stats has no such
-  // term). tests/test_ops_gpu.py::test_linear_rowstats_with_a_large_row_mean holds the bound at mean / std = 30 and 100.
+  // relative), so the variance carries ~5e-7 * (mean / std)^2 whatever is done here (the two-pass haff_row_stats has no such
+  // term). Adding the slots, dividing by C and forming the difference in double contributes 2^-53 * (mean / std)^2 and no more —
+  // but only with the division in double too: multiplying by an fp32 1 / C scales E[x^2] and mean^2 by (1 + e) and (1 + e)^2
+  // (e = 1.5e-8 at C = 1280) and leaves -e * mean^2 in the variance, 1.5e-2 of it at mean / std = 1000.
+  // tests/test_ops_gpu.py::test_linear_rowstats_with_a_large_row_mean holds the bound on a GEMM's partials at mean / std = 30 and
+  // 100, tests/test_norm_ingest_kernels_gpu.py::test_row_stats_finalize_exact_partials on exact partials up to 1000.
   double s1 = 0.0, s2 = 0.0;
   for (int i = 0; i < slots; ++i) {
     const float2 v = p[i];
     s1 += (double)v.x;
     s2 += (double)v.y;
   }
-  const double mean = s1 * (double)inv_c;
-  const double var = fmax(s2 * (double)inv_c - mean * mean, 0.0);
+  const double mean = s1 / (double)C;
+  const double var = fmax(s2 / (double)C - mean * mean, 0.0);
   reinterpret_cast<float2*>(stats)[r] = float2{(float)mean, (float)(1.0 / sqrt(var + (double)eps))};
 }
 }  // namespace
@@ -305,17 +308,18 @@ __global__ __launch_bounds__(256) void row_stats_finalize_kernel(const float* pa
 extern "C" int haff_row_stats_finalize(const float* partials, float* stats, int rows, int slots, int C, float eps, void* stream) {
   if (rows <= 0 || slots <= 0 || C <= 0 || !partials || !stats) return HAFF_ERR_BAD_ARG;
   hipLaunchKernelGGL(row_stats_finalize_kernel, dim3((rows + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     partials, stats, rows, slots, 1.0f / (float)C, eps);
+                     partials, stats, rows, slots, C, eps);
   return haff_check_launch();
 }
 
 // stats[rows][2] = {mean, rstd} of each row (rms != 0: {0, rsqrt(mean(x^2) + eps)} — LlamaRMSNorm). dtype: 0 = bf16,
-// 1 = f32, 3 = f16. For haff_gemm_bf16_ln, which applies the normalisation inside the consumer product.
+// 1 = f32, 3 = f16, any other code is refused. For haff_gemm_bf16_ln, which applies the normalisation inside the consumer product.
 extern "C" int haff_row_stats(const void* x, long ldx, float* stats, int rows, int C, float eps, int rms, int dtype,
                               void* stream) {
   if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || !stats) return HAFF_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (dtype == 0) return rms ? launch_stats<bf16_t, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<bf16_t, false>(x, ldx, stats, rows, C, eps, s);
   if (dtype == 3) return rms ? launch_stats<f16_t, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<f16_t, false>(x, ldx, stats, rows, C, eps, s);
+  if (dtype != 1) return HAFF_ERR_BAD_ARG;
   return rms ? launch_stats<float, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<float, false>(x, ldx, stats, rows, C, eps, s);
 }

@@ -416,16 +416,20 @@ int haff_global_attention_f16(const void* q, long q_sb, long q_sh, long q_st, co
  * haff_layernorm: nn.LayerNorm / LayerNorm2d on channels-last rows (common.py:31-43; image_encoder.py:179,191;
  * transformer.py:134-144; CLIP layer norms). in_map (int32[rows], may be null): out row i normalises in row
  * in_map[i]; negative = zero row (window_partition's zero pad AFTER norm1, image_encoder.py:179-183,276-288).
- * haff_rmsnorm: LlamaRMSNorm (fp32 variance). w, b: f32[C]. C % 8 == 0, C <= 8192.
- * dtype: 0 = bf16 rows, 1 = f32 rows, 2 = f32 x -> bf16 y (an fp32 residual stream feeding a bf16 product), 3 = f16 rows. */
+ * haff_rmsnorm: LlamaRMSNorm (fp32 variance). w, b: f32[C]. C % 8 == 0, C <= 8192 (wider: HAFF_ERR_UNSUPPORTED), ldx / ldy % 8 == 0.
+ * dtype: 0 = bf16 rows, 1 = f32 rows, 2 = f32 x -> bf16 y (an fp32 residual stream feeding a bf16 product), 3 = f16 rows.
+ * Columns C .. ld of x are not read and those of y not written, nor any row past `rows`. in_map is a DEVICE array: the caller
+ * guarantees that every non-negative entry is a row of x; nothing checks it. */
 int haff_layernorm(const void* x, long ldx, void* y, long ldy, const float* w, const float* b, const int* in_map,
                    int rows, int C, float eps, int dtype, void* stream);
 int haff_rmsnorm(const void* x, long ldx, void* y, long ldy, const float* w, int rows, int C, float eps, int dtype,
                  void* stream);
-/* per-row {mean, rstd} only (rms != 0: {0, rsqrt(mean(x^2)+eps)}): stats f32 [rows][2]; dtype 0 = bf16, 1 = f32, 3 = f16. */
+/* per-row {mean, rstd} only (rms != 0: {0, rsqrt(mean(x^2)+eps)}): stats f32 [rows][2]; dtype 0 = bf16, 1 = f32, 3 = f16, any
+ * other code (2 included: there is no output row to round) returns HAFF_ERR_BAD_ARG. Same C / ldx rules as the norms. */
 int haff_row_stats(const void* x, long ldx, float* stats, int rows, int C, float eps, int rms, int dtype, void* stream);
 
-/* stats[rows][2] = {mean, rstd} from haff_gemm_bf16_rowstats' partials f32 [rows][slots][2] (slots added in order); C = row length. */
+/* stats[rows][2] = {mean, rstd} from haff_gemm_bf16_rowstats' partials f32 [rows][slots][2] (slots added in order); C = row length.
+ * Sums, the division by C and E[x^2] - mean^2 (clamped at 0) are in double; only the two results are rounded to fp32. */
 int haff_row_stats_finalize(const float* partials, float* stats, int rows, int slots, int C, float eps, void* stream);
 
 /* ---- data movement ------------------------------------------------------------------------------------------ */
