@@ -569,7 +569,7 @@ class FlashAttentionFn(Function):
         Nk = k.shape[1]
         d = HD // H
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        n_ws = B * H * (Nq + 4 + ((Nq + 63) // 64) * 64 * d)
+        n_ws = (B * H * Nq + 3) // 4 * 4 + B * H * ((Nq + 63) // 64) * 64 * d   # delta, then the 16-byte aligned fp32 dq sums (haff_hip.h)
         ws = torch.empty((n_ws,), dtype=torch.float32, device=q.device)
         check(_fn16(lib, "haff_attention_bwd_bf16", q.dtype)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), do.data_ptr(), lse.data_ptr(),
                                           dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), n_ws, HD, B, H, Nq, Nk, d,

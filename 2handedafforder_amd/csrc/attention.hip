@@ -1314,15 +1314,27 @@ extern "C" int haff_attention_f16(const void* q, long q_sb, long q_sh, long q_st
                                    Nk, d, scale, causal, q_pos0, relh, relw, S, nullptr, stream);
 }
 
+// what the two lse entry points refuse before attention_bf16_impl's own checks: null operands, bases the 16-byte loads of
+// q / k / v and the 8-byte stores of o cannot take, and a causal mask under which a query row sees no key
+static bool lse_args_ok(const void* q, const void* k, const void* v, const void* o, const float* lse, int causal, int q_pos0) {
+  if (!q || !k || !v || !o || !lse) return false;
+  if ((reinterpret_cast<uintptr_t>(q) & 15) || (reinterpret_cast<uintptr_t>(k) & 15) || (reinterpret_cast<uintptr_t>(v) & 15) ||
+      (reinterpret_cast<uintptr_t>(o) & 7) || (reinterpret_cast<uintptr_t>(lse) & 3))
+    return false;
+  return !(causal && q_pos0 < 0);
+}
+
 // haff_attention_bf16 that also returns the per-row log-sum-exp of the scores, LOG2 domain (log2 sum_k 2^(scale*log2(e)*q.k)), f32
 // [B][H][Nq]: the forward half of the flash pair whose backward is haff_attention_bwd_bf16 (no probabilities are kept).
+// Null q / k / v / o / lse, q / k / v not 16-byte or o not 8-byte aligned, and causal with q_pos0 < 0 (a query row that sees no
+// key has no log-sum-exp) are HAFF_ERR_BAD_ARG.
 extern "C" int haff_attention_lse_bf16(const void* q, long q_sb, long q_sh, long q_st,
                                        const void* k, long k_sb, long k_sh, long k_st,
                                        const void* v, long v_sb, long v_sh, long v_st,
                                        void* o, long o_sb, long o_sh, long o_st,
                                        int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
                                        float* lse, void* stream) {
-  if (!lse) return HAFF_ERR_BAD_ARG;
+  if (!lse_args_ok(q, k, v, o, lse, causal, q_pos0)) return HAFF_ERR_BAD_ARG;
   return attention_bf16_impl(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq, Nk, d,
                              scale, causal, q_pos0, nullptr, nullptr, 0, nullptr, stream, lse);
 }
@@ -1333,7 +1345,7 @@ extern "C" int haff_attention_lse_f16(const void* q, long q_sb, long q_sh, long 
                                       void* o, long o_sb, long o_sh, long o_st,
                                       int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
                                       float* lse, void* stream) {
-  if (!lse) return HAFF_ERR_BAD_ARG;
+  if (!lse_args_ok(q, k, v, o, lse, causal, q_pos0)) return HAFF_ERR_BAD_ARG;
   return attention_bf16_impl<true>(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq,
                                    Nk, d, scale, causal, q_pos0, nullptr, nullptr, 0, nullptr, stream, lse);
 }

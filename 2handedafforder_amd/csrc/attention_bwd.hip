@@ -282,24 +282,27 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const bf16_t* o, co
 
 // dq, dk, dv of out = softmax(scale * q k^T [causal: key j visible to query i iff j <= i + q_pos0]) v, bf16, d == 128.
 // q / dout / o / dq: [B][Nq][ld], k / v / dk / dv: [B][Nk][ld] token-major with head h at columns h*128 (ld = H*128 for the
-// fused projections); lse f32 [B][H][Nq] from haff_attention_lse_bf16; workspace f32, >= B*H*(Nq + 128*roundup(Nq, 64)) values.
+// fused projections); lse f32 [B][H][Nq] from haff_attention_lse_bf16; workspace f32, 16-byte aligned, at least
+// roundup(B*H*Nq, 4) + B*H*128*roundup(Nq, 64) values: delta [B*H*Nq], then (on the next 16-byte boundary) the fp32 dq sums.
+// causal needs q_pos0 >= 0 (key block 0 must be seen by every query block: it is the one that writes the dq sums).
 template <bool F16>
 static int attention_bwd_impl(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq,
                               void* dk, void* dv, float* workspace, long workspace_elems, long ld, int B, int H, int Nq, int Nk, int d,
                               float scale, int causal, int q_pos0, void* stream) {
   if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || !q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !workspace)
     return HAFF_ERR_BAD_ARG;
+  if (causal && q_pos0 < 0) return HAFF_ERR_BAD_ARG;
   if (d != BD) return HAFF_ERR_UNSUPPORTED;
   if ((ld & 7) || ld < (long)H * BD) return HAFF_ERR_BAD_ARG;
   const void* ptrs[8] = {q, k, v, o, dout, dq, dk, dv};
   for (const void* x : ptrs)
     if (reinterpret_cast<uintptr_t>(x) & 15) return HAFF_ERR_BAD_ARG;
   const long nqp = (long)((Nq + BB - 1) / BB) * BB;
-  const long need = (long)B * H * (Nq + nqp * BD);
+  const long dq_off = (((long)B * H * Nq + 3) / 4) * 4;   // delta, then the dq sums on the next 16-byte boundary
+  const long need = dq_off + (long)B * H * nqp * BD;
   if (workspace_elems < need || (reinterpret_cast<uintptr_t>(workspace) & 15)) return HAFF_ERR_BAD_ARG;
   float* delta = workspace;
-  float* dq_acc = workspace + (((long)B * H * Nq + 3) / 4) * 4;
-  if (dq_acc + (long)B * H * nqp * BD > workspace + workspace_elems) return HAFF_ERR_BAD_ARG;
+  float* dq_acc = workspace + dq_off;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long rows = (long)B * Nq * H;
   hipLaunchKernelGGL((attn_bwd_delta_kernel<F16>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, s,

@@ -148,6 +148,7 @@ template <bool F16>
 static int gemm_tn_impl(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
                         long workspace_elems, void* out, int out_f32, void* stream) {
   if (M <= 0 || N1 <= 0 || N2 <= 0 || !A || !B || !workspace || !out || lda < N1 || ldb < N2) return HAFF_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return HAFF_ERR_BAD_ARG;   // the partials are written and read 16 bytes at a time
   if ((N1 & 7) || (N2 & 7) || (lda & 7) || (ldb & 7) || (reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15) ||
       (reinterpret_cast<uintptr_t>(out) & 15))
     return HAFF_ERR_UNSUPPORTED;
@@ -170,6 +171,7 @@ static int gemm_tn_impl(const void* A, long lda, const void* B, long ldb, long M
 
 // out [N1][N2] (contiguous; bf16 or f32) = A^T . B with A [M][lda] (N1 columns), B [M][ldb] (N2 columns), both bf16.
 // N1, N2, lda, ldb multiples of 8 and 16-byte aligned bases (anything else: HAFF_ERR_UNSUPPORTED, the caller transposes).
+// workspace: f32, 16-byte aligned, at least haff_gemm_tn_workspace_elems(M, N1, N2) values (else HAFF_ERR_BAD_ARG).
 extern "C" int haff_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
                                  long workspace_elems, void* out, int out_f32, void* stream) {
   return gemm_tn_impl<false>(A, lda, B, ldb, M, N1, N2, workspace, workspace_elems, out, out_f32, stream);

@@ -284,7 +284,10 @@ int haff_relpos_tables_bf16(const void* q, long q_sb, long q_sh, long q_st, cons
  * haff_attention_lse_bf16 = haff_attention_bf16 (no bias) that also returns lse f32 [B][H][Nq] = log2 sum_k 2^(scale*log2(e)*q.k)
  * over the visible keys; haff_attention_bwd_bf16 = dq, dk, dv from q, k, v, o, dout and lse without the probabilities ever
  * existing in HBM (d == 128; bitwise repeatable: no atomics). q / o / dout / dq: [B][Nq][ld], k / v / dk / dv: [B][Nk][ld],
- * head h at columns h*128; workspace f32 with >= B*H*(Nq + 3 + 128*roundup(Nq, 64)) values; causal needs q_pos0 >= 0. */
+ * head h at columns h*128 (ld >= H*128, ld % 8 == 0, 16-byte aligned bases); workspace f32, 16-byte aligned, with at least
+ * roundup(B*H*Nq, 4) + B*H*128*roundup(Nq, 64) values (B*H*(Nq + 3 + 128*roundup(Nq, 64)) is always enough). Refused with
+ * HAFF_ERR_BAD_ARG before any launch, by all four entry points: a null or misaligned operand, result, lse or workspace; causal with
+ * q_pos0 < 0 (a query that sees no key has no log-sum-exp, and the backward's key block 0 must be seen by every query block). */
 int haff_attention_lse_bf16(const void* q, long q_sb, long q_sh, long q_st, const void* k, long k_sb, long k_sh, long k_st,
                             const void* v, long v_sb, long v_sh, long v_st, void* o, long o_sb, long o_sh, long o_st, int B, int H,
                             int Nq, int Nk, int d, float scale, int causal, int q_pos0, float* lse, void* stream);
@@ -303,8 +306,10 @@ int haff_attention_bwd_f16(const void* q, const void* k, const void* v, const vo
  * over the M rows — the weight gradient dW = dY^T . X of a trainable Linear (torch.nn.Linear under autograd: text_hidden_fcs and
  * the mask decoders, train_ds.py:232-244) without transposed copies of dY and X (csrc/gemm_tn.hip: fragments through the
  * transposing LDS read). N1, N2, lda, ldb % 8 == 0, 16-byte aligned bases, else HAFF_ERR_UNSUPPORTED (the caller then takes
- * haff_transpose + haff_gemm_bf16). out contiguous, bf16 or f32; workspace f32 with haff_gemm_tn_workspace_elems values
- * (split partials, added in index order: repeatable to the bit). */
+ * haff_transpose + haff_gemm_bf16). out contiguous, bf16 or f32; workspace f32, 16-byte aligned, with at least
+ * haff_gemm_tn_workspace_elems(M, N1, N2) values (split partials, added in index order: repeatable to the bit); a null,
+ * misaligned or shorter workspace is HAFF_ERR_BAD_ARG. haff_gemm_tn_workspace_elems answers HAFF_ERR_BAD_ARG for a size <= 0
+ * and HAFF_ERR_UNSUPPORTED for a count past INT_MAX. */
 int haff_gemm_tn_workspace_elems(long M, int N1, int N2);
 int haff_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
                       long workspace_elems, void* out, int out_f32, void* stream);
