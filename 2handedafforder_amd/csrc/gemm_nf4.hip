@@ -17,6 +17,8 @@
 // multiply and rounded to f16 with one packed convert.
 #include "haff_common.h"
 
+#include <type_traits>
+
 namespace {
 
 // bitsandbytes' NF4 code values (index 7 is 0)
@@ -172,6 +174,52 @@ __global__ __launch_bounds__(256) void nf4_dequant_kernel(const unsigned char* _
   store8(reinterpret_cast<f16_t*>(out) + dst * ldo + 8 * g, v);
 }
 
+// nf4_dequant_kernel with the rank-8 update of unmerged LoRA adapters folded into the same pass (serving adapters fitted on the NF4
+// base; prefill-sized products):
+//   out[map[n]][k] = f16_rn(fl32(d + fl32(s * u))),  d = fl32(NF4[code] * absmax),
+//   u_0 = 0, u_{j+1} = fl32(u_j + B[n][j] * A[8 seg(n) + j][k]), j = 0..7 in that order (an f16 x f16 product is exact in fp32, so
+//   one fused multiply-add per step rounds exactly once, as written), seg(n) = (n / seg_rows) % nseg.
+// Thread = 8 consecutive k of 8 consecutive stored rows (seg_rows % 16 == 0: one segment): its 8 x 8 block of A_cat is read once
+// (L2-resident: 16 nseg K bytes in all) and serves the 8 rows, so the kernel moves the plain dequantisation's HBM bytes plus N K / 4
+// bytes of L2 reads. Lanes walk k: the code words of a wave are 256 contiguous bytes of a row, its stores 1 KiB of one.
+__global__ __launch_bounds__(256) void nf4_dequant_lora_kernel(const unsigned char* __restrict__ packed, const float* __restrict__ absmax,
+                                                               int N, int K, const int* row_map, f16_t* out, long ldo,
+                                                               const f16_t* __restrict__ A, long lda, const f16_t* __restrict__ B,
+                                                               int nseg, int seg_rows, float scale) {
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int g8 = K >> 3;
+  const int groups = (N + 7) >> 3;
+  if (gid >= (long)groups * g8) return;
+  const int n0 = (int)(gid / g8) * 8, g = (int)(gid % g8);
+  const int seg = (n0 / seg_rows) % nseg;
+  float a[8][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) load8(A + (long)(8 * seg + j) * lda + 8 * g, a[j]);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int n = min(n0 + i, N - 1);   // rows past N: re-read, skipped at the store (no branch between the rows' loads)
+    const unsigned word = *reinterpret_cast<const unsigned*>(packed + (long)n * (K >> 1) + 4 * g);
+    const float am = absmax[(long)n * (K >> 6) + (g >> 3)];
+    float b[8];
+    load8(B + (long)n * 8, b);
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float d = __fmul_rn(kNF4[(word >> (e & 1 ? 8 * (e >> 1) : 8 * (e >> 1) + 4)) & 15u], am);
+      float u = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) u = __fmaf_rn(b[j], a[j][e], u);
+      float su = __fmul_rn(scale, u);
+      asm volatile("" : "+v"(d), "+v"(su));   // the build contracts across statements (-ffp-contract=fast): keep both products' roundings
+      float o = __fadd_rn(d, su);
+      asm volatile("" : "+v"(o));             // ... and the sum's: rounded to fp32 first, then to f16
+      v[e] = o;
+    }
+    const long dst = row_map ? row_map[n] : n;
+    if (n0 + i < N) store8(out + dst * ldo + 8 * g, v);
+  }
+}
+
 typedef float nf4_f2 __attribute__((ext_vector_type(2)));
 
 // The transposed dequantisation (NF4 fine-tuning: the f16 W^T of a dX product, written straight from the codes):
@@ -269,11 +317,24 @@ struct Nf4Args {
   int M, N, K, act, out_f32;
 };
 
+// Unmerged LoRA adapters of a fused weight (serving adapters fitted on the NF4 base): t = x . A_cat^T as f16 [M][ldt], 8 rank
+// values per row segment; B f16 [N][8], each stored row's own coefficients; stored row n belongs to segment (n / seg_rows) % nseg
+// (q | k | v: 3 segments of H rows; [gate x16 | up x16]: 2 of 16; o / down: 1). An unadapted segment has zero coefficients.
+struct Nf4LoraArgs : Nf4Args {
+  const bf16_t* t; long ldt;
+  const bf16_t* B;
+  int nseg, seg_rows;
+  float scale;
+};
+
 // Activation 16-B fragments per 64-block per tile row of 16: two k-steps. Blocks per batch of loads (two register sets).
 template <int MT> constexpr int nf4_batch() { return MT == 1 ? 4 : (MT == 2 ? 2 : 1); }
 
-template <int MT, int NT, bool SWIGLU, int KW>
-__global__ __launch_bounds__(64 * KW) void gemm_nf4_kernel(Nf4Args p) {
+// LORA: the rank update s * sum_j t[m][8 seg + j] * B[n][j] joins the reduced sums before bias, activation, SwiGLU and residual,
+// as ONE MFMA per 16 x 16 tile (the trick of lora_qkv_rope_fwd_kernel): the weight operand of lane (fr, fh) holds row fr's 8
+// coefficients where fh is the row tile's segment and zeros elsewhere, the activation operand t[m][8 fh .. 8 fh + 7].
+template <int MT, int NT, bool SWIGLU, int KW, bool LORA = false>
+__global__ __launch_bounds__(64 * KW) void gemm_nf4_kernel(std::conditional_t<LORA, Nf4LoraArgs, Nf4Args> p) {
   using E = h16<true>;
   static_assert(!SWIGLU || (NT % 2) == 0, "SwiGLU pairs a gate tile with an up tile");
   constexpr int U = nf4_batch<MT>();
@@ -296,6 +357,17 @@ __global__ __launch_bounds__(64 * KW) void gemm_nf4_kernel(Nf4Args p) {
     const long n = min(n0 + t * 16 + fr, p.N - 1);
     wrow[t] = p.Wq + n * (p.K >> 1) + 8 * fh;
     arow[t] = p.absmax + n * kb;
+  }
+  // (LORA) both operands of the rank update, requested ahead of the K loop; every wave loads (clamped rows), waves < MT use them
+  uint4 lb[LORA ? NT : 1], lt = uint4{0u, 0u, 0u, 0u};
+  if constexpr (LORA) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int seg = ((n0 + t * 16) / p.seg_rows) % p.nseg;
+      lb[t] = uint4{0u, 0u, 0u, 0u};
+      if (fh == seg) lb[t] = *reinterpret_cast<const uint4*>(p.B + (long)min(n0 + t * 16 + fr, p.N - 1) * 8);
+    }
+    if (fh < p.nseg) lt = *reinterpret_cast<const uint4*>(p.t + (long)min(wave * 16 + fr, p.M - 1) * p.ldt + 8 * fh);
   }
   f32x4 acc[NT][MT];
 #pragma unroll
@@ -378,6 +450,11 @@ __global__ __launch_bounds__(64 * KW) void gemm_nf4_kernel(Nf4Args p) {
         for (int w4 = 0; w4 < KW; ++w4) sum += red[w4][wave][lane][r];
         o[t][r] = sum;
       }
+      if constexpr (LORA) {
+        const f32x4 d = E::mfma16(__builtin_bit_cast(bf16x8, lb[t]), __builtin_bit_cast(bf16x8, lt), f32x4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[t][r] += p.scale * d[r];
+      }
     }
     if (t + 1 < NT) __syncthreads();
   }
@@ -425,14 +502,31 @@ __global__ __launch_bounds__(64 * KW) void gemm_nf4_kernel(Nf4Args p) {
 
 constexpr int kNf4Waves = 8;
 
-template <int MT>
-void launch_nf4(const Nf4Args& p, int swiglu, hipStream_t s) {
+template <int MT, bool LORA, typename Args>
+void launch_nf4(const Args& p, int swiglu, hipStream_t s) {
   // 16 weight rows per workgroup while that leaves >= 192 workgroups (SwiGLU: a gate and an up tile), wider otherwise
   const int tiles = (p.N + 15) / 16;
   const dim3 b(64 * kNf4Waves);
-  if (swiglu) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, true, kNf4Waves>), dim3((tiles + 1) / 2), b, 0, s, p);
-  else if (MT >= 2 && tiles / 2 >= 192) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, false, kNf4Waves>), dim3((tiles + 1) / 2), b, 0, s, p);
-  else hipLaunchKernelGGL((gemm_nf4_kernel<MT, 1, false, kNf4Waves>), dim3(tiles), b, 0, s, p);
+  if (swiglu) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, true, kNf4Waves, LORA>), dim3((tiles + 1) / 2), b, 0, s, p);
+  else if (MT >= 2 && tiles / 2 >= 192) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, false, kNf4Waves, LORA>), dim3((tiles + 1) / 2), b, 0, s, p);
+  else hipLaunchKernelGGL((gemm_nf4_kernel<MT, 1, false, kNf4Waves, LORA>), dim3(tiles), b, 0, s, p);
+}
+
+// the host-side refusals of haff_gemm_nf4_f16 (0: go on)
+int nf4_gemm_args_bad(const void* A, long lda, const void* Wq, const float* absmax, const void* C, const void* resid, int M, int N, int K,
+                      int swiglu) {
+  if (M <= 0 || N <= 0 || K <= 0) return HAFF_ERR_BAD_ARG;
+  if (M > 64) return HAFF_ERR_UNSUPPORTED;   // decode-sized products only: prefill dequantises and runs haff_gemm_f16
+  if ((K & 63) || (lda & 7) || lda < K || !A || !Wq || !absmax || !C) return HAFF_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(Wq) & 7) || (reinterpret_cast<uintptr_t>(absmax) & 3))
+    return HAFF_ERR_BAD_ARG;
+  if (swiglu && ((N & 31) || resid)) return HAFF_ERR_BAD_ARG;
+  return 0;
+}
+
+// ... and of the adapters' layout, shared by both LoRA entry points
+bool nf4_lora_layout_bad(const void* B, int nseg, int seg_rows) {
+  return nseg < 1 || nseg > 4 || seg_rows <= 0 || (seg_rows & 15) || !B || (reinterpret_cast<uintptr_t>(B) & 15);
 }
 
 }  // namespace
@@ -483,17 +577,44 @@ extern "C" int haff_nf4_dequant_t_f16(const void* packed, const float* absmax, i
 extern "C" int haff_gemm_nf4_f16(const void* A, long lda, const void* Wq, const float* absmax, void* C, long ldc, const float* bias,
                                  const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
                                  void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return HAFF_ERR_BAD_ARG;
-  if (M > 64) return HAFF_ERR_UNSUPPORTED;   // decode-sized products only: prefill dequantises and runs haff_gemm_f16
-  if ((K & 63) || (lda & 7) || lda < K || !A || !Wq || !absmax || !C) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(Wq) & 7) || (reinterpret_cast<uintptr_t>(absmax) & 3))
-    return HAFF_ERR_BAD_ARG;
-  if (swiglu && ((N & 31) || resid)) return HAFF_ERR_BAD_ARG;
+  if (const int bad = nf4_gemm_args_bad(A, lda, Wq, absmax, C, resid, M, N, K, swiglu)) return bad;
   Nf4Args p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const unsigned char*>(Wq), absmax, C, ldc, bias, resid, ldr,
             row_map, M, N, K, act, out_f32};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (M <= 16) launch_nf4<1>(p, swiglu, s);
-  else if (M <= 32) launch_nf4<2>(p, swiglu, s);
-  else launch_nf4<4>(p, swiglu, s);
+  if (M <= 16) launch_nf4<1, false>(p, swiglu, s);
+  else if (M <= 32) launch_nf4<2, false>(p, swiglu, s);
+  else launch_nf4<4, false>(p, swiglu, s);
+  return haff_check_launch();
+}
+
+extern "C" int haff_gemm_nf4_lora_f16(const void* A, long lda, const void* Wq, const float* absmax, void* C, long ldc, const float* bias,
+                                      const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
+                                      int swiglu, const void* t, long ldt, const void* B, int nseg, int seg_rows, float scale,
+                                      void* stream) {
+  if (const int bad = nf4_gemm_args_bad(A, lda, Wq, absmax, C, resid, M, N, K, swiglu)) return bad;
+  if (nf4_lora_layout_bad(B, nseg, seg_rows) || !t || (reinterpret_cast<uintptr_t>(t) & 15) || ldt < 8 * nseg || (ldt & 7))
+    return HAFF_ERR_BAD_ARG;
+  Nf4LoraArgs p{{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const unsigned char*>(Wq), absmax, C, ldc, bias, resid, ldr,
+                 row_map, M, N, K, act, out_f32},
+                reinterpret_cast<const bf16_t*>(t), ldt, reinterpret_cast<const bf16_t*>(B), nseg, seg_rows, scale};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (M <= 16) launch_nf4<1, true>(p, swiglu, s);
+  else if (M <= 32) launch_nf4<2, true>(p, swiglu, s);
+  else launch_nf4<4, true>(p, swiglu, s);
+  return haff_check_launch();
+}
+
+extern "C" int haff_nf4_dequant_lora_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out, long ldo,
+                                         const void* A_cat, long lda, const void* B, int nseg, int seg_rows, float scale,
+                                         void* stream) {
+  if (N <= 0 || K <= 0 || (K & 63) || (ldo & 7) || ldo < K || !packed || !absmax || !out) return HAFF_ERR_BAD_ARG;
+  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(absmax) & 3) || (reinterpret_cast<uintptr_t>(out) & 15))
+    return HAFF_ERR_BAD_ARG;
+  if (nf4_lora_layout_bad(B, nseg, seg_rows) || !A_cat || (reinterpret_cast<uintptr_t>(A_cat) & 15) || lda < K || (lda & 7))
+    return HAFF_ERR_BAD_ARG;
+  const long thr = (long)((N + 7) >> 3) * (K >> 3);
+  hipLaunchKernelGGL(nf4_dequant_lora_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const unsigned char*>(packed), absmax, N, K, row_map, reinterpret_cast<f16_t*>(out), ldo,
+                     reinterpret_cast<const f16_t*>(A_cat), lda, reinterpret_cast<const f16_t*>(B), nseg, seg_rows, scale);
   return haff_check_launch();
 }

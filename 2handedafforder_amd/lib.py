@@ -52,6 +52,10 @@ _PROTOS = {
     "haff_nf4_dequant_t_f16": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p],
     "haff_gemm_nf4_f16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
                           c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "haff_nf4_dequant_lora_f16": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int,
+                                  c_float, c_void_p],
+    "haff_gemm_nf4_lora_f16": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                               c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_int, c_int, c_float, c_void_p],
     "haff_int8_quantize_weight_f16": [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "haff_int8_quantize_act_f16": [c_void_p, c_long, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
                                    c_void_p, c_void_p, c_void_p],

@@ -50,7 +50,8 @@ def _check_fp16_weights(sd, device):
 class LisaMI355:
     def __init__(self, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", sam_chunk=8, fp32_tail=True, fp32_stream=False,
                  neck_f32=False, load_in_4bit=False, bnb_4bit_use_double_quant=True, bnb_4bit_quant_type="nf4", nf4_lm_head=True,
-                 load_in_8bit=False, llm_int8_threshold=6.0, llm_int8_has_fp16_weight=False, int8_lm_head=True):
+                 load_in_8bit=False, llm_int8_threshold=6.0, llm_int8_has_fp16_weight=False, int8_lm_head=True, lora_state=None,
+                 lora_alpha=16):
         # load_in_4bit: the reference's bitsandbytes 4-bit load (inference.py:133-146): the fp16 mode with the Llama projections,
         # mm_projector, text_hidden_fcs and (nf4_lm_head) lm_head quantised to NF4 (quant.py). Refused combinations are ValueErrors
         if load_in_4bit:
@@ -71,6 +72,21 @@ class LisaMI355:
                 raise ValueError("load_in_8bit: llm_int8_has_fp16_weight=True (the 8-bit training layout) is not supported")
             if not llm_int8_threshold >= 0:
                 raise ValueError(f"load_in_8bit: llm_int8_threshold must be >= 0 (got {llm_int8_threshold})")
+        # lora_state (load_in_4bit only): LisaTrainable.state_dict() of an NF4 fine-tune (train_ds.py --load_in_4bit: latest.pt["params"]).
+        # Its .lora_A / .lora_B pairs are served UNMERGED on the NF4 codes, y = x deq(W)^T + (lora_alpha / r) (x A^T) B^T: the function
+        # the trainer optimised (merging and quantising again is not: DESIGN.md section 8). Its other tensors (embed_tokens, lm_head,
+        # text_hidden_fcs, both mask decoders) replace the same-named entries of state_dict, and the quantised set becomes the
+        # trainer's (train_model.nf4_frozen_linear): lm_head and text_hidden_fcs stay as trained, mm_projector stays NF4
+        lora_pairs, lora_rank = {}, None
+        if lora_state is not None:
+            if not load_in_4bit:
+                raise ValueError("lora_state: unmerged adapters are served on the NF4 base only (load_in_4bit=True); 16-bit bases are "
+                                 "served merged (merge_lora.py)")
+            from . import quant
+            lora_pairs, lora_rank = quant.lora_pairs(lora_state, cfg)
+            state_dict = dict(state_dict)
+            state_dict.update({k: v for k, v in lora_state.items() if not (k.endswith(".lora_A") or k.endswith(".lora_B"))})
+            nf4_lm_head = False
         if not torch.cuda.is_available():
             raise RuntimeError("LisaMI355 needs an MI355X (HIP device); there is no CPU fallback for the hot path")
         from .lib import load_library
@@ -140,7 +156,7 @@ class LisaMI355:
         self.llm_int8_threshold = float(llm_int8_threshold)
         self.llm = LlamaHip(sd, cfg.llm, dtype, dev, nf4=self.load_in_4bit, nf4_double_quant=bnb_4bit_use_double_quant,
                             nf4_lm_head=nf4_lm_head, int8=self.load_in_8bit, int8_threshold=self.llm_int8_threshold,
-                            int8_lm_head=int8_lm_head)
+                            int8_lm_head=int8_lm_head, lora=lora_pairs, lora_scale=(lora_alpha / lora_rank) if lora_rank else 0.0)
         # fp32 residual streams in the bf16 mode: True / "sam" / "llm" — the ViT-H and / or Llama hidden-state
         # stream kept in fp32 between the bf16 MFMA products (2.8x closer to the reference on the image embedding at depth 32)
         self.sam_encoder.fp32_stream = fp32_stream in (True, "sam", "both")
@@ -149,7 +165,7 @@ class LisaMI355:
         def lin_w(name, dt):
             # 4-bit mode: mm_projector and text_hidden_fcs are NF4 Linears in the reference; their values are quantised and
             # dequantised once here and their products keep the 16 / 32-bit paths (their bytes are not what a frame waits for)
-            if self.load_in_4bit:
+            if self.load_in_4bit and (lora_state is None or "text_hidden_fcs" not in name):
                 from . import quant
                 return quant.round_trip(sd[name], dev, bnb_4bit_use_double_quant).to(dt).contiguous()
             if self.load_in_8bit:
@@ -615,15 +631,32 @@ class LisaMI355:
     def from_state_dict(cls, cfg, state_dict, dtype=torch.bfloat16, device="cuda:0", **kw):
         return cls(cfg, state_dict, dtype=dtype, device=device, **kw)
 
+    @staticmethod
+    def read_lora_checkpoint(path, load_in_4bit=True):
+        """The trained tensors of train_ds.py's latest.pt for lora_state=: an NF4 fine-tune's (`base_format` "nf4") only. Adapters
+        fitted on a 16-bit base, and any checkpoint without load_in_4bit, are refused by name: those are served merged."""
+        if not load_in_4bit:
+            raise ValueError(f"lora_checkpoint={path!r} needs load_in_4bit=True: unmerged adapters are served on the NF4 base only; "
+                             "16-bit bases are served merged (merge_lora.py)")
+        blob = torch.load(path, map_location="cpu", weights_only=False)
+        if not (isinstance(blob, dict) and "params" in blob):
+            raise ValueError(f"lora_checkpoint={path!r} is not a train_ds.py checkpoint (no 'params' entry)")
+        if blob.get("base_format") != "nf4":
+            raise ValueError(f"lora_checkpoint={path!r} has base_format={blob.get('base_format')!r}: its adapters were fitted on a "
+                             "16-bit base, not on the NF4 codes (train_ds.py --load_in_4bit); merge it with merge_lora.py instead")
+        return blob["params"]
+
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, vision_tower=None, seg_token_idx=None,
-                        torch_dtype=torch.bfloat16, sam_checkpoint=None, device="cuda:0", **kw):
+                        torch_dtype=torch.bfloat16, sam_checkpoint=None, device="cuda:0", lora_checkpoint=None, **kw):
         """The constructor the reference's CLIs use (inference.py:158-168, chat.py:104-114):
         `LISAForCausalLM.from_pretrained(version, vision_tower=, seg_token_idx=, torch_dtype=)` followed by
         `initialize_vision_modules` — a merged checkpoint directory (merge_lora_weights_and_save_hf_model.py:149-155 layout:
         sharded weights + index + config.json, `vision_tower` keys excluded) plus the CLIP tower from its own directory
         (clip_encoder.py:21-29). Local directories only: there is no hub access in this setting."""
         from . import checkpoint
+        if lora_checkpoint is not None:
+            kw["lora_state"] = cls.read_lora_checkpoint(lora_checkpoint, kw.get("load_in_4bit", False))
         cfg = checkpoint.config_from_dir(pretrained_model_name_or_path)
         if seg_token_idx is not None:
             cfg.seg_token_idx = int(seg_token_idx)

@@ -98,7 +98,7 @@ class ClipTowerHip:
 
 class LlamaHip:
     def __init__(self, sd, cfg, dtype, device, nf4=False, nf4_double_quant=True, nf4_lm_head=True, int8=False, int8_threshold=6.0,
-                 int8_lm_head=True):
+                 int8_lm_head=True, lora=None, lora_scale=0.0):
         l = self.cfg = cfg
         self.dtype, self.device = dtype, device
         dev = device
@@ -110,11 +110,16 @@ class LlamaHip:
         # load_in_4bit (quant.py): the seven projections of every layer (and lm_head unless nf4_lm_head=False) are quant.Nf4Weight.
         # Products of <= 64 rows stream the packed weights (ops.linear_nf4); larger ones dequantise the weight into one f16 scratch
         # right before the existing f16 product (_lin)
+        # lora ({module: (A, B)}, quant.lora_pairs) with lora_scale = alpha / r: adapters fitted on the NF4 base, served UNMERGED on
+        # the codes. Each fused weight carries its quant.Nf4Lora; the streamed product adds the rank update in its epilogue, the
+        # dequantisation folds it into its pass (one kernel each; weights without adapters keep today's)
         self.nf4 = bool(nf4)
         self._scratch = None
+        if lora and not self.nf4:
+            raise ValueError("LlamaHip(lora=): unmerged adapters are served on the NF4 base only; 16-bit bases are served merged")
         if self.nf4:
             assert dtype == torch.float16
-            self._load_nf4(sd, nf4_double_quant, nf4_lm_head)
+            self._load_nf4(sd, nf4_double_quant, nf4_lm_head, lora or {}, lora_scale)
         # load_in_8bit (quant.py, LLM.int8): the seven projections (and lm_head unless int8_lm_head=False) are quant.Int8Weight; every
         # product quantises its input rows with the outlier decomposition and runs on the int8 matrix cores (ops.linear_int8). The
         # outlier columns are per frame and sticky across a frame's decode steps: masks beside the KV cache (new_cache, "i8")
@@ -161,21 +166,27 @@ class LlamaHip:
         # for the bf16 MFMA products. Off by default (it gives up the norm-carrying 5-launch decode layer at <= 8 rows).
         self.fp32_stream = False
 
-    def _load_nf4(self, sd, double_quant, lm_head):
+    def _load_nf4(self, sd, double_quant, lm_head, lora, lora_scale):
         from . import quant
         l, dev = self.cfg, self.device
         H, F = l.hidden, l.ffn
         g_rows, u_rows = quant.swiglu_rows(F)
+
+        def q(parts, seg_rows=16):
+            # parts = [(module, rows)]: the source weights quantised each on its own, their adapters in the same stored row order
+            w = quant.quantize([(sd[m + ".weight"], rows) for m, rows in parts], dev, double_quant)
+            w.lora = quant.lora_pack([(lora.get(m), sd[m + ".weight"].shape[0], rows) for m, rows in parts], w.shape[1], seg_rows,
+                                     lora_scale, dev)
+            return w
         for i in range(l.layers):
             L = f"model.layers.{i}"
-            q = lambda parts: quant.quantize(parts, dev, double_quant)   # noqa: E731
             self.layers.append({
                 "n1": _f32(sd[L + ".input_layernorm.weight"], dev),
-                "wqkv": q([(sd[f"{L}.self_attn.{n}_proj.weight"], None) for n in ("q", "k", "v")]),
-                "wo": q([(sd[L + ".self_attn.o_proj.weight"], None)]),
+                "wqkv": q([(f"{L}.self_attn.{n}_proj", None) for n in ("q", "k", "v")], seg_rows=H),
+                "wo": q([(L + ".self_attn.o_proj", None)]),
                 "n2": _f32(sd[L + ".post_attention_layernorm.weight"], dev),
-                "wgu": q([(sd[L + ".mlp.gate_proj.weight"], g_rows), (sd[L + ".mlp.up_proj.weight"], u_rows)]),
-                "wd": q([(sd[L + ".mlp.down_proj.weight"], None)])})
+                "wgu": q([(L + ".mlp.gate_proj", g_rows), (L + ".mlp.up_proj", u_rows)]),
+                "wd": q([(L + ".mlp.down_proj", None)])})
         if lm_head:
             self.lm_head = quant.quantize([(sd["lm_head.weight"], None)], dev, double_quant)
         # one f16 scratch for the dequantised weight of a prefill-sized product, sized to the largest one (gate|up)
@@ -222,7 +233,7 @@ class LlamaHip:
             q = ops.int8_quantize_act(x, self.int8_threshold, seg_rows, valid, masks)
             return ops.linear_int8(q, w.cb, w.scb, **kw)
         if x.shape[0] <= 64:
-            return ops.linear_nf4(x, w.packed, w.absmax, **kw)
+            return ops.linear_nf4(x, w.packed, w.absmax, lora=w.lora, **kw)
         return ops.linear(x, self._deq(w), **kw)
 
     def weight_bytes(self):
@@ -230,6 +241,11 @@ class LlamaHip:
         def nb(w):
             return w.numel() * w.element_size() if isinstance(w, torch.Tensor) else w.nbytes
         return sum(nb(L[k]) for L in self.layers for k in ("wqkv", "wo", "wgu", "wd")) + nb(self.lm_head)
+
+    def lora_bytes(self):
+        """Device bytes of the unmerged adapters (A_cat and B of every fused weight that has any)."""
+        return sum(L[k].lora.nbytes for L in self.layers for k in ("wqkv", "wo", "wgu", "wd")
+                   if getattr(L[k], "lora", None) is not None)
 
     def _cos_sin(self, tmax):
         if self._cs is None or self._cs.shape[0] < tmax:

@@ -316,6 +316,33 @@ def nf4_dequant(packed, absmax, row_map=None, out=None):
     return out
 
 
+def _check_nf4_lora(lora, N, K):
+    """The adapters of a fused NF4 weight [N, K] (quant.Nf4Lora): a_cat f16 [8 nseg, K], b f16 [N, 8], nseg, seg_rows, scale."""
+    a, b = lora.a_cat, lora.b
+    assert a.dtype == torch.float16 and a.dim() == 2 and a.stride(1) == 1 and a.shape == (8 * lora.nseg, K), (a.shape, lora.nseg, K)
+    assert b.dtype == torch.float16 and b.is_contiguous() and b.shape == (N, 8), (b.shape, N)
+
+
+def nf4_dequant_lora(packed, absmax, lora, row_map=None, out=None):
+    """nf4_dequant with unmerged LoRA adapters folded in (haff_nf4_dequant_lora_f16): f16 [N, K] = f16_rn(NF4[code] * absmax +
+    scale * (B A_cat)[n, k]), each stored row against its own segment's 8 rank rows of A_cat; same row_map contract."""
+    lib = load_library()
+    _req(packed, "packed")
+    N, K = packed.shape[0], packed.shape[1] * 2
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and absmax.dtype == torch.float32 and absmax.is_contiguous()
+    assert absmax.shape == (N, K // 64)
+    _check_nf4_lora(lora, N, K)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float16, device=packed.device)
+    assert out.dtype == torch.float16 and out.stride(1) == 1 and out.shape[1] == K
+    if row_map is not None:
+        assert row_map.dtype == torch.int32 and row_map.numel() == N
+    check(lib.haff_nf4_dequant_lora_f16(packed.data_ptr(), absmax.data_ptr(), N, K, _p(row_map), out.data_ptr(), out.stride(0),
+                                        lora.a_cat.data_ptr(), lora.a_cat.stride(0), lora.b.data_ptr(), lora.nseg, lora.seg_rows,
+                                        float(lora.scale), _stream()), "haff_nf4_dequant_lora_f16")
+    return out
+
+
 def nf4_dequant_t(packed, absmax, row_map=None, out=None):
     """f16 [K, Np] = the TRANSPOSE of nf4_dequant's result (stored row n in column row_map[n], or n), Np = roundup(N, 8), the pad
     columns zero: the layout autograd.transpose(w, Rp=_pad8(N)) gives a frozen weight's resident W^T (haff_nf4_dequant_t_f16).
@@ -336,9 +363,12 @@ def nf4_dequant_t(packed, absmax, row_map=None, out=None):
     return out
 
 
-def linear_nf4(x, packed, absmax, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, out_dtype=None, swiglu=False):
+def linear_nf4(x, packed, absmax, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, out_dtype=None, swiglu=False, lora=None,
+               lora_t=None):
     """linear() with NF4 weights (haff_gemm_nf4_f16): x f16 [M <= 64, K], packed uint8 [N, K/2], absmax f32 [N, K/64]; same
-    epilogue contract as linear()."""
+    epilogue contract as linear(). lora (quant.Nf4Lora): the weight's unmerged adapters; scale * (x A_cat^T) B^T joins the fp32 sums
+    before the epilogue (haff_gemm_nf4_lora_f16). lora_t: t = x A_cat^T as f16 [M, 8 nseg] when the caller has it (one
+    linear(x, a_cat) launch otherwise)."""
     lib = load_library()
     _req(x, "x")
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float16
@@ -357,6 +387,16 @@ def linear_nf4(x, packed, absmax, bias=None, act=ACT_NONE, resid=None, row_map=N
         assert bias.dtype == torch.float32 and bias.numel() == N
     if row_map is not None:
         assert row_map.dtype == torch.int32 and row_map.numel() == M
+    if lora is not None:
+        _check_nf4_lora(lora, N, K)
+        t = linear(x, lora.a_cat) if lora_t is None else lora_t
+        assert t.dtype == torch.float16 and t.stride(1) == 1 and t.shape == (M, 8 * lora.nseg)
+        rc = lib.haff_gemm_nf4_lora_f16(x.data_ptr(), x.stride(0), packed.data_ptr(), absmax.data_ptr(), out.data_ptr(), out.stride(0),
+                                        _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
+                                        1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, t.data_ptr(), t.stride(0),
+                                        lora.b.data_ptr(), lora.nseg, lora.seg_rows, float(lora.scale), _stream())
+        check(rc, "haff_gemm_nf4_lora_f16")
+        return out
     rc = lib.haff_gemm_nf4_f16(x.data_ptr(), x.stride(0), packed.data_ptr(), absmax.data_ptr(), out.data_ptr(), out.stride(0),
                                _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
                                1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, _stream())

@@ -83,12 +83,15 @@ class Nf4Weight:
     def __init__(self, packed, absmax):
         self.packed, self.absmax = packed, absmax
         self.shape = (packed.shape[0], packed.shape[1] * 2)
+        self.lora = None   # Nf4Lora: unmerged adapters served on top of the codes (lora_pack)
 
     @property
     def nbytes(self):
         return self.packed.numel() + self.absmax.numel() * 4
 
     def dequant(self, row_map=None, out=None):
+        if self.lora is not None:
+            return ops.nf4_dequant_lora(self.packed, self.absmax, self.lora, row_map=row_map, out=out)
         return ops.nf4_dequant(self.packed, self.absmax, row_map=row_map, out=out)
 
     def dequant_t(self, row_map=None, out=None):
@@ -114,6 +117,85 @@ def quantize(parts, device, double_quant=True):
         del w16
         r0 += n
     return Nf4Weight(packed, absmax)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Unmerged LoRA adapters on NF4 weights: serving what `train_ds.py --load_in_4bit` (QLoRA) fitted against the codes
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The trainer optimised y = x deq(Q(W))^T + s (x A^T) B^T. Merging s B A into the 16-bit W and quantising again serves another
+# function (the second quantisation's error exceeds a small adapter's whole effect), so the adapters stay
+# beside the codes. Per fused weight: A_cat f16 [8 nseg, K] (8 rank rows per row segment: q | k | v, gate | up, or the one of o /
+# down; rank < 8 zero-padded, an unadapted segment zero) and B f16 [N, 8] in the STORED row order (the quantiser's row maps).
+LORA_MAX_RANK = 8   # the fused training nodes' limit (autograd.py), and the 8 k-slots of a segment in the decode kernel's MFMA
+LORA_PROJ = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+_LORA_MODULE = re.compile(r"^model\.layers\.(\d+)\.(self_attn\.(q|k|v|o)_proj|mlp\.(gate|up|down)_proj)$")
+
+
+class Nf4Lora:
+    """The adapters of one fused NF4 weight on the device (layout above); scale = lora_alpha / r."""
+
+    def __init__(self, a_cat, b, nseg, seg_rows, scale):
+        self.a_cat, self.b, self.nseg, self.seg_rows, self.scale = a_cat, b, int(nseg), int(seg_rows), float(scale)
+
+    @property
+    def nbytes(self):
+        return (self.a_cat.numel() + self.b.numel()) * 2
+
+
+def lora_pairs(lora_state, cfg):
+    """{module: (A [r, in], B [out, r])} of a LisaTrainable.state_dict()'s `.lora_A` / `.lora_B` keys, checked on the host against the
+    Llama geometry of cfg: a module outside the seven projections of an existing layer, a missing half of a pair, rank > 8, ranks
+    that differ between modules (one scale alpha / r serves a fused weight) and shapes that do not fit raise ValueError naming the
+    module. Returns (pairs, r) (r None without adapters)."""
+    H, F = cfg.llm.hidden, cfg.llm.ffn
+    dims = {"q_proj": (H, H), "k_proj": (H, H), "v_proj": (H, H), "o_proj": (H, H), "gate_proj": (H, F), "up_proj": (H, F),
+            "down_proj": (F, H)}   # (in_features, out_features)
+    if H % 16:
+        raise ValueError(f"lora_state: the q | k | v row segments need hidden % 16 == 0 (hidden = {H})")
+    pairs, rank = {}, None
+    mods = sorted({k.rsplit(".", 1)[0] for k in lora_state if k.endswith(".lora_A") or k.endswith(".lora_B")})
+    for mod in mods:
+        m = _LORA_MODULE.match(mod)
+        if not m or int(m.group(1)) >= cfg.llm.layers:
+            raise ValueError(f"lora_state: {mod} is not one of the Llama projections ({', '.join(LORA_PROJ)} of layers 0.."
+                             f"{cfg.llm.layers - 1}); adapters are served on those only")
+        if mod + ".lora_A" not in lora_state or mod + ".lora_B" not in lora_state:
+            raise ValueError(f"lora_state: {mod} has only one of .lora_A / .lora_B")
+        a, b = lora_state[mod + ".lora_A"], lora_state[mod + ".lora_B"]
+        fin, fout = dims[mod.rsplit(".", 1)[1]]
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != fin or b.shape[0] != fout or b.shape[1] != a.shape[0] or a.shape[0] < 1:
+            raise ValueError(f"lora_state: {mod}: lora_A {tuple(a.shape)} / lora_B {tuple(b.shape)} do not fit a [{fout}, {fin}] "
+                             f"weight (expected [r, {fin}] and [{fout}, r])")
+        r = a.shape[0]
+        if r > LORA_MAX_RANK:
+            raise ValueError(f"lora_state: {mod} has rank {r}; adapters are served up to rank {LORA_MAX_RANK}")
+        if rank is not None and r != rank:
+            raise ValueError(f"lora_state: {mod} has rank {r}, other modules {rank}; one lora_alpha / r serves every adapter")
+        rank = r
+        pairs[mod] = (a, b)
+    return pairs, rank
+
+
+def lora_pack(parts, K, seg_rows, scale, device):
+    """Nf4Lora of a fused weight from its source weights' adapters, in quantize()'s order and with its row maps: parts =
+    [(pair or None, n_i, rows or None)], pair = (A [r, K], B [n_i, r]). None when no part is adapted."""
+    if all(pair is None for pair, _, _ in parts):
+        return None
+    nseg = len(parts)
+    R = sum(n for _, n, _ in parts)
+    a_cat = torch.zeros((8 * nseg, K), dtype=torch.float16)
+    b_all = torch.zeros((R, 8), dtype=torch.float16)
+    r0 = 0
+    for i, (pair, n, rows) in enumerate(parts):
+        if rows is None:
+            rows = torch.arange(r0, r0 + n)
+        if pair is not None:
+            a, b = pair
+            r = a.shape[0]
+            a_cat[8 * i:8 * i + r] = a.detach().to("cpu", torch.float16)
+            b_all[rows, :r] = b.detach().to("cpu", torch.float16)
+        r0 += n
+    return Nf4Lora(a_cat.to(device).contiguous(), b_all.to(device).contiguous(), nseg, seg_rows, scale)
 
 
 def swiglu_rows(F):

@@ -105,6 +105,22 @@ int haff_nf4_dequant_t_f16(const void* packed, const float* absmax, int N, int K
 int haff_gemm_nf4_f16(const void* A, long lda, const void* Wq, const float* absmax, void* C, long ldc, const float* bias,
                       const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
                       void* stream);
+/* Unmerged LoRA adapters on an NF4 weight (serving adapters fitted on the NF4 base): y = x . deq(W)^T + scale * (x . A^T) . B^T.
+ * A fused weight has nseg (1..4) row segments of seg_rows stored rows (seg_rows % 16 == 0): stored row n belongs to segment
+ * (n / seg_rows) % nseg (q | k | v: 3 x H; [gate x16 | up x16]: 2 x 16; o / down: 1). A_cat f16 [8 nseg][lda >= K]: 8 rank rows per
+ * segment (rank < 8 zero-padded, an unadapted segment's rows zero); B f16 [N][8]: each stored row's own coefficients, in the stored
+ * row order. A_cat / B / t 16-B aligned, lda % 8 == 0. Layout violations: -1, before any launch.
+ * haff_nf4_dequant_lora_f16: haff_nf4_dequant_f16 (same arguments, same refusals) with the update folded into the pass:
+ *   out[row_map[n]][k] = f16_rn(fl32(d + fl32(scale * u))), d = fl32(NF4[code] * absmax), u = the fp32 sum over j = 0..7, in that
+ *   order, of B[n][j] * A_cat[8 seg(n) + j][k] (each product exact, each add rounded once).
+ * haff_gemm_nf4_lora_f16: haff_gemm_nf4_f16 (same arguments, same refusals) with scale * sum_j t[m][8 seg(n) + j] * B[n][j] added
+ *   to the fp32 sums before bias, act, SwiGLU and resid; t = x . A_cat^T as f16 [M][ldt], ldt >= 8 nseg, ldt % 8 == 0. Bitwise
+ *   repeatable. */
+int haff_nf4_dequant_lora_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out, long ldo,
+                              const void* A_cat, long lda, const void* B, int nseg, int seg_rows, float scale, void* stream);
+int haff_gemm_nf4_lora_f16(const void* A, long lda, const void* Wq, const float* absmax, void* C, long ldc, const float* bias,
+                           const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
+                           const void* t, long ldt, const void* B, int nseg, int seg_rows, float scale, void* stream);
 /* LLM.int8 language-model weights of the fp16 mode (load_in_8bit; csrc/gemm_int8.hip, arithmetic restated in quant.py). K % 64 == 0.
  * haff_int8_quantize_weight_f16: f16 W [N][K] (row stride ldw, 16-B aligned) -> CB int8 [.][K] = rint(w * (127 / SCB)) and
  * SCB f32 = max |W[n][:]| (0: all-zero codes), source row n written to row row_map[n] (NULL: n). CB 16-B aligned. */
