@@ -193,6 +193,31 @@ class AffRecordsDataset(torch.utils.data.Dataset):
                torch.from_numpy(right).unsqueeze(0), taxonomy, label, resize, [question], [text])
         return out + (self.inference,)
 
+    def raw_item(self, idx):
+        """What train_ingest.DeviceIngest builds the sample from on the device: no resize, no normalised tensor, no filled mask, no
+        label planes. Draws from self.rng in __getitem__'s order (record, then question, then answer), so a seeded run sees the
+        same samples and prompts either way."""
+        item = self.records[self.rng.randint(0, self.size - 1)]
+        text = item.get("narration", item.get("text", ""))
+        if isinstance(text, bytes):
+            text = text.decode("utf-8")
+        image = np.array(item["image"] if "image" in item else item["inpainted"])
+        if image.ndim == 2:
+            image = np.stack([image] * 3, -1)
+        image = np.ascontiguousarray(image[..., :3]).astype(np.uint8)
+        m = item.get("masks") or {}
+        shape = tuple(int(x) for x in m.get("original_size", self.original_size or image.shape[:2]))
+        question = self.rng.choice(SHORT_QUESTION_LIST).format(class_name=text.lower())
+        answer = self.rng.choice(ANSWER_LIST)
+        conv = hprompt.default_conversation()
+        conv.append_message(conv.roles[0], question)
+        conv.append_message(conv.roles[1], answer)
+        # the vertex lists as cvlite.draw_contours_filled reads them (int32 [n,2]): converted here, off the main thread
+        left, right = ([np.asarray(c, dtype=np.int32).reshape(-1, 2) for c in m.get(k) or []] for k in ("aff_left", "aff_right"))
+        return {"frame": image, "contours_left": left, "contours_right": right, "mask_hw": shape,
+                "taxonomy": _taxonomy_vector(item.get("taxonomy", 2)), "conversations": [conv.get_prompt()],
+                "questions": [question], "texts": [text], "inference": self.inference}
+
 
 class AffValDataset(torch.utils.data.Dataset):
     """AffDatasetVal (aff_dataset.py:350-544): the ActAffordance-style benchmark folders as validation samples."""
@@ -259,3 +284,20 @@ class AffValDataset(torch.utils.data.Dataset):
         conv.append_message(conv.roles[1], answer)
         return (None, image_t, image_clip, [conv.get_prompt()], torch.from_numpy(left).unsqueeze(0),
                 torch.from_numpy(right).unsqueeze(0), taxonomy, label, resize, [question], [text], True)
+
+    def raw_item(self, idx):
+        """AffRecordsDataset.raw_item for the benchmark folders: the ground truth is the PNG planes themselves. Same rng order as
+        __getitem__ (sample, then question, then answer)."""
+        idx = self.rng.randint(0, self.size - 1)
+        text, image, taxonomy = self.narrations[idx], self.images[idx], self.taxonomies[idx]
+        if image.ndim == 2:
+            image = np.stack([image] * 3, -1)
+        image = np.ascontiguousarray(image[..., :3]).astype(np.uint8)
+        left, right = self.affs_left[idx], self.affs_right[idx]
+        question = self.rng.choice(SHORT_QUESTION_LIST).format(class_name=text.lower())
+        answer = self.rng.choice(ANSWER_LIST)
+        conv = hprompt.default_conversation()
+        conv.append_message(conv.roles[0], question)
+        conv.append_message(conv.roles[1], answer)
+        return {"frame": image, "plane_left": left, "plane_right": right, "mask_hw": tuple(left.shape), "taxonomy": taxonomy,
+                "conversations": [conv.get_prompt()], "questions": [question], "texts": [text], "inference": True}

@@ -1060,3 +1060,56 @@ def clip_normalize_u8(frames, top, left, size, lut, out_dtype):
                                     _dt(out), _stream())
     check(rc, "haff_clip_normalize_u8")
     return out
+
+
+FILL_MAX_VERTS, FILL_MAX_COORD = 4096, 32768   # haff_fill_contours_u8's host-checked limits (csrc/contour_fill.hip)
+
+
+def contour_points(contour):
+    """One OpenCV-style contour ([n,2] or [n,1,2], any number type) as cvlite.draw_contours_filled reads it: int32 [n,2]."""
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(contour, dtype=np.int32).reshape(-1, 2))
+
+
+def fill_contours_supported(contour):
+    """Whether haff_fill_contours_u8 takes this polygon (vertex count and coordinate range); beyond that the caller fills on the host."""
+    pts = contour_points(contour)
+    return len(pts) <= FILL_MAX_VERTS and (len(pts) == 0 or int(abs(pts).max()) < FILL_MAX_COORD)
+
+
+def fill_contours(planes, hw, device, out=None):
+    """cvlite.draw_contours_filled for a batch of planes in one launch. planes: one list of contours per output plane;
+    returns uint8 [len(planes), H, W] of 0 / 1 (zeroed by the call itself: `out` may hold anything)."""
+    import numpy as np
+    lib = load_library()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("fill_contours runs in HBM (cuda device); the hot path has no CPU fallback")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    H, W = int(hw[0]), int(hw[1])
+    polys, plane_of = [], []
+    for i, contours in enumerate(planes):
+        for c in contours or []:
+            polys.append(contour_points(c))
+            plane_of.append(i)
+    n_poly, n_planes = len(polys), len(planes)
+    off = np.zeros((n_poly + 1,), dtype=np.int32)
+    if n_poly:
+        off[1:] = np.cumsum([len(p) for p in polys])
+    n_pts = int(off[-1])
+    desc = torch.empty((2 * n_poly + 1 + 2 * n_pts,), dtype=torch.int32, pin_memory=True)
+    d = desc.numpy()
+    d[:n_poly + 1] = off
+    d[n_poly + 1:2 * n_poly + 1] = plane_of
+    if n_pts:
+        d[2 * n_poly + 1:] = np.concatenate(polys, 0).reshape(-1)
+    if out is None:
+        out = torch.empty((n_planes, H, W), dtype=torch.uint8, device=device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n_planes, H, W) and out.device == device
+    desc_dev = desc.to(device, non_blocking=True)
+    host = desc.data_ptr()
+    rc = lib.haff_fill_contours_u8(host + 4 * (2 * n_poly + 1), host, host + 4 * (n_poly + 1), desc_dev.data_ptr(), n_poly, n_planes,
+                                   out.data_ptr(), H, W, _stream())
+    check(rc, "haff_fill_contours_u8")
+    return out

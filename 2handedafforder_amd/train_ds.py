@@ -12,6 +12,9 @@ step with bucketed RCCL all-reduces over xGMI; optimizer state is 
 The 2HANDS loaders (h5 / HF datasets, cv2 contour masks) are replaced by a seeded synthetic sample generator that
 emits the same 12-tuple per sample and the same collate_fn batch dict (utils/dataset.py:47-60,152-169).
 
+--device_ingest (off by default; real datasets only): the batch is made on the device from uint8 frames, contour lists and token
+ids that one prefetch thread prepares (train_ingest.py) instead of on the main thread inside the step loop.
+
   python -m torch.distributed.run --nproc-per-node 8 2handedafforder_amd/train_ds.py --synthetic 7b --epochs 1 ...
 """
 import argparse
@@ -27,10 +30,12 @@ if __package__ in (None, ""):
     import haff  # noqa: F401
     from haff import checkpoint, config as hcfg, dist as hdist, prompt as hprompt, train_ops as T
     from haff.aff_dataset import AffRecordsDataset
+    from haff.train_ingest import DeviceIngest, Prefetcher
     from haff.train_model import LisaTrainable
 else:
     from . import checkpoint, config as hcfg, dist as hdist, prompt as hprompt, train_ops as T
     from .aff_dataset import AffRecordsDataset
+    from .train_ingest import DeviceIngest, Prefetcher
     from .train_model import LisaTrainable
 
 
@@ -89,6 +94,10 @@ def parse_args(args):
     p.add_argument("--val_samples", default=4, type=int)
     p.add_argument("--mask_hw", default=None, type=int, nargs=2, help="ground-truth mask size (default: image size)")
     p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--device_ingest", action="store_true", default=False,
+                   help="make the batch on the device (train_ingest.py): the loader hands over uint8 frames, contour lists and token "
+                        "ids from one prefetch thread; resizes, normalisation and the contour fill are HIP kernels. Same samples and "
+                        "prompts as the host loader for one --seed. Not with --synthetic, whose dataset yields tensors")
     return p.parse_args(args)
 
 
@@ -174,24 +183,13 @@ class SyntheticAffDataset:
                 (S, S), [QUESTION.format(action)], [action], self.inference)
 
 
-def collate_fn(batch, tokenizer, model_max_length=575, use_mm_start_end=True, conv_type="llava_v1"):
-    """utils/dataset.py:30-169: pad with pad_token, mask the instruction spans with -100; conv_type picks the template whose sep2
-    splits the rounds and the separator that ends a round's instruction (:97-101: " ASSISTANT: " or "[/INST] ")."""
-    images, clips, convs, ml, mr, labels_l, resizes, tax, offs = [], [], [], [], [], [], [], [], [0]
-    paths, questions, classes = [], [], []
-    for (path, image, image_clip, conversations, m_left, m_right, taxonomy, label, resize, _q, _c, inference) in batch:
-        paths.append(path)
-        questions.append(_q)
-        classes.append(_c)
-        images.append(image)
-        clips.append(image_clip)
-        convs.extend(conversations)
-        ml.append(m_left.float())
-        mr.append(m_right.float())
-        labels_l.append(label)
-        resizes.append(resize)
-        tax.append(torch.tensor(taxonomy))
-        offs.append(offs[-1] + len(conversations))
+def collate_text(conversations, tokenizer, model_max_length=575, use_mm_start_end=True, conv_type="llava_v1", inference=False,
+                 offsets=None):
+    """The text half of collate_fn (utils/dataset.py:62-150), shared with train_ingest.DeviceIngest: image placeholder, token ids
+    padded with pad_token, the instruction spans masked with -100, truncation for training batches. `conversations` is the flat
+    list of prompts, `offsets` the per-sample prefix counts (one conversation per sample when left out)."""
+    convs = list(conversations)
+    offs = list(offsets) if offsets is not None else list(range(len(convs) + 1))
     if use_mm_start_end:
         convs = [c.replace(hprompt.DEFAULT_IMAGE_TOKEN, hprompt.image_placeholder(True)) for c in convs]
     ids = [hprompt.tokenizer_image_token(c, tokenizer, return_tensors="pt") for c in convs]
@@ -214,13 +212,36 @@ def collate_fn(batch, tokenizer, model_max_length=575, use_mm_start_end=True, co
             target[cur:cur + instruction_len] = -100
             cur += round_len
         target[cur:] = -100
-    if not batch[0][-1]:
+    if not inference:
         trunc = model_max_length - 255
         input_ids, targets, attention_masks = input_ids[:, :trunc], targets[:, :trunc], attention_masks[:, :trunc]
-    return {"images": torch.stack(images, 0), "images_clip": torch.stack(clips, 0), "input_ids": input_ids,
-            "labels": targets, "attention_masks": attention_masks, "masks_list_left": ml, "masks_list_right": mr,
-            "label_list": labels_l, "resize_list": resizes, "offset": torch.LongTensor(offs),
-            "inference": batch[0][-1], "conversation_list": convs, "taxonomies_list": torch.stack(tax, 0),
+    return {"input_ids": input_ids, "labels": targets, "attention_masks": attention_masks, "offset": torch.LongTensor(offs),
+            "conversation_list": convs}
+
+
+def collate_fn(batch, tokenizer, model_max_length=575, use_mm_start_end=True, conv_type="llava_v1"):
+    """utils/dataset.py:30-169: pad with pad_token, mask the instruction spans with -100; conv_type picks the template whose sep2
+    splits the rounds and the separator that ends a round's instruction (:97-101: " ASSISTANT: " or "[/INST] ")."""
+    images, clips, convs, ml, mr, labels_l, resizes, tax, offs = [], [], [], [], [], [], [], [], [0]
+    paths, questions, classes = [], [], []
+    for (path, image, image_clip, conversations, m_left, m_right, taxonomy, label, resize, _q, _c, inference) in batch:
+        paths.append(path)
+        questions.append(_q)
+        classes.append(_c)
+        images.append(image)
+        clips.append(image_clip)
+        convs.extend(conversations)
+        ml.append(m_left.float())
+        mr.append(m_right.float())
+        labels_l.append(label)
+        resizes.append(resize)
+        tax.append(torch.tensor(taxonomy))
+        offs.append(offs[-1] + len(conversations))
+    text = collate_text(convs, tokenizer, model_max_length, use_mm_start_end, conv_type, inference=batch[0][-1], offsets=offs)
+    return {"images": torch.stack(images, 0), "images_clip": torch.stack(clips, 0), "input_ids": text["input_ids"],
+            "labels": text["labels"], "attention_masks": text["attention_masks"], "masks_list_left": ml, "masks_list_right": mr,
+            "label_list": labels_l, "resize_list": resizes, "offset": text["offset"],
+            "inference": batch[0][-1], "conversation_list": text["conversation_list"], "taxonomies_list": torch.stack(tax, 0),
             "image_paths": paths, "questions_list": questions, "sampled_classes_list": classes}
 
 
@@ -240,14 +261,18 @@ def calculate_iocm(benchmark_mask, comparison_mask):
 
 
 @torch.no_grad()
-def validate(model, dataset, tokenizer, args, rank, world, device):
-    """train_ds.py:625-758: teacher-forced forward(inference=True), masks > 0, taxonomy-gated union of L/R vs GT union."""
+def validate(model, dataset, tokenizer, args, rank, world, device, ingest=None):
+    """train_ds.py:625-758: teacher-forced forward(inference=True), masks > 0, taxonomy-gated union of L/R vs GT union.
+    ingest (--device_ingest): the DeviceIngest that makes each batch on the device from dataset.raw_item."""
     model.eval()
     iou_m, iocm_m = AverageMeter("IoU"), AverageMeter("IoCM")
     lo, hi = hdist.shard_bounds(len(dataset), rank, world)
     for idx in range(lo, hi):
-        batch = collate_fn([dataset[idx]], tokenizer, args.model_max_length, conv_type=args.conv_type)
-        batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
+        if ingest is not None:
+            batch = ingest.batch([dataset.raw_item(idx)], tokenizer, args.model_max_length, args.conv_type)
+        else:
+            batch = collate_fn([dataset[idx]], tokenizer, args.model_max_length, conv_type=args.conv_type)
+            batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
         out = model(**batch)
         t = int(out["pred_taxonomies"][0][0].argmax())
         left = (out["pred_masks_left"][0][0] > 0).cpu().numpy()
@@ -275,7 +300,19 @@ def precision_dtype(precision):
 
 
 def main(argv):
+    closers = []   # what must end with the run however it ends (the --device_ingest prefetch thread)
+    try:
+        _main(argv, closers)
+    finally:
+        for close in closers:
+            close()
+
+
+def _main(argv, closers):
     args = parse_args(argv)
+    if args.device_ingest and args.synthetic:
+        raise SystemExit("--device_ingest cannot be combined with --synthetic: the synthetic dataset yields tensors, not uint8 frames "
+                         "and contours (use --sam_records or --dataset_dir)")
     if args.load_in_8bit:
         raise SystemExit("--load_in_8bit: LLM.int8 is not built for training (inference only; --load_in_4bit trains on the NF4 base)")
     if args.load_in_4bit and args.precision != "fp16":
@@ -371,12 +408,18 @@ def main(argv):
         if rank == 0:
             print(f"Training with {len(train_ds)} examples and validating with {len(val_ds)} examples.")
     total_steps = args.epochs * args.steps_per_epoch
+    ingest = DeviceIngest(cfg, device, dtype) if args.device_ingest else None
     if args.eval_only:
-        iou, iocm = validate(model, val_ds, tokenizer, args, rank, world, device)
+        iou, iocm = validate(model, val_ds, tokenizer, args, rank, world, device, ingest)
         if rank == 0:
             print(f"IoU: {iou:.4f}, IoCM: {iocm:.4f}")
         return
     sample_idx = global_step * args.grad_accumulation_steps * args.batch_size
+    prefetch = None
+    if ingest is not None:   # one thread, two batches ahead: raw_item (decode, prompt) and the tokeniser, in sample order
+        prefetch = Prefetcher(train_ds.raw_item, sample_idx, args.batch_size,
+                              prepare=lambda raws: ingest.text(raws, tokenizer, args.model_max_length, args.conv_type))
+        closers.append(prefetch.close)
     for epoch in range(start_epoch, args.epochs):
         meters = [AverageMeter("Time", ":6.3f"), AverageMeter("Loss", ":.4f"), AverageMeter("CeLoss", ":.4f"),
                   AverageMeter("MaskLoss", ":.4f"), AverageMeter("MaskBCELoss", ":.4f"), AverageMeter("MaskDICELoss", ":.4f"),
@@ -389,10 +432,14 @@ def main(argv):
         for step in range(args.steps_per_epoch):
             reducer.zero()
             for micro in range(args.grad_accumulation_steps):
-                batch = collate_fn([train_ds[sample_idx + j] for j in range(args.batch_size)], tokenizer, args.model_max_length,
-                                   conv_type=args.conv_type)
+                if prefetch is not None:
+                    raws, text = prefetch.get()
+                    batch = ingest.batch(raws, tokenizer, args.model_max_length, args.conv_type, text=text)
+                else:
+                    batch = collate_fn([train_ds[sample_idx + j] for j in range(args.batch_size)], tokenizer, args.model_max_length,
+                                       conv_type=args.conv_type)
+                    batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
                 sample_idx += args.batch_size
-                batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
                 out = model(**batch)
                 # gradients accumulate into the bucket views across the micro-steps; on the last one each bucket's
                 # all-reduce (RCCL) is issued as soon as its last gradient lands, under the rest of backward
@@ -446,7 +493,7 @@ def main(argv):
                 for m in meters:
                     m.reset()
         if not args.no_eval:
-            iou, iocm = validate(model, val_ds, tokenizer, args, rank, world, device)
+            iou, iocm = validate(model, val_ds, tokenizer, args, rank, world, device, ingest)
             if rank == 0:
                 print(f"IoU: {iou:.4f}, IoCM: {iocm:.4f}")
             is_best = iou > best_score

@@ -20,6 +20,7 @@ import torch
 from . import autograd as A
 from . import ops
 from .lisa import IMAGE_TOKEN_INDEX, N_IMG_PAD, LisaMI355
+from .preprocess import SAM_MEAN, SAM_STD
 
 V = "model.visual_model"
 ACT_GELU, ACT_RELU = 1, 3
@@ -385,7 +386,10 @@ class LisaTrainable:
 
     # -- model_forward -----------------------------------------------------------------------------------------------
     def forward(self, images, images_clip, input_ids, labels, attention_masks, offset, masks_list_left, masks_list_right,
-                taxonomies_list, label_list, resize_list, inference=False, **kwargs):
+                taxonomies_list, label_list, resize_list, inference=False, frames_u8=None, **kwargs):
+        """frames_u8 (train_ds.py --device_ingest): the batch's uint8 HWC frames, one [B,H,W,3] tensor or a list of [H,W,3] of different
+        sizes. The frozen SAM encoder is then fed from them on the device, as LisaMI355.evaluate(frames_u8=) does, and `images` may be
+        None. Everything behind the encoder is the same code either way."""
         cfg, dev = self.cfg, self.device
         base = self.base
         # Host-side bookkeeping FIRST, from host copies of the small integer inputs (one early read of input_ids / offset /
@@ -423,11 +427,20 @@ class LisaTrainable:
         cur = torch.cuda.current_stream(dev)
         sam_stream = base._sam_stream if (self.overlap_sam and dev.type == "cuda") else cur
         with torch.no_grad():
-            images = images.to(dev)
+            if frames_u8 is None:
+                images = images.to(dev)
+            elif torch.is_tensor(frames_u8):
+                frames_u8 = frames_u8.to(dev)
             if sam_stream is not cur:
                 sam_stream.wait_stream(cur)
             with torch.cuda.stream(sam_stream):
-                emb = base.get_visual_embs(images)                                # frozen SAM encoder (LISA.py:191)
+                if frames_u8 is None:
+                    emb = base.get_visual_embs(images)                            # frozen SAM encoder (LISA.py:191)
+                elif torch.is_tensor(frames_u8):   # ResizeLongestSide on the device, normalise + pad fused into the patchify
+                    sam_u8, _ = base.frame_ingest().sam_frames(frames_u8, cfg.sam.img_size)
+                    emb = base.get_visual_embs_u8(sam_u8, SAM_MEAN, SAM_STD)
+                else:
+                    emb = base.get_visual_embs_frames(list(frames_u8), SAM_MEAN, SAM_STD)
             n_conv = input_ids.shape[0]
             reps = [off_host[i + 1] - off_host[i] for i in range(len(off_host) - 1)]
             clip_rep = torch.cat([images_clip[i:i + 1].expand(r, -1, -1, -1) for i, r in enumerate(reps)], 0)

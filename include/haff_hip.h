@@ -517,6 +517,19 @@ int haff_resample_u8(const void* in, void* out, int B, int Hin, int Win, int Hou
  * -> out [B][3][S][S], out_dtype 0 bf16 / 1 f32 (the images_clip argument of LISAForCausalLM.evaluate, LISA.py:432) */
 int haff_clip_normalize_u8(const void* in, void* out, int B, int Hin, int Win, int top, int left, int S, const float* lut,
                            int out_dtype, void* stream);
+/* Ground-truth masks of the fine-tune loader on the device: cv2.drawContours(mask, [contour], -1, 1, thickness=FILLED) per contour
+ * (utils/aff_dataset.py:340-346) for a batch of planes in one call, byte for byte what cvlite.draw_contours_filled gives: the
+ * 8-connected Bresenham outline of every edge (closing edge included, from the smaller-x end, clipped per pixel), then the 16.16
+ * fixed-point scanline fill with crossings paired in x order WITHIN one polygon. out u8 [n_planes][H][W] holds 0 / 1.
+ * ZEROING `out` IS PART OF THE CALL (a memset on `stream` in front of the kernels): the caller hands over any buffer.
+ * pts i32 [n_pts][2] (x, y), poly_off i32 [n_poly + 1] (poly_off[0] == 0, non-decreasing, n_pts = poly_off[n_poly]) and poly_plane
+ * i32 [n_poly] (the output plane of each polygon) are HOST arrays: they are checked here and never read by a kernel. desc_dev is the
+ * caller's DEVICE copy of the same values, i32 [poly_off | poly_plane | pts] back to back, uploaded in stream order before the call.
+ * Limits, all checked on the host copy before anything is enqueued: at most 4096 vertices per polygon, every |coordinate| < 32768,
+ * H, W <= 32768, planes in range. Beyond them HAFF_ERR_BAD_ARG, and nothing is launched or zeroed. Within them no input can fail on
+ * the device: the per-row crossing list lives in LDS sized by the launch's longest polygon. n_poly == 0 only zeroes. */
+int haff_fill_contours_u8(const int* pts, const int* poly_off, const int* poly_plane, const int* desc_dev, int n_poly, int n_planes,
+                          void* out, int H, int W, void* stream);
 /* mask > logit_th -> 0/255 bytes (inference.py:294-301 with logit_th = logit(th); chat.py:226 with 0) */
 int haff_threshold_masks(const float* in, void* out, long total, float logit_th, void* stream);
 /* a15 in one pass — the output gating + thresholds of 2Haff/inference.py:276-334 and chat.py:226-253:
