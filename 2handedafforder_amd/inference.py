@@ -6,6 +6,9 @@
 
 Offline extras: --synthetic (seeded random weights + byte tokenizer, for plumbing runs without checkpoints).
 Images are read/written with PIL (cv2 is not a dependency here); thresholds and file names follow :197,299,331.
+
+--score scores the run against the aff_*.png under --benchmark-dir on the device, as `evaluation.py --map` would score the written
+tree (scoring.BenchmarkScorer, one kernel launch per batch, one host read at the end); --score_only writes no PNGs at all.
 """
 import argparse
 import json
@@ -18,10 +21,10 @@ import torch
 if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import haff  # noqa: F401
-    from haff import checkpoint, config as hcfg, postprocess, preprocess, prompt as hprompt
+    from haff import checkpoint, config as hcfg, postprocess, preprocess, prompt as hprompt, scoring
     from haff.lisa import LisaMI355
 else:
-    from . import checkpoint, config as hcfg, postprocess, preprocess, prompt as hprompt
+    from . import checkpoint, config as hcfg, postprocess, preprocess, prompt as hprompt, scoring
     from .lisa import LisaMI355
 
 
@@ -46,7 +49,30 @@ def parse_args(args):
     parser.add_argument("--max-new-tokens", default=512, type=int)
     parser.add_argument("--batch-size", default=1, type=int,
                         help="frames per evaluate() call (the reference runs 1; prompts of different lengths are right-padded)")
-    return parser.parse_args(args)
+    # scoring on the device (scoring.py): off by default, the written files are the same either way
+    parser.add_argument("--score", action="store_true", default=False,
+                        help="also score the masks against <benchmark-dir>/<video>/<frame>/aff_{left,right}.png on the device and "
+                             "print what `evaluation.py --map` prints for the written tree")
+    parser.add_argument("--score_only", action="store_true", default=False,
+                        help="--score without writing any PNG: nothing is read back per frame")
+    parser.add_argument("--score_cropped", action="store_true", default=False, help="evaluation.py --cropped: score at the frame's size")
+    parser.add_argument("--score_intersection", action="store_true", default=False,
+                        help="evaluation.py --intersection: a hand counts only inside its obj_<side>.png")
+    parser.add_argument("--score_hausdorff", action="store_true", default=False,
+                        help="also the two Hausdorff distances (the union planes are read back; the contour walk runs in a host thread)")
+    args = parser.parse_args(args)
+    check_score_args(args)
+    return args
+
+
+def check_score_args(args):
+    """--score_only implies --score; the modifiers mean nothing without it, and scoring needs the benchmark's masks."""
+    args.score = bool(args.score or args.score_only)
+    for flag in ("score_cropped", "score_intersection", "score_hausdorff"):
+        if getattr(args, flag) and not args.score:
+            raise SystemExit(f"--{flag} modifies --score / --score_only: pass one of them")
+    if args.score and not args.benchmark_dir:
+        raise SystemExit("--score needs --benchmark-dir: the ground truth is its aff_{left,right}.png")
 
 
 PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -165,9 +191,26 @@ def iter_examples(benchmark_dir):
 
 
 def main(argv):
+    """Returns the score report (evaluation.evaluate_folders' dict) with --score, else None."""
     args = parse_args(argv)
+    closers = []   # what must end with the run however it ends (the --score_hausdorff worker thread)
+    try:
+        return _main(args, closers)
+    finally:
+        for close in closers:
+            close()
+
+
+def _main(args, closers):
     model, tokenizer, cfg, dtype = build_model_and_tokenizer(args)
     device = model.device
+    scorer = None
+    if args.score:
+        stem = os.path.basename(os.path.normpath(args.vis_save_path))
+        scorer = scoring.BenchmarkScorer(args.benchmark_dir, device, postprocess.THRESHOLDS,
+                                         names=[stem + str(th) for th in postprocess.THRESHOLDS], cropped=args.score_cropped,
+                                         intersection=args.score_intersection, hausdorff=args.score_hausdorff)
+        closers.append(scorer.close)
     examples = list(iter_examples(args.benchmark_dir))
     for i in range(0, len(examples), max(args.batch_size, 1)):
         chunk = examples[i:i + max(args.batch_size, 1)]
@@ -183,9 +226,16 @@ def main(argv):
         output_ids, masks_left, masks_right, taxonomies = model.evaluate(
             None, None, input_ids.to(device), resize_list, original_size_list, max_new_tokens=args.max_new_tokens,
             tokenizer=tokenizer, frames_u8=frames, attention_mask=mask)
+        if scorer is not None:   # one launch for the chunk; the counts stay on the device until the report
+            scorer.add_batch([(d, f) for d, f, _, _ in chunk], masks_left, masks_right, taxonomies, original_size_list)
+        if args.score_only:
+            continue
         for b, (dir_name, folder_name, _, _) in enumerate(chunk):   # per frame, exactly the reference's B = 1 rule
             for (side, th), plane in output_planes(masks_left[b:b + 1], masks_right[b:b + 1], taxonomies[b:b + 1]).items():
                 save_mask(os.path.join(args.vis_save_path + str(th), dir_name, folder_name, f"aff_{side}.png"), plane)
+    if scorer is not None:
+        return scorer.report(verbose=True)
+    return None
 
 
 if __name__ == "__main__":

@@ -1113,3 +1113,35 @@ def fill_contours(planes, hw, device, out=None):
                                    out.data_ptr(), H, W, _stream())
     check(rc, "haff_fill_contours_u8")
     return out
+
+
+SCORE_FRAME_WORDS = 16                     # haff_score_frame (include/haff_hip.h): 128 bytes as 16 int64 words
+SCORE_MAX_SIDE, SCORE_MAX_THRESHOLDS = 4096, 8
+
+
+def score_masks(frames, logit_ths, device, out_counts=None):
+    """haff_score_masks on a packed descriptor table. frames: int64 [n, SCORE_FRAME_WORDS] (numpy or a CPU tensor, as
+    scoring.pack_frames builds it; every pointer in it a device pointer the caller keeps alive until the call returns).
+    Returns int32 [n, n_th, 4] on the device = {intersection, union, predicted area, ground-truth area} per frame and LOGIT
+    threshold (zeroed by the call itself; the values are below 2^25). out_counts: a contiguous int32 [n, n_th, 4] to write into."""
+    import ctypes
+    lib = load_library()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("score_masks runs in HBM (cuda device); the hot path has no CPU fallback")
+    frames = torch.as_tensor(frames)
+    assert frames.dtype == torch.int64 and frames.dim() == 2 and frames.shape[1] == SCORE_FRAME_WORDS and frames.shape[0] >= 1
+    n, n_th = frames.shape[0], len(logit_ths)
+    host = torch.empty((n, SCORE_FRAME_WORDS), dtype=torch.int64, pin_memory=True)
+    host.copy_(frames)
+    if out_counts is None:
+        out_counts = torch.empty((n, n_th, 4), dtype=torch.int32, device=device)
+    assert out_counts.dtype == torch.int32 and out_counts.is_contiguous() and tuple(out_counts.shape) == (n, n_th, 4)
+    assert out_counts.device.type == "cuda"
+    ths = (ctypes.c_float * max(n_th, 1))(*[float(v) for v in logit_ths])
+    with torch.cuda.device(out_counts.device):
+        dev_copy = host.to(out_counts.device, non_blocking=True)
+        rc = lib.haff_score_masks(host.data_ptr(), dev_copy.data_ptr(), n, ctypes.cast(ths, ctypes.c_void_p), n_th,
+                                  out_counts.data_ptr(), _stream())
+    check(rc, "haff_score_masks")
+    return out_counts

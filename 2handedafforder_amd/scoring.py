@@ -1,0 +1,248 @@
+"""Benchmark scoring and validation metrics on the device (csrc/mask_score.hip, ops.score_masks).
+
+`inference.py` used to leave the device three times per frame to be scored: a host read of the taxonomy argmax, ten PNG planes,
+and `evaluation.py` decoding and resampling them again to count four integers per frame and threshold. Here the fp32 mask logits
+`evaluate()` returns are compared, resampled to the benchmark's 855 x 855 (the 0/255 plane's bilinear resample followed by `> 0`,
+in exact integers), gated, ANDed and counted by ONE kernel launch per batch of frames; the counts stay in HBM for the whole run
+and are read back once.
+
+  pack_frames      the kernel's per-frame descriptor table (haff_score_frame, include/haff_hip.h) from tensors
+  BenchmarkScorer  `evaluation.evaluate_folders` for an inference run: the frame rules of `evaluation.score_frame`, the same
+                   accumulation order and the same report dict, from the integer counts
+  counts_to_iou    `evaluation.calculate_iou` / `calculate_iocm` on the integers
+
+Relation to evaluation.py: it resamples with fp32 `F.interpolate` (its stand-in for cv2.resize), whose source coordinates carry a few
+ulp of error; the device rule is the exact rational value of the same formula. The two can differ only at pixels whose coverage is
+within a hair of the tie (tests/test_score_ref_cpu.py bounds the band and its population).
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from . import postprocess
+
+BENCHMARK_HW = (855, 855)                  # calculate_iou.py:139: the uncropped benchmark resolution
+
+
+def _plane(t, dtype, name):
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live in HBM (cuda tensor); the hot path has no CPU fallback")
+    assert t.dtype == dtype and t.is_contiguous(), (name, t.dtype, t.is_contiguous())
+    return t
+
+
+def pack_frames(frames):
+    """frames: dicts with the keys left, right (fp32 [Hs, Ws] logits or None), taxonomy (fp32, 4 n values, or None: gate open),
+    gt_left, gt_right, obj_left, obj_right (uint8 2-D planes or None), out (uint8 [T, Hb, Wb] or None), target_hw and, when
+    both hands are None, src_hw. Returns the int64 [n, 16] descriptor table of ops.score_masks; the caller keeps the tensors alive
+    until the launch is enqueued. Shapes are recorded as the tensors have them: the library refuses a ground-truth or object plane
+    whose shape is not the target's, and sizes it does not take."""
+    table = np.zeros((len(frames), ops.SCORE_FRAME_WORDS), dtype=np.int64)
+    ints = table.view(np.int32).reshape(len(frames), 2 * ops.SCORE_FRAME_WORDS)
+    for i, f in enumerate(frames):
+        left, right = _plane(f.get("left"), torch.float32, "left"), _plane(f.get("right"), torch.float32, "right")
+        src = left if left is not None else right
+        hs, ws = (src.shape if src is not None else f.get("src_hw", (1, 1)))
+        assert src is None or src.dim() == 2
+        assert left is None or right is None or left.shape == right.shape
+        tax = _plane(f.get("taxonomy"), torch.float32, "taxonomy")
+        out = _plane(f.get("out"), torch.uint8, "out")
+        hb, wb = f["target_hw"]
+        assert out is None or (out.dim() == 3 and tuple(out.shape[1:]) == (hb, wb))
+        ptrs = [left, right, tax]
+        shapes = []
+        for key in ("gt_left", "gt_right", "obj_left", "obj_right"):
+            p = _plane(f.get(key), torch.uint8, key)
+            assert p is None or p.dim() == 2
+            ptrs.append(p)
+            shapes += list(p.shape) if p is not None else [0, 0]
+        ptrs.append(out)
+        table[i, :8] = [0 if p is None else p.data_ptr() for p in ptrs]
+        ints[i, 16:29] = [hs, ws, hb, wb, 0 if tax is None else tax.numel()] + shapes
+    return table
+
+
+def counts_to_iou(inter, union, area):
+    """evaluation.calculate_iou / calculate_iocm from the counts: float(inter) / float(denominator), 0.0 on an empty one."""
+    inter, union, area = int(inter), int(union), int(area)
+    return (float(inter) / float(union) if union != 0 else 0.0), (float(inter) / float(area) if area != 0 else 0.0)
+
+
+def report_from_frames(names, frames, want_hausdorff):
+    """evaluation.evaluate_folders' result from per-frame results. names: the threshold folder names; frames: per scored frame, in
+    the benchmark's sorted folder order, (label, counts int [T, 4], hausdorff [T] of (directed, symmetric) or None). The thresholds
+    are reported in sorted name order, as evaluate_folders lists the comparison folder."""
+    order = sorted(range(len(names)), key=lambda k: names[k])
+    per_th = []
+    for k in order:
+        tot = np.zeros(4)
+        count = zero = 0
+        for _, counts, hd in frames:
+            iou, iocm = counts_to_iou(counts[k][0], counts[k][1], counts[k][2])
+            dhd, shd = hd[k] if want_hausdorff else (0.0, 0.0)
+            tot += np.asarray((iou, iocm, dhd, shd))
+            zero += int(iou == 0 and iocm == 0)
+            count += 1
+        avg = tot / max(count, 1)
+        per_th.append({"threshold": names[k], "count": count, "failed": zero, "iou": avg[0], "iocm": avg[1],
+                       "directed_hd": avg[2] if want_hausdorff else None, "hd": avg[3] if want_hausdorff else None})
+    best = max(per_th, key=lambda r: r["iocm"])
+    return {"per_threshold": per_th, "best": best, "mean_average_precision": float(np.mean([r["iocm"] for r in per_th]))}
+
+
+def print_report(res, frames=None, names=None, file=None):
+    """The lines `evaluation.py --map` prints (per frame and threshold folder, then the summary)."""
+    if frames is not None:
+        for k in sorted(range(len(names)), key=lambda j: names[j]):
+            for label, counts, _ in frames:
+                iou, iocm = counts_to_iou(counts[k][0], counts[k][1], counts[k][2])
+                print(f"IoU for {label}: {iou:.4f}\nIoCM for {label}: {iocm:.4f}", file=file)
+    b = res["best"]
+    print(f"mean average precision: {res['mean_average_precision']}", file=file)
+    print(f"Best performing threshold was {b['threshold']}", file=file)
+    if b["hd"] is None:
+        print(f"IoU: {b['iou']}\nPrecision: {b['iocm']}\nHausdorff-Distance: not computed (--score_hausdorff)\n"
+              "Directed Hausdorff-Distance: not computed (--score_hausdorff)", file=file)
+    else:
+        print(f"IoU: {b['iou']}\nPrecision: {b['iocm']}\nHausdorff-Distance: {b['hd']}\nDirected Hausdorff-Distance: {b['directed_hd']}",
+              file=file)
+
+
+def _read_gray(path):
+    from PIL import Image
+    return np.array(Image.open(path).convert("L"))
+
+
+class BenchmarkScorer:
+    """Scores an inference run against `<benchmark>/<video>/<frame>/{aff_left, aff_right, obj_left, obj_right}.png` as
+    `evaluation.evaluate_folders(benchmark, predictions, calc_map=True, is_cropped=cropped, take_intersection=intersection)` would
+    score the PNG tree inference.py writes, without the tree: add_batch() per evaluate() call (in the benchmark's sorted folder
+    order, which is inference.iter_examples'), report() once at the end.
+
+    Frame rules (evaluation.score_frame): a frame without [SEG] is skipped (no prediction folder would exist), as is one with no
+    ground-truth plane at all, one whose ground-truth shape differs from the target shape ((855, 855), or the frame's own size when
+    cropped), and, with intersection, one whose obj_<side>.png is missing or mis-sized for a hand that is written. Which hands are
+    written is the taxonomy gate's decision and stays on the device: such a frame is scored anyway and dropped in report(), from the
+    frame's argmax read back together with the counts.
+
+    hausdorff: the kernel also writes the predicted union planes; they are read back per batch and `evaluation.calculate_hausdorff`
+    runs on them in one worker thread (close() ends it). Without it the two Hausdorff fields of the report are None."""
+
+    def __init__(self, benchmark_dir, device, thresholds=postprocess.THRESHOLDS, names=None, cropped=False, intersection=False,
+                 hausdorff=False):
+        self.benchmark_dir, self.device = benchmark_dir, torch.device(device)
+        self.thresholds = tuple(thresholds)
+        self.names = list(names) if names is not None else [str(t) for t in self.thresholds]
+        assert len(self.names) == len(self.thresholds) and 1 <= len(self.thresholds) <= ops.SCORE_MAX_THRESHOLDS
+        self.logit_ths = [postprocess.sigmoid_logit_threshold(t) for t in self.thresholds]
+        self.cropped, self.intersection, self.hausdorff = bool(cropped), bool(intersection), bool(hausdorff)
+        self._labels, self._counts, self._gates, self._needs_gate, self._hd = [], [], [], [], []
+        self._pool = None
+        if self.hausdorff:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="haff-hausdorff")
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True, cancel_futures=True)
+            self._pool = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _upload(self, plane):
+        return torch.from_numpy(plane).pin_memory().to(self.device, non_blocking=True)
+
+    def _frame(self, dir_name, folder_name, masks_left, masks_right, taxonomy, frame_hw):
+        """The descriptor dict of one frame, or None when the frame rules skip it on the host's knowledge alone."""
+        if taxonomy.numel() == 0:                              # no [SEG]: inference.py writes nothing
+            return None
+        hands = {}
+        for side, masks in (("left", masks_left), ("right", masks_right)):
+            if masks.shape[0] != 0:
+                hands[side] = masks[0].float().contiguous()
+        if not hands:
+            return None
+        target_hw = (int(frame_hw[0]), int(frame_hw[1])) if self.cropped else BENCHMARK_HW
+        leaf = os.path.join(self.benchmark_dir, dir_name, folder_name)
+        f = {"left": hands.get("left"), "right": hands.get("right"), "target_hw": target_hw,
+             "taxonomy": taxonomy.reshape(-1).float().contiguous(), "gt_host": {}, "obj_missing": []}
+        for side in ("left", "right"):
+            p = os.path.join(leaf, f"aff_{side}.png")
+            if os.path.exists(p):
+                g = _read_gray(p)
+                if g.shape != target_hw:
+                    return None
+                f["gt_host"][side] = g
+                f[f"gt_{side}"] = self._upload(g)
+        if not f["gt_host"]:
+            return None
+        if self.intersection:
+            for side in hands:
+                p = os.path.join(leaf, f"obj_{side}.png")
+                o = _read_gray(p) if os.path.exists(p) else None
+                if o is None or o.shape != target_hw:
+                    f["obj_missing"].append(side)              # skipped iff this hand is written: the gate decides
+                else:
+                    f[f"obj_{side}"] = self._upload(o)
+        return f
+
+    def add_batch(self, keys, masks_left, masks_right, taxonomies, frame_hws):
+        """One evaluate() call: keys = [(dir_name, folder_name)], the three lists evaluate() returns, the frames' (H0, W0)."""
+        frames = []
+        for b, (dir_name, folder_name) in enumerate(keys):
+            f = self._frame(dir_name, folder_name, masks_left[b], masks_right[b], taxonomies[b], frame_hws[b])
+            if f is None:
+                continue
+            if self.hausdorff:
+                f["out"] = torch.empty((len(self.thresholds),) + f["target_hw"], dtype=torch.uint8, device=self.device)
+            f["label"] = f"{dir_name}/{folder_name}"
+            frames.append(f)
+        if not frames:
+            return
+        counts = ops.score_masks(pack_frames(frames), self.logit_ths, self.device)
+        self._counts.append(counts.reshape(-1))
+        for f in frames:
+            self._labels.append(f["label"])
+            self._needs_gate.append(f["obj_missing"])
+            self._gates.append(torch.argmax(f["taxonomy"]).to(torch.int32).reshape(1) if f["obj_missing"] else None)
+            if self.hausdorff:
+                g = f["gt_host"]
+                bench = np.logical_or(g["left"] > 0, g["right"] > 0) if len(g) == 2 else next(iter(g.values())) > 0
+                self._hd.append(self._pool.submit(_hausdorff_planes, bench, f["out"].cpu().numpy()))
+
+    def report(self, verbose=False, file=None):
+        """The dict evaluation.evaluate_folders(..., calc_map=True) returns. ONE device -> host read: every frame's counts, and the
+        argmax of the frames whose object plane was missing."""
+        T = len(self.thresholds)
+        if not self._labels:
+            frames = []
+        else:
+            gates = [g for g in self._gates if g is not None]
+            flat = torch.cat(self._counts + gates).cpu().numpy().astype(np.int64)
+            n = len(self._labels)
+            counts = flat[:n * T * 4].reshape(n, T, 4)
+            gate_vals = iter(flat[n * T * 4:].tolist())
+            frames = []
+            for i, label in enumerate(self._labels):
+                if self._needs_gate[i]:
+                    t = next(gate_vals)
+                    if any(t != (1 if side == "left" else 0) for side in self._needs_gate[i]):
+                        continue                               # a written hand without its object plane: score_frame returns None
+                frames.append((label, counts[i], self._hd[i].result() if self.hausdorff else None))
+        res = report_from_frames(self.names, frames, self.hausdorff)
+        if verbose:
+            print_report(res, frames, self.names, file=file)
+        return res
+
+
+def _hausdorff_planes(bench_union, pred_planes):
+    from . import evaluation
+    return [evaluation.calculate_hausdorff(bench_union, pred_planes[t] > 0) for t in range(pred_planes.shape[0])]

@@ -28,12 +28,12 @@ import torch
 if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import haff  # noqa: F401
-    from haff import checkpoint, config as hcfg, dist as hdist, prompt as hprompt, train_ops as T
+    from haff import checkpoint, config as hcfg, dist as hdist, ops, prompt as hprompt, scoring, train_ops as T
     from haff.aff_dataset import AffRecordsDataset
     from haff.train_ingest import DeviceIngest, Prefetcher
     from haff.train_model import LisaTrainable
 else:
-    from . import checkpoint, config as hcfg, dist as hdist, prompt as hprompt, train_ops as T
+    from . import checkpoint, config as hcfg, dist as hdist, ops, prompt as hprompt, scoring, train_ops as T
     from .aff_dataset import AffRecordsDataset
     from .train_ingest import DeviceIngest, Prefetcher
     from .train_model import LisaTrainable
@@ -260,31 +260,61 @@ def calculate_iocm(benchmark_mask, comparison_mask):
     return inter / area if area != 0 else 0.0
 
 
+def _label_hw(sample, raw):
+    """The ground-truth mask size of one validation sample: what decides which samples can share a forward."""
+    return tuple(sample["mask_hw"]) if raw else tuple(sample[4].shape[-2:])
+
+
+def validation_groups(fetch, lo, hi, batch_size, raw):
+    """Consecutive samples lo..hi-1 in runs of at most batch_size whose label sizes are equal (forward(inference=True) stacks the
+    predictions of a batch, so one batch has one label size). Yields lists of samples, in order."""
+    group, hw = [], None
+    for idx in range(lo, hi):
+        sample = fetch(idx)
+        shw = _label_hw(sample, raw)
+        if group and (shw != hw or len(group) >= max(int(batch_size), 1)):
+            yield group
+            group = []
+        group.append(sample)
+        hw = shw
+    if group:
+        yield group
+
+
+def validation_frames(out):
+    """The scoring descriptors (scoring.pack_frames) of one forward(inference=True): per sample the first prompt's two logit planes
+    at the label size, its four taxonomy probabilities as the gate, and the two ground-truth planes as uint8."""
+    gt_l, gt_r = (out["gt_masks_left"] > 0).to(torch.uint8), (out["gt_masks_right"] > 0).to(torch.uint8)
+    tax = out["pred_taxonomies"].float().contiguous()
+    left, right = out["pred_masks_left"].float().contiguous(), out["pred_masks_right"].float().contiguous()
+    return [{"left": left[b][0], "right": right[b][0], "taxonomy": tax[b][0], "gt_left": gt_l[b][0], "gt_right": gt_r[b][0],
+             "target_hw": tuple(left.shape[-2:])} for b in range(left.shape[0])]
+
+
 @torch.no_grad()
 def validate(model, dataset, tokenizer, args, rank, world, device, ingest=None):
     """train_ds.py:625-758: teacher-forced forward(inference=True), masks > 0, taxonomy-gated union of L/R vs GT union.
-    ingest (--device_ingest): the DeviceIngest that makes each batch on the device from dataset.raw_item."""
+    ingest (--device_ingest): the DeviceIngest that makes each batch on the device from dataset.raw_item.
+    --val_batch_size consecutive samples of one label size share a forward. The three integers of each sample (intersection, union,
+    predicted area) are counted on the device (ops.score_masks: threshold 0.0 on the raw logits, equal sizes, the gate from
+    pred_taxonomies) and read back once per validation; the meters then see the same numbers in the same order as before."""
     model.eval()
     iou_m, iocm_m = AverageMeter("IoU"), AverageMeter("IoCM")
     lo, hi = hdist.shard_bounds(len(dataset), rank, world)
-    for idx in range(lo, hi):
+    fetch = dataset.raw_item if ingest is not None else dataset.__getitem__
+    counts = []
+    for group in validation_groups(fetch, lo, hi, args.val_batch_size, ingest is not None):
         if ingest is not None:
-            batch = ingest.batch([dataset.raw_item(idx)], tokenizer, args.model_max_length, args.conv_type)
+            batch = ingest.batch(group, tokenizer, args.model_max_length, args.conv_type)
         else:
-            batch = collate_fn([dataset[idx]], tokenizer, args.model_max_length, conv_type=args.conv_type)
+            batch = collate_fn(group, tokenizer, args.model_max_length, conv_type=args.conv_type)
             batch = {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        out = model(**batch)
-        t = int(out["pred_taxonomies"][0][0].argmax())
-        left = (out["pred_masks_left"][0][0] > 0).cpu().numpy()
-        right = (out["pred_masks_right"][0][0] > 0).cpu().numpy()
-        if t == 1:
-            left[:] = False
-        if t == 0:
-            right[:] = False
-        pred = np.logical_or(left, right)
-        gt = np.logical_or(out["gt_masks_left"][0][0].cpu().numpy() > 0, out["gt_masks_right"][0][0].cpu().numpy() > 0)
-        iou_m.update(calculate_iou(pred, gt))
-        iocm_m.update(calculate_iocm(gt, pred))
+        frames = validation_frames(model(**batch))
+        counts.append(ops.score_masks(scoring.pack_frames(frames), [0.0], device).reshape(-1, 4))
+    if counts:
+        for inter, union, area, _ in torch.cat(counts).cpu().tolist():   # the one read-back
+            iou_m.update(inter / union if union != 0 else 0.0)
+            iocm_m.update(inter / area if area != 0 else 0.0)
     all_reduce_meters([iou_m, iocm_m], device)
     model.train()
     return iou_m.avg, iocm_m.avg

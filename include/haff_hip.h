@@ -554,6 +554,35 @@ int haff_robot_heatmap(const float* logits, int n, int H, int W, const void* jet
  * on_value. -1 when mask's size is not the padded size (cv2.bitwise_and raises) or the padded size is empty. */
 int haff_robot_mask(const float* logits, int H0, int W0, int left, int top, int right, int bottom, float th, const void* mask,
                     int mask_h, int mask_w, int on_value, void* out, void* stream);
+/* ---- benchmark scoring and validation metrics on the device (calculate_iou.py:117-337 as evaluation.py restates it,
+ * 2Haff/train_ds.py:625-796; csrc/mask_score.hip) ----
+ * One frame of a haff_score_masks batch: 128 bytes, every pointer a DEVICE pointer. */
+typedef struct haff_score_frame {
+  const float* logit[2];          /* left, right hand: f32 [Hs][Ws] mask logits as evaluate() returns them; NULL = hand missing */
+  const float* taxonomy;          /* n_tax = 4 n class probabilities of the frame's n prompts, flattened; NULL = gated by the caller */
+  const unsigned char* gt[2];     /* left, right ground truth: u8 [Hb][Wb], on where > 0; NULL = empty (calculate_iou.py:237-255) */
+  const unsigned char* obj[2];    /* left, right object mask: u8 [Hb][Wb]; the hand counts only where obj > 0; NULL = no AND */
+  unsigned char* out;             /* u8 [T][Hb][Wb]: the predicted two-hand union per threshold, 0/1; NULL = not written */
+  int Hs, Ws, Hb, Wb, n_tax;
+  int gt_hw[2][2], obj_hw[2][2];  /* (rows, columns) of each gt / obj plane as the caller holds it: checked against (Hb, Wb) */
+  int pad[3];
+} haff_score_frame;
+/* counts u32 [n_frames][n_th][4] = {intersection, union, predicted area, ground-truth area} of the two-hand unions of every frame
+ * and LOGIT threshold, zeroed by the call itself (a kernel in front of the scoring launch, same stream), then one launch over
+ * grid (blocks per frame, frames). Per target pixel and hand: the bilinear resample (half-pixel centres, no antialiasing) of the
+ * 0/255 plane `logit > th` from (Hs, Ws) to (Hb, Wb) followed by `> 0`, in exact integers: per axis
+ * num = max((2o+1) n_in - n_out, 0), i0 = min(num / 2 n_out, n_in - 1), i1 = min(i0 + 1, n_in - 1), w1 = num mod 2 n_out (0 when
+ * i1 == i0), w0 = 2 n_out - w1; S = sum of wy wx [logit(tap) > th]; on iff 510 S > 4 Hb Wb. Strict compares: a NaN logit is off.
+ * Equal sizes are the identity. Then AND with obj > 0, then the OR of the hands. Gate: argmax of taxonomy[0 .. n_tax) (first
+ * maximum); index 1 blanks the left hand, index 0 the right one, any other neither. Integer atomics only: repeat runs are bitwise
+ * equal. frames_host is the HOST copy of the n_frames descriptors, checked here and never read by a kernel; frames_dev the caller's
+ * DEVICE copy, uploaded in stream order before the call. thresholds_host: HOST array of n_th floats.
+ * Refused before anything is enqueued: -1 for n_th outside 1..8, n_frames outside 1..65535, a side <= 0, a gt / obj plane whose
+ * shape is not (Hb, Wb), n_tax outside 1..1024 with a taxonomy, a logit or taxonomy pointer that is not 4-B aligned, a descriptor
+ * table that is not 8-B aligned, counts not 4-B aligned, a NULL table, thresholds or counts; -2 for a side over 4096. The u8
+ * planes may sit at any address (4-B aligned quads move as words, the rest as bytes). */
+int haff_score_masks(const void* frames_host, const void* frames_dev, int n_frames, const float* thresholds_host, int n_th,
+                     void* counts, void* stream);
 
 
 /* ==== training path (LoRA fine-tune: train_ds.py:489-622 driving model_forward, LISA.py:175-430) ==================
