@@ -60,6 +60,9 @@ def parse_args(args):
                         help="evaluation.py --intersection: a hand counts only inside its obj_<side>.png")
     parser.add_argument("--score_hausdorff", action="store_true", default=False,
                         help="also the two Hausdorff distances (the union planes are read back; the contour walk runs in a host thread)")
+    parser.add_argument("--score_hausdorff_device", action="store_true", default=False,
+                        help="the two Hausdorff distances from the device: contour walk and point-set distance in HIP, nothing read "
+                             "back per batch and no host thread")
     args = parser.parse_args(args)
     check_score_args(args)
     return args
@@ -68,9 +71,11 @@ def parse_args(args):
 def check_score_args(args):
     """--score_only implies --score; the modifiers mean nothing without it, and scoring needs the benchmark's masks."""
     args.score = bool(args.score or args.score_only)
-    for flag in ("score_cropped", "score_intersection", "score_hausdorff"):
-        if getattr(args, flag) and not args.score:
+    for flag in ("score_cropped", "score_intersection", "score_hausdorff", "score_hausdorff_device"):
+        if getattr(args, flag, False) and not args.score:
             raise SystemExit(f"--{flag} modifies --score / --score_only: pass one of them")
+    if args.score_hausdorff and getattr(args, "score_hausdorff_device", False):
+        raise SystemExit("--score_hausdorff_device and --score_hausdorff are two routes to the same numbers: pass one of them")
     if args.score and not args.benchmark_dir:
         raise SystemExit("--score needs --benchmark-dir: the ground truth is its aff_{left,right}.png")
 
@@ -209,7 +214,8 @@ def _main(args, closers):
         stem = os.path.basename(os.path.normpath(args.vis_save_path))
         scorer = scoring.BenchmarkScorer(args.benchmark_dir, device, postprocess.THRESHOLDS,
                                          names=[stem + str(th) for th in postprocess.THRESHOLDS], cropped=args.score_cropped,
-                                         intersection=args.score_intersection, hausdorff=args.score_hausdorff)
+                                         intersection=args.score_intersection,
+                                         hausdorff="device" if args.score_hausdorff_device else args.score_hausdorff)
         closers.append(scorer.close)
     examples = list(iter_examples(args.benchmark_dir))
     for i in range(0, len(examples), max(args.batch_size, 1)):

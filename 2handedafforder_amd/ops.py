@@ -1145,3 +1145,58 @@ def score_masks(frames, logit_ths, device, out_counts=None):
                                   out_counts.data_ptr(), _stream())
     check(rc, "haff_score_masks")
     return out_counts
+
+
+HAUSDORFF_MAX_SIDE, HAUSDORFF_MAX_PLANES, HAUSDORFF_MAX_VERTICES = 4096, 4096, 1 << 22   # csrc/contour_hausdorff.hip
+HAUSDORFF_OVERFLOW, HAUSDORFF_FAULT = 0b0101, 0b1010     # result[:, 4]: either plane of the pair ran past max_vertices / hit a bound
+
+
+def contour_hausdorff(planes, pairs, max_vertices=65536, return_vertices=False):
+    """haff_contour_hausdorff: planes = uint8 CUDA tensors [H, W] (a list, or one [n, H, W] tensor), on where != 0; pairs = (bench,
+    pred) indices into planes, two planes of one shape each. Returns int32 [n_pairs, 6] on the device = {bench vertices, pred
+    vertices, d2(pred -> bench), d2(bench -> pred), flags, 0}: the squared directed Hausdorff distances between the vertex lists of
+    `cvlite.find_contours_external(plane)[0]`, exact integers, both 0 when a side is empty or a flag is set. Only enqueues: no
+    synchronisation, the caller keeps the planes alive until the stream has run. return_vertices: also int16 [n, max_vertices, 2]
+    (x, y) in walk order (rows past a plane's count hold whatever the buffer held) and the int32 [n] vertex counts; True, or the
+    uint8 CUDA buffer of at least 4 n max_vertices + 4 n bytes they are to be views of."""
+    import numpy as np
+    lib = load_library()
+    planes = list(planes)
+    assert planes, "no planes"
+    for p in planes:
+        _req(p, "planes")
+        assert p.dtype == torch.uint8 and p.dim() == 2 and p.is_contiguous(), (p.dtype, tuple(p.shape), p.is_contiguous())
+        assert p.device == planes[0].device
+    device = planes[0].device
+    n, max_vertices = len(planes), int(max_vertices)
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n_pairs = len(pairs)
+    words = 2 * n + n_pairs                                  # int64 words: 16-byte plane descriptors, then the int32 pairs
+    host = torch.zeros((words,), dtype=torch.int64, pin_memory=True)
+    h64 = host.numpy()
+    h32 = h64.view(np.int32)
+    for i, p in enumerate(planes):
+        h64[2 * i] = p.data_ptr()
+        h32[4 * i + 2], h32[4 * i + 3] = p.shape
+    h32[4 * n:4 * n + 2 * n_pairs] = pairs.reshape(-1)
+    need = ctypes.c_long(0)
+    check(lib.haff_contour_hausdorff_workspace(host.data_ptr(), n, max_vertices, ctypes.addressof(need)),
+          "haff_contour_hausdorff_workspace")
+    result = torch.empty((n_pairs, 6), dtype=torch.int32, device=device)
+    verts = None
+    if torch.is_tensor(return_vertices):
+        verts, return_vertices = return_vertices, True
+        assert verts.dtype == torch.uint8 and verts.is_contiguous() and verts.device == device
+        assert verts.numel() >= n * max_vertices * 4 + n * 4
+    elif return_vertices:
+        verts = torch.empty((n * max_vertices * 4 + n * 4,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        ws = _workspace(device, need.value)
+        dev = host.to(device, non_blocking=True)
+        rc = lib.haff_contour_hausdorff(host.data_ptr(), dev.data_ptr(), n, host.data_ptr() + 16 * n, dev.data_ptr() + 16 * n, n_pairs,
+                                        max_vertices, ws.data_ptr(), ws.numel(), _p(verts), result.data_ptr(), _stream())
+    check(rc, "haff_contour_hausdorff")
+    if not return_vertices:
+        return result
+    return (result, verts[:n * max_vertices * 4].view(torch.int16).reshape(n, max_vertices, 2),
+            verts[n * max_vertices * 4:n * max_vertices * 4 + 4 * n].view(torch.int32))

@@ -14,8 +14,14 @@ and are read back once.
 Relation to evaluation.py: it resamples with fp32 `F.interpolate` (its stand-in for cv2.resize), whose source coordinates carry a few
 ulp of error; the device rule is the exact rational value of the same formula. The two can differ only at pixels whose coverage is
 within a hair of the tie (tests/test_score_ref_cpu.py bounds the band and its population).
+
+With hausdorff="device" the two Hausdorff distances stay on the device too (csrc/contour_hausdorff.hip, ops.contour_hausdorff): the
+contour walk of every predicted union plane and of the frame's ground-truth union, and the two directed point-set distances, as
+integers that join the same single read-back; report() takes the square roots.
 """
+import math
 import os
+import sys
 
 import numpy as np
 import torch
@@ -129,20 +135,29 @@ class BenchmarkScorer:
     written is the taxonomy gate's decision and stays on the device: such a frame is scored anyway and dropped in report(), from the
     frame's argmax read back together with the counts.
 
-    hausdorff: the kernel also writes the predicted union planes; they are read back per batch and `evaluation.calculate_hausdorff`
-    runs on them in one worker thread (close() ends it). Without it the two Hausdorff fields of the report are None."""
+    hausdorff: the kernel also writes the predicted union planes. True: they are read back per batch and
+    `evaluation.calculate_hausdorff` runs on them in one worker thread (close() ends it). "device": one ops.contour_hausdorff call
+    per batch walks them and the ground-truth union (built on the device from the uploaded planes) and measures the T pairs of every
+    frame; the integers are read back with the counts, and no thread exists. The planes (T + 1 per frame, 0.7 MB each at 855 x 855)
+    stay in HBM until report(): a frame whose result carries a flag (a contour of more than `max_vertices` vertices, or a kernel
+    bound that no input should reach) is read back and recomputed by `evaluation.calculate_hausdorff` there, and counted in
+    `host_walks`. Without hausdorff the two fields of the report are None."""
 
     def __init__(self, benchmark_dir, device, thresholds=postprocess.THRESHOLDS, names=None, cropped=False, intersection=False,
-                 hausdorff=False):
+                 hausdorff=False, max_vertices=65536):
         self.benchmark_dir, self.device = benchmark_dir, torch.device(device)
         self.thresholds = tuple(thresholds)
         self.names = list(names) if names is not None else [str(t) for t in self.thresholds]
         assert len(self.names) == len(self.thresholds) and 1 <= len(self.thresholds) <= ops.SCORE_MAX_THRESHOLDS
         self.logit_ths = [postprocess.sigmoid_logit_threshold(t) for t in self.thresholds]
+        if hausdorff not in (False, True, "device"):
+            raise ValueError(f"hausdorff={hausdorff!r}: False, True (host thread) or 'device'")
         self.cropped, self.intersection, self.hausdorff = bool(cropped), bool(intersection), bool(hausdorff)
+        self.hausdorff_device, self.max_vertices, self.host_walks = hausdorff == "device", int(max_vertices), 0
         self._labels, self._counts, self._gates, self._needs_gate, self._hd = [], [], [], [], []
+        self._hd_results, self._hd_planes = [], []
         self._pool = None
-        if self.hausdorff:
+        if self.hausdorff and not self.hausdorff_device:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="haff-hausdorff")
 
@@ -213,10 +228,27 @@ class BenchmarkScorer:
             self._labels.append(f["label"])
             self._needs_gate.append(f["obj_missing"])
             self._gates.append(torch.argmax(f["taxonomy"]).to(torch.int32).reshape(1) if f["obj_missing"] else None)
-            if self.hausdorff:
+            if self.hausdorff and not self.hausdorff_device:
                 g = f["gt_host"]
                 bench = np.logical_or(g["left"] > 0, g["right"] > 0) if len(g) == 2 else next(iter(g.values())) > 0
                 self._hd.append(self._pool.submit(_hausdorff_planes, bench, f["out"].cpu().numpy()))
+        if self.hausdorff_device:
+            self._hausdorff_device(frames)
+
+    def _hausdorff_device(self, frames):
+        """One ops.contour_hausdorff call over the batch, behind ops.score_masks in the same stream: per frame the ground-truth union
+        and the T predicted unions the scoring kernel just wrote, paired (ground truth, threshold t)."""
+        T = len(self.thresholds)
+        planes, pairs = [], []
+        for f in frames:
+            gts = [f[k] > 0 for k in ("gt_left", "gt_right") if k in f]          # a missing hand counts as empty
+            bench = (gts[0] | gts[1] if len(gts) == 2 else gts[0]).to(torch.uint8)
+            base = len(planes)
+            planes.append(bench)
+            planes += [f["out"][t] for t in range(T)]
+            pairs += [(base, base + 1 + t) for t in range(T)]
+            self._hd_planes.append((bench, f["out"]))
+        self._hd_results.append(ops.contour_hausdorff(planes, pairs, max_vertices=self.max_vertices).reshape(-1))
 
     def report(self, verbose=False, file=None):
         """The dict evaluation.evaluate_folders(..., calc_map=True) returns. ONE device -> host read: every frame's counts, and the
@@ -226,21 +258,56 @@ class BenchmarkScorer:
             frames = []
         else:
             gates = [g for g in self._gates if g is not None]
-            flat = torch.cat(self._counts + gates).cpu().numpy().astype(np.int64)
+            flat = torch.cat(self._counts + gates + self._hd_results).cpu().numpy().astype(np.int64)
             n = len(self._labels)
             counts = flat[:n * T * 4].reshape(n, T, 4)
-            gate_vals = iter(flat[n * T * 4:].tolist())
+            gate_vals = iter(flat[n * T * 4:n * T * 4 + len(gates)].tolist())
+            if self.hausdorff_device:
+                self._hd = self._device_distances(flat[n * T * 4 + len(gates):].reshape(n, T, 6))
             frames = []
             for i, label in enumerate(self._labels):
                 if self._needs_gate[i]:
                     t = next(gate_vals)
                     if any(t != (1 if side == "left" else 0) for side in self._needs_gate[i]):
                         continue                               # a written hand without its object plane: score_frame returns None
-                frames.append((label, counts[i], self._hd[i].result() if self.hausdorff else None))
+                hd = None
+                if self.hausdorff:
+                    hd = self._hd[i] if self.hausdorff_device else self._hd[i].result()
+                frames.append((label, counts[i], hd))
         res = report_from_frames(self.names, frames, self.hausdorff)
         if verbose:
             print_report(res, frames, self.names, file=file)
         return res
+
+
+    def _device_distances(self, res):
+        """Per frame the [T] (directed, symmetric) tuples evaluation.calculate_hausdorff returns, from the device's integers
+        res [n, T, 6]: math.sqrt of an integer is scipy's value to the bit; no predicted contour gives the plane's diagonal, otherwise
+        no ground-truth contour gives (0, 0). A flagged frame is walked on the host."""
+        out = []
+        self.host_walks = 0
+        for i, label in enumerate(self._labels):
+            bench, pred = self._hd_planes[i]
+            flags = int(np.bitwise_or.reduce(res[i, :, 4]))
+            if flags:
+                if flags & ops.HAUSDORFF_FAULT:
+                    print(f"warning: the device contour walk reported a fault on frame {label} (flags {flags:#x}); "
+                          "its Hausdorff distances are recomputed on the host", file=sys.stderr)
+                self.host_walks += 1
+                out.append(_hausdorff_planes(bench.cpu().numpy() > 0, pred.cpu().numpy()))
+                continue
+            h, w = bench.shape
+            row = []
+            for nb, npred, d_pb, d_bp, _, _ in res[i].tolist():
+                if npred == 0:
+                    d = float(np.sqrt(h ** 2 + w ** 2))
+                    row.append((d, d))
+                elif nb == 0:
+                    row.append((0, 0))
+                else:
+                    row.append((math.sqrt(d_pb), math.sqrt(max(d_pb, d_bp))))
+            out.append(row)
+        return out
 
 
 def _hausdorff_planes(bench_union, pred_planes):

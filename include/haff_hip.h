@@ -583,6 +583,40 @@ typedef struct haff_score_frame {
  * planes may sit at any address (4-B aligned quads move as words, the rest as bytes). */
 int haff_score_masks(const void* frames_host, const void* frames_dev, int n_frames, const float* thresholds_host, int n_th,
                      void* counts, void* stream);
+/* ---- the benchmark's Hausdorff distances on the device (calculate_iou.py:9-24 as evaluation.calculate_hausdorff and
+ * cvlite.find_contours_external restate it; csrc/contour_hausdorff.hip) ----
+ * One plane of a haff_contour_hausdorff batch: 16 bytes, `plane` a DEVICE pointer to u8 [H][W] at any address, on where != 0. */
+typedef struct haff_contour_plane {
+  const unsigned char* plane;
+  int H, W;
+} haff_contour_plane;
+/* For every plane: the CHAIN_APPROX_SIMPLE vertices of cv2.findContours(plane, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE)[0] as cvlite
+ * restates it. The plane is read inside one ring of background; foreground is 8-connected, background 4-connected; "outside" is
+ * the background component of the ring; an 8-connected foreground component is external when one of its pixels has an outside
+ * left neighbour; [0] is the outer border of the external component whose raster-first pixel comes LAST, followed from that pixel
+ * as cvlite._follow does. For every pair (bench plane, pred plane), by index into the plane table (a frame of T thresholds is T + 1
+ * planes and T pairs: the ground truth is walked once): d2(A -> B) = max over a in A of min over b in B of |a - b|^2 on the two
+ * vertex lists, in integers. The caller takes the square roots and applies calculate_hausdorff's two empty rules.
+ *   result     u32 [n_pairs][6] = {bench vertices, pred vertices, d2(pred -> bench), d2(bench -> pred), flags, 0}, every word
+ *              written by the call. flags: bit 0 bench overflow (more than max_vertices vertices; the count is still the walk's
+ *              full count), bit 1 bench fault (a bound of the labelling or of the walk, 8 H W + 8 steps, was reached: no input
+ *              should), bits 2 and 3 the same for pred. A pair with a flag set or an empty side has both d2 fields 0.
+ *   verts_out  NULL, or i16 [n_planes][max_vertices][2] (x, y) in walk order followed by i32 [n_planes] vertex counts; entries
+ *              past a plane's count are left as they were. Without it the lists live in the workspace.
+ *   workspace  workspace_bytes >= what haff_contour_hausdorff_workspace answers for the same planes and max_vertices, 16-B aligned.
+ * planes_host / pairs_host are the HOST copies of the tables (pairs: int [n_pairs][2]), checked here and never read by a kernel;
+ * planes_dev / pairs_dev the caller's DEVICE copies, uploaded in stream order before the call. Six launches on `stream`, integer
+ * atomics on order-independent values only: repeat runs are bitwise equal.
+ * Refused before anything is enqueued: -1 for a NULL table, workspace or result, n_planes outside 1..4096, n_pairs outside
+ * 1..65535, a side <= 0, max_vertices outside 1..2^22, a workspace that is too small or not 16-B aligned, a plane table that is
+ * not 8-B aligned, pairs, result or verts_out not 4-B aligned, a pair index outside the plane table, a pair whose two planes differ
+ * in shape; -2 for a side over 4096 (coordinates are int16, d2 <= 2 * 4095^2). */
+int haff_contour_hausdorff(const void* planes_host, const void* planes_dev, int n_planes, const int* pairs_host, const int* pairs_dev,
+                           int n_pairs, int max_vertices, void* workspace, long workspace_bytes, void* verts_out, void* result,
+                           void* stream);
+/* Host only: *bytes_out = the workspace haff_contour_hausdorff needs for these planes (only H and W are read) and max_vertices.
+ * The same refusals for the plane table and max_vertices; -1 for a NULL bytes_out. */
+int haff_contour_hausdorff_workspace(const void* planes_host, int n_planes, int max_vertices, long* bytes_out);
 
 
 /* ==== training path (LoRA fine-tune: train_ds.py:489-622 driving model_forward, LISA.py:175-430) ==================
