@@ -54,10 +54,53 @@ def _taxonomy_vector(t):
     return v
 
 
-class AffRecordsDataset(torch.utils.data.Dataset):
-    """AffDataset over in-memory records (what `load_dataset(name, split="train")` yields)."""
+JITTER_RANGE = (0.4, 1.6)   # apply_jitter.py: brightness, contrast and colour factors
 
-    def __init__(self, records, cfg, samples_per_epoch=500 * 8 * 2 * 10, inference=False, seed=None):
+
+def check_probability(name, p):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"{name} is a probability in [0, 1], not {p}")
+    return p
+
+
+def draw_augmentation(seed, idx, p_flip, p_jitter):
+    """The training augmentation of sample `idx`: {"flip": bool, "jitter": None | (fb, fc, fs)}. A pure function of its arguments
+    (a generator of its own per (dataset seed, idx), never the dataset's rng), so it is the same on resume, on either feed and
+    whatever the fetch order. Five draws in a fixed order, made whether or not they are used: flip, jitter, then the brightness,
+    contrast and colour factors, uniform in JITTER_RANGE and rounded to fp32 once (Pillow hands `(float)alpha` to its C code)."""
+    g = random.Random(f"haff-aug/{seed}/{idx}")
+    u_flip, u_jitter = g.random(), g.random()
+    factors = tuple(float(np.float32(g.uniform(*JITTER_RANGE))) for _ in range(3))
+    return {"flip": u_flip < p_flip, "jitter": factors if u_jitter < p_jitter else None}
+
+
+def augment_frame(image, aug):
+    """`aug` on a uint8 HWC frame with Pillow itself (the yardstick of csrc/frame_augment.hip): apply_jitter.py's
+    Brightness -> Contrast -> Color and horizontal_flip.py's mirror. They commute: the jitter is pointwise apart from one
+    whole-frame mean, which a mirror keeps."""
+    from PIL import Image, ImageEnhance
+    if not aug["flip"] and aug["jitter"] is None:
+        return image
+    im = Image.fromarray(image, "RGB")
+    if aug["jitter"] is not None:
+        for enhance, f in zip((ImageEnhance.Brightness, ImageEnhance.Contrast, ImageEnhance.Color), aug["jitter"]):
+            im = enhance(im).enhance(f)
+    if aug["flip"]:
+        im = im.transpose(Image.FLIP_LEFT_RIGHT)
+    return np.array(im)          # a writable copy, as the record's own frame is
+
+
+def flip_taxonomy(v):
+    """horizontal_flip.py exchanges the hands: left-only <-> right-only, entries 0 and 1 of the 4-vector."""
+    return [v[1], v[0]] + list(v[2:])
+
+
+class AffRecordsDataset(torch.utils.data.Dataset):
+    """AffDataset over in-memory records (what `load_dataset(name, split="train")` yields). aug_flip / aug_jitter: the probabilities
+    of the training augmentation (draw_augmentation; both 0: none, and nothing about the samples changes)."""
+
+    def __init__(self, records, cfg, samples_per_epoch=500 * 8 * 2 * 10, inference=False, seed=None, aug_flip=0.0, aug_jitter=0.0):
         self.records = list(records)
         if not self.records:
             raise ValueError("no records")
@@ -70,6 +113,18 @@ class AffRecordsDataset(torch.utils.data.Dataset):
                 self.original_size = tuple(int(x) for x in m["original_size"])
                 break
         self.rng = random.Random(seed)
+        self._set_augmentation(seed, aug_flip, aug_jitter)
+
+    def _set_augmentation(self, seed, aug_flip, aug_jitter):
+        self.aug_flip, self.aug_jitter = check_probability("aug_flip", aug_flip), check_probability("aug_jitter", aug_jitter)
+        # an unseeded dataset draws its samples from the OS; so does its augmentation
+        self.aug_seed = seed if seed is not None else random.SystemRandom().getrandbits(63)
+
+    def _draw_aug(self, idx):
+        """None when both probabilities are 0 (no draw is made), else draw_augmentation for this sample."""
+        if self.aug_flip == 0.0 and self.aug_jitter == 0.0:
+            return None
+        return draw_augmentation(self.aug_seed, idx, self.aug_flip, self.aug_jitter)
 
     @classmethod
     def from_hf(cls, name, cfg, **kw):
@@ -158,6 +213,7 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         ds.records = _LocalRecords()
         ds.cfg, ds.samples_per_epoch, ds.inference = cfg, kw.get("samples_per_epoch", 500 * 8 * 2 * 10), kw.get("inference", False)
         ds.size, ds.original_size, ds.rng = size, tuple(original_size), random.Random(kw.get("seed"))
+        ds._set_augmentation(kw.get("seed"), kw.get("aug_flip", 0.0), kw.get("aug_jitter", 0.0))
         return ds
 
     def __len__(self):
@@ -177,6 +233,12 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         shape = tuple(int(x) for x in m.get("original_size", self.original_size or image.shape[:2]))
         left = recreate_mask_from_contours(m.get("aff_left", []), shape)
         right = recreate_mask_from_contours(m.get("aff_right", []), shape)
+        aug = self._draw_aug(idx)
+        if aug is not None:                 # before any resize; the masks are mirrored rasters, never fills of mirrored vertices
+            image = augment_frame(image, aug)
+            if aug["flip"]:
+                left, right = np.ascontiguousarray(right[:, ::-1]), np.ascontiguousarray(left[:, ::-1])
+                taxonomy = flip_taxonomy(taxonomy)
         label = {"left": torch.from_numpy((left == 0).astype(np.int64) * 255),
                  "right": torch.from_numpy((right == 0).astype(np.int64) * 255)}
         cfg = self.cfg
@@ -196,7 +258,8 @@ class AffRecordsDataset(torch.utils.data.Dataset):
     def raw_item(self, idx):
         """What train_ingest.DeviceIngest builds the sample from on the device: no resize, no normalised tensor, no filled mask, no
         label planes. Draws from self.rng in __getitem__'s order (record, then question, then answer), so a seeded run sees the
-        same samples and prompts either way."""
+        same samples and prompts either way. With an augmentation probability set the dict also carries "aug" (draw_augmentation
+        for this idx): what __getitem__ applies with Pillow, DeviceIngest applies on the device."""
         item = self.records[self.rng.randint(0, self.size - 1)]
         text = item.get("narration", item.get("text", ""))
         if isinstance(text, bytes):
@@ -214,15 +277,20 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         conv.append_message(conv.roles[1], answer)
         # the vertex lists as cvlite.draw_contours_filled reads them (int32 [n,2]): converted here, off the main thread
         left, right = ([np.asarray(c, dtype=np.int32).reshape(-1, 2) for c in m.get(k) or []] for k in ("aff_left", "aff_right"))
-        return {"frame": image, "contours_left": left, "contours_right": right, "mask_hw": shape,
-                "taxonomy": _taxonomy_vector(item.get("taxonomy", 2)), "conversations": [conv.get_prompt()],
-                "questions": [question], "texts": [text], "inference": self.inference}
+        raw = {"frame": image, "contours_left": left, "contours_right": right, "mask_hw": shape,
+               "taxonomy": _taxonomy_vector(item.get("taxonomy", 2)), "conversations": [conv.get_prompt()],
+               "questions": [question], "texts": [text], "inference": self.inference}
+        aug = self._draw_aug(idx)
+        if aug is not None:                 # applied by DeviceIngest; frame, contours and taxonomy are the record's own here
+            raw["aug"] = aug
+        return raw
 
 
 class AffValDataset(torch.utils.data.Dataset):
     """AffDatasetVal (aff_dataset.py:350-544): the ActAffordance-style benchmark folders as validation samples."""
 
-    def __init__(self, base_image_dir, cfg, seed=None):
+    def __init__(self, base_image_dir, cfg, seed=None, aug_flip=0.0, aug_jitter=0.0):
+        # the validation set is never augmented: the training set's keywords are accepted and ignored
         self.cfg = cfg
         self.images, self.affs_left, self.affs_right, self.narrations, self.taxonomies = self.load_data_from_nested_folders(base_image_dir)
         self.size = len(self.images)

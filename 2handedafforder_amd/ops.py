@@ -1115,6 +1115,98 @@ def fill_contours(planes, hw, device, out=None):
     return out
 
 
+AUG_FLIP, AUG_JITTER = 1, 2            # the flag bits of csrc/frame_augment.hip
+AUG_MAX_PIXELS = 1 << 24               # H * W per frame haff_jitter_stats_u8 / haff_augment_u8 take; beyond: the caller's host route
+
+
+def augment_frames_supported(hw):
+    """Whether the frame kernels take a frame of this (H, W); beyond that the caller augments it on the host."""
+    return int(hw[0]) * int(hw[1]) <= AUG_MAX_PIXELS
+
+
+def _aug_args(frames, flags, factors):
+    _req(frames, "frames")
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), tuple(frames.shape)
+    B = frames.shape[0]
+    assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (B,) and flags.device == frames.device
+    assert factors.dtype == torch.float32 and factors.is_contiguous() and tuple(factors.shape) == (B, 3)
+    assert factors.device == frames.device
+    return B, frames.shape[1], frames.shape[2]
+
+
+def jitter_stats(frames, flags, factors, out=None):
+    """haff_jitter_stats_u8: int64 [B] on the device = the sum of L over the brightness-scaled frame for every frame whose flags
+    carry AUG_JITTER, 0 for the others (zeroed by the call itself: `out` may hold anything)."""
+    lib = load_library()
+    B, H, W = _aug_args(frames, flags, factors)
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int64, device=frames.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (B,) and out.device == frames.device
+    with torch.cuda.device(frames.device):
+        rc = lib.haff_jitter_stats_u8(frames.data_ptr(), B, H, W, flags.data_ptr(), factors.data_ptr(), out.data_ptr(), _stream())
+    check(rc, "haff_jitter_stats_u8")
+    return out
+
+
+def augment_u8(frames, flags, factors, sums, out=None):
+    """haff_augment_u8: the jittered and / or mirrored copy of uint8 [B,H,W,3] frames (`sums` from jitter_stats on the same arguments)."""
+    lib = load_library()
+    B, H, W = _aug_args(frames, flags, factors)
+    assert sums.dtype == torch.int64 and sums.is_contiguous() and tuple(sums.shape) == (B,) and sums.device == frames.device
+    if out is None:
+        out = torch.empty_like(frames)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == frames.shape and out.device == frames.device
+    with torch.cuda.device(frames.device):
+        rc = lib.haff_augment_u8(frames.data_ptr(), out.data_ptr(), B, H, W, flags.data_ptr(), factors.data_ptr(), sums.data_ptr(),
+                                 _stream())
+    check(rc, "haff_augment_u8")
+    return out
+
+
+def flip_planes(planes, flags, out=None):
+    """haff_flip_planes_u8: uint8 [P,H,W] with the planes whose flags carry AUG_FLIP mirrored left-right and the others copied."""
+    lib = load_library()
+    _req(planes, "planes")
+    assert planes.dtype == torch.uint8 and planes.dim() == 3 and planes.is_contiguous(), tuple(planes.shape)
+    P, H, W = planes.shape
+    assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (P,) and flags.device == planes.device
+    if out is None:
+        out = torch.empty_like(planes)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == planes.shape and out.device == planes.device
+    with torch.cuda.device(planes.device):
+        rc = lib.haff_flip_planes_u8(planes.data_ptr(), out.data_ptr(), P, H, W, flags.data_ptr(), _stream())
+    check(rc, "haff_flip_planes_u8")
+    return out
+
+
+def augment_table(augs, device):
+    """The device arrays of the augment kernels from one `aug` dict per frame ({"flip": bool, "jitter": None | (fb, fc, fs)}, or None):
+    int32 [B] flags and float32 [B,3] factors, uploaded together from one pinned buffer."""
+    import numpy as np
+    B = len(augs)
+    host = torch.zeros((4 * B,), dtype=torch.float32, pin_memory=True)      # [flags B | factors 3 B]
+    h = host.numpy()
+    bits = h.view(np.int32)
+    for i, a in enumerate(augs):
+        if a:
+            bits[i] = (AUG_FLIP if a["flip"] else 0) | (AUG_JITTER if a["jitter"] is not None else 0)
+            if a["jitter"] is not None:
+                h[B + 3 * i:B + 3 * i + 3] = a["jitter"]
+    dev = host.to(device, non_blocking=True)
+    return dev[:B].view(torch.int32), dev[B:].view(B, 3)
+
+
+def augment_frames(frames, augs):
+    """One `aug` dict per frame applied to uint8 [B,H,W,3] frames in HBM: the stats pass only when a frame is jittered, then the
+    one augment pass. Returns a new tensor (the input is left as it is)."""
+    flags, factors = augment_table(augs, frames.device)
+    if any(a and a["jitter"] is not None for a in augs):
+        sums = jitter_stats(frames, flags, factors)
+    else:
+        sums = torch.zeros((frames.shape[0],), dtype=torch.int64, device=frames.device)
+    return augment_u8(frames, flags, factors, sums)
+
+
 SCORE_FRAME_WORDS = 16                     # haff_score_frame (include/haff_hip.h): 128 bytes as 16 int64 words
 SCORE_MAX_SIDE, SCORE_MAX_THRESHOLDS = 4096, 8
 

@@ -15,6 +15,10 @@ emits the same 12-tuple per sample and the same collate_fn batch dict (utils/dat
 --device_ingest (off by default; real datasets only): the batch is made on the device from uint8 frames, contour lists and token
 ids that one prefetch thread prepares (train_ingest.py) instead of on the main thread inside the step loop.
 
+--aug_flip P / --aug_jitter P (both 0 by default; real datasets only, training set only): 2HANDS' offline augmentations
+(horizontal_flip.py, apply_jitter.py) drawn per sample from (--seed, sample index): Pillow on the host loader, HIP kernels with
+--device_ingest (csrc/frame_augment.hip), the same augmented samples either way.
+
   python -m torch.distributed.run --nproc-per-node 8 2handedafforder_amd/train_ds.py --synthetic 7b --epochs 1 ...
 """
 import argparse
@@ -98,6 +102,13 @@ def parse_args(args):
                    help="make the batch on the device (train_ingest.py): the loader hands over uint8 frames, contour lists and token "
                         "ids from one prefetch thread; resizes, normalisation and the contour fill are HIP kernels. Same samples and "
                         "prompts as the host loader for one --seed. Not with --synthetic, whose dataset yields tensors")
+    p.add_argument("--aug_flip", default=0.0, type=float,
+                   help="probability of mirroring a training sample left-right, hands and taxonomy exchanged (2HANDS' "
+                        "horizontal_flip.py; its data corresponds to 0.5). Training set only; not with --synthetic")
+    p.add_argument("--aug_jitter", default=0.0, type=float,
+                   help="probability of Pillow's Brightness -> Contrast -> Color jitter with factors from U(0.4, 1.6) on a training "
+                        "frame (2HANDS' apply_jitter.py; its data corresponds to 0.25). With --device_ingest both run in HIP, "
+                        "byte for byte what the host loader's Pillow gives for one --seed. Training set only; not with --synthetic")
     return p.parse_args(args)
 
 
@@ -343,6 +354,13 @@ def _main(argv, closers):
     if args.device_ingest and args.synthetic:
         raise SystemExit("--device_ingest cannot be combined with --synthetic: the synthetic dataset yields tensors, not uint8 frames "
                          "and contours (use --sam_records or --dataset_dir)")
+    for flag in ("aug_flip", "aug_jitter"):
+        value = getattr(args, flag)
+        if not 0.0 <= value <= 1.0:
+            raise SystemExit(f"--{flag} is a probability in [0, 1], not {value}")
+        if value > 0.0 and args.synthetic:
+            raise SystemExit(f"--{flag} cannot be combined with --synthetic: the synthetic dataset yields tensors, not uint8 frames "
+                             "and contours (use --sam_records or --dataset_dir)")
     if args.load_in_8bit:
         raise SystemExit("--load_in_8bit: LLM.int8 is not built for training (inference only; --load_in_4bit trains on the NF4 base)")
     if args.load_in_4bit and args.precision != "fp16":
@@ -422,21 +440,25 @@ def _main(argv, closers):
         val_ds = SyntheticAffDataset(cfg, args.val_samples, 777, args.mask_hw, inference=True)
     else:
         # AffRecordsDataset = utils/aff_dataset.py:48-346 on the records' HF layout
+        aug = {"aug_flip": args.aug_flip, "aug_jitter": args.aug_jitter}   # the training set only: validation is never augmented
         if args.sam_records:
             records = torch.load(args.sam_records, weights_only=False)
-            train_ds = AffRecordsDataset(records, cfg, seed=args.seed + 1000 * rank)
+            train_ds = AffRecordsDataset(records, cfg, seed=args.seed + 1000 * rank, **aug)
             val_ds = AffRecordsDataset(records[:max(args.val_samples, 1)], cfg, samples_per_epoch=args.val_samples, inference=True, seed=777)
         elif os.path.isdir(args.dataset_dir):
-            train_ds = AffRecordsDataset.from_local(args.dataset_dir, cfg, seed=args.seed + 1000 * rank)
+            train_ds = AffRecordsDataset.from_local(args.dataset_dir, cfg, seed=args.seed + 1000 * rank, **aug)
             val_ds = AffRecordsDataset.from_local(args.dataset_dir, cfg, samples_per_epoch=args.val_samples, inference=True, seed=777)
         else:
-            train_ds = AffRecordsDataset.from_hf(args.dataset_dir, cfg, seed=args.seed + 1000 * rank)
+            train_ds = AffRecordsDataset.from_hf(args.dataset_dir, cfg, seed=args.seed + 1000 * rank, **aug)
             val_ds = AffRecordsDataset.from_hf(args.dataset_dir, cfg, samples_per_epoch=args.val_samples, inference=True, seed=777)
     if not args.synthetic and args.benchmark_dir and os.path.isdir(args.benchmark_dir) and not args.no_eval:
         AffValDataset = sys.modules[AffRecordsDataset.__module__].AffValDataset   # the reference's validation set (train_ds.py:330-336)
         val_ds = AffValDataset(args.benchmark_dir, cfg, seed=777)
         if rank == 0:
             print(f"Training with {len(train_ds)} examples and validating with {len(val_ds)} examples.")
+    if rank == 0 and (args.aug_flip > 0.0 or args.aug_jitter > 0.0):
+        print(f"training augmentation: flip p={args.aug_flip:g}, colour jitter p={args.aug_jitter:g} "
+              f"({'HIP kernels on the device' if args.device_ingest else 'Pillow on the host'})")
     total_steps = args.epochs * args.steps_per_epoch
     ingest = DeviceIngest(cfg, device, dtype) if args.device_ingest else None
     if args.eval_only:
@@ -542,6 +564,8 @@ def _main(argv, closers):
                     blob["loss_scaler"] = scaler.state_dict()
                 torch.save(blob, os.path.join(ckpt_dir, "latest.pt"))
                 print(f"saved checkpoint to {ckpt_dir} (global_step{global_step})")
+    if ingest is not None and ingest.host_augments:
+        print(f"[rank {rank}] {ingest.host_augments} frames beyond {ops.AUG_MAX_PIXELS} pixels were augmented on the host (Pillow)")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -7,6 +7,7 @@ of the reference). Here the loader hands over only the uint8 frame, the contour 
   images_clip       FrameIngest.clip_pixels           (csrc/frame_ingest.hip, Pillow-exact)
   SAM input         LisaTrainable.forward(frames_u8=)  (FrameIngest.sam_frames + haff_patchify_u8, as evaluate(frames_u8=))
   ground-truth masks ops.fill_contours                  (csrc/contour_fill.hip, cvlite-exact)
+  augmentation      ops.augment_frames / flip_planes   (csrc/frame_augment.hip, Pillow-exact; only for samples that carry "aug")
 
 are made from them in HBM. The text half is train_ds.collate_text, the code collate_fn itself runs. `Prefetcher` is the one
 background thread that calls `raw_item` (decode, HDF5 read, prompt) and the tokeniser ahead of the step loop; the main thread
@@ -20,6 +21,7 @@ import torch
 
 from . import cvlite
 from . import ops
+from .aff_dataset import augment_frame, flip_taxonomy
 from .preprocess import FrameIngest, get_preprocess_shape
 
 
@@ -97,7 +99,11 @@ class DeviceIngest:
     """raw samples (dataset.raw_item) -> the dict train_ds.collate_fn returns, with `images` None, `frames_u8` the batch's uint8 HWC
     frames in HBM (one [B,H,W,3] tensor when the sizes agree, else a list of [H,W,3]), `images_clip` / the mask lists made on the
     device and `label_list` carrying shapes only. `host_fills` counts the planes that had a polygon beyond the fill kernel's
-    host-checked limits (ops.FILL_MAX_VERTS vertices, |coordinate| < ops.FILL_MAX_COORD) and were filled by cvlite instead."""
+    host-checked limits (ops.FILL_MAX_VERTS vertices, |coordinate| < ops.FILL_MAX_COORD) and were filled by cvlite instead.
+    A sample that carries "aug" (aff_dataset.draw_augmentation) is augmented here as AffRecordsDataset.__getitem__ does it on the
+    host: the uploaded frame is jittered and / or mirrored before anything is derived from it, the filled planes are mirrored and
+    exchanged between the hands, taxonomy entries 0 and 1 are exchanged. `host_augments` counts the frames beyond
+    ops.AUG_MAX_PIXELS, which Pillow augmented before the upload."""
 
     def __init__(self, cfg, device, dtype):
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
@@ -105,6 +111,7 @@ class DeviceIngest:
             raise RuntimeError("DeviceIngest builds the batch in HBM (cuda device); the host loader is train_ds.collate_fn")
         self.ingest = FrameIngest(self.device)
         self.host_fills = 0
+        self.host_augments = 0
 
     def text(self, raw_samples, tokenizer, model_max_length=575, conv_type="llava_v1"):
         """The text half (host only: what Prefetcher runs in its thread)."""
@@ -119,7 +126,22 @@ class DeviceIngest:
         return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(self.device, non_blocking=True)
 
     def _frames(self, raw_samples):
+        """The uploaded frames, augmented: one [B,H,W,3] tensor with per-frame flags, or one call per frame of a list."""
         frames = [r["frame"] for r in raw_samples]
+        # None for a sample that drew nothing (or carries no draw: the validation sets)
+        augs = [a if a and (a["flip"] or a["jitter"] is not None) else None for a in (r.get("aug") for r in raw_samples)]
+        for i, a in enumerate(augs):
+            if a and not ops.augment_frames_supported(frames[i].shape[:2]):
+                frames[i], augs[i] = augment_frame(frames[i], a), None       # beyond the kernels' limit: Pillow, before the upload
+                self.host_augments += 1
+        frames = self._upload_frames(frames)
+        if not any(augs):
+            return frames
+        if torch.is_tensor(frames):
+            return ops.augment_frames(frames, augs)
+        return [ops.augment_frames(f[None], [a])[0] if a else f for f, a in zip(frames, augs)]
+
+    def _upload_frames(self, frames):
         if len({f.shape for f in frames}) == 1:
             host = torch.empty((len(frames),) + frames[0].shape, dtype=torch.uint8, pin_memory=True)
             for i, f in enumerate(frames):
@@ -152,9 +174,14 @@ class DeviceIngest:
             for k, contours in redo:
                 filled[k].copy_(self._upload(cvlite.draw_contours_filled(hw, contours)), non_blocking=True)
                 self.host_fills += 1
+            flips = [bool((raw_samples[i].get("aug") or {}).get("flip")) for i in idxs]
+            if any(flips):                 # flip(fill(contours)), never a fill of mirrored vertices: the scanline fill is not symmetric
+                flags = torch.tensor([ops.AUG_FLIP * f for f in flips for _ in range(2)], dtype=torch.int32).pin_memory()
+                filled = ops.flip_planes(filled, flags.to(self.device, non_blocking=True))
             filled = filled.float()
             for j, i in enumerate(idxs):
-                left[i], right[i] = filled[2 * j][None], filled[2 * j + 1][None]
+                a, b = (1, 0) if flips[j] else (0, 1)          # a mirrored sample's right hand is its old left one
+                left[i], right[i] = filled[2 * j + a][None], filled[2 * j + b][None]
         return left, right
 
     def batch(self, raw_samples, tokenizer, model_max_length=575, conv_type="llava_v1", text=None):
@@ -174,6 +201,7 @@ class DeviceIngest:
                 "label_list": [{"left": _ShapeOnly(r["mask_hw"]), "right": _ShapeOnly(r["mask_hw"])} for r in raw_samples],
                 "resize_list": [get_preprocess_shape(r["frame"].shape[0], r["frame"].shape[1], cfg.sam.img_size) for r in raw_samples],
                 "offset": text["offset"], "inference": raw_samples[0]["inference"], "conversation_list": text["conversation_list"],
-                "taxonomies_list": torch.stack([torch.tensor(r["taxonomy"]) for r in raw_samples], 0),
+                "taxonomies_list": torch.stack([torch.tensor(flip_taxonomy(r["taxonomy"]) if (r.get("aug") or {}).get("flip")
+                                                             else r["taxonomy"]) for r in raw_samples], 0),
                 "image_paths": [None] * len(raw_samples), "questions_list": [r["questions"] for r in raw_samples],
                 "sampled_classes_list": [r["texts"] for r in raw_samples]}

@@ -530,6 +530,26 @@ int haff_clip_normalize_u8(const void* in, void* out, int B, int Hin, int Win, i
  * the device: the per-row crossing list lives in LDS sized by the launch's longest polygon. n_poly == 0 only zeroes. */
 int haff_fill_contours_u8(const int* pts, const int* poly_off, const int* poly_plane, const int* desc_dev, int n_poly, int n_planes,
                           void* out, int H, int W, void* stream);
+/* ---- training augmentation on the device (train_ds.py --aug_flip / --aug_jitter; csrc/frame_augment.hip): the offline
+ * augmentations of the 2HANDS training set (2HANDS/scripts/data_augmentation/horizontal_flip.py, apply_jitter.py) per sample, byte
+ * for byte what Pillow gives. frames u8 [B][H][W][3] at any address; flags i32 [B] (bit 0 mirror left-right, bit 1 colour jitter),
+ * factors f32 [B][3] (brightness, contrast, colour; read only where bit 1 is set) and sums u64 [B] are DEVICE arrays.
+ *   L(r,g,b)       = (19595 r + 38470 g + 7471 b + 32768) >> 16
+ *   blend(d, i, f) = clip8(trunc(fl32(fl32(d) + fl32(f * fl32(i - d)))))   product and sum rounded separately, as Image.blend
+ *   p1 = blend(0, p, fb);  S = sum of L(p1) over the frame, m = (2 S + H W) div (2 H W);  p2 = blend(m, p1, fc);
+ *   p3 = blend(L(p2), p2, fs)   = ImageEnhance.Brightness(im).enhance(fb) -> Contrast(..).enhance(fc) -> Color(..).enhance(fs)
+ * haff_jitter_stats_u8 writes S into sums[b] for every frame with bit 1 set and 0 for the others: the B slots are zeroed by the call
+ * itself (a memset on `stream` in front of the kernel) and the partial sums are integers, so repeat runs are bitwise equal.
+ * haff_augment_u8 is out of place and one pass: jitter (with sums as haff_jitter_stats_u8 left them for the same frames, flags and
+ * factors) and / or Image.transpose(FLIP_LEFT_RIGHT) per frame; a frame with neither bit is copied.
+ * haff_flip_planes_u8 mirrors the planes of u8 [P][H][W] whose flags[p] has bit 0 set and copies the others (the filled masks).
+ * Refused before anything is enqueued: -1 for a NULL pointer, flags or factors not 4-B aligned, sums not 8-B aligned, a size <= 0,
+ * out overlapping in (out == in included); -2 for H * W > 2^24 pixels in the two frame entry points (the caller augments such a
+ * frame on the host). */
+int haff_jitter_stats_u8(const void* frames, int B, int H, int W, const int* flags, const float* factors, void* sums, void* stream);
+int haff_augment_u8(const void* in, void* out, int B, int H, int W, const int* flags, const float* factors, const void* sums,
+                    void* stream);
+int haff_flip_planes_u8(const void* in, void* out, int P, int H, int W, const int* flags, void* stream);
 /* mask > logit_th -> 0/255 bytes (inference.py:294-301 with logit_th = logit(th); chat.py:226 with 0) */
 int haff_threshold_masks(const float* in, void* out, long total, float logit_th, void* stream);
 /* a15 in one pass — the output gating + thresholds of 2Haff/inference.py:276-334 and chat.py:226-253:
