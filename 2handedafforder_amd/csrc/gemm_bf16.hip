@@ -42,67 +42,68 @@ constexpr int BK = 64;
 __device__ __attribute__((aligned(16))) unsigned int haff_zero_page[8];  // 32 B of zeros for K-tail chunks
 
 struct GemmArgs {
-  const bf16_t* A; long lda;
-  const bf16_t* W; long ldw;
-  void* C; long ldc;
-  const float* bias;
-  const void* resid; long ldr;
-  const int* row_map;
-  const int* a_map;   // optional gather: logical A row m is stored at A row a_map[m]
-  int group_m;        // M-tiles per raster group (L2 reuse window), chosen by the launcher
+  const bf16_t* A = nullptr; long lda = 0;
+  const bf16_t* W = nullptr; long ldw = 0;
+  void* C = nullptr; long ldc = 0;
+  const float* bias = nullptr;
+  const void* resid = nullptr; long ldr = 0;
+  const int* row_map = nullptr;
+  const int* a_map = nullptr;   // optional gather: logical A row m is stored at A row a_map[m]
+  int group_m = 8;    // M-tiles per raster group (L2 reuse window), chosen by the launcher
   // LayerNorm / RMSNorm folded into the product (gamma pre-multiplied into W, beta into bias by the caller):
   //   C[m][n] = act( rstd_m * (acc[m][n] - mean_m * colsum[n]) + bias[n] ),  ln_stats[m] = {mean_m, rstd_m}
   // colsum[n] = sum_k W[n][k] (of the gamma-scaled, bf16-rounded weights); null colsum (RMSNorm): mean term dropped.
-  const float* ln_stats;
-  const float* ln_colsum;
-  int M, N, K;
-  int act, out_f32, swiglu;
+  const float* ln_stats = nullptr;
+  const float* ln_colsum = nullptr;
+  int M = 0, N = 0, K = 0;
+  int act = 0, out_f32 = 0, swiglu = 0;
   // batched launches (blockIdx.y = z): operand z lives at base + (z / nb_inner) * s?o + (z % nb_inner) * s?i elements
-  int nb_inner;
-  long sAo, sAi, sWo, sWi, sCo, sCi;
-  int deep_k;         // 128x128 tile: K loop with TWO K-tiles of DMA in flight (two barriers per K-tile); set by the launcher
-  int k_total;        // split-K with a short last slice: inner batch zi covers K columns [zi*K, min((zi+1)*K, k_total)); 0 = every slice has K
-  int nt_out;         // non-temporal output stores (large outputs; chosen by the launcher)
+  int nb_inner = 0;
+  long sAo = 0, sAi = 0, sWo = 0, sWi = 0, sCo = 0, sCi = 0;
+  int deep_k = 0;     // 128x128 tile: K loop with TWO K-tiles of DMA in flight (two barriers per K-tile); set by the launcher
+  int k_total = 0;    // split-K with a short last slice: inner batch zi covers K columns [zi*K, min((zi+1)*K, k_total)); 0 = every slice has K
+  int nt_out = 0;     // non-temporal output stores (large outputs; chosen by the launcher)
   // weight-streaming kernel with K split over blockIdx.y: each slice writes its fp32 partial tile to ws[slice][M][N]
   // (caller-provided workspace) and skinny_reduce_kernel applies the epilogue to the slice sum, in slice order
-  float* ws;
-  int ksplit;
+  float* ws = nullptr;
+  int ksplit = 0;
   // RMSNorm carried between decode-sized products without a norm kernel (weight-streaming kernel, M <= 16):
   //   producer (ssq_out): workgroup b writes ssq_out[b][m] = sum over ITS output columns of bf16(C[m][n])^2, m < 16;
   //   consumer (ssq_in):  rstd_m = rsqrt(sum_b ssq_in[b][m] / K + ssq_eps) (b < ssq_n, fixed order) scales row m of the
   //   product of the RAW activations with gamma-folded weights — the same fold as ln_stats, with the statistic assembled
   //   from the producer's partials instead of a pass over the row.
-  float* ssq_out;
-  const float* ssq_in;
-  int ssq_n;
-  float ssq_eps;
+  float* ssq_out = nullptr;
+  const float* ssq_in = nullptr;
+  int ssq_n = 0;
+  float ssq_eps = 0.f;
   // LayerNorm statistics of the OUTPUT rows, emitted by the producer (8-wave tile, register epilogue with a bf16 residual,
   // whole interior tiles only — haff_gemm_bf16_rowstats): wave (n-tile, wn) writes {sum, sum of squares} of its 64 output
   // columns of row m to stat_out[m][stat_slots][2], slot = first column / 64; haff_row_stats_finalize adds the slots in
   // order. The consumer product then needs no pass over the rows it normalises.
-  float* stat_out;
-  int stat_slots;
+  float* stat_out = nullptr;
+  int stat_slots = 0;
   // fp32 RESIDUAL STREAM beside the bf16 one (round 6, haff_gemm_bf16_rowstats32; specialised 8-wave instance only): the residual
   // is read from and the sum written back to res32[m][ld32] in fp32 (in place), and C receives the bf16 copy of the same values
   // (the next product's MFMA operand); stat_out as above, from the fp32 values. The stream is rounded to bf16 ONCE per consumer
   // instead of once per residual add (64 times through a ViT-H).
-  float* res32;
-  long ld32;
+  float* res32 = nullptr;
+  long ld32 = 0;
   // Llama prefill q|k|v projection with RoPE and the KV-cache append in the epilogue (haff_gemm_bf16_qkv_rope; 8-wave tile,
   // register epilogue, bf16, no residual). W's rows arrive PERMUTED inside every 256-row tile so that a lane holds column c
   // of a head in col-block t and its rotate-half partner c + 64 in col-block t + 2 (natural tile column wn*64 + t*16 + i is
   // logical column (wn>>1)*128 + (t>>1)*64 + (wn&1)*32 + (t&1)*16 + i). Tiles of the q block: rotated, stored to C (the q
   // buffer, ldc); k block: rotated, stored to rope_k; v block: stored to rope_v; caches [B][rope_tmax][rope_hd], row (b, pos0 + t)
   // for product row m = b * rope_t + t. rope_cs: f32 [rope_tmax][128] = cos(0..63) | sin(0..63).
-  const float* rope_cs;
-  void *rope_k, *rope_v;
-  int rope_t, rope_tmax, rope_pos0, rope_hd;
+  const float* rope_cs = nullptr;
+  void *rope_k = nullptr, *rope_v = nullptr;
+  int rope_t = 0, rope_tmax = 0, rope_pos0 = 0, rope_hd = 0;
   // HEAD-MAJOR scatter of the output (haff_gemm_bf16_heads; 8-wave tile, register epilogue, bf16, row map, no residual): product
   // column n = part * hm_hd + h * hm_d + c of product row m is stored at C[part * hm_part + h * hm_head + row_map[m] * hm_d + c]
   // (elements). hm_d == 0: off.
-  int hm_d, hm_hd;
-  long hm_part, hm_head;
+  int hm_d = 0, hm_hd = 0;
+  long hm_part = 0, hm_head = 0;
 };
+static_assert(std::is_trivially_copyable_v<GemmArgs>, "GemmArgs is passed to the kernels by value");
 
 // Epilogue activations of the throughput (bf16) path. GELU matters for the K=1280 SAM MLP GEMM, whose epilogue touches
 // 5120 columns per row: a polynomial erf (below) instead of ocml erff. The fp32 parity kernel keeps erff.
@@ -1605,6 +1606,42 @@ extern "C" int haff_gemm_stream_cap(void* stream, int cap) {
   return old < 0 ? HAFF_ERR_UNSUPPORTED : old;
 }
 
+// The host-side rules the entry points below share, one function each. al16: 16-byte aligned (or null)
+static inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+// the operand contract of every entry point: rows are read in 16-byte chunks (K, lda, ldw in whole chunks, aligned bases)
+static inline bool operands_ok(const void* A, long lda, const void* W, long ldw, int K) {
+  return !((K & 7) || (lda & 7) || (ldw & 7)) && al16(A) && al16(W);
+}
+// the 8-wave tile addresses operands with 32-bit byte offsets (a_rows: the rows of A behind a gather, see GemmArgs::a_map)
+static inline bool operands_in_4g(const GemmArgs& p, long a_rows) {
+  return (long)(p.a_map ? a_rows : p.M) * p.lda * 2 < (1L << 32) && (long)p.N * p.ldw * 2 < (1L << 32);
+}
+
+// Raster group depth: 8 M-tiles share their A panels across the N sweep; with a long K loop (>= 5120) and few N tiles
+// the concurrently running tiles drift apart and a 2-deep group keeps more of the sweep in the 4 MiB L2
+// (measured +5 % on 131072x1280x5120 and 18624x4096x11008 with an experiment build removed after 58cf410).
+static inline int raster_group_m(int N, int K) {
+  // (sweep of 1..32 on the bench shapes, with an experiment build removed after 58cf410: <= 5 N-tiles: 1 (+4 % on
+  // 131072x1280x1280), <= 16 N-tiles: 4 (+1.4 % on 131072x3840x1280), 20 N-tiles: 8; all within 3 % of each other)
+  // (round 3, ring loop: <= 5 N-tiles 1; long K with <= 8 N-tiles 2; <= 16 N-tiles 4 (18624x4096x11008: 1351 vs 1315 at 2); 8)
+  const int tn = (N + 255) / 256;
+  if (tn <= 5) return 1;
+  if (K >= 5120 && tn <= 8) return 2;
+  if (tn <= 16) return 4;
+  return 8;
+}
+
+// The common core of an argument block; every other field keeps its default (off) until an entry point sets it BY NAME.
+// nt_out is set by gemm_bf16_impl and haff_gemm_*_heads only (not by the qkv_rope, rowstats and rowstats32 entry points).
+static inline GemmArgs gemm_args(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K) {
+  GemmArgs p;
+  p.A = reinterpret_cast<const bf16_t*>(A); p.lda = lda;
+  p.W = reinterpret_cast<const bf16_t*>(W); p.ldw = ldw;
+  p.C = C; p.ldc = ldc;
+  p.M = M; p.N = N; p.K = K;
+  return p;
+}
+
 template <int BM, int BN, int WM, int WN, bool F16 = false>
 static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
@@ -1614,17 +1651,15 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
     if (cap > 0 && gx > cap) gx = cap;
   }
   dim3 grid(gx, nbatch), block(64 * WM * WN);
-  GemmArgs pd = p;
+  GemmArgs pl = p;
   if (WM * WN == 4) {
     constexpr long deep_max = 1024;   // 128x128 work items (tiles x slices) up to which the launch takes the two-K-tiles-in-flight loop
-    pd.deep_k = (long)tiles * nbatch <= deep_max && ((p.K + BK - 1) / BK) >= 3;
+    pl.deep_k = (long)tiles * nbatch <= deep_max && ((p.K + BK - 1) / BK) >= 3;
   }
-  const GemmArgs& pl = pd;
   if constexpr (BM == 256 && BN == 256 && WM * WN == 8) {
     // a specialised instance (see the GF_* flags) when the launch meets its host-side contract and its feature set has one
-    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && a16(p.C) && (p.ldc & 7) == 0 && a16(p.bias) &&
-                    a16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && a16(p.ln_stats) && a16(p.ln_colsum) && a16(p.row_map) &&
+    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && al16(p.C) && (p.ldc & 7) == 0 && al16(p.bias) &&
+                    al16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && al16(p.ln_stats) && al16(p.ln_colsum) && al16(p.row_map) &&
                     (!p.ln_colsum || p.ln_stats);
     if (ok) {
       const unsigned f = (p.bias ? GF_BIAS : 0u) | (p.ln_stats ? GF_LN : 0u) | (p.ln_colsum ? GF_CSUM : 0u) |
@@ -1656,9 +1691,8 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
     }
   }
   if constexpr (BM == 192 && BN == 256 && WM * WN == 8) {   // the fine-tune step's 2808-row products (forward, dX): plain / residual / SwiGLU
-    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && a16(p.C) && (p.ldc & 7) == 0 && a16(p.bias) &&
-                    a16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && !p.ln_stats && !p.ln_colsum && !p.row_map && !p.stat_out && !p.hm_d &&
+    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && al16(p.C) && (p.ldc & 7) == 0 && al16(p.bias) &&
+                    al16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && !p.ln_stats && !p.ln_colsum && !p.row_map && !p.stat_out && !p.hm_d &&
                     !p.rope_cs && p.act == 0;
     if (ok) {
       const unsigned f = (p.bias ? GF_BIAS : 0u) | (p.resid ? GF_RES : 0u);
@@ -1686,18 +1720,14 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
   return haff_check_launch();
 }
 
+// The dispatcher of the general product. p: the argument block as the entry point built it (operands, epilogue, a_map, ln_*);
+// a_rows: rows of A behind p.a_map; tile_cfg: see haff_gemm_bf16_cfg; workspace: see haff_gemm_bf16_ws.
 template <bool F16 = false>
-static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw, void* C,
-                          long ldc, const float* bias, const void* resid, long ldr, const int* row_map, int M, int N,
-                          int K, int act, int out_f32, int swiglu, int tile_cfg, void* stream,
-                          const float* ln_stats = nullptr, const float* ln_colsum = nullptr, void* workspace = nullptr,
-                          long workspace_bytes = 0) {
+static int gemm_bf16_impl(GemmArgs p, long a_rows, int tile_cfg, void* workspace, long workspace_bytes, void* stream) {
+  const int M = p.M, N = p.N, K = p.K, swiglu = p.swiglu;
   if (M <= 0 || N <= 0 || K <= 0) return HAFF_ERR_BAD_ARG;
-  if ((K & 7) || (lda & 7) || (ldw & 7)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return HAFF_ERR_BAD_ARG;
-  if (swiglu && ((N & 31) || (ldc & 3) || resid)) return HAFF_ERR_BAD_ARG;
-  GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), ldw, C, ldc,
-             bias, resid, ldr, row_map, a_map, 8, ln_stats, ln_colsum, M, N, K, act, out_f32, swiglu, 0, 0, 0, 0, 0, 0, 0};
+  if (!operands_ok(p.A, p.lda, p.W, p.ldw, K)) return HAFF_ERR_BAD_ARG;
+  if (swiglu && ((N & 31) || (p.ldc & 3) || p.resid)) return HAFF_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // weight-streaming kernel for decode-sized M; past 32 rows the 128x128 tile is faster again on very wide outputs
   // (M = 64: gate/up 53 vs 75 us, lm_head 68 vs 84 us; qkv 49 vs 42, o_proj 46 vs 24, down 113 vs 63)
@@ -1705,9 +1735,9 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
   // 33..64 rows with a workspace: wide or deep weights go to the split-K tile path below (M = 64: qkv 31.7 vs 36.7 us, down_proj
   // 31.5 vs 42.4 us with 16 uneven K slices; o_proj stays here: 17.3 vs 20.6 us; tools/skinny64_ab.py)
   constexpr int tile_min_m = 32;
-  const bool tile_rows = M > tile_min_m && workspace && (K % BK) == 0 && !ln_stats && (N >= 8192 || K >= 8192);
+  const bool tile_rows = M > tile_min_m && workspace && (K % BK) == 0 && !p.ln_stats && (N >= 8192 || K >= 8192);
   if (M <= skinny_max_m && (K % 128) == 0 && tile_cfg == 0 && !(M > 32 && N >= 16384) && !tile_rows) {
-    if (M > 32 && workspace && workspace_bytes >= 4L * 4 * M * N && !a_map) {
+    if (M > 32 && workspace && workspace_bytes >= 4L * 4 * M * N && !p.a_map) {
       p.ws = reinterpret_cast<float*>(workspace);
       if (launch_skinny_splitk<F16>(p, s)) return haff_check_launch();
       p.ws = nullptr;
@@ -1722,7 +1752,7 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
   // 64-step K loop each on 96 CUs: 62 us; 4 slices: 384 workgroups x 16 steps). Each slice is a "batch" of the batched
   // launch — operands offset by slice * K/ks along K, fp32 partial tile into ws[slice][M][N] — and skinny_reduce_kernel
   // adds the slices in index order and applies the epilogue: deterministic.
-  if (tile_cfg == 0 && workspace && !ln_stats && M > tile_min_m && (K % BK) == 0) {
+  if (tile_cfg == 0 && workspace && !p.ln_stats && M > tile_min_m && (K % BK) == 0) {
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     const int ksteps = K / BK;
     int ks = 0;
@@ -1747,7 +1777,7 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
     }
   }
   // the 8-wave tile addresses operands with 32-bit byte offsets and has no K-tail path
-  const bool big_ok = (K % BK == 0) && ((long)(a_map ? a_rows : M) * lda * 2 < (1L << 32)) && ((long)N * ldw * 2 < (1L << 32));
+  const bool big_ok = (K % BK == 0) && operands_in_4g(p, a_rows);
   bool big = tile_cfg == 2 && big_ok;
   bool mid_tile = tile_cfg == 3 && big_ok;   // the 192 x 256 form of the 8-wave tile
   if (tile_cfg == 0 && big_ok) {
@@ -1765,21 +1795,10 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
     // TFLOP/s; K = 22016: 986 -> 1207); 5000 x 4096: 1010 -> 1115
     const long t192 = (long)((M + 191) / 192) * ((N + 255) / 256);
     const double e192 = (double)t192 / (double)(((t192 + 255) / 256) * 256) * 1.22 * 0.93;
-    if (M >= 192 && N >= 256 && !ln_stats && e192 > 1.05 * (e256 > e128 ? e256 : e128)) { mid_tile = true; big = false; }
+    if (M >= 192 && N >= 256 && !p.ln_stats && e192 > 1.05 * (e256 > e128 ? e256 : e128)) { mid_tile = true; big = false; }
   }
-  // Raster group depth: 8 M-tiles share their A panels across the N sweep; with a long K loop (>= 5120) and few N tiles
-  // the concurrently running tiles drift apart and a 2-deep group keeps more of the sweep in the 4 MiB L2
-  // (measured +5 % on 131072x1280x5120 and 18624x4096x11008 with an experiment build removed after 58cf410).
-  if (big || mid_tile) {
-    // (sweep of 1..32 on the bench shapes, with an experiment build removed after 58cf410: <= 5 N-tiles: 1 (+4 % on
-    // 131072x1280x1280), <= 16 N-tiles: 4 (+1.4 % on 131072x3840x1280), 20 N-tiles: 8; all within 3 % of each other)
-    // (round 3, ring loop: <= 5 N-tiles 1; long K with <= 8 N-tiles 2; <= 16 N-tiles 4 (18624x4096x11008: 1351 vs 1315 at 2); 8)
-    const int tn = (N + 255) / 256;
-    if (tn <= 5) p.group_m = 1;
-    else if (K >= 5120 && tn <= 8) p.group_m = 2;
-    else if (tn <= 16) p.group_m = 4;
-  }
-  p.nt_out = (long)M * (swiglu ? N / 2 : N) * (out_f32 ? 4 : 2) >= (64L << 20);
+  if (big || mid_tile) p.group_m = raster_group_m(N, K);   // the 4-wave tile keeps the default depth
+  p.nt_out = (long)M * (swiglu ? N / 2 : N) * (p.out_f32 ? 4 : 2) >= (64L << 20);
   if (mid_tile) return launch_gemm<192, 256, 2, 4, F16>(p, s);
   return big ? launch_gemm<256, 256, 2, 4, F16>(p, s) : launch_gemm<128, 128, 2, 2, F16>(p, s);
 }
@@ -1788,15 +1807,17 @@ static int gemm_bf16_impl(const void* A, long lda, const int* a_map, long a_rows
 extern "C" int haff_gemm_bf16_cfg(const void* A, long lda, const void* W, long ldw, void* C, long ldc,
                                   const float* bias, const void* resid, long ldr, const int* row_map,
                                   int M, int N, int K, int act, int out_f32, int swiglu, int tile_cfg, void* stream) {
-  return gemm_bf16_impl(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu,
-                        tile_cfg, stream);
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  return gemm_bf16_impl(p, 0, tile_cfg, nullptr, 0, stream);
 }
 
 extern "C" int haff_gemm_bf16(const void* A, long lda, const void* W, long ldw, void* C, long ldc,
                               const float* bias, const void* resid, long ldr, const int* row_map,
                               int M, int N, int K, int act, int out_f32, int swiglu, void* stream) {
-  return gemm_bf16_impl(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
-                        stream);
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  return gemm_bf16_impl(p, 0, 0, nullptr, 0, stream);
 }
 
 // haff_gemm_bf16 with a caller-provided workspace (DEVICE memory, 16-B aligned, >= 16 * M * N bytes to be used): lets the
@@ -1806,9 +1827,10 @@ extern "C" int haff_gemm_bf16(const void* A, long lda, const void* W, long ldw, 
 extern "C" int haff_gemm_bf16_ws(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                                  const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
                                  int swiglu, void* workspace, long workspace_bytes, void* stream) {
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15)) return HAFF_ERR_BAD_ARG;
-  return gemm_bf16_impl(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
-                        stream, nullptr, nullptr, workspace, workspace_bytes);
+  if (!al16(workspace)) return HAFF_ERR_BAD_ARG;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  return gemm_bf16_impl(p, 0, 0, workspace, workspace_bytes, stream);
 }
 
 // fp16 instances of the three entry points above (inference in fp16: A, W and a 16-bit C or resid are IEEE binary16,
@@ -1816,23 +1838,26 @@ extern "C" int haff_gemm_bf16_ws(const void* A, long lda, const void* W, long ld
 extern "C" int haff_gemm_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc,
                              const float* bias, const void* resid, long ldr, const int* row_map,
                              int M, int N, int K, int act, int out_f32, int swiglu, void* stream) {
-  return gemm_bf16_impl<true>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
-                              stream);
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  return gemm_bf16_impl<true>(p, 0, 0, nullptr, 0, stream);
 }
 
 extern "C" int haff_gemm_f16_cfg(const void* A, long lda, const void* W, long ldw, void* C, long ldc,
                                  const float* bias, const void* resid, long ldr, const int* row_map,
                                  int M, int N, int K, int act, int out_f32, int swiglu, int tile_cfg, void* stream) {
-  return gemm_bf16_impl<true>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu,
-                              tile_cfg, stream);
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  return gemm_bf16_impl<true>(p, 0, tile_cfg, nullptr, 0, stream);
 }
 
 extern "C" int haff_gemm_f16_ws(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                                 const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
                                 int swiglu, void* workspace, long workspace_bytes, void* stream) {
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15)) return HAFF_ERR_BAD_ARG;
-  return gemm_bf16_impl<true>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
-                              stream, nullptr, nullptr, workspace, workspace_bytes);
+  if (!al16(workspace)) return HAFF_ERR_BAD_ARG;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  return gemm_bf16_impl<true>(p, 0, 0, workspace, workspace_bytes, stream);
 }
 
 // Decode-sized product (M <= 16; with ssq_in M <= 8 and ssq_n <= 512; K % 128 == 0; weight-streaming kernel) that carries Llama's RMSNorm between products
@@ -1847,14 +1872,12 @@ template <bool F16 = false>
 static int gemm_rms_impl(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                          const void* resid, long ldr, int M, int N, int K, int act, int out_f32, int swiglu,
                          const float* ssq_in, int ssq_n, float eps, float* ssq_out, int* n_parts_out, void* stream) {
-  if (M <= 0 || M > 16 || N <= 0 || K <= 0 || (K % 128) || (lda & 7) || (ldw & 7)) return HAFF_ERR_BAD_ARG;
-  if (ssq_in && (M > 8 || ssq_n > 512)) return HAFF_ERR_BAD_ARG;   // consumer side: <= 8 rows, <= 512 producer workgroups
-  if (ssq_in && (reinterpret_cast<uintptr_t>(ssq_in) & 15)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return HAFF_ERR_BAD_ARG;
+  if (M <= 0 || M > 16 || N <= 0 || K <= 0 || (K % 128) || !operands_ok(A, lda, W, ldw, K)) return HAFF_ERR_BAD_ARG;
+  if (ssq_in && (M > 8 || ssq_n > 512 || !al16(ssq_in))) return HAFF_ERR_BAD_ARG;   // consumer side: <= 8 rows, <= 512 producer workgroups
   if (swiglu && ((N & 31) || (ldc & 3) || resid)) return HAFF_ERR_BAD_ARG;
   if ((ssq_in && ssq_n <= 0) || (ssq_out && (out_f32 || swiglu))) return HAFF_ERR_BAD_ARG;
-  GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), ldw, C, ldc,
-             bias, resid, ldr, nullptr, nullptr, 8, nullptr, nullptr, M, N, K, act, out_f32, swiglu, 0, 0, 0, 0, 0, 0, 0};
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
   p.ssq_in = ssq_in; p.ssq_n = ssq_n; p.ssq_eps = eps; p.ssq_out = ssq_out;
   // launch_skinny<1>: 16 weight rows per workgroup (32 for SwiGLU pairs)
   if (n_parts_out) *n_parts_out = swiglu ? (N + 31) / 32 : (N + 15) / 16;
@@ -1875,26 +1898,25 @@ extern "C" int haff_gemm_f16_rms(const void* A, long lda, const void* W, long ld
 // Same with a gather on the A side: logical row m of the product reads A row a_map[m] (0 <= a_map[m] < a_rows).
 // Used to run the window-unpartition projection only over real tokens (image_encoder.py:186-188,291-318: the padded
 // window rows are dropped right after the projection, so they are never multiplied).
-template <bool F16 = false>
-static int gemm_gather_impl(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
-                            void* C, long ldc, const float* bias, const void* resid, long ldr,
-                            const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
-                            void* stream) {
-  if (!a_map || a_rows <= 0) return HAFF_ERR_BAD_ARG;
-  return gemm_bf16_impl<F16>(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu,
-                        0, stream);
-}
 extern "C" int haff_gemm_bf16_gather(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
                                      void* C, long ldc, const float* bias, const void* resid, long ldr,
                                      const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
                                      void* stream) {
-  return gemm_gather_impl(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, stream);
+  if (!a_map || a_rows <= 0) return HAFF_ERR_BAD_ARG;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  p.a_map = a_map;
+  return gemm_bf16_impl(p, a_rows, 0, nullptr, 0, stream);
 }
 extern "C" int haff_gemm_f16_gather(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
                                     void* C, long ldc, const float* bias, const void* resid, long ldr,
                                     const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
                                     void* stream) {
-  return gemm_gather_impl<true>(A, lda, a_map, a_rows, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, stream);
+  if (!a_map || a_rows <= 0) return HAFF_ERR_BAD_ARG;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  p.a_map = a_map;
+  return gemm_bf16_impl<true>(p, a_rows, 0, nullptr, 0, stream);
 }
 
 // Llama prefill q|k|v projection with rotate-half RoPE and the KV-cache append in the epilogue (transformers LlamaAttention.forward
@@ -1910,22 +1932,16 @@ static int gemm_qkv_rope_impl(const void* A, long lda, const void* Wp, long ldw,
                               void* stream) {
   if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || !q_out || !kcache || !vcache || !cos_sin || pos0 < 0 || pos0 + T > Tmax)
     return HAFF_ERR_BAD_ARG;
-  if ((K & 7) || (lda & 7) || (ldw & 7) || (ldq & 7)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(Wp) & 15) || (reinterpret_cast<uintptr_t>(q_out) & 15) ||
-      (reinterpret_cast<uintptr_t>(kcache) & 15) || (reinterpret_cast<uintptr_t>(vcache) & 15) || (reinterpret_cast<uintptr_t>(cos_sin) & 15))
+  if (!operands_ok(A, lda, Wp, ldw, K) || (ldq & 7) || !al16(q_out) || !al16(kcache) || !al16(vcache) || !al16(cos_sin))
     return HAFF_ERR_BAD_ARG;
   const long M = (long)B * T;
   const int hd = H * d, N = 3 * hd;
   if (d != 128 || (hd % 256) || (K % BK) || M >= (1L << 22)) return HAFF_ERR_UNSUPPORTED;
-  if (M * lda * 2 >= (1L << 32) || (long)N * ldw * 2 >= (1L << 32)) return HAFF_ERR_UNSUPPORTED;
-  GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(Wp), ldw, q_out, ldq,
-             nullptr, nullptr, 0, nullptr, nullptr, 8, nullptr, nullptr, (int)M, N, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  GemmArgs p = gemm_args(A, lda, Wp, ldw, q_out, ldq, (int)M, N, K);
+  if (!operands_in_4g(p, 0)) return HAFF_ERR_UNSUPPORTED;
   p.rope_cs = cos_sin; p.rope_k = kcache; p.rope_v = vcache;
   p.rope_t = T; p.rope_tmax = Tmax; p.rope_pos0 = pos0; p.rope_hd = hd;
-  const int tn = N / 256;
-  if (tn <= 5) p.group_m = 1;
-  else if (K >= 5120 && tn <= 8) p.group_m = 2;
-  else if (tn <= 16) p.group_m = 4;
+  p.group_m = raster_group_m(N, K);
   return launch_gemm<256, 256, 2, 4, F16>(p, reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int haff_gemm_bf16_qkv_rope(const void* A, long lda, const void* Wp, long ldw, void* q_out, long ldq, void* kcache,
@@ -1950,20 +1966,14 @@ static int gemm_rowstats_impl(const void* A, long lda, const int* a_map, long a_
                               void* C, long ldc, const float* bias, const void* resid, long ldr, int M, int N, int K,
                               float* stat_out, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || !resid || !stat_out) return HAFF_ERR_BAD_ARG;
-  if ((K & 7) || (lda & 7) || (ldw & 7) || (ldc & 7) || (ldr & 7)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(C) & 15) ||
-      (reinterpret_cast<uintptr_t>(resid) & 15) || (reinterpret_cast<uintptr_t>(stat_out) & 7))
+  if (!operands_ok(A, lda, W, ldw, K) || (ldc & 7) || (ldr & 7) || !al16(C) || !al16(resid) || (reinterpret_cast<uintptr_t>(stat_out) & 7))
     return HAFF_ERR_BAD_ARG;
   if ((M % 256) || (N % 256) || (K % BK) || (a_map && a_rows <= 0)) return HAFF_ERR_UNSUPPORTED;
-  if ((long)(a_map ? a_rows : M) * lda * 2 >= (1L << 32) || (long)N * ldw * 2 >= (1L << 32)) return HAFF_ERR_UNSUPPORTED;
-  GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), ldw, C, ldc,
-             bias, resid, ldr, nullptr, a_map, 8, nullptr, nullptr, M, N, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  p.stat_out = stat_out;
-  p.stat_slots = N / 64;
-  const int tn = N / 256;   // raster depth: the rule of gemm_bf16_impl
-  if (tn <= 5) p.group_m = 1;
-  else if (K >= 5120 && tn <= 8) p.group_m = 2;
-  else if (tn <= 16) p.group_m = 4;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.a_map = a_map;
+  if (!operands_in_4g(p, a_rows)) return HAFF_ERR_UNSUPPORTED;
+  p.stat_out = stat_out; p.stat_slots = N / 64;
+  p.group_m = raster_group_m(N, K);
   return launch_gemm<256, 256, 2, 4, F16>(p, reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int haff_gemm_bf16_rowstats(const void* A, long lda, const int* a_map, long a_rows, const void* W, long ldw,
@@ -1985,22 +1995,16 @@ extern "C" int haff_gemm_bf16_rowstats32(const void* A, long lda, const int* a_m
                                          float* X32, long ldx, void* C16, long ldc, const float* bias, int M, int N, int K,
                                          float* stat_out, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || !X32 || !C16 || !stat_out || !bias) return HAFF_ERR_BAD_ARG;
-  if ((K & 7) || (lda & 7) || (ldw & 7) || (ldc & 7) || (ldx & 3)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(C16) & 15) ||
-      (reinterpret_cast<uintptr_t>(X32) & 15) || (reinterpret_cast<uintptr_t>(stat_out) & 7) || (reinterpret_cast<uintptr_t>(bias) & 15))
+  if (!operands_ok(A, lda, W, ldw, K) || (ldc & 7) || (ldx & 3) || !al16(C16) || !al16(X32) || !al16(bias) ||
+      (reinterpret_cast<uintptr_t>(stat_out) & 7))
     return HAFF_ERR_BAD_ARG;
   if ((M % 256) || (N % 256) || (K % BK) || (a_map && a_rows <= 0)) return HAFF_ERR_UNSUPPORTED;
-  if ((long)(a_map ? a_rows : M) * lda * 2 >= (1L << 32) || (long)N * ldw * 2 >= (1L << 32)) return HAFF_ERR_UNSUPPORTED;
-  GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), ldw, C16, ldc,
-             bias, nullptr, 0, nullptr, a_map, 8, nullptr, nullptr, M, N, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  p.stat_out = stat_out;
-  p.stat_slots = N / 64;
-  p.res32 = X32;
-  p.ld32 = ldx;
-  const int tn = N / 256;   // raster depth: the rule of gemm_bf16_impl
-  if (tn <= 5) p.group_m = 1;
-  else if (K >= 5120 && tn <= 8) p.group_m = 2;
-  else if (tn <= 16) p.group_m = 4;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C16, ldc, M, N, K);
+  p.bias = bias; p.a_map = a_map;
+  if (!operands_in_4g(p, a_rows)) return HAFF_ERR_UNSUPPORTED;
+  p.stat_out = stat_out; p.stat_slots = N / 64;
+  p.res32 = X32; p.ld32 = ldx;
+  p.group_m = raster_group_m(N, K);
   return launch_gemm<256, 256, 2, 4>(p, reinterpret_cast<hipStream_t>(stream));   // always meets the specialised instance's contract
 }
 
@@ -2008,26 +2012,25 @@ extern "C" int haff_gemm_bf16_rowstats32(const void* A, long lda, const int* a_m
 // HBM. The caller scales W's columns by gamma, adds W.beta to the bias (haff side: sam.py / llava.py at load time) and
 // passes the per-row {mean, rstd} from haff_row_stats. Replaces norm1->qkv and norm2->lin1 of the SAM blocks
 // (image_encoder.py:179,191), input/post-attention RMSNorm -> qkv / gate-up of Llama, layer_norm1/2 of CLIP.
-template <bool F16 = false>
-static int gemm_ln_impl(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
-                        const void* resid, long ldr, const int* row_map, const float* ln_stats,
-                        const float* ln_colsum, int M, int N, int K, int act, int out_f32, int swiglu,
-                        void* stream) {
-  if (!ln_stats) return HAFF_ERR_BAD_ARG;
-  return gemm_bf16_impl<F16>(A, lda, nullptr, 0, W, ldw, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu, 0,
-                        stream, ln_stats, ln_colsum);
-}
 extern "C" int haff_gemm_bf16_ln(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                                  const void* resid, long ldr, const int* row_map, const float* ln_stats,
                                  const float* ln_colsum, int M, int N, int K, int act, int out_f32, int swiglu,
                                  void* stream) {
-  return gemm_ln_impl(A, lda, W, ldw, C, ldc, bias, resid, ldr, row_map, ln_stats, ln_colsum, M, N, K, act, out_f32, swiglu, stream);
+  if (!ln_stats) return HAFF_ERR_BAD_ARG;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  p.ln_stats = ln_stats; p.ln_colsum = ln_colsum;
+  return gemm_bf16_impl(p, 0, 0, nullptr, 0, stream);
 }
 extern "C" int haff_gemm_f16_ln(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                                 const void* resid, long ldr, const int* row_map, const float* ln_stats,
                                 const float* ln_colsum, int M, int N, int K, int act, int out_f32, int swiglu,
                                 void* stream) {
-  return gemm_ln_impl<true>(A, lda, W, ldw, C, ldc, bias, resid, ldr, row_map, ln_stats, ln_colsum, M, N, K, act, out_f32, swiglu, stream);
+  if (!ln_stats) return HAFF_ERR_BAD_ARG;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
+  p.ln_stats = ln_stats; p.ln_colsum = ln_colsum;
+  return gemm_bf16_impl<true>(p, 0, 0, nullptr, 0, stream);
 }
 
 // Product (optionally with a folded norm, as haff_gemm_bf16_ln) whose output is scattered HEAD-MAJOR: the windowed q|k|v
@@ -2045,19 +2048,14 @@ static int gemm_heads_impl(const void* A, long lda, const void* W, long ldw, voi
                            const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads,
                            long part_stride, long head_stride, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || d <= 0 || heads <= 0 || !row_map || !C) return HAFF_ERR_BAD_ARG;
-  if ((K & 7) || (lda & 7) || (ldw & 7) || (part_stride & 7) || (head_stride & 7)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(C) & 15))
-    return HAFF_ERR_BAD_ARG;
+  if (!operands_ok(A, lda, W, ldw, K) || (part_stride & 7) || (head_stride & 7) || !al16(C)) return HAFF_ERR_BAD_ARG;
   const long hd = (long)heads * d;
   if ((d & 7) || d > 4096 || (M % 256) || (N % 256) || (K % BK) || N % hd != 0 || N / hd > 3 || hd >= (1L << 16)) return HAFF_ERR_UNSUPPORTED;
-  if ((long)M * lda * 2 >= (1L << 32) || (long)N * ldw * 2 >= (1L << 32)) return HAFF_ERR_UNSUPPORTED;
-  GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), ldw, C, (long)d,
-             bias, nullptr, 0, row_map, nullptr, 8, ln_stats, ln_colsum, M, N, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, (long)d, M, N, K);
+  if (!operands_in_4g(p, 0)) return HAFF_ERR_UNSUPPORTED;
+  p.bias = bias; p.row_map = row_map; p.ln_stats = ln_stats; p.ln_colsum = ln_colsum;
   p.hm_d = d; p.hm_hd = (int)hd; p.hm_part = part_stride; p.hm_head = head_stride;
-  const int tn = N / 256;   // raster depth: the rule of gemm_bf16_impl
-  if (tn <= 5) p.group_m = 1;
-  else if (K >= 5120 && tn <= 8) p.group_m = 2;
-  else if (tn <= 16) p.group_m = 4;
+  p.group_m = raster_group_m(N, K);
   p.nt_out = (long)M * N * 2 >= (64L << 20);
   return launch_gemm<256, 256, 2, 4, F16>(p, reinterpret_cast<hipStream_t>(stream));
 }
@@ -2078,10 +2076,10 @@ template <bool F16>
 static int gemm_batched_impl(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo, long sWi, void* C,
                              long ldc, long sCo, long sCi, int nb_outer, int nb_inner, int M, int N, int K, int out_f32, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || nb_outer <= 0 || nb_inner <= 0) return HAFF_ERR_BAD_ARG;
-  if ((K & 7) || (lda & 7) || (ldw & 7) || (sAo & 7) || (sAi & 7) || (sWo & 7) || (sWi & 7)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(W) & 15)) return HAFF_ERR_BAD_ARG;
-  GemmArgs p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(W), ldw, C, ldc,
-             nullptr, nullptr, 0, nullptr, nullptr, 8, nullptr, nullptr, M, N, K, 0, out_f32, 0, nb_inner, sAo, sAi, sWo, sWi, sCo, sCi};
+  if (!operands_ok(A, lda, W, ldw, K) || (sAo & 7) || (sAi & 7) || (sWo & 7) || (sWi & 7)) return HAFF_ERR_BAD_ARG;
+  GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
+  p.out_f32 = out_f32; p.nb_inner = nb_inner;
+  p.sAo = sAo; p.sAi = sAi; p.sWo = sWo; p.sWi = sWi; p.sCo = sCo; p.sCi = sCi;
   return launch_gemm<128, 128, 2, 2, F16>(p, reinterpret_cast<hipStream_t>(stream), nb_outer * nb_inner);
 }
 extern "C" int haff_gemm_bf16_batched(const void* A, long lda, long sAo, long sAi, const void* W, long ldw, long sWo,
