@@ -28,29 +28,30 @@
 namespace {
 
 struct AttnArgs {
-  const bf16_t *q, *k, *v;
-  bf16_t* o;
-  long q_sb, q_sh, q_st;
-  long k_sb, k_sh, k_st;
-  long v_sb, v_sh, v_st;
-  long o_sb, o_sh, o_st;
-  int B, H, Nq, Nk, d;
-  float scale;
-  int q_pos0;  // causal: key j visible to query i iff j <= i + q_pos0
-  const float *relh, *relw;  // [B*H][Nq][S]
-  int S;
-  const int* nk_rows;  // optional, device int32 [B]: batch b sees only its first nk_rows[b] (<= Nk) keys (ragged KV caches)
+  const bf16_t *q = nullptr, *k = nullptr, *v = nullptr;
+  bf16_t* o = nullptr;
+  long q_sb = 0, q_sh = 0, q_st = 0;
+  long k_sb = 0, k_sh = 0, k_st = 0;
+  long v_sb = 0, v_sh = 0, v_st = 0;
+  long o_sb = 0, o_sh = 0, o_st = 0;
+  int B = 0, H = 0, Nq = 0, Nk = 0, d = 0;
+  float scale = 0.f;
+  int q_pos0 = 0;  // causal: key j visible to query i iff j <= i + q_pos0
+  const float *relh = nullptr, *relw = nullptr;  // [B*H][Nq][S]
+  int S = 0;
+  const int* nk_rows = nullptr;  // optional, device int32 [B]: batch b sees only its first nk_rows[b] (<= Nk) keys (ragged KV caches)
   // decode kernel with RoPE + cache append fused in (attn_decode_kernel<.., true>): q/k/v above are the RAW q row and the
   // K/V caches; the newest position (nk_rows[b] - 1) comes from knew/vnew (raw, same (batch, head) strides as q), is
   // rotated here and appended to the caches by this kernel
-  const bf16_t *knew, *vnew;
-  const float* cos_sin;   // [Tmax][d] = cos(0..d/2) | sin(0..d/2)
+  const bf16_t *knew = nullptr, *vnew = nullptr;
+  const float* cos_sin = nullptr;   // [Tmax][d] = cos(0..d/2) | sin(0..d/2)
   // attn_global_pp_kernel<true>: the decomposed rel-pos TABLES (bf16 [2S-1][d]); rel_h / rel_w are computed in the prologue
-  const bf16_t *tab_h, *tab_w;
+  const bf16_t *tab_h = nullptr, *tab_w = nullptr;
   // attn_fwd_kernel: optional per-row log-sum-exp of the scores in the LOG2 domain (scale * log2(e) * q.k, masked), f32
   // [B][H][Nq] — what the flash backward (attention_bwd.hip) recomputes the probabilities from
-  float* lse;
+  float* lse = nullptr;
 };
+static_assert(std::is_trivially_copyable<AttnArgs>::value && sizeof(AttnArgs) == 240, "AttnArgs is passed to the kernels by value");
 
 constexpr int QB = 128;   // queries per workgroup
 constexpr int KT = 64;    // keys per tile
@@ -1038,12 +1039,9 @@ static bool attn_global_pp_ok(const AttnArgs& p, bool fused_rel) {
   if (p.k_sb != p.v_sb || p.k_sh != p.v_sh || p.k_st != p.v_st || p.v < p.k) return false;
   const long span = (p.v - p.k) * 2 + (long)p.Nk * p.k_st * 2;
   if (span >= (1L << 31)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.k) & 15) || (reinterpret_cast<uintptr_t>(p.v) & 15) || (reinterpret_cast<uintptr_t>(p.q) & 15))
-    return false;
-  if (fused_rel)
-    return p.Nq == KT * KT && p.Nk == KT * KT && p.tab_h && p.tab_w && (reinterpret_cast<uintptr_t>(p.tab_h) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(p.tab_w) & 15) == 0;
-  return (reinterpret_cast<uintptr_t>(p.relh) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.relw) & 15) == 0;
+  if (!haff_aligned(p.k) || !haff_aligned(p.v) || !haff_aligned(p.q)) return false;
+  if (fused_rel) return p.Nq == KT * KT && p.Nk == KT * KT && p.tab_h && p.tab_w && haff_aligned(p.tab_h) && haff_aligned(p.tab_w);
+  return haff_aligned(p.relh) && haff_aligned(p.relw);
 }
 
 template <bool FUSED_REL, bool F16 = false>
@@ -1229,6 +1227,52 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
 
 }  // namespace
 
+// The common core of an argument block: the four operands with their (batch, head, token) strides in elements, shape and scale.
+// Every other field keeps its default until the entry point that needs it sets it by name.
+static AttnArgs attn_args(const void* q, long q_sb, long q_sh, long q_st,
+                          const void* k, long k_sb, long k_sh, long k_st,
+                          const void* v, long v_sb, long v_sh, long v_st,
+                          void* o, long o_sb, long o_sh, long o_st,
+                          int B, int H, int Nq, int Nk, int d, float scale) {
+  AttnArgs p;
+  p.q = reinterpret_cast<const bf16_t*>(q); p.q_sb = q_sb; p.q_sh = q_sh; p.q_st = q_st;
+  p.k = reinterpret_cast<const bf16_t*>(k); p.k_sb = k_sb; p.k_sh = k_sh; p.k_st = k_st;
+  p.v = reinterpret_cast<const bf16_t*>(v); p.v_sb = v_sb; p.v_sh = v_sh; p.v_st = v_st;
+  p.o = reinterpret_cast<bf16_t*>(o); p.o_sb = o_sb; p.o_sh = o_sh; p.o_st = o_st;
+  p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.d = d; p.scale = scale;
+  return p;
+}
+
+// attn_fwd_kernel<dp, BIAS, CAUSAL> at the padded head dimension dp (64, 96 or 128).
+// fp16: the rel-pos instances stop at dp = 96 (ViT-H: 80); the d = 128 ones use scratch, and no fp16 caller needs them
+template <int BIAS, bool CAUSAL, bool F16>
+static int launch_attn_dp(int dp, const AttnArgs& p, hipStream_t s) {
+  switch (dp) {
+    case 64: return launch_attn<64, BIAS, CAUSAL, 64 / 16, false, false, F16>(p, s);
+    case 96: return launch_attn<96, BIAS, CAUSAL, 96 / 16, false, false, F16>(p, s);
+    default:
+      if constexpr (F16 && BIAS != 0) return HAFF_ERR_UNSUPPORTED;
+      else return launch_attn<128, BIAS, CAUSAL, 128 / 16, false, false, F16>(p, s);
+  }
+}
+// The two rel-pos forms of one head dimension: BIAS 2 when a KV tile is exactly one key-grid row (S == 64), else BIAS 1. They are
+// named per head dimension, not through launch_attn_dp, because the device code object lists the kernels in the order of their
+// first use: BIAS 2 at 64 / 96 / 128 before BIAS 1 at 64 / 96 / 128 would permute them.
+template <int DP, bool F16>
+static int launch_attn_rel(bool tile_is_row, const AttnArgs& p, hipStream_t s) {
+  return tile_is_row ? launch_attn<DP, 2, false, DP / 16, false, false, F16>(p, s) : launch_attn<DP, 1, false, DP / 16, false, false, F16>(p, s);
+}
+
+// The decode step's three forms by the number of (batch, head) pairs: 16 waves sharing one pair, 4 waves sharing one, one wave each
+template <bool ROPE, bool F16>
+static int launch_attn_decode(const AttnArgs& p, hipStream_t s) {
+  const int bh = p.B * p.H;
+  if (bh <= 128) hipLaunchKernelGGL((attn_decode_kernel<true, ROPE, 16, F16>), dim3(bh), dim3(1024), 0, s, p);
+  else if (bh <= 1024) hipLaunchKernelGGL((attn_decode_kernel<true, ROPE, 4, F16>), dim3(bh), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((attn_decode_kernel<false, ROPE, 4, F16>), dim3((bh + 3) / 4), dim3(256), 0, s, p);
+  return haff_check_launch();
+}
+
 // q/k/v/o: bf16; strides in elements (batch, head, token). d % 8 == 0, d <= 128.
 // causal != 0: key j visible to query i iff j <= i + q_pos0.
 // relh/relw (may be null): fp32 [B*H][Nq][S] decomposed rel-pos terms; key index -> (kh, kw) = (j / S, j % S).
@@ -1242,53 +1286,36 @@ static int attention_bf16_impl(const void* q, long q_sb, long q_sh, long q_st,
                                const float* relh, const float* relw, int S, const int* nk_rows, void* stream,
                                float* lse = nullptr) {
   if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || d <= 0 || d > 128 || (d & 7)) return HAFF_ERR_BAD_ARG;
-  if ((q_st & 7) || (k_st & 7) || (v_st & 7) || (o_st & 3) || (q_sh & 7) || (k_sh & 7) || (v_sh & 7) || (o_sh & 3) ||
-      (q_sb & 7) || (k_sb & 7) || (v_sb & 7) || (o_sb & 3))
-    return HAFF_ERR_BAD_ARG;
+  if (!haff_strides_ok(q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st, 7, 3)) return HAFF_ERR_BAD_ARG;
   const bool rel = relh != nullptr && relw != nullptr;
   if (rel && (causal || S <= 0 || (Nk % S) != 0)) return HAFF_ERR_BAD_ARG;
-  // fp16: the rel-pos instances stop at d <= 96 (ViT-H: 80); the d = 128 ones use scratch, and no fp16 caller needs them
-  if (F16 && rel && d > 96) return HAFF_ERR_UNSUPPORTED;
-  AttnArgs p{reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const bf16_t*>(v),
-             reinterpret_cast<bf16_t*>(o), q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st,
-             B, H, Nq, Nk, d, scale, q_pos0, relh, relw, S, nk_rows, nullptr, nullptr, nullptr};
+  if (F16 && rel && d > 96) return HAFF_ERR_UNSUPPORTED;   // (launch_attn_dp's fp16 rule)
+  AttnArgs p = attn_args(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq, Nk, d, scale);
+  p.q_pos0 = q_pos0;
+  p.relh = relh;
+  p.relw = relw;
+  p.S = S;
+  p.nk_rows = nk_rows;
   p.lse = lse;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (!lse && !rel && Nq == 1 && d == DEC_D && (!causal || q_pos0 >= Nk - 1) && (o_sh & 7) == 0 && (o_sb & 7) == 0 &&
-      (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-    if (B * H <= 128) hipLaunchKernelGGL((attn_decode_kernel<true, false, 16, F16>), dim3(B * H), dim3(1024), 0, s, p);
-    else if (B * H <= 1024) hipLaunchKernelGGL((attn_decode_kernel<true, false, 4, F16>), dim3(B * H), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((attn_decode_kernel<false, false, 4, F16>), dim3((B * H + 3) / 4), dim3(256), 0, s, p);
-    return haff_check_launch();
-  }
+  if (!lse && !rel && Nq == 1 && d == DEC_D && (!causal || q_pos0 >= Nk - 1) && (o_sh & 7) == 0 && (o_sb & 7) == 0 && haff_aligned(o))
+    return launch_attn_decode<false, F16>(p, s);
   const int dp = d <= 64 ? 64 : (d <= 96 ? 96 : 128);
   if (rel) {
     const int mode = (S == 64) ? 2 : (S <= 16 && Nk == S * S ? 3 : 1);
     if (mode == 1 && S > 32) return HAFF_ERR_UNSUPPORTED;
-    if (mode == 3) {
-      if (dp == 64) return launch_attn<64, 3, false, 64 / 16, false, false, F16>(p, s);
-      if (dp == 96) return launch_attn<96, 3, false, 96 / 16, false, false, F16>(p, s);
-      if constexpr (!F16) return launch_attn<128, 3, false, 128 / 16, false, false, F16>(p, s);
-      return HAFF_ERR_UNSUPPORTED;
-    }
-    if (dp == 64) return mode == 2 ? launch_attn<64, 2, false, 64 / 16, false, false, F16>(p, s) : launch_attn<64, 1, false, 64 / 16, false, false, F16>(p, s);
-    if (dp == 96 && mode == 2 && d == 80) {   // SAM global blocks
+    if (mode == 3) return launch_attn_dp<3, false, F16>(dp, p, s);
+    if (dp == 64) return launch_attn_rel<64, F16>(mode == 2, p, s);
+    if (mode == 2 && d == 80) {   // SAM global blocks
       if (attn_global_pp_ok(p, false)) return launch_attn_global_pp<false, F16>(p, s);
       if ((Nq % 128) == 0 && (Nk % KT) == 0 && !nk_rows) return launch_attn<96, 2, false, 6, true, true, F16>(p, s);
       return launch_attn<96, 2, false, 6, true, false, F16>(p, s);
     }
-    if (dp == 96) return mode == 2 ? launch_attn<96, 2, false, 96 / 16, false, false, F16>(p, s) : launch_attn<96, 1, false, 96 / 16, false, false, F16>(p, s);
-    if constexpr (!F16) return mode == 2 ? launch_attn<128, 2, false, 128 / 16, false, false, F16>(p, s) : launch_attn<128, 1, false, 128 / 16, false, false, F16>(p, s);
+    if (dp == 96) return launch_attn_rel<96, F16>(mode == 2, p, s);
+    if constexpr (!F16) return launch_attn_rel<128, F16>(mode == 2, p, s);   // (the fp16 rule above: d <= 96)
     return HAFF_ERR_UNSUPPORTED;
   }
-  if (causal) {
-    if (dp == 64) return launch_attn<64, 0, true, 64 / 16, false, false, F16>(p, s);
-    if (dp == 96) return launch_attn<96, 0, true, 96 / 16, false, false, F16>(p, s);
-    return launch_attn<128, 0, true, 128 / 16, false, false, F16>(p, s);
-  }
-  if (dp == 64) return launch_attn<64, 0, false, 64 / 16, false, false, F16>(p, s);
-  if (dp == 96) return launch_attn<96, 0, false, 96 / 16, false, false, F16>(p, s);
-  return launch_attn<128, 0, false, 128 / 16, false, false, F16>(p, s);
+  return causal ? launch_attn_dp<0, true, F16>(dp, p, s) : launch_attn_dp<0, false, F16>(dp, p, s);
 }
 
 extern "C" int haff_attention_bf16(const void* q, long q_sb, long q_sh, long q_st,
@@ -1318,9 +1345,7 @@ extern "C" int haff_attention_f16(const void* q, long q_sb, long q_sh, long q_st
 // q / k / v and the 8-byte stores of o cannot take, and a causal mask under which a query row sees no key
 static bool lse_args_ok(const void* q, const void* k, const void* v, const void* o, const float* lse, int causal, int q_pos0) {
   if (!q || !k || !v || !o || !lse) return false;
-  if ((reinterpret_cast<uintptr_t>(q) & 15) || (reinterpret_cast<uintptr_t>(k) & 15) || (reinterpret_cast<uintptr_t>(v) & 15) ||
-      (reinterpret_cast<uintptr_t>(o) & 7) || (reinterpret_cast<uintptr_t>(lse) & 3))
-    return false;
+  if (!haff_aligned(q) || !haff_aligned(k) || !haff_aligned(v) || !haff_aligned(o, 8) || !haff_aligned(lse, 4)) return false;
   return !(causal && q_pos0 < 0);
 }
 
@@ -1363,13 +1388,11 @@ static int global_attention_impl(const void* q, long q_sb, long q_sh, long q_st,
                                  int B, int H, int S, int d, float scale,
                                  const void* tab_h, const void* tab_w, void* stream) {
   if (B <= 0 || H <= 0 || S <= 0 || d <= 0 || !tab_h || !tab_w) return HAFF_ERR_BAD_ARG;
-  if ((q_st & 7) || (k_st & 7) || (v_st & 7) || (o_st & 3) || (q_sh & 7) || (k_sh & 7) || (v_sh & 7) || (o_sh & 3) ||
-      (q_sb & 7) || (k_sb & 7) || (v_sb & 7) || (o_sb & 3))
-    return HAFF_ERR_BAD_ARG;
-  AttnArgs p{reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const bf16_t*>(v),
-             reinterpret_cast<bf16_t*>(o), q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st,
-             B, H, S * S, S * S, d, scale, 0, nullptr, nullptr, S, nullptr, nullptr, nullptr, nullptr,
-             reinterpret_cast<const bf16_t*>(tab_h), reinterpret_cast<const bf16_t*>(tab_w)};
+  if (!haff_strides_ok(q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st, 7, 3)) return HAFF_ERR_BAD_ARG;
+  AttnArgs p = attn_args(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, S * S, S * S, d, scale);
+  p.S = S;
+  p.tab_h = reinterpret_cast<const bf16_t*>(tab_h);
+  p.tab_w = reinterpret_cast<const bf16_t*>(tab_w);
   if (!attn_global_pp_ok(p, true)) return HAFF_ERR_UNSUPPORTED;
   return launch_attn_global_pp<true, F16>(p, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1429,19 +1452,17 @@ static int decode_attention_rope_rows_impl(const void* qkv, long ld, void* kcach
                                            void* out, int B, int H, int d, int Tmax, float scale, const int* nk_rows,
                                            void* stream) {
   if (B <= 0 || H <= 0 || d != DEC_D || Tmax <= 0 || !nk_rows || !cos_sin || (ld & 7)) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(kcache) & 15) ||
-      (reinterpret_cast<uintptr_t>(vcache) & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
-    return HAFF_ERR_BAD_ARG;
-  const bf16_t* q = reinterpret_cast<const bf16_t*>(qkv);
-  const long hd = (long)H * d;
-  AttnArgs p{q, reinterpret_cast<const bf16_t*>(kcache), reinterpret_cast<const bf16_t*>(vcache), reinterpret_cast<bf16_t*>(out),
-             ld, d, hd, (long)Tmax * hd, d, hd, (long)Tmax * hd, d, hd, hd, d, hd,
-             B, H, 1, Tmax, d, scale, 0, nullptr, nullptr, 0, nk_rows, q + hd, q + 2 * hd, cos_sin};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (B * H <= 128) hipLaunchKernelGGL((attn_decode_kernel<true, true, 16, F16>), dim3(B * H), dim3(1024), 0, s, p);
-  else if (B * H <= 1024) hipLaunchKernelGGL((attn_decode_kernel<true, true, 4, F16>), dim3(B * H), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((attn_decode_kernel<false, true, 4, F16>), dim3((B * H + 3) / 4), dim3(256), 0, s, p);
-  return haff_check_launch();
+  if (!haff_aligned(qkv) || !haff_aligned(kcache) || !haff_aligned(vcache) || !haff_aligned(out)) return HAFF_ERR_BAD_ARG;
+  const long hd = (long)H * d, cache = (long)Tmax * hd;   // a token's row of all heads; one batch entry's cache
+  AttnArgs p = attn_args(qkv, /*q_sb*/ ld, /*q_sh*/ d, /*q_st*/ hd,
+                         kcache, /*k_sb*/ cache, /*k_sh*/ d, /*k_st*/ hd,
+                         vcache, /*v_sb*/ cache, /*v_sh*/ d, /*v_st*/ hd,
+                         out, /*o_sb*/ hd, /*o_sh*/ d, /*o_st*/ hd, B, H, 1, Tmax, d, scale);
+  p.nk_rows = nk_rows;
+  p.knew = p.q + hd;
+  p.vnew = p.q + 2 * hd;
+  p.cos_sin = cos_sin;
+  return launch_attn_decode<true, F16>(p, reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int haff_decode_attention_rope_rows_bf16(const void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin,
                                                     void* out, int B, int H, int d, int Tmax, float scale, const int* nk_rows,
@@ -1598,6 +1619,17 @@ __global__ __launch_bounds__(256) void relpos_tables_mfma_kernel(const bf16_t* q
     }
   }
 }
+
+// instance NKD of the MFMA tables kernel: its launch, and the rise of its dynamic-LDS limit that tables above 64 KB need first
+template <int NKD>
+void launch_relpos_mfma(dim3 grid, size_t lds, hipStream_t s, const bf16_t* q, long q_sb, long q_sh, long q_st, const bf16_t* tab_h,
+                        const bf16_t* tab_w, float* relh, float* relw, int H, int S, int d) {
+  hipLaunchKernelGGL((relpos_tables_mfma_kernel<NKD>), grid, dim3(256), lds, s, q, q_sb, q_sh, q_st, tab_h, tab_w, relh, relw, H, S, d);
+}
+template <int NKD>
+void relpos_mfma_raise_lds() {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(relpos_tables_mfma_kernel<NKD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
 }  // namespace
 
 // tab_h/tab_w: bf16 [2S-1][d]; q bf16; d % 8 == 0, d <= 128.
@@ -1609,22 +1641,17 @@ extern "C" int haff_relpos_tables_bf16(const void* q, long q_sb, long q_sh, long
   const int RT = (2 * S - 1 + 15) / 16;
   const size_t lds = (size_t)4 * 16 * (RT * 16 + 4) * sizeof(float);   // one table's products per wave at a time
   if (lds > 150 * 1024) return HAFF_ERR_UNSUPPORTED;
-  dim3 grid((N + 64 * RELPOS_QT - 1) / (64 * RELPOS_QT), H, B), block(256);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (lds > 64 * 1024) {  // S > 120
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(relpos_tables_mfma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(relpos_tables_mfma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(relpos_tables_mfma_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(relpos_tables_mfma_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (lds > 64 * 1024) {  // S > 120: on all four instances (the attribute is per device and this entry point keeps no state)
+    relpos_mfma_raise_lds<1>();
+    relpos_mfma_raise_lds<2>();
+    relpos_mfma_raise_lds<3>();
+    relpos_mfma_raise_lds<4>();
   }
-  const bf16_t* qp = reinterpret_cast<const bf16_t*>(q);
-  const bf16_t* th = reinterpret_cast<const bf16_t*>(tab_h);
-  const bf16_t* tw = reinterpret_cast<const bf16_t*>(tab_w);
-  const int nkd = (d + 31) / 32;
-  if (nkd == 1) hipLaunchKernelGGL((relpos_tables_mfma_kernel<1>), grid, block, lds, s, qp, q_sb, q_sh, q_st, th, tw, relh, relw, H, S, d);
-  else if (nkd == 2) hipLaunchKernelGGL((relpos_tables_mfma_kernel<2>), grid, block, lds, s, qp, q_sb, q_sh, q_st, th, tw, relh, relw, H, S, d);
-  else if (nkd == 3) hipLaunchKernelGGL((relpos_tables_mfma_kernel<3>), grid, block, lds, s, qp, q_sb, q_sh, q_st, th, tw, relh, relw, H, S, d);
-  else hipLaunchKernelGGL((relpos_tables_mfma_kernel<4>), grid, block, lds, s, qp, q_sb, q_sh, q_st, th, tw, relh, relw, H, S, d);
+  const int nkd = (d + 31) / 32;   // k-steps of 32 over the head dim
+  auto* launch = nkd == 1 ? launch_relpos_mfma<1> : nkd == 2 ? launch_relpos_mfma<2> : nkd == 3 ? launch_relpos_mfma<3> : launch_relpos_mfma<4>;
+  launch(dim3((N + 64 * RELPOS_QT - 1) / (64 * RELPOS_QT), H, B), lds, reinterpret_cast<hipStream_t>(stream),
+         reinterpret_cast<const bf16_t*>(q), q_sb, q_sh, q_st, reinterpret_cast<const bf16_t*>(tab_h), reinterpret_cast<const bf16_t*>(tab_w),
+         relh, relw, H, S, d);
   return haff_check_launch();
 }
 

@@ -18,18 +18,21 @@
 // d == 128 only (Llama heads). The small decoder attentions of the fine-tune path keep the materialised form.
 #include "haff_common.h"
 
+#include <type_traits>
+
 namespace {
 
 struct BwdArgs {
-  const bf16_t *q, *k, *v, *dout;
-  const float *lse, *delta;
-  bf16_t *dq, *dk, *dv;
-  float* dq_acc;    // [B*H][Nqp][128], Nqp = Nq rounded up to 64
-  long ld;          // elements between consecutive tokens of q / k / v / dout / dq / dk / dv (= H * 128)
-  int B, H, Nq, Nk;
-  float scale;
-  int causal, q_pos0;
+  const bf16_t *q = nullptr, *k = nullptr, *v = nullptr, *dout = nullptr;
+  const float *lse = nullptr, *delta = nullptr;
+  bf16_t *dq = nullptr, *dk = nullptr, *dv = nullptr;
+  float* dq_acc = nullptr;    // [B*H][Nqp][128], Nqp = Nq rounded up to 64
+  long ld = 0;                // elements between consecutive tokens of q / k / v / dout / dq / dk / dv (= H * 128)
+  int B = 0, H = 0, Nq = 0, Nk = 0;
+  float scale = 0.f;
+  int causal = 0, q_pos0 = 0;
 };
+static_assert(std::is_trivially_copyable<BwdArgs>::value && sizeof(BwdArgs) == 120, "BwdArgs is passed to the kernel by value");
 
 constexpr int BD = 128;            // head dim
 constexpr int BB = 64;             // queries / keys per block
@@ -280,6 +283,17 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const bf16_t* o, co
 
 }  // namespace
 
+// The common core of an argument block: the 16-bit operands and results with their casts, the token stride, shape and scale
+static BwdArgs bwd_args(const void* q, const void* k, const void* v, const void* dout, void* dq, void* dk, void* dv, long ld, int B, int H,
+                        int Nq, int Nk, float scale) {
+  BwdArgs p;
+  p.q = reinterpret_cast<const bf16_t*>(q); p.k = reinterpret_cast<const bf16_t*>(k); p.v = reinterpret_cast<const bf16_t*>(v);
+  p.dout = reinterpret_cast<const bf16_t*>(dout);
+  p.dq = reinterpret_cast<bf16_t*>(dq); p.dk = reinterpret_cast<bf16_t*>(dk); p.dv = reinterpret_cast<bf16_t*>(dv);
+  p.ld = ld; p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.scale = scale;
+  return p;
+}
+
 // dq, dk, dv of out = softmax(scale * q k^T [causal: key j visible to query i iff j <= i + q_pos0]) v, bf16, d == 128.
 // q / dout / o / dq: [B][Nq][ld], k / v / dk / dv: [B][Nk][ld] token-major with head h at columns h*128 (ld = H*128 for the
 // fused projections); lse f32 [B][H][Nq] from haff_attention_lse_bf16; workspace f32, 16-byte aligned, at least
@@ -296,20 +310,23 @@ static int attention_bwd_impl(const void* q, const void* k, const void* v, const
   if ((ld & 7) || ld < (long)H * BD) return HAFF_ERR_BAD_ARG;
   const void* ptrs[8] = {q, k, v, o, dout, dq, dk, dv};
   for (const void* x : ptrs)
-    if (reinterpret_cast<uintptr_t>(x) & 15) return HAFF_ERR_BAD_ARG;
+    if (!haff_aligned(x)) return HAFF_ERR_BAD_ARG;
   const long nqp = (long)((Nq + BB - 1) / BB) * BB;
   const long dq_off = (((long)B * H * Nq + 3) / 4) * 4;   // delta, then the dq sums on the next 16-byte boundary
   const long need = dq_off + (long)B * H * nqp * BD;
-  if (workspace_elems < need || (reinterpret_cast<uintptr_t>(workspace) & 15)) return HAFF_ERR_BAD_ARG;
+  if (workspace_elems < need || !haff_aligned(workspace)) return HAFF_ERR_BAD_ARG;
   float* delta = workspace;
   float* dq_acc = workspace + dq_off;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long rows = (long)B * Nq * H;
   hipLaunchKernelGGL((attn_bwd_delta_kernel<F16>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const bf16_t*>(o), reinterpret_cast<const bf16_t*>(dout), delta, ld, B, H, Nq);
-  BwdArgs p{reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const bf16_t*>(v),
-            reinterpret_cast<const bf16_t*>(dout), lse, delta, reinterpret_cast<bf16_t*>(dq), reinterpret_cast<bf16_t*>(dk),
-            reinterpret_cast<bf16_t*>(dv), dq_acc, ld, B, H, Nq, Nk, scale, causal, q_pos0};
+  BwdArgs p = bwd_args(q, k, v, dout, dq, dk, dv, ld, B, H, Nq, Nk, scale);
+  p.lse = lse;
+  p.delta = delta;
+  p.dq_acc = dq_acc;
+  p.causal = causal;
+  p.q_pos0 = q_pos0;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<F16>), hipFuncAttributeMaxDynamicSharedMemorySize, BWD_LDS) !=
       hipSuccess)
     return HAFF_ERR_LAUNCH;

@@ -5,21 +5,24 @@
 // transformers CLIPAttention / LlamaAttention (third-party, reached from clip_encoder.py:53-56, llava_llama.py:93-102).
 #include "haff_common.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int QPB = 4;
 
 struct AttnF32Args {
-  const float *q, *k, *v;
-  float* o;
-  long q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st;
-  int B, H, Nq, Nk, d;
-  float scale;
-  int causal, q_pos0;
-  const float *relh, *relw;
-  int S;
-  const int* nk_rows;   // optional device int32 [B]: batch b sees only its first nk_rows[b] keys
+  const float *q = nullptr, *k = nullptr, *v = nullptr;
+  float* o = nullptr;
+  long q_sb = 0, q_sh = 0, q_st = 0, k_sb = 0, k_sh = 0, k_st = 0, v_sb = 0, v_sh = 0, v_st = 0, o_sb = 0, o_sh = 0, o_st = 0;
+  int B = 0, H = 0, Nq = 0, Nk = 0, d = 0;
+  float scale = 0.f;
+  int causal = 0, q_pos0 = 0;
+  const float *relh = nullptr, *relw = nullptr;
+  int S = 0;
+  const int* nk_rows = nullptr;   // optional device int32 [B]: batch b sees only its first nk_rows[b] keys
 };
+static_assert(std::is_trivially_copyable<AttnF32Args>::value && sizeof(AttnF32Args) == 192, "AttnF32Args is passed to the kernels by value");
 
 __global__ __launch_bounds__(256) void attn_f32_kernel(AttnF32Args p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -190,6 +193,21 @@ __global__ __launch_bounds__(256) void attn_f32_fewkeys_kernel(AttnF32Args p) {
 
 }  // namespace
 
+// The common core of an argument block: the four operands with their (batch, head, token) strides in elements, shape and scale
+static AttnF32Args attn_f32_args(const float* q, long q_sb, long q_sh, long q_st,
+                                 const float* k, long k_sb, long k_sh, long k_st,
+                                 const float* v, long v_sb, long v_sh, long v_st,
+                                 float* o, long o_sb, long o_sh, long o_st,
+                                 int B, int H, int Nq, int Nk, int d, float scale) {
+  AttnF32Args p;
+  p.q = q; p.q_sb = q_sb; p.q_sh = q_sh; p.q_st = q_st;
+  p.k = k; p.k_sb = k_sb; p.k_sh = k_sh; p.k_st = k_st;
+  p.v = v; p.v_sb = v_sb; p.v_sh = v_sh; p.v_st = v_st;
+  p.o = o; p.o_sb = o_sb; p.o_sh = o_sh; p.o_st = o_st;
+  p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.d = d; p.scale = scale;
+  return p;
+}
+
 static int attention_f32_impl(const float* q, long q_sb, long q_sh, long q_st,
                               const float* k, long k_sb, long k_sh, long k_st,
                               const float* v, long v_sb, long v_sh, long v_st,
@@ -197,28 +215,28 @@ static int attention_f32_impl(const float* q, long q_sb, long q_sh, long q_st,
                               int B, int H, int Nq, int Nk, int d, float scale, int causal, int q_pos0,
                               const float* relh, const float* relw, int S, const int* nk_rows, void* stream) {
   if (B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || d <= 0 || d > 256 || (d & 3)) return HAFF_ERR_BAD_ARG;
-  if ((q_st & 3) || (k_st & 3) || (v_st & 3) || (o_st & 3) || (q_sh & 3) || (k_sh & 3) || (v_sh & 3) || (o_sh & 3) ||
-      (q_sb & 3) || (k_sb & 3) || (v_sb & 3) || (o_sb & 3))
-    return HAFF_ERR_BAD_ARG;
+  if (!haff_strides_ok(q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st, 3, 3)) return HAFF_ERR_BAD_ARG;
   const bool rel = relh != nullptr && relw != nullptr;
   if (rel && (S <= 0 || (Nk % S) != 0)) return HAFF_ERR_BAD_ARG;
-  if (!rel && !causal && Nk <= 16 && Nq >= 256 && (d == 16 || d == 32)) {
-    AttnF32Args pf{q, k, v, o, q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st,
-                   B, H, Nq, Nk, d, scale, 0, 0, nullptr, nullptr, 0, nk_rows};
+  AttnF32Args p = attn_f32_args(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, B, H, Nq, Nk, d, scale);
+  p.nk_rows = nk_rows;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!rel && !causal && Nk <= 16 && Nq >= 256 && (d == 16 || d == 32)) {   // few keys: no mask, no bias, the block as it stands
     dim3 g((Nq + 255) / 256, H, B);
-    if (d == 16) hipLaunchKernelGGL(attn_f32_fewkeys_kernel<16>, g, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pf);
-    else hipLaunchKernelGGL(attn_f32_fewkeys_kernel<32>, g, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pf);
+    if (d == 16) hipLaunchKernelGGL(attn_f32_fewkeys_kernel<16>, g, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(attn_f32_fewkeys_kernel<32>, g, dim3(256), 0, s, p);
     return haff_check_launch();
   }
   size_t lds = ((size_t)QPB * Nk + (size_t)QPB * d + 256 * 4) * sizeof(float);
   if (lds > 150 * 1024) return HAFF_ERR_UNSUPPORTED;
-  AttnF32Args p{q, k, v, o, q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st,
-                B, H, Nq, Nk, d, scale, causal, q_pos0, rel ? relh : nullptr, rel ? relw : nullptr, S, nk_rows};
+  p.causal = causal;
+  p.q_pos0 = q_pos0;
+  p.relh = rel ? relh : nullptr;
+  p.relw = rel ? relw : nullptr;
+  p.S = S;
   dim3 grid((Nq + QPB - 1) / QPB, H, B), block(256);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_f32_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)e;
-  hipLaunchKernelGGL(attn_f32_kernel, grid, block, lds, reinterpret_cast<hipStream_t>(stream), p);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(attn_f32_kernel, grid, block, lds, s, p);
   return haff_check_launch();
 }
 

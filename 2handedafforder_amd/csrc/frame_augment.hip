@@ -192,7 +192,6 @@ __global__ __launch_bounds__(256) void flip_planes_kernel(const unsigned char* i
   }
 }
 
-inline bool misaligned(const void* p, unsigned long a) { return (reinterpret_cast<unsigned long>(p) & (a - 1)) != 0; }
 
 // blocks of 256 lanes over `items` work items of one frame / plane: at most 1024 per frame, the rest by grid stride
 inline dim3 aug_grid(long items, int count) {
@@ -205,7 +204,7 @@ inline dim3 aug_grid(long items, int count) {
 extern "C" int haff_jitter_stats_u8(const void* frames, int B, int H, int W, const int* flags, const float* factors, void* sums,
                                     void* stream) {
   if (!frames || !flags || !factors || !sums || B <= 0 || H <= 0 || W <= 0) return HAFF_ERR_BAD_ARG;
-  if (misaligned(flags, 4) || misaligned(factors, 4) || misaligned(sums, 8)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(flags, 4) || !haff_aligned(factors, 4) || !haff_aligned(sums, 8)) return HAFF_ERR_BAD_ARG;
   if ((long)H * W > HAFF_AUG_MAX_PIXELS) return HAFF_ERR_UNSUPPORTED;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (hipMemsetAsync(sums, 0, (size_t)B * 8, s) != hipSuccess) return HAFF_ERR_LAUNCH;
@@ -218,7 +217,7 @@ extern "C" int haff_jitter_stats_u8(const void* frames, int B, int H, int W, con
 extern "C" int haff_augment_u8(const void* in, void* out, int B, int H, int W, const int* flags, const float* factors, const void* sums,
                                void* stream) {
   if (!in || !out || !flags || !factors || !sums || B <= 0 || H <= 0 || W <= 0) return HAFF_ERR_BAD_ARG;
-  if (misaligned(flags, 4) || misaligned(factors, 4) || misaligned(sums, 8)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(flags, 4) || !haff_aligned(factors, 4) || !haff_aligned(sums, 8)) return HAFF_ERR_BAD_ARG;
   if ((long)H * W > HAFF_AUG_MAX_PIXELS) return HAFF_ERR_UNSUPPORTED;
   const long bytes = 3L * H * W * B;
   const long gap = (const char*)out - (const char*)in;
@@ -230,7 +229,7 @@ extern "C" int haff_augment_u8(const void* in, void* out, int B, int H, int W, c
 }
 
 extern "C" int haff_flip_planes_u8(const void* in, void* out, int P, int H, int W, const int* flags, void* stream) {
-  if (!in || !out || !flags || P <= 0 || H <= 0 || W <= 0 || misaligned(flags, 4)) return HAFF_ERR_BAD_ARG;
+  if (!in || !out || !flags || P <= 0 || H <= 0 || W <= 0 || !haff_aligned(flags, 4)) return HAFF_ERR_BAD_ARG;
   const long bytes = (long)P * H * W;
   const long gap = (const char*)out - (const char*)in;
   if (gap < bytes && -gap < bytes) return HAFF_ERR_BAD_ARG;

@@ -1606,11 +1606,10 @@ extern "C" int haff_gemm_stream_cap(void* stream, int cap) {
   return old < 0 ? HAFF_ERR_UNSUPPORTED : old;
 }
 
-// The host-side rules the entry points below share, one function each. al16: 16-byte aligned (or null)
-static inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+// The host-side rules the entry points below share, one function each (haff_aligned: 16-byte aligned, or null)
 // the operand contract of every entry point: rows are read in 16-byte chunks (K, lda, ldw in whole chunks, aligned bases)
 static inline bool operands_ok(const void* A, long lda, const void* W, long ldw, int K) {
-  return !((K & 7) || (lda & 7) || (ldw & 7)) && al16(A) && al16(W);
+  return !((K & 7) || (lda & 7) || (ldw & 7)) && haff_aligned(A) && haff_aligned(W);
 }
 // the 8-wave tile addresses operands with 32-bit byte offsets (a_rows: the rows of A behind a gather, see GemmArgs::a_map)
 static inline bool operands_in_4g(const GemmArgs& p, long a_rows) {
@@ -1658,8 +1657,8 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
   }
   if constexpr (BM == 256 && BN == 256 && WM * WN == 8) {
     // a specialised instance (see the GF_* flags) when the launch meets its host-side contract and its feature set has one
-    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && al16(p.C) && (p.ldc & 7) == 0 && al16(p.bias) &&
-                    al16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && al16(p.ln_stats) && al16(p.ln_colsum) && al16(p.row_map) &&
+    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && haff_aligned(p.C) && (p.ldc & 7) == 0 && haff_aligned(p.bias) &&
+                    haff_aligned(p.resid) && (!p.resid || (p.ldr & 7) == 0) && haff_aligned(p.ln_stats) && haff_aligned(p.ln_colsum) && haff_aligned(p.row_map) &&
                     (!p.ln_colsum || p.ln_stats);
     if (ok) {
       const unsigned f = (p.bias ? GF_BIAS : 0u) | (p.ln_stats ? GF_LN : 0u) | (p.ln_colsum ? GF_CSUM : 0u) |
@@ -1691,8 +1690,8 @@ static int launch_gemm(const GemmArgs& p, hipStream_t s, int nbatch = 1) {
     }
   }
   if constexpr (BM == 192 && BN == 256 && WM * WN == 8) {   // the fine-tune step's 2808-row products (forward, dX): plain / residual / SwiGLU
-    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && al16(p.C) && (p.ldc & 7) == 0 && al16(p.bias) &&
-                    al16(p.resid) && (!p.resid || (p.ldr & 7) == 0) && !p.ln_stats && !p.ln_colsum && !p.row_map && !p.stat_out && !p.hm_d &&
+    const bool ok = nbatch == 1 && p.nb_inner == 0 && !p.out_f32 && (p.N % 256) == 0 && haff_aligned(p.C) && (p.ldc & 7) == 0 && haff_aligned(p.bias) &&
+                    haff_aligned(p.resid) && (!p.resid || (p.ldr & 7) == 0) && !p.ln_stats && !p.ln_colsum && !p.row_map && !p.stat_out && !p.hm_d &&
                     !p.rope_cs && p.act == 0;
     if (ok) {
       const unsigned f = (p.bias ? GF_BIAS : 0u) | (p.resid ? GF_RES : 0u);
@@ -1827,7 +1826,7 @@ extern "C" int haff_gemm_bf16(const void* A, long lda, const void* W, long ldw, 
 extern "C" int haff_gemm_bf16_ws(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                                  const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
                                  int swiglu, void* workspace, long workspace_bytes, void* stream) {
-  if (!al16(workspace)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(workspace)) return HAFF_ERR_BAD_ARG;
   GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
   p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
   return gemm_bf16_impl(p, 0, 0, workspace, workspace_bytes, stream);
@@ -1854,7 +1853,7 @@ extern "C" int haff_gemm_f16_cfg(const void* A, long lda, const void* W, long ld
 extern "C" int haff_gemm_f16_ws(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const float* bias,
                                 const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32,
                                 int swiglu, void* workspace, long workspace_bytes, void* stream) {
-  if (!al16(workspace)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(workspace)) return HAFF_ERR_BAD_ARG;
   GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
   p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map; p.act = act; p.out_f32 = out_f32; p.swiglu = swiglu;
   return gemm_bf16_impl<true>(p, 0, 0, workspace, workspace_bytes, stream);
@@ -1873,7 +1872,7 @@ static int gemm_rms_impl(const void* A, long lda, const void* W, long ldw, void*
                          const void* resid, long ldr, int M, int N, int K, int act, int out_f32, int swiglu,
                          const float* ssq_in, int ssq_n, float eps, float* ssq_out, int* n_parts_out, void* stream) {
   if (M <= 0 || M > 16 || N <= 0 || K <= 0 || (K % 128) || !operands_ok(A, lda, W, ldw, K)) return HAFF_ERR_BAD_ARG;
-  if (ssq_in && (M > 8 || ssq_n > 512 || !al16(ssq_in))) return HAFF_ERR_BAD_ARG;   // consumer side: <= 8 rows, <= 512 producer workgroups
+  if (ssq_in && (M > 8 || ssq_n > 512 || !haff_aligned(ssq_in))) return HAFF_ERR_BAD_ARG;   // consumer side: <= 8 rows, <= 512 producer workgroups
   if (swiglu && ((N & 31) || (ldc & 3) || resid)) return HAFF_ERR_BAD_ARG;
   if ((ssq_in && ssq_n <= 0) || (ssq_out && (out_f32 || swiglu))) return HAFF_ERR_BAD_ARG;
   GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
@@ -1932,7 +1931,7 @@ static int gemm_qkv_rope_impl(const void* A, long lda, const void* Wp, long ldw,
                               void* stream) {
   if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || !q_out || !kcache || !vcache || !cos_sin || pos0 < 0 || pos0 + T > Tmax)
     return HAFF_ERR_BAD_ARG;
-  if (!operands_ok(A, lda, Wp, ldw, K) || (ldq & 7) || !al16(q_out) || !al16(kcache) || !al16(vcache) || !al16(cos_sin))
+  if (!operands_ok(A, lda, Wp, ldw, K) || (ldq & 7) || !haff_aligned(q_out) || !haff_aligned(kcache) || !haff_aligned(vcache) || !haff_aligned(cos_sin))
     return HAFF_ERR_BAD_ARG;
   const long M = (long)B * T;
   const int hd = H * d, N = 3 * hd;
@@ -1966,7 +1965,7 @@ static int gemm_rowstats_impl(const void* A, long lda, const int* a_map, long a_
                               void* C, long ldc, const float* bias, const void* resid, long ldr, int M, int N, int K,
                               float* stat_out, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || !resid || !stat_out) return HAFF_ERR_BAD_ARG;
-  if (!operands_ok(A, lda, W, ldw, K) || (ldc & 7) || (ldr & 7) || !al16(C) || !al16(resid) || (reinterpret_cast<uintptr_t>(stat_out) & 7))
+  if (!operands_ok(A, lda, W, ldw, K) || (ldc & 7) || (ldr & 7) || !haff_aligned(C) || !haff_aligned(resid) || (reinterpret_cast<uintptr_t>(stat_out) & 7))
     return HAFF_ERR_BAD_ARG;
   if ((M % 256) || (N % 256) || (K % BK) || (a_map && a_rows <= 0)) return HAFF_ERR_UNSUPPORTED;
   GemmArgs p = gemm_args(A, lda, W, ldw, C, ldc, M, N, K);
@@ -1995,7 +1994,7 @@ extern "C" int haff_gemm_bf16_rowstats32(const void* A, long lda, const int* a_m
                                          float* X32, long ldx, void* C16, long ldc, const float* bias, int M, int N, int K,
                                          float* stat_out, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || !X32 || !C16 || !stat_out || !bias) return HAFF_ERR_BAD_ARG;
-  if (!operands_ok(A, lda, W, ldw, K) || (ldc & 7) || (ldx & 3) || !al16(C16) || !al16(X32) || !al16(bias) ||
+  if (!operands_ok(A, lda, W, ldw, K) || (ldc & 7) || (ldx & 3) || !haff_aligned(C16) || !haff_aligned(X32) || !haff_aligned(bias) ||
       (reinterpret_cast<uintptr_t>(stat_out) & 7))
     return HAFF_ERR_BAD_ARG;
   if ((M % 256) || (N % 256) || (K % BK) || (a_map && a_rows <= 0)) return HAFF_ERR_UNSUPPORTED;
@@ -2048,7 +2047,7 @@ static int gemm_heads_impl(const void* A, long lda, const void* W, long ldw, voi
                            const float* ln_stats, const float* ln_colsum, int M, int N, int K, int d, int heads,
                            long part_stride, long head_stride, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || d <= 0 || heads <= 0 || !row_map || !C) return HAFF_ERR_BAD_ARG;
-  if (!operands_ok(A, lda, W, ldw, K) || (part_stride & 7) || (head_stride & 7) || !al16(C)) return HAFF_ERR_BAD_ARG;
+  if (!operands_ok(A, lda, W, ldw, K) || (part_stride & 7) || (head_stride & 7) || !haff_aligned(C)) return HAFF_ERR_BAD_ARG;
   const long hd = (long)heads * d;
   if ((d & 7) || d > 4096 || (M % 256) || (N % 256) || (K % BK) || N % hd != 0 || N / hd > 3 || hd >= (1L << 16)) return HAFF_ERR_UNSUPPORTED;
   GemmArgs p = gemm_args(A, lda, W, ldw, C, (long)d, M, N, K);

@@ -441,14 +441,13 @@ void launch_i8_skinny(const I8Args& p, int swiglu, hipStream_t s) {
   else hipLaunchKernelGGL((gemm_i8_skinny_kernel<MT, 1, false, kI8Waves>), dim3(tiles), b, 0, s, p);
 }
 
-inline bool mis(const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; }
 
 }  // namespace
 
 extern "C" int haff_int8_quantize_weight_f16(const void* W, long ldw, int N, int K, const int* row_map, void* CB, float* SCB,
                                              void* stream) {
   if (N <= 0 || K <= 0 || (K & 63) || (ldw & 7) || ldw < K || !W || !CB || !SCB) return HAFF_ERR_BAD_ARG;
-  if (mis(W, 16) || mis(CB, 16) || mis(SCB, 4)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(W, 16) || !haff_aligned(CB, 16) || !haff_aligned(SCB, 4)) return HAFF_ERR_BAD_ARG;
   hipLaunchKernelGGL(i8_weight_kernel, dim3(N), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16_t*>(W),
                      ldw, K, row_map, reinterpret_cast<signed char*>(CB), SCB);
   return haff_check_launch();
@@ -458,7 +457,7 @@ extern "C" int haff_int8_quantize_act_f16(const void* A, long lda, int M, int K,
                                           unsigned* masks, void* CA, long ldca, float* SCA, int* cols, int* ncols, void* stream) {
   if (M <= 0 || K <= 0 || (K & 63) || seg_rows <= 0 || (lda & 7) || lda < K || (ldca & 15) || ldca < K) return HAFF_ERR_BAD_ARG;
   if (!(threshold >= 0.f) || !A || !CA || !SCA || !cols || !ncols || (threshold > 0.f && !masks)) return HAFF_ERR_BAD_ARG;
-  if (mis(A, 16) || mis(CA, 16) || mis(SCA, 4) || mis(masks, 4)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(A, 16) || !haff_aligned(CA, 16) || !haff_aligned(SCA, 4) || !haff_aligned(masks, 4)) return HAFF_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int S = (M + seg_rows - 1) / seg_rows;
   const unsigned* mk = threshold > 0.f ? masks : nullptr;
@@ -482,7 +481,7 @@ extern "C" int haff_gemm_int8_f16(const void* A, long lda, const void* CA, long 
   if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || seg_rows <= 0 || form < 0 || form > 2) return HAFF_ERR_BAD_ARG;
   if (!CA || !SCA || !CB || !SCB || !C || (ldca & 15) || ldca < K) return HAFF_ERR_BAD_ARG;
   if (!cols != !ncols || (ncols && (!A || lda < K))) return HAFF_ERR_BAD_ARG;
-  if (mis(CA, 16) || mis(CB, 16) || mis(SCA, 4) || mis(SCB, 4)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(CA, 16) || !haff_aligned(CB, 16) || !haff_aligned(SCA, 4) || !haff_aligned(SCB, 4)) return HAFF_ERR_BAD_ARG;
   if (swiglu && ((N & 31) || resid)) return HAFF_ERR_BAD_ARG;
   const int f = form ? form : (M <= 64 ? 1 : 2);
   if (f == 1 && M > 64) return HAFF_ERR_UNSUPPORTED;

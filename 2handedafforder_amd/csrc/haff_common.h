@@ -210,3 +210,11 @@ static inline int haff_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? HAFF_OK : HAFF_ERR_LAUNCH;
 }
+// host side: p sits on a `bytes` boundary (a power of two; 16 = one dwordx4 access). A null pointer passes.
+static inline bool haff_aligned(const void* p, unsigned bytes = 16) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+// host side: the (batch, head, token) strides of q / k / v are multiples of in_mask + 1 elements, those of the output of out_mask + 1
+// (16-bit attention: 7 / 3, whole 16-byte input chunks and 8-byte output chunks; f32: 3 / 3)
+static inline bool haff_strides_ok(long q_sb, long q_sh, long q_st, long k_sb, long k_sh, long k_st, long v_sb, long v_sh, long v_st,
+                                   long o_sb, long o_sh, long o_st, long in_mask, long out_mask) {
+  return !(((q_sb | q_sh | q_st | k_sb | k_sh | k_st | v_sb | v_sh | v_st) & in_mask) || ((o_sb | o_sh | o_st) & out_mask));
+}

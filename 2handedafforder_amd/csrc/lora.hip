@@ -427,8 +427,6 @@ __global__ __launch_bounds__(256) void lora_gu_swiglu_kernel(const bf16_t* tT, l
 }
 
 inline hipStream_t HS(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int check_launch() { return hipGetLastError() == hipSuccess ? HAFF_OK : HAFF_ERR_LAUNCH; }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -437,10 +435,12 @@ static int lora_qkv_rope_fwd_impl(const void* qkv, long ld_qkv, const void* tT, 
                                   int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int d,
                                   int T, float scale, void* stream) {
   if (M <= 0 || T <= 0 || H <= 0 || !qkv || !tT || !Bq || !Bv || !cos_sin || !q_out || !k_out || !v_out) return HAFF_ERR_BAD_ARG;
-  if (NA == 3 && (!Bk || !al16(Bk))) return HAFF_ERR_BAD_ARG;
+  if (NA == 3 && (!Bk || !haff_aligned(Bk))) return HAFF_ERR_BAD_ARG;
   if (d != HD || H % HD || ldb != 8) return HAFF_ERR_UNSUPPORTED;
   if (ld_qkv < 3L * H || ldo < H || ldt < M || (ld_qkv & 7) || (ldo & 7)) return HAFF_ERR_BAD_ARG;
-  if (!al16(qkv) || !al16(Bq) || !al16(Bv) || !al16(cos_sin) || !al16(q_out) || !al16(k_out) || !al16(v_out)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(qkv) || !haff_aligned(Bq) || !haff_aligned(Bv) || !haff_aligned(cos_sin) || !haff_aligned(q_out) ||
+      !haff_aligned(k_out) || !haff_aligned(v_out))
+    return HAFF_ERR_BAD_ARG;
   LoraFwdArgs p{(const bf16_t*)qkv, ld_qkv, (const bf16_t*)tT, ldt, (const bf16_t*)Bq, (const bf16_t*)Bv, ldb, cos_sin,
                 (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, ldo, M, H, T, scale, (const bf16_t*)Bk};
   const long n_rt = (M + 15) / 16;
@@ -449,7 +449,7 @@ static int lora_qkv_rope_fwd_impl(const void* qkv, long ld_qkv, const void* tT, 
   const long cap = (2048 + nh - 1) / nh;   // ~2048 workgroups: 8 per CU
   if (gy > cap) gy = cap;
   hipLaunchKernelGGL((lora_qkv_rope_fwd_kernel<F16, NA>), dim3(nh, (unsigned)gy), dim3(256), 0, HS(stream), p);
-  return check_launch();
+  return haff_check_launch();
 }
 
 template <bool F16>
@@ -458,23 +458,23 @@ static int lora_qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv
   if (M <= 0 || T <= 0 || H <= 0 || !dq || !dk || !dv || !cos_sin || !dqkv) return HAFF_ERR_BAD_ARG;
   if (d != HD || H % HD) return HAFF_ERR_UNSUPPORTED;
   if (ld_in < H || ld_out < 3L * H || (ld_in & 7) || (ld_out & 7)) return HAFF_ERR_BAD_ARG;
-  if (!al16(dq) || !al16(dk) || !al16(dv) || !al16(cos_sin) || !al16(dqkv)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(dq) || !haff_aligned(dk) || !haff_aligned(dv) || !haff_aligned(cos_sin) || !haff_aligned(dqkv)) return HAFF_ERR_BAD_ARG;
   const long total = M * (H / HD) * 8;
   long g = (total + 255) / 256;
   if (g > 16384) g = 16384;
   hipLaunchKernelGGL((lora_qkv_rope_bwd_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)dq, (const bf16_t*)dk,
                      (const bf16_t*)dv, ld_in, cos_sin, (bf16_t*)dqkv, ld_out, M, H, T);
-  return check_launch();
+  return haff_check_launch();
 }
 
 template <bool F16>
 static int lora_dx_launch(const void* dtT, long ldt, const void* A2, long lda, const void* keep, const void* keep_v, long ldk, void* dx,
                           long ldx, int accumulate, long M, int K, float scale, void* stream, int na = 2, const void* keep_k = nullptr) {
   if (M <= 0 || K <= 0 || !dtT || !A2 || !dx || (keep_v && !keep) || (keep_k && !keep_v)) return HAFF_ERR_BAD_ARG;
-  if (keep_k && !al16(keep_k)) return HAFF_ERR_BAD_ARG;
+  if (keep_k && !haff_aligned(keep_k)) return HAFF_ERR_BAD_ARG;
   if (K % 128) return HAFF_ERR_UNSUPPORTED;
   if (ldt < M || lda < K || ldx < K || (ldx & 7) || (keep && (ldk < K || (ldk & 7)))) return HAFF_ERR_BAD_ARG;
-  if (!al16(dx) || (keep && !al16(keep)) || (keep_v && !al16(keep_v))) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(dx) || (keep && !haff_aligned(keep)) || (keep_v && !haff_aligned(keep_v))) return HAFF_ERR_BAD_ARG;
   LoraDxArgs p{(const bf16_t*)dtT, ldt, (const bf16_t*)A2, lda, (const bf16_t*)keep, ldk, (bf16_t*)dx, ldx, M, K, accumulate, scale,
                (const bf16_t*)keep_v, (const bf16_t*)keep_k, na};
   const long n_rt = (M + 15) / 16;
@@ -483,7 +483,7 @@ static int lora_dx_launch(const void* dtT, long ldt, const void* A2, long lda, c
   const long cap = (2048 + gx - 1) / gx;
   if (gy > cap) gy = cap;
   hipLaunchKernelGGL((lora_dx_kernel<F16>), dim3(gx, (unsigned)gy), dim3(256), 0, HS(stream), p);
-  return check_launch();
+  return haff_check_launch();
 }
 
 // rows per block of haff_lora_tn (multiple of 64): ~16 row blocks
@@ -501,7 +501,7 @@ static int lora_tn_impl(const void* sT, long lds, int R, const void* big, long l
                         void* out, long ldo, int out_f32, int transposed, int j_valid, float scale, void* stream) {
   if (M <= 0 || N <= 0 || !sT || !big || !workspace || !out || j_valid <= 0 || j_valid > R) return HAFF_ERR_BAD_ARG;
   if (R != 8 && R != 16) return HAFF_ERR_UNSUPPORTED;
-  if ((lds & 7) || lds < (M + 15) / 16 * 16 || !al16(sT) || (N & 1) || (ldb & 1) || ldb < N || (reinterpret_cast<uintptr_t>(big) & 3))
+  if ((lds & 7) || lds < (M + 15) / 16 * 16 || !haff_aligned(sT) || (N & 1) || (ldb & 1) || ldb < N || (reinterpret_cast<uintptr_t>(big) & 3))
     return HAFF_ERR_BAD_ARG;
   if (workspace_elems < lora_tn_ws(M, R, N)) return HAFF_ERR_BAD_ARG;
   if (ldo < (transposed ? j_valid : N)) return HAFF_ERR_BAD_ARG;
@@ -521,7 +521,7 @@ static int lora_tn_impl(const void* sT, long lds, int R, const void* big, long l
     hipLaunchKernelGGL((lora_tn_reduce_kernel<f16_t>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (f16_t*)out, ldo, transposed, j_valid, scale);
   else
     hipLaunchKernelGGL((lora_tn_reduce_kernel<bf16_t>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (bf16_t*)out, ldo, transposed, j_valid, scale);
-  return check_launch();
+  return haff_check_launch();
 }
 
 extern "C" int haff_lora_qkv_rope_fwd(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv,
@@ -591,14 +591,14 @@ template <bool F16>
 static int lora_out_impl(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream) {
   if (M <= 0 || N <= 0 || !tT || !B || !y) return HAFF_ERR_BAD_ARG;
   if (N % 8) return HAFF_ERR_UNSUPPORTED;
-  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || (reinterpret_cast<uintptr_t>(tT) & 7) || ldy < N || (ldy & 7) || !al16(y) || !al16(B))
+  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || (reinterpret_cast<uintptr_t>(tT) & 7) || ldy < N || (ldy & 7) || !haff_aligned(y) || !haff_aligned(B))
     return HAFF_ERR_BAD_ARG;
   const long total = (M + 3) / 4 * (N / 8);
   long g = (total + 255) / 256;
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL((lora_out_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)tT, ldt, (const bf16_t*)B, (bf16_t*)y,
                      ldy, M, N, scale);
-  return check_launch();
+  return haff_check_launch();
 }
 
 template <bool F16>
@@ -608,13 +608,13 @@ static int lora_gu_swiglu_impl(const void* tT, long ldt, const void* Bg, const v
   if (F % 16) return HAFF_ERR_UNSUPPORTED;
   if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || (reinterpret_cast<uintptr_t>(tT) & 7) || ldg < 2L * F || (ldg & 7) || ldy < F || (ldy & 7))
     return HAFF_ERR_BAD_ARG;
-  if (!al16(Bg) || !al16(Bu) || !al16(gu) || !al16(y)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(Bg) || !haff_aligned(Bu) || !haff_aligned(gu) || !haff_aligned(y)) return HAFF_ERR_BAD_ARG;
   const long total = (M + 3) / 4 * (F / 8);
   long g = (total + 255) / 256;
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL((lora_gu_swiglu_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)tT, ldt, (const bf16_t*)Bg,
                      (const bf16_t*)Bu, (bf16_t*)gu, ldg, (bf16_t*)y, ldy, M, F, scale);
-  return check_launch();
+  return haff_check_launch();
 }
 
 extern "C" int haff_lora_qkv3_rope_fwd(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, const void* Bk,

@@ -23,24 +23,27 @@
 // the P.V MFMA from registers and V^T fragments come from transposed LDS reads with the same permuted k order.
 #include "haff_common.h"
 
+#include <type_traits>
+
 namespace {
 
 struct WinArgs {
-  const bf16_t *q, *k, *v;
-  bf16_t* o;
-  long q_sb, q_sh, q_st;
-  long k_sb, k_sh, k_st;
-  long v_sb, v_sh, v_st;
-  long o_sb, o_sh, o_st;
-  int B, H;  // B = number of windows
-  float scale;
-  const bf16_t *tab_h, *tab_w;  // [2S-1][D] bf16, contiguous
+  const bf16_t *q = nullptr, *k = nullptr, *v = nullptr;
+  bf16_t* o = nullptr;
+  long q_sb = 0, q_sh = 0, q_st = 0;
+  long k_sb = 0, k_sh = 0, k_st = 0;
+  long v_sb = 0, v_sh = 0, v_st = 0;
+  long o_sb = 0, o_sh = 0, o_st = 0;
+  int B = 0, H = 0;  // B = number of windows
+  float scale = 0.f;
+  const bf16_t *tab_h = nullptr, *tab_w = nullptr;  // [2S-1][D] bf16, contiguous
   // window padding (image_encoder.py:263-288): windows tile a grid_h x grid_w token grid, wps per side; window
   // tokens beyond the grid are pads whose q/k/v are those of token row `pad_token` (relative to the base pointers).
   // grid_h == 0: every token is real.
-  int grid_h, grid_w, wps;
-  long pad_token;
+  int grid_h = 0, grid_w = 0, wps = 0;
+  long pad_token = 0;
 };
+static_assert(std::is_trivially_copyable<WinArgs>::value && sizeof(WinArgs) == 184, "WinArgs is passed to the kernel by value");
 
 constexpr float WLOG2E = 1.4426950408889634f;
 typedef __attribute__((address_space(3))) bf16x4* wlds_v4_ptr;
@@ -442,6 +445,20 @@ __global__ __launch_bounds__((WinCfg<D, S>::NTHREADS)) void window_attn_kernel(W
 
 }  // namespace
 
+// The common core of an argument block: the four operands with their (window, head, token) strides in elements, shape and scale
+static WinArgs win_args(const void* q, long q_sb, long q_sh, long q_st,
+                        const void* k, long k_sb, long k_sh, long k_st,
+                        const void* v, long v_sb, long v_sh, long v_st,
+                        void* o, long o_sb, long o_sh, long o_st, int n_windows, int H, float scale) {
+  WinArgs p;
+  p.q = reinterpret_cast<const bf16_t*>(q); p.q_sb = q_sb; p.q_sh = q_sh; p.q_st = q_st;
+  p.k = reinterpret_cast<const bf16_t*>(k); p.k_sb = k_sb; p.k_sh = k_sh; p.k_st = k_st;
+  p.v = reinterpret_cast<const bf16_t*>(v); p.v_sb = v_sb; p.v_sh = v_sh; p.v_st = v_st;
+  p.o = reinterpret_cast<bf16_t*>(o); p.o_sb = o_sb; p.o_sh = o_sh; p.o_st = o_st;
+  p.B = n_windows; p.H = H; p.scale = scale;
+  return p;
+}
+
 // Fused window attention with in-kernel decomposed rel-pos (bf16). q/k/v/o: strides in elements (window, head,
 // token); n_tokens = S*S per window. grid_h/grid_w > 0: the windows tile images of grid_h x grid_w tokens
 // (ceil(grid/S)^2 windows per image, window-major as window_partition orders them) and tokens beyond the grid are
@@ -459,26 +476,22 @@ static int window_attention_impl(const void* q, long q_sb, long q_sh, long q_st,
                                  const void* tab_h, const void* tab_w, int grid_h, int grid_w,
                                  long pad_token, void* stream) {
   if (n_windows <= 0 || H <= 0 || S <= 0 || d <= 0 || !tab_h || !tab_w) return HAFF_ERR_BAD_ARG;
-  if ((q_st & 7) || (k_st & 7) || (v_st & 7) || (o_st & 3) || (q_sh & 7) || (k_sh & 7) || (v_sh & 7) || (o_sh & 3) ||
-      (q_sb & 7) || (k_sb & 7) || (v_sb & 7) || (o_sb & 3))
-    return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(q) & 15) || (reinterpret_cast<uintptr_t>(k) & 15) ||
-      (reinterpret_cast<uintptr_t>(v) & 15) || (reinterpret_cast<uintptr_t>(o) & 7) ||
-      (reinterpret_cast<uintptr_t>(tab_h) & 15) || (reinterpret_cast<uintptr_t>(tab_w) & 15))
+  if (!haff_strides_ok(q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st, 7, 3)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(q) || !haff_aligned(k) || !haff_aligned(v) || !haff_aligned(o, 8) || !haff_aligned(tab_h) || !haff_aligned(tab_w))
     return HAFF_ERR_BAD_ARG;
   if (S != 14 || d != 80) return HAFF_ERR_UNSUPPORTED;
   // the staging DMA addresses K and V of an item from one base with 32-bit offsets: same (window, head, token)
-  // strides for both (true for the fused qkv buffer) and an item span under 4 GiB
+  // strides for both (true for the fused qkv buffer), V behind K, and an item span under 4 GiB
   if (k_sb != v_sb || k_sh != v_sh || k_st != v_st) return HAFF_ERR_UNSUPPORTED;
-  {
-    const long dvk = reinterpret_cast<const bf16_t*>(v) - reinterpret_cast<const bf16_t*>(k);
-    const long span = (dvk < 0 ? -dvk : dvk) + (long)S * S * k_st + d;
-    if (dvk < 0 || span * 2 >= (1L << 32)) return HAFF_ERR_UNSUPPORTED;
-  }
-  WinArgs p{reinterpret_cast<const bf16_t*>(q), reinterpret_cast<const bf16_t*>(k), reinterpret_cast<const bf16_t*>(v),
-            reinterpret_cast<bf16_t*>(o), q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st,
-            n_windows, H, scale, reinterpret_cast<const bf16_t*>(tab_h), reinterpret_cast<const bf16_t*>(tab_w),
-            grid_h, grid_w, grid_h > 0 ? (grid_h + S - 1) / S : 0, pad_token};
+  const long dvk = reinterpret_cast<const bf16_t*>(v) - reinterpret_cast<const bf16_t*>(k);
+  if (dvk < 0 || (dvk + (long)S * S * k_st + d) * 2 >= (1L << 32)) return HAFF_ERR_UNSUPPORTED;
+  WinArgs p = win_args(q, q_sb, q_sh, q_st, k, k_sb, k_sh, k_st, v, v_sb, v_sh, v_st, o, o_sb, o_sh, o_st, n_windows, H, scale);
+  p.tab_h = reinterpret_cast<const bf16_t*>(tab_h);
+  p.tab_w = reinterpret_cast<const bf16_t*>(tab_w);
+  p.grid_h = grid_h;
+  p.grid_w = grid_w;
+  p.wps = grid_h > 0 ? (grid_h + S - 1) / S : 0;
+  p.pad_token = pad_token;
   if (grid_h > 0) {
     // padded windows: square window grid, whole images, pad row addressable with the 32-bit staging offsets
     // ... and at or after every window's base: the kernel reaches the pad row through an UNSIGNED 32-bit byte offset from
@@ -489,7 +502,6 @@ static int window_attention_impl(const void* q, long q_sb, long q_sh, long q_st,
     // the V pad row is reached as pad base + (v - k) in ONE unsigned 32-bit byte offset (issue_dma: nx_pad_base + chunk +
     // vmk_bytes): the SUM must fit too — on head-major planes both terms are ~ part * 2 bytes and wrap together from ~171
     // frames per pass on; the caller keeps the token-major layout then
-    const long dvk = reinterpret_cast<const bf16_t*>(v) - reinterpret_cast<const bf16_t*>(k);
     if ((pad_token * k_st + dvk + d) * 2 >= (1L << 32)) return HAFF_ERR_UNSUPPORTED;
   }
   using C = WinCfg<80, 14>;

@@ -24,9 +24,14 @@ def _dt(t):
     raise TypeError(f"unsupported dtype {t.dtype}")
 
 
-def _fn(lib, name, dtype):
-    """The entry point of the 16-bit format: haff_*_bf16 for bf16, its haff_*_f16 sibling for fp16 (same arguments)."""
-    return getattr(lib, name.replace("_bf16", "_f16") if dtype == torch.float16 else name)
+def _fn(lib, name, dtype, f32=False):
+    """The entry point of the operand format: haff_*_bf16 for bf16, its haff_*_f16 sibling for fp16 (same arguments) and, in a
+    family that has one (f32=True), the haff_*_f32 sibling for every other dtype."""
+    if dtype == torch.float16:
+        name = name.replace("_bf16", "_f16")
+    elif f32 and dtype != torch.bfloat16:
+        name = name.replace("_bf16", "_f32")
+    return getattr(lib, name)
 
 
 def _stream():
@@ -623,6 +628,18 @@ def decode_chain_status(sync, n_layers):
     return rc == 0
 
 
+def _qkvo(q, k, v, out):
+    """The 16 operand arguments the attention entry points start with — base address and (batch, head, token) strides of the q, k, v
+    [B,H,N,d] views and of the token-major output [B,Nq,H*d] seen the same way — and that output, allocated here when out is None."""
+    B, H, Nq, d = q.shape
+    if out is None:
+        out = torch.empty((B, Nq, H * d), dtype=q.dtype, device=q.device)
+    (q_sb, q_sh, q_st, _), (k_sb, k_sh, k_st, _), (v_sb, v_sh, v_st, _) = q.stride(), k.stride(), v.stride()
+    o_sb, o_st, o_sh, _ = out.view(B, Nq, H, d).stride()
+    return [q.data_ptr(), q_sb, q_sh, q_st, k.data_ptr(), k_sb, k_sh, k_st, v.data_ptr(), v_sb, v_sh, v_st,
+            out.data_ptr(), o_sb, o_sh, o_st], out
+
+
 def attention(q, k, v, scale, causal=False, q_pos0=0, relh=None, relw=None, S=0, out=None):
     """q [B,H,Nq,d], k/v [B,H,Nk,d] strided views (unit stride on d). Returns out [B,Nq,H*d] (token-major)."""
     lib = load_library()
@@ -630,22 +647,11 @@ def attention(q, k, v, scale, causal=False, q_pos0=0, relh=None, relw=None, S=0,
     B, H, Nq, d = q.shape
     Nk = k.shape[2]
     assert q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
-    if out is None:
-        out = torch.empty((B, Nq, H * d), dtype=q.dtype, device=q.device)
-    o4 = out.view(B, Nq, H, d).permute(0, 2, 1, 3)
-    args = [q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
-            k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
-            v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
-            out.data_ptr(), o4.stride(0), o4.stride(1), o4.stride(2),
-            B, H, Nq, Nk, d, float(scale), 1 if causal else 0, int(q_pos0), _p(relh), _p(relw), int(S), _stream()]
+    qkvo, out = _qkvo(q, k, v, out)
     if relh is not None:
         assert relh.dtype == torch.float32 and relh.is_contiguous() and relw.is_contiguous()
-    if q.dtype == torch.bfloat16:
-        rc = lib.haff_attention_bf16(*args)
-    elif q.dtype == torch.float16:
-        rc = lib.haff_attention_f16(*args)
-    else:
-        rc = lib.haff_attention_f32(*args)
+    rc = _fn(lib, "haff_attention_bf16", q.dtype, f32=True)(*qkvo, B, H, Nq, Nk, d, float(scale), 1 if causal else 0, int(q_pos0),
+                                                            _p(relh), _p(relw), int(S), _stream())
     check(rc, "haff_attention")
     return out
 
@@ -694,18 +700,12 @@ def window_attention(q, k, v, scale, tab_h, tab_w, S, out=None, grid=0, pad_toke
     are taken from token row `pad_token` of the views (the caller stores the qkv bias there)."""
     lib = load_library()
     _req(q, "q")
-    B, H, N, d = q.shape
+    B, H, _, d = q.shape
     assert window_attention_supported(q, S) and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
     th, tw = _bf16_table(tab_h, q.dtype), _bf16_table(tab_w, q.dtype)
-    if out is None:
-        out = torch.empty((B, N, H * d), dtype=q.dtype, device=q.device)
-    o4 = out.view(B, N, H, d).permute(0, 2, 1, 3)
-    rc = _fn(lib, "haff_window_attention_bf16", q.dtype)(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
-                                        k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
-                                        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
-                                        out.data_ptr(), o4.stride(0), o4.stride(1), o4.stride(2),
-                                        B, H, S, d, float(scale), th.data_ptr(), tw.data_ptr(), int(grid), int(grid),
-                                        int(pad_token), _stream())
+    qkvo, out = _qkvo(q, k, v, out)
+    rc = _fn(lib, "haff_window_attention_bf16", q.dtype)(*qkvo, B, H, S, d, float(scale), th.data_ptr(), tw.data_ptr(), int(grid),
+                                                         int(grid), int(pad_token), _stream())
     check(rc, "haff_window_attention_bf16")
     return out
 
@@ -722,17 +722,11 @@ def global_attention(q, k, v, scale, tab_h, tab_w, S, out=None):
     [2S-1,d] (rounded to bf16 once and cached, as the reference's bf16 checkpoint stores them). Returns [B,S*S,H*d]."""
     lib = load_library()
     _req(q, "q")
-    B, H, N, d = q.shape
+    B, H, _, d = q.shape
     assert global_attention_supported(q, k, v, S) and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
     th, tw = _bf16_table(tab_h, q.dtype), _bf16_table(tab_w, q.dtype)
-    if out is None:
-        out = torch.empty((B, N, H * d), dtype=q.dtype, device=q.device)
-    o4 = out.view(B, N, H, d).permute(0, 2, 1, 3)
-    rc = _fn(lib, "haff_global_attention_bf16", q.dtype)(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
-                                        k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
-                                        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2),
-                                        out.data_ptr(), o4.stride(0), o4.stride(1), o4.stride(2),
-                                        B, H, S, d, float(scale), th.data_ptr(), tw.data_ptr(), _stream())
+    qkvo, out = _qkvo(q, k, v, out)
+    rc = _fn(lib, "haff_global_attention_bf16", q.dtype)(*qkvo, B, H, S, d, float(scale), th.data_ptr(), tw.data_ptr(), _stream())
     check(rc, "haff_global_attention_bf16")
     return out
 
@@ -859,13 +853,10 @@ def attention_decode_rows(q, k, v, scale, nk_rows, out=None):
     B, H, Nq, d = q.shape
     assert Nq == 1 and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
     assert nk_rows.dtype == torch.int32 and nk_rows.is_cuda and nk_rows.numel() == B
-    if out is None:
-        out = torch.empty((B, 1, H * d), dtype=q.dtype, device=q.device)
-    fn = {torch.bfloat16: lib.haff_attention_decode_rows_bf16, torch.float16: lib.haff_attention_decode_rows_f16}.get(
-        q.dtype, lib.haff_attention_decode_rows_f32)
-    rc = fn(q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
-            v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), out.data_ptr(), H * d, d, B, H, k.shape[2], d, float(scale),
-            nk_rows.data_ptr(), _stream())
+    qkvo, out = _qkvo(q, k, v, out)
+    del qkvo[15], qkvo[3]   # one query row per (batch, head): the entry point takes no token stride for q and the output
+    rc = _fn(lib, "haff_attention_decode_rows_bf16", q.dtype, f32=True)(*qkvo, B, H, k.shape[2], d, float(scale), nk_rows.data_ptr(),
+                                                                        _stream())
     check(rc, "haff_attention_decode_rows")
     return out
 
@@ -879,9 +870,9 @@ def decode_attention_rope(qkv, kcache, vcache, cos_sin, H, d, scale, nk_rows):
     assert kcache.dtype == qkv.dtype and vcache.dtype == qkv.dtype
     assert nk_rows.dtype == torch.int32 and nk_rows.is_cuda and nk_rows.numel() == B and cos_sin.dtype == torch.float32
     out = torch.empty((B, 1, H * d), dtype=qkv.dtype, device=qkv.device)
-    fn = lib.haff_decode_attention_rope_rows_bf16 if qkv.dtype == torch.bfloat16 else lib.haff_decode_attention_rope_rows_f16
-    rc = fn(qkv.data_ptr(), qkv.stride(0), kcache.data_ptr(), vcache.data_ptr(), cos_sin.data_ptr(), out.data_ptr(), B, H, d,
-            kcache.shape[1], float(scale), nk_rows.data_ptr(), _stream())
+    rc = _fn(lib, "haff_decode_attention_rope_rows_bf16", qkv.dtype)(qkv.data_ptr(), qkv.stride(0), kcache.data_ptr(), vcache.data_ptr(),
+                                                                     cos_sin.data_ptr(), out.data_ptr(), B, H, d, kcache.shape[1],
+                                                                     float(scale), nk_rows.data_ptr(), _stream())
     check(rc, "haff_decode_attention_rope_rows")
     return out
 
