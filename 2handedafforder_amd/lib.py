@@ -176,6 +176,8 @@ _PROTOS = {
                           c_void_p],
     "haff_rope_cache": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                         c_int, c_int, c_void_p],
+    "haff_kv_prefix_broadcast": [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                 c_void_p],
     "haff_argmax_rows": [c_void_p, c_long, c_void_p, c_int, c_int, c_void_p],
     "haff_decode_book": [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, c_long, c_int, c_void_p],

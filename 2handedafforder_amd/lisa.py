@@ -18,7 +18,7 @@ import os
 
 import torch
 
-from . import ops, overlap
+from . import ops, overlap, prompt_groups
 from .llava import ClipTowerHip, LlamaHip, _f32
 from .sam import SamEncoderHip, SamPromptDecoderHip
 
@@ -137,6 +137,15 @@ class LisaMI355:
         # one after another — the split-K workspaces baked into them (ops._workspace) may be the same buffer
         self._graph_pool = None
         self._caches = {}
+        self._prefix_caches = {}
+        # evaluate(offset=): what the last call did — frames, rows, shared_prefix_ids (ids of the prompt prefix prefilled once per frame),
+        # prefix_positions (its cache positions), shared (that path was taken), encoder_frames (frames the encoders ran over)
+        self.last_group_plan = None
+        # True: the mask decoders run once per [SEG] row (the batch-1 launch sequence, replayed) instead of once over all rows. The fp32
+        # products of the tail pick their kernel by row count (csrc/gemm_f32.hip), so a batched tail's bits depend on how many rows share
+        # the call; per row they do not — robot_demo.py --multi_prompt wants an action's files not to depend on the other actions.
+        # Costs one tail per row: off by default (throughput).
+        self.tail_per_row = False
         sd, dev = state_dict, self.device
         self.fp16_flushed_weights = _check_fp16_weights(sd, dev) if dtype == torch.float16 else 0
         assert cfg.clip.n_patches == N_IMG_PAD + 1, "the reference hard-codes 256 image tokens (LISA.py:461)"
@@ -203,13 +212,17 @@ class LisaMI355:
     # ---- a6-a8: splice + greedy generate -----------------------------------------------------------------
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, forced_answer=None, attention_mask=None, after_prefill=None,
-                 needed_hidden_only=False):
+                 needed_hidden_only=False, frame_of=None):
         """Greedy KV-cached decode (LISA.py:443-450). Rows may have different prompt lengths: input_ids is right-padded
         (utils/dataset.py:90-93) and attention_mask [B, L] (bool, True on real tokens; None = every row is full length)
         marks the real prefix of each row, as collate_fn builds it (:144-150). Row b's generated tokens are appended right
         after ITS last real token, so output_ids [B, L + N] is left-aligned per row (pad_token_id behind the end) and the
         hidden states [B, T + N - 1, H] line up with it position by position — the [SEG] rule of LISA.py:457-465 then
-        applies per row unchanged. Equal to B independent batch-1 runs."""
+        applies per row unchanged. Equal to B independent batch-1 runs.
+        frame_of (int32 [B] on the CPU, prompt_groups.check_offset; None = one frame per row): images_clip holds F frames and row b
+        reads frame frame_of[b]. The CLIP tower and the projector run over the F frames; when every row starts with the same ids up to
+        and past the <image> sentinel, that prefix is prefilled once per frame and its K / V are broadcast to the rows
+        (ops.kv_prefix_broadcast); the rows' own ids are then prefilled behind it. `last_group_plan` says what was done."""
         cfg = self.cfg
         input_ids = input_ids.to(self.device)
         B, L = input_ids.shape
@@ -225,12 +238,37 @@ class LisaMI355:
             assert bool((img_pos.long() < lens).all())
         img = self.encode_images(images_clip)
         n_img = img.shape[1]
-        # the sentinel slot itself is never dereferenced by the splice kernel
-        x = ops.embed_splice(input_ids.clamp_min(IMAGE_TOKEN_INDEX).contiguous(), img_pos, self.llm.embed, img.contiguous())
         T = L + n_img - 1
         t_rows = lens + (n_img - 1)                      # real positions per row after the splice
+        P = 0                                            # ids of the prefix that is prefilled once per frame (0: the plain prefill)
+        if frame_of is not None:
+            F = img.shape[0]
+            # the 8-bit mode's sticky outlier masks are defined per frame over ALL of its prefill rows: splitting the prefill would
+            # change them, so it prefills every row whole (as does a call whose rows share nothing, or one row per frame at most)
+            if not self.load_in_8bit and int(torch.bincount(frame_of.long(), minlength=1).max()) >= 2:
+                P = prompt_groups.shared_prefix_len(input_ids, lens, self.seg_token_idx)
+            self.last_group_plan = {"frames": F, "rows": B, "shared_prefix_ids": P, "prefix_positions": prompt_groups.prefix_positions(P, n_img),
+                                    "shared": P > 0, "encoder_frames": F}
+            frame_of = frame_of.to(self.device)
+            if P == 0:
+                img = img.index_select(0, frame_of.long())
         cache = self._persistent_cache(B, T + max_new_tokens)
         st = cache["book"]
+        p0 = P + n_img - 1 if P > 0 else 0               # cache positions filled by the broadcast: `prefill` below starts there
+        if P > 0:
+            # the F prefix rows (every row's first P ids are row 0's) through all layers into a cache of their own, no hidden state kept
+            pre = self._prefix_cache(img.shape[0], p0)
+            xp = ops.embed_splice(input_ids[:1, :P].clamp_min(IMAGE_TOKEN_INDEX).expand(img.shape[0], P).contiguous(),
+                                  img_pos[:1].expand(img.shape[0]).contiguous(), self.llm.embed, img.contiguous())
+            self.llm.forward(xp, pre, keep_rows=torch.empty((0,), dtype=torch.int64, device=self.device))
+            for li in range(len(self.llm.layers)):
+                ops.kv_prefix_broadcast(pre["k"][li], pre["v"][li], cache["k"][li], cache["v"][li], frame_of, p0)
+            cache["len"] = p0
+            # the rows' own ids: plain embedding rows (no sentinel behind the prefix), right-padded as before
+            x = self.llm.embed.index_select(0, input_ids[:, P:].reshape(-1)).view(B, L - P, -1)
+        else:
+            # the sentinel slot itself is never dereferenced by the splice kernel
+            x = ops.embed_splice(input_ids.clamp_min(IMAGE_TOKEN_INDEX).contiguous(), img_pos, self.llm.embed, img.contiguous())
         keep = None
         if needed_hidden_only and self.prune_last_layer and not self.load_in_8bit:
             # evaluate() reads two kinds of prefill rows only: each row's last real position (the first token's logits) and the
@@ -242,12 +280,17 @@ class LisaMI355:
             # id position j + 1 holds [SEG] -> seg_embeddings reads hidden row j + 255 (the reference's fixed 255-row shift, wherever
             # the <image> sentinel sits: LISA.py:459-463)
             keep = torch.unique(torch.cat([b_last, pb * T + pt + (n_img - 1)]))
+            if p0:
+                # the same rows counted in the [B, T - p0] tail: none of them lies in the shared part (shared_prefix_len, rules ii / iii)
+                keep = (keep // T) * (T - p0) + (keep % T - p0)
         i8 = {"valid": t_rows.to(torch.int32)} if self.load_in_8bit else {}
         prefill = self.llm.forward(x, cache, keep_rows=keep, **i8)   # causal: a row's real positions never see its padding
         if after_prefill is not None:                    # work the caller wants enqueued (elsewhere) behind the prefill
             after_prefill()
         hidden, out_ids = st["hidden"], st["out_ids"]    # persistent [B, tmax, H] / [B, tmax]: the decode graph writes into them
-        hidden[:, :T] = prefill
+        if p0:
+            hidden[:, :p0].zero_()                       # never gathered: no [SEG] reads a hidden row of the shared part
+        hidden[:, p0:T] = prefill
         hidden[:, T:].zero_()
         out_ids.fill_(cfg.pad_token_id)
         out_ids[:, :L] = torch.where(torch.arange(L, device=self.device)[None, :] < lens[:, None], input_ids,
@@ -263,7 +306,7 @@ class LisaMI355:
             st["forced"][:, :max_new_tokens] = forced_answer[:, :max_new_tokens].to(self.device)
         st["use_forced"].fill_(0 if forced_answer is None else 1)
         rows = torch.arange(B, device=self.device)
-        logits = self.llm.next_token_logits(prefill[rows, t_rows - 1].contiguous())
+        logits = self.llm.next_token_logits(prefill[rows, t_rows - (1 + p0)].contiguous())
         # token 0 (from the prefill logits), then one decode step per further token: embedding of the token just written ->
         # layers at each row's own position -> logits -> argmax -> bookkeeping of the next token, all device-side; the host
         # only reads the rows' finished flags between steps (generate()'s stopping rule)
@@ -297,6 +340,19 @@ class LisaMI355:
                          "t_rows": torch.zeros((B,), dtype=i32, device=dev), "tok": torch.zeros((B,), dtype=i64, device=dev),
                          "pos": c["pos"], "nk": c["nk"],
                          "hidden": torch.zeros((B, tmax, self.cfg.llm.hidden), dtype=self.dtype, device=dev)}
+        c["len"] = 0
+        return c
+
+    def _prefix_cache(self, F, tmax):
+        """K / V of the prompt prefix that the rows of a frame share: [F, tmax, H] per layer, the source of ops.kv_prefix_broadcast.
+        No decode state hangs on it; the last two shapes stay resident (7B, 8 frames, 275 positions: 1.2 GB)."""
+        key = (F, tmax)
+        c = self._prefix_caches.pop(key, None)
+        if c is None:
+            if len(self._prefix_caches) >= 2:
+                del self._prefix_caches[next(iter(self._prefix_caches))]
+            c = self.llm._new_cache(F, tmax)
+        self._prefix_caches[key] = c
         c["len"] = 0
         return c
 
@@ -470,9 +526,45 @@ class LisaMI355:
         return self._ingest
 
     # ---- the boundary --------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_grouped(offset, images_clip, images, input_ids, resize_list, original_size_list, frames_u8, attention_mask, forced_answer):
+        """evaluate(offset=)'s arguments, checked on the host before anything is enqueued: -> (frame_of int32 [B] on the CPU, F).
+        A ValueError names the argument that does not fit."""
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2:
+            raise ValueError("input_ids: a [B, L] tensor of prompt rows is expected with offset=")
+        B = input_ids.shape[0]
+        counts = {name: len(v) for name, v in (("images_clip", images_clip), ("frames_u8", frames_u8), ("images", images),
+                                               ("resize_list", resize_list), ("original_size_list", original_size_list)) if v is not None}
+        if not any(n in counts for n in ("images_clip", "frames_u8", "images")):
+            raise ValueError("images / frames_u8: evaluate() needs the frames")
+        F = counts.get("images_clip", counts.get("frames_u8", counts.get("images")))
+        for name, n in counts.items():
+            if n != F:
+                raise ValueError(f"{name}: {n} entries, but the call has {F} frames (per-frame inputs have one entry per frame with offset=)")
+        if attention_mask is not None and tuple(attention_mask.shape) != tuple(input_ids.shape):
+            raise ValueError(f"attention_mask: shape {tuple(attention_mask.shape)}, input_ids has {tuple(input_ids.shape)}")
+        if forced_answer is not None and forced_answer.shape[0] != B:
+            raise ValueError(f"forced_answer: {forced_answer.shape[0]} rows, input_ids has {B}")
+        return prompt_groups.check_offset(offset, B, F), F
+
     @torch.no_grad()
     def evaluate(self, images_clip, images, input_ids, resize_list, original_size_list, max_new_tokens=32,
-                 tokenizer=None, forced_answer=None, frames_u8=None, attention_mask=None):
+                 tokenizer=None, forced_answer=None, frames_u8=None, attention_mask=None, *, offset=None):
+        """offset (keyword only; int64 [F+1], the convention of the reference's model_forward, LISA.py:224-262): several prompt rows
+        per frame. images_clip / images / frames_u8 / resize_list / original_size_list then have F entries, input_ids / attention_mask
+        / forced_answer B = offset[-1] rows, and row b belongs to frame f where offset[f] <= b < offset[f+1] (a frame without rows is
+        encoded and unused). Everything that does not depend on the prompt runs once per frame: the SAM encoder, the CLIP tower, the
+        projector and — when the rows share their ids up to and past the <image> sentinel — the Llama prefill of that prefix
+        (generate(frame_of=)). Returns are per prompt row, as without offset. None, or arange(B+1): one frame per row, the plain path."""
+        frame_of, n_frames = None, input_ids.shape[0]
+        if offset is not None:
+            frame_of, n_frames = self._check_grouped(offset, images_clip, images, input_ids, resize_list, original_size_list, frames_u8,
+                                                     attention_mask, forced_answer)
+            if prompt_groups.is_identity(offset):
+                frame_of = None
+        if frame_of is None:
+            self.last_group_plan = {"frames": n_frames, "rows": n_frames, "shared_prefix_ids": 0, "prefix_positions": 0, "shared": False,
+                                    "encoder_frames": n_frames}
         # The SAM encoder (MFMA-bound, ~60 % of the FLOPs) does not depend on the language model: it runs on its own
         # HIP stream so its big GEMMs fill the CUs while the HBM/latency-bound greedy decode steps of the LLM trickle
         # through on the caller's stream. Joined before the mask decoders.
@@ -518,7 +610,7 @@ class LisaMI355:
         # (round 5, bench.py --sam-beside-decode on / off at 8 and 16 frames: behind the prefill is +0.4 ... +1.8 % for 7B and 13B there
         # too; at 64 frames the encoder is 60 % of the step and has to start first)
         late = self.overlap_streams and self.sam_beside_decode is not False and \
-            (self.sam_beside_decode is True or input_ids.shape[0] <= 16)
+            (self.sam_beside_decode is True or n_frames <= 16)
         # Which kernels decode: a function of the BATCH alone, never of the schedule (every schedule of one batch must give the same
         # bits: tests/test_lisa_gpu.py::test_stream_schedules_do_not_change_results, tools/two_stream_soak.py). "auto": the chained
         # launch below overlap.MIN_FRAMES frames — where no encoder pass is ever capped beside the decode steps — five launches per
@@ -531,8 +623,8 @@ class LisaMI355:
             # launch whose workgroups hold every CU, the encoder's launches cannot slip in between (same box, one frame: encoder
             # first + chain 40.6 ms, behind the prefill + five launches 41.3, behind the prefill + chain 41.8-42.1)
             late = False
-        # ... and which CUs its GEMM launches leave to the decode steps (overlap.py)
-        n_frames = input_ids.shape[0]
+        # ... and which CUs its GEMM launches leave to the decode steps (overlap.py), for the frames that are encoded (with offset=: F, not
+        # the number of prompt rows)
         chunk = overlap.auto_chunk(n_frames, late) if self.sam_chunk == "auto" else self.sam_chunk
         caps, wait = None, False
         if self.overlap_streams:
@@ -554,17 +646,25 @@ class LisaMI355:
             launch_sam()
         try:
             output_ids, hidden = self.generate(images_clip, input_ids, max_new_tokens, forced_answer, attention_mask,
-                                               after_prefill=launch_sam if late else None, needed_hidden_only=True)
+                                               after_prefill=launch_sam if late else None, needed_hidden_only=True, frame_of=frame_of)
         finally:
             self.llm.decode_chain = chain_prev
         emb = sam_out[0]
         self._plan = (None, False, chunk)     # the encoder is enqueued: direct get_visual_embs* calls take no caps
         pred, frame_idx, counts = self.seg_embeddings(output_ids, hidden)
+        if frame_of is not None:
+            # prompt rows -> their frames: the embedding the mask decoders gather, and the sizes each row's masks are restored to
+            frame_idx = frame_of.to(self.device).long().index_select(0, frame_idx)
+            resize_list = [resize_list[f] for f in frame_of.tolist()]
+            original_size_list = [original_size_list[f] for f in frame_of.tolist()]
         cur.wait_stream(side)
         emb.record_stream(cur)
         B = output_ids.shape[0]
         pred_masks_left, pred_masks_right, taxonomies = [], [], []
-        if pred.shape[0] > 0:
+        if pred.shape[0] > 1 and self.tail_per_row:
+            parts = [self._decoder_tail(emb, frame_idx[i:i + 1], pred[i:i + 1]) for i in range(pred.shape[0])]
+            lo_l, lo_r, tax = (torch.cat(p, 0) for p in zip(*parts))
+        elif pred.shape[0] > 0:
             lo_l, lo_r, tax = self._decoder_tail(emb, frame_idx, pred)
         offs = torch.cat([torch.zeros(1, dtype=torch.long), counts.cpu().long().cumsum(0)]).tolist()
         # frames of one size (a batch of equally sized frames: the throughput case): ONE postprocess launch per hand over all

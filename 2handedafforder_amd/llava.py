@@ -279,7 +279,8 @@ class LlamaHip:
         read. Every position still runs through every layer's attention inputs (its K / V are what later tokens attend to), but in
         the LAST layer only these rows take o_proj, the MLP and the final norm — nothing downstream of the last layer's K / V
         depends on the other rows (llava_llama.py:93-105 returns them, LISA.py:443-485 never looks at them); their rows of the
-        result are zero. 75 % of the last layer's linear FLOPs: 0.9 % of the step at 64 frames.
+        result are zero. 75 % of the last layer's linear FLOPs: 0.9 % of the step at 64 frames. An EMPTY keep_rows (no row is read:
+        the call only fills the cache) ends the last layer behind its K / V append and returns zeros.
         valid (int32 [B] device, LLM.int8 only): real rows per frame (right padding): a prefill from position 0 resets the frames'
         sticky masks and sets them from these rows (the outlier columns of lm_head's input too: the reference's lm_head sees every row)."""
         l = self.cfg
@@ -316,6 +317,11 @@ class LlamaHip:
                 qkv = self._lin(h, L["wqkv"], slot=4 * li, **i8)
                 ops.rope_cache(qkv, kc, vc, cs, B, T, nh, nh, hd, pos0)
                 q = qkv.view(B, T, 3, nh, hd)[:, :, 0].permute(0, 2, 1, 3)
+            if keep_rows is not None and keep_rows.numel() == 0 and li == len(self.layers) - 1:
+                # no row's final hidden state is read (a shared prompt prefix: lisa.py, evaluate(offset=)): the last layer's K / V
+                # are in the cache, and its attention, o_proj, MLP and the final norm feed nothing
+                cache["len"] = pos0 + T
+                return torch.zeros((B, T, H), dtype=self.dtype, device=x.device)
             k = kc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)[:, :, :tk]
             v = vc.view(B, cache["tmax"], nh, hd).permute(0, 2, 1, 3)[:, :, :tk]
             a = ops.attention(q, k, v, hd ** -0.5, causal=T > 1, q_pos0=tk - T)

@@ -845,6 +845,25 @@ def rope_cache_rows(qkv, kcache, vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0_rows):
     check(rc, "haff_rope_cache_rows")
 
 
+def kv_prefix_broadcast(k_src, v_src, k_dst, v_dst, frame_of, P):
+    """Positions 0 .. P-1 of the K and V caches k_src / v_src [F,tmax_src,H], row frame_of[b], into row b of k_dst / v_dst
+    [B,tmax_dst,H] (haff_kv_prefix_broadcast: one launch for both tensors). frame_of int32 [B] on the device, every entry in [0, F):
+    the caller has validated it (prompt_groups.check_offset); positions >= P of the destination keep their bytes."""
+    lib = load_library()
+    _req(k_src, "k_src")
+    F, _, H = k_src.shape
+    B = k_dst.shape[0]
+    for s, d in ((k_src, k_dst), (v_src, v_dst)):
+        assert s.dim() == 3 and d.dim() == 3 and s.shape == k_src.shape and d.shape == k_dst.shape and d.shape[2] == H
+        assert s.dtype == k_src.dtype and d.dtype == k_src.dtype and s.stride() == k_src.stride() and d.stride() == k_dst.stride()
+        assert s.stride(2) == 1 and d.stride(2) == 1 and s.stride(1) == H and d.stride(1) == H
+    assert 1 <= P <= k_src.shape[1] and P <= k_dst.shape[1], (P, k_src.shape, k_dst.shape)
+    assert frame_of.dtype == torch.int32 and frame_of.is_cuda and frame_of.is_contiguous() and frame_of.numel() == B
+    rc = lib.haff_kv_prefix_broadcast(k_src.data_ptr(), v_src.data_ptr(), k_src.stride(0), k_dst.data_ptr(), v_dst.data_ptr(),
+                                      k_dst.stride(0), frame_of.data_ptr(), B, F, int(P), H, _dt(k_src), _stream())
+    check(rc, "haff_kv_prefix_broadcast")
+
+
 def attention_decode_rows(q, k, v, scale, nk_rows, out=None):
     """One query per (batch, head) against ragged KV caches: q [B,H,1,d] view, k/v [B,H,Nk,d] views of the whole cache,
     nk_rows int32 [B] on the device (keys visible per batch entry). Returns [B,1,H*d]."""

@@ -10,6 +10,10 @@ A robot-side process drops img.png, prompt.txt (first line: the action) and marg
 img.png, prompt.txt and margins.txt (never the masks). The heat map and the padded, ANDed mask are computed on the device
 (postprocess.robot_planes: haff_robot_heatmap, haff_robot_mask); only the finished uint8 planes leave it.
 
+--multi_prompt (off by default: the first line of prompt.txt, as above): every non-empty line of prompt.txt is an action on the one
+frame. They go through one evaluate(offset=[0, n]) call; line 0 writes the file names above, line i >= 1 the same set with _<i> in front
+of the extension (aff_left_1.png, aff_left_heat_1.png, cropped_img_1.png, ...).
+
 Offline extras as in inference.py: --synthetic, --sam-checkpoint, --max-new-tokens. Stated deviation: the two waits sleep
 --poll-interval seconds between polls instead of busy-looping. Images are read and written with PIL (cv2 is not a dependency).
 """
@@ -29,6 +33,11 @@ if __package__ in (None, ""):
 else:
     from . import postprocess, prompt as hprompt
     from .inference import build_model_and_tokenizer, load_rgb, prepare_frame
+
+
+# Every non-empty line of prompt.txt is an action on the one frame: ONE evaluate(offset=[0, n]) call, so the frame is encoded and the
+# prompt's common head prefilled once. Line 0 writes today's file names, line i >= 1 the same set with _<i> in front of the extension.
+MULTI_PROMPT_FLAG = "--multi_prompt"
 
 
 def parse_args(args):
@@ -79,9 +88,10 @@ def read_margins(path):
     return int(m[0]), int(m[1]), int(m[2]), int(m[3])
 
 
-def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, device):
+def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, device, suffix=""):
     """robot_demo.py:266-327 for a request whose taxonomy is not empty: the hands the --force_* flags select, every non-empty
-    entry of pred_masks_<hand> in order (a later one overwrites the files of an earlier one, as there)."""
+    entry of pred_masks_<hand> in order (a later one overwrites the files of an earlier one, as there). suffix ("_<i>", --multi_prompt:
+    prompt line i >= 1) goes in front of the file names' extension."""
     from PIL import Image
     hands = []
     for side, masks, forced in (("left", masks_left, args.force_left), ("right", masks_right, args.force_right)):
@@ -99,8 +109,8 @@ def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, d
     heat, planes = postprocess.robot_planes(torch.stack([x for _, x in hands]), args.th, margins, and_masks)
     heat, planes = heat.cpu().numpy(), planes.cpu().numpy()
     for k, (side, _) in enumerate(hands):
-        Image.fromarray(heat[k]).save(os.path.join(args.vis_save_path, f"aff_{side}_heat.png"))
-        mask_save_path = os.path.join(args.vis_save_path, f"aff_{side}.png")
+        Image.fromarray(heat[k]).save(os.path.join(args.vis_save_path, f"aff_{side}_heat{suffix}.png"))
+        mask_save_path = os.path.join(args.vis_save_path, f"aff_{side}{suffix}.png")
         os.makedirs(os.path.dirname(mask_save_path), exist_ok=True)
         Image.fromarray(planes[k]).save(mask_save_path)
         print(f"{mask_save_path} has been saved.")
@@ -108,12 +118,18 @@ def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, d
 
 def main(argv, max_requests=None):
     """max_requests: return after that many passes that found img.png, prompt.txt and margins.txt (a test hook, like
-    chat.main(max_turns=)); None polls forever, as the reference does."""
+    chat.main(max_turns=)); None polls forever, as the reference does.
+    --multi_prompt is an option of this loop, not one of parse_args' flags (those stay the reference's plus the four offline extras):
+    it is taken out of argv here."""
     from PIL import Image
-    args = parse_args(argv)
+    multi_prompt = MULTI_PROMPT_FLAG in argv
+    args = parse_args([a for a in argv if a != MULTI_PROMPT_FLAG])
     os.makedirs(args.vis_save_path, exist_ok=True)
     model, tokenizer, cfg, dtype = build_model_and_tokenizer(args)
     device = model.device
+    if multi_prompt:
+        # an action's files must not depend on which other actions share its call: one mask-decoder pass per action (lisa.py)
+        model.tail_per_row = True
     print("Ready")
     requests = 0
     while max_requests is None or requests < max_requests:
@@ -134,20 +150,38 @@ def main(argv, max_requests=None):
             time.sleep(args.poll_interval)
             continue
         with open(prompt_path, "r") as f:
-            narration = f.readline()
+            narrations = [line for line in f.readlines() if line.strip()] if multi_prompt else [f.readline()]
         margins = read_margins(margins_path)
-        prompt = hprompt.build_inference_prompt(narration, args.use_mm_start_end)
         image_np = load_rgb(image_path)
         frames, resize_list, original_size_list = prepare_frame(image_np, cfg, dtype, device)
-        input_ids = hprompt.tokenizer_image_token(prompt, tokenizer, return_tensors="pt").unsqueeze(0).to(device)
-        output_ids, masks_left, masks_right, taxonomies = model.evaluate(
-            None, None, input_ids, resize_list, original_size_list, max_new_tokens=args.max_new_tokens,
-            tokenizer=tokenizer, frames_u8=frames)
-        if taxonomies[0].numel() != 0:   # the taxonomy does not gate here (robot_demo.py:268,298 are commented out)
-            write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, device)
+        rows = [hprompt.tokenizer_image_token(hprompt.build_inference_prompt(n, args.use_mm_start_end), tokenizer, return_tensors="pt")
+                for n in narrations]
+        if len(rows) <= 1:
+            input_ids = rows[0].unsqueeze(0).to(device) if rows else None
+            grouped = {}
         else:
-            print("No taxonomy found!!")
-        Image.fromarray(image_np).save(os.path.join(args.vis_save_path, "cropped_img.png"))
+            # several actions on the one frame: right-padded rows, one call; the frame is encoded once (evaluate(offset=))
+            input_ids = torch.full((len(rows), max(r.numel() for r in rows)), cfg.pad_token_id, dtype=torch.long)
+            attention_mask = torch.zeros(input_ids.shape, dtype=torch.bool)
+            for i, r in enumerate(rows):
+                input_ids[i, :r.numel()] = r
+                attention_mask[i, :r.numel()] = True
+            input_ids = input_ids.to(device)
+            grouped = {"attention_mask": attention_mask.to(device), "offset": torch.tensor([0, len(rows)], dtype=torch.int64)}
+        if input_ids is None:
+            print("No action found in prompt.txt")
+            masks_left, masks_right, taxonomies = [], [], []
+        else:
+            output_ids, masks_left, masks_right, taxonomies = model.evaluate(
+                None, None, input_ids, resize_list, original_size_list, max_new_tokens=args.max_new_tokens,
+                tokenizer=tokenizer, frames_u8=frames, **grouped)
+        for i, taxonomy in enumerate(taxonomies):
+            suffix = f"_{i}" if i else ""
+            if taxonomy.numel() != 0:   # the taxonomy does not gate here (robot_demo.py:268,298 are commented out)
+                write_hands(args, masks_left[i:i + 1], masks_right[i:i + 1], mask_left, mask_right, margins, device, suffix)
+            else:
+                print("No taxonomy found!!")
+            Image.fromarray(image_np).save(os.path.join(args.vis_save_path, f"cropped_img{suffix}.png"))
         os.remove(image_path)
         os.remove(prompt_path)
         os.remove(margins_path)

@@ -472,6 +472,14 @@ int haff_embed_splice(const long* ids, const int* img_pos, const void* embed, co
  * (caches [B][Tmax][Hkv*d]); cos_sin f32 [Tmax][d] = cos(d/2) | sin(d/2). d % 16 == 0. */
 int haff_rope_cache(void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, int B, int Tq, int Hq, int Hkv,
                     int d, int pos0, int Tmax, int dtype, void* stream);
+/* Shared-prefix K/V broadcast (LisaMI355.evaluate(offset=): several prompt rows on one frame): positions 0 .. P-1 of k_src / v_src
+ * [F][tmax_src][H], row frame_of[b], are copied into row b of k_dst / v_dst [B][tmax_dst][H]; both tensors in one launch, nothing
+ * is written at positions >= P. Row strides in ELEMENTS (>= P*H, a whole number of 16-byte units); unit stride on H and H elements
+ * between positions in both caches; H * elem % 16 == 0; the four pointers 16-byte aligned; P >= 1 (P <= tmax of both caches is the
+ * caller's contract); dtype 0 bf16 / 1 f32 / 3 f16. frame_of: DEVICE int32 [B], validated by the caller against F; an entry outside
+ * [0, F) is never dereferenced (that row is left as it was). 16-byte loads and stores only; bound: the 2*B*P*H*elem bytes written. */
+int haff_kv_prefix_broadcast(const void* k_src, const void* v_src, long src_row_stride, void* k_dst, void* v_dst,
+                             long dst_row_stride, const int* frame_of, int B, int F, int P, int H, int dtype, void* stream);
 /* same with a per-row start position: row b's Tq new positions begin at pos0_rows[b] (DEVICE int32 [B];
  * pos0_rows[b] + Tq <= Tmax is the caller's contract) — greedy decode of right-padded prompts of different lengths */
 int haff_rope_cache_rows(void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, int B, int Tq, int Hq,
