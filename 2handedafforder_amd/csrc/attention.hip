@@ -1089,7 +1089,7 @@ __device__ __forceinline__ void rope8(float (&x)[8], const float* cs_row, int c)
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float other = __shfl_xor(x[j], 8, 64);
-    float r = c < 8 ? x[j] * cv[j] - other * sv[j] : x[j] * cv[j] + other * sv[j];
+    float r = haff_sum_of_products(x[j], cv[j], c < 8 ? -other : other, sv[j]);
     // f16: r is rounded to f32 first, as the stand-alone rope kernel stores it (without the barrier the last fma and the f16
     // conversion fuse into v_fma_mixlo_f16: ONE rounding, a last-bit difference from rope_cache_rows on q)
     if constexpr (F16) asm volatile("" : "+v"(r));
@@ -1160,11 +1160,15 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_kernel(AttnArgs p) {
     for (int u = 0; u < DEC_UNROLL; ++u) {
       const int key = (it0 + u) * 4 + g;
       const unsigned kw[4] = {kr[u].x, kr[u].y, kr[u].z, kr[u].w};
+      // explicit fmas: under -ffp-contract=fast hipcc fused some of these eight terms and packed the others into v_pk_mul_f32 +
+      // v_add_f32, differently in each of the four unrolled copies, so a key's score depended on the slot u it fell into: two
+      // keys with the same K row came out an fp32 ulp of the score apart (p = 1 and 1 - 8e-5 for a tie;
+      // tests/test_attn_edge_kernels_gpu.py::test_decode_rows, the pair cases)
       float s = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        s += qv[2 * j] * E::lo(kw[j]);
-        s += qv[2 * j + 1] * E::hi(kw[j]);
+        s = __builtin_fmaf(qv[2 * j], E::lo(kw[j]), s);
+        s = __builtin_fmaf(qv[2 * j + 1], E::hi(kw[j]), s);
       }
       s = row16_sum(s);
       s = key < Nk ? s : -INFINITY;

@@ -375,7 +375,7 @@ __device__ __forceinline__ void ch_rope8(float (&x)[8], const float* cs_row, int
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float other = __shfl_xor(x[j], 8, 64);
-    const float r = c < 8 ? x[j] * cv[j] - other * sv[j] : x[j] * cv[j] + other * sv[j];
+    const float r = haff_sum_of_products(x[j], cv[j], c < 8 ? -other : other, sv[j]);
     x[j] = bf16_to_f32(f32_to_bf16(r));
   }
 }

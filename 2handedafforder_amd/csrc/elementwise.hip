@@ -117,8 +117,8 @@ __global__ void rope_cache_kernel(T* qkv, long ld, T* kcache, T* vcache, const f
       load8(cs + (long)pos * d + half + ch * 8, s);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        o1[j] = x1[j] * c[j] - x2[j] * s[j];
-        o2[j] = x2[j] * c[j] + x1[j] * s[j];
+        o1[j] = haff_sum_of_products(x1[j], c[j], -x2[j], s[j]);
+        o2[j] = haff_sum_of_products(x2[j], c[j], x1[j], s[j]);
       }
       store8(base, o1);
       store8(base + half, o2);

@@ -25,6 +25,18 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define HAFF_ACT_RELU 3        // SAM decoder MLPs
 #define HAFF_ACT_SILU 4
 
+// a * b + c * d with an error of about two fp32 ulps of the RESULT (Kahan's algorithm; the rotate-half RoPE of the cache kernels):
+// the plain form rounds both products at the size of the operands, and where they cancel below 2^-12 of them that error exceeds
+// an f16 ulp of the result (1.51 storage ulps from the float64 rotation:
+// tests/test_attn_edge_kernels_gpu.py::test_decode_rope_appended_k_row). Here the rounding error e of c * d is exact (one fma)
+// and is added back after the fma that sums the two products: two roundings, the fma's and the last add's, both at the size of
+// the result.
+__device__ __forceinline__ float haff_sum_of_products(float a, float b, float c, float d) {
+  const float p = c * d;
+  const float e = __builtin_fmaf(c, d, -p);
+  return __builtin_fmaf(a, b, p) + e;
+}
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) {
   return __uint_as_float(((unsigned)v) << 16);
 }
