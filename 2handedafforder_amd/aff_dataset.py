@@ -96,11 +96,90 @@ def flip_taxonomy(v):
     return [v[1], v[0]] + list(v[2:])
 
 
+CROP_MARGIN = 50                         # process_cropped_sequences.py: the object box is grown by 50 px on every side
+CROP_ALWAYS = ("something", "things")    # a narration with one of these names no object: the reference always crops it
+
+
+def draw_crop(seed, idx, p_crop, narration=""):
+    """Whether sample `idx` is replaced by its object-centred view (process_cropped_sequences.py). A pure function with a generator
+    of its own, apart from draw_augmentation's, so setting it leaves the flip and jitter draws of every index as they were.
+    One uniform draw; a narration that says "something" or "things" is cropped whatever the draw."""
+    if p_crop <= 0.0:
+        return False
+    u = random.Random(f"haff-crop/{seed}/{idx}").random()
+    return u < p_crop or any(w in narration for w in CROP_ALWAYS)
+
+
+def crop_box(obj_left, obj_right, hw, flip=False):
+    """The crop of process_cropped_sequences.py for planes of hw = (H, W): the inclusive extremes of fill(obj_left) | fill(obj_right),
+    grown by CROP_MARGIN and clamped (x1 / y1 exclusive although max_x / max_y are inclusive, as in the script), then centred on a
+    square of side S = max(cw, ch). flip: the box of the MIRRORED planes (the mirror of a crop is not the crop of the mirror).
+    Vertex extremes when every vertex lies inside the plane (a filled polygon touches its extreme vertices), else the extremes of
+    the filled union. None when there is no object pixel."""
+    H, W = int(hw[0]), int(hw[1])
+    polys = [np.asarray(c, dtype=np.int32).reshape(-1, 2) for c in list(obj_left or []) + list(obj_right or [])]
+    polys = [p for p in polys if len(p)]
+    if not polys:
+        return None
+    pts = np.concatenate(polys, 0)
+    lo, hi = pts.min(0), pts.max(0)
+    if lo[0] >= 0 and lo[1] >= 0 and hi[0] < W and hi[1] < H:
+        min_x, min_y, max_x, max_y = int(lo[0]), int(lo[1]), int(hi[0]), int(hi[1])
+    else:
+        ys, xs = np.nonzero(cvlite.draw_contours_filled((H, W), polys, 1))
+        if len(ys) == 0:
+            return None
+        min_x, min_y, max_x, max_y = int(xs.min()), int(ys.min()), int(xs.max()), int(ys.max())
+    if flip:
+        min_x, max_x = W - 1 - max_x, W - 1 - min_x
+    x0, y0 = max(min_x - CROP_MARGIN, 0), max(min_y - CROP_MARGIN, 0)
+    x1, y1 = min(max_x + CROP_MARGIN, W), min(max_y + CROP_MARGIN, H)
+    cw, ch = x1 - x0, y1 - y0
+    S = max(cw, ch)
+    return {"x0": x0, "y0": y0, "cw": cw, "ch": ch, "px": (S - cw) // 2, "py": (S - ch) // 2, "S": S}
+
+
+def crop_image(image, box):
+    """crop_and_pad of process_cropped_sequences.py with Pillow itself (the yardstick of csrc/frame_crop.hip) on a uint8 HWC frame
+    or a uint8 HW plane: the box cut out, pasted centred on a black square and stretched back to the image's size (bicubic)."""
+    from PIL import Image
+    im = Image.fromarray(image, "RGB" if image.ndim == 3 else "L")
+    square = Image.new(im.mode, (box["S"], box["S"]))
+    square.paste(im.crop((box["x0"], box["y0"], box["x0"] + box["cw"], box["y0"] + box["ch"])), (box["px"], box["py"]))
+    return np.array(square.resize(im.size, Image.BICUBIC))
+
+
+def crop_plane(plane, box):
+    """A 0/1 filled plane through crop_image as a 0/255 `L` plane; the new mask is every non-zero pixel of the result."""
+    return (crop_image((plane != 0).astype(np.uint8) * 255, box) != 0).astype(np.uint8)
+
+
+def resize_frame(image, hw):
+    """The frame at the planes' size (process_cropped_sequences.py resizes it before it crops): Pillow's bicubic."""
+    from PIL import Image
+    return np.array(Image.fromarray(image, "RGB").resize((int(hw[1]), int(hw[0])), Image.BICUBIC))
+
+
+def host_crop_sample(image, left, right, taxonomy, aug, box):
+    """flip -> crop of one sample on the host: the frame (brought to the planes' size first), both filled planes and the taxonomy.
+    `box` is crop_box(..., flip=aug's flip). The jitter is left to the caller: it follows the crop."""
+    if aug is not None and aug["flip"]:
+        image = augment_frame(image, {"flip": True, "jitter": None})
+        left, right = np.ascontiguousarray(right[:, ::-1]), np.ascontiguousarray(left[:, ::-1])
+        taxonomy = flip_taxonomy(taxonomy)
+    if image.shape[:2] != left.shape:
+        image = resize_frame(image, left.shape)
+    return crop_image(image, box), crop_plane(left, box), crop_plane(right, box), taxonomy
+
+
 class AffRecordsDataset(torch.utils.data.Dataset):
     """AffDataset over in-memory records (what `load_dataset(name, split="train")` yields). aug_flip / aug_jitter: the probabilities
-    of the training augmentation (draw_augmentation; both 0: none, and nothing about the samples changes)."""
+    of the training augmentation (draw_augmentation; both 0: none, and nothing about the samples changes). aug_crop: the probability
+    of the object-centred view (draw_crop; 0: no draw, no new key anywhere); the records then carry masks["obj_left" / "obj_right"].
+    `crop_skipped` counts the samples that drew a crop and had no object to centre on."""
 
-    def __init__(self, records, cfg, samples_per_epoch=500 * 8 * 2 * 10, inference=False, seed=None, aug_flip=0.0, aug_jitter=0.0):
+    def __init__(self, records, cfg, samples_per_epoch=500 * 8 * 2 * 10, inference=False, seed=None, aug_flip=0.0, aug_jitter=0.0,
+                 aug_crop=0.0):
         self.records = list(records)
         if not self.records:
             raise ValueError("no records")
@@ -113,10 +192,11 @@ class AffRecordsDataset(torch.utils.data.Dataset):
                 self.original_size = tuple(int(x) for x in m["original_size"])
                 break
         self.rng = random.Random(seed)
-        self._set_augmentation(seed, aug_flip, aug_jitter)
+        self._set_augmentation(seed, aug_flip, aug_jitter, aug_crop)
 
-    def _set_augmentation(self, seed, aug_flip, aug_jitter):
+    def _set_augmentation(self, seed, aug_flip, aug_jitter, aug_crop=0.0):
         self.aug_flip, self.aug_jitter = check_probability("aug_flip", aug_flip), check_probability("aug_jitter", aug_jitter)
+        self.aug_crop, self.crop_skipped = check_probability("aug_crop", aug_crop), 0
         # an unseeded dataset draws its samples from the OS; so does its augmentation
         self.aug_seed = seed if seed is not None else random.SystemRandom().getrandbits(63)
 
@@ -125,6 +205,15 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         if self.aug_flip == 0.0 and self.aug_jitter == 0.0:
             return None
         return draw_augmentation(self.aug_seed, idx, self.aug_flip, self.aug_jitter)
+
+    def _draw_crop_box(self, idx, text, masks, shape, aug):
+        """None, or crop_box of a sample that drew the crop (no draw at all with aug_crop == 0). `aug` decides the mirror."""
+        if self.aug_crop == 0.0 or not draw_crop(self.aug_seed, idx, self.aug_crop, text):
+            return None
+        box = crop_box(masks.get("obj_left"), masks.get("obj_right"), shape, flip=bool(aug and aug["flip"]))
+        if box is None:
+            self.crop_skipped += 1
+        return box
 
     @classmethod
     def from_hf(cls, name, cfg, **kw):
@@ -177,6 +266,8 @@ class AffRecordsDataset(torch.utils.data.Dataset):
             if hasattr(h, "close"):
                 h.close()
         masks_left, masks_right, original_size = [], [], None
+        keep_objects = float(kw.get("aug_crop", 0.0)) > 0.0     # the object contours beside the affordance ones, only for the crop
+        objs_left, objs_right = [], []
         for name in sorted(os.listdir(json_dir), key=first_number):
             with open(os.path.join(json_dir, name)) as fh:
                 data = json.load(fh)
@@ -185,6 +276,9 @@ class AffRecordsDataset(torch.utils.data.Dataset):
             for key in data:
                 masks_left.append(data[key].get("aff_left", []))
                 masks_right.append(data[key].get("aff_right", []))
+                if keep_objects:
+                    objs_left.append(data[key].get("obj_left", []))
+                    objs_right.append(data[key].get("obj_right", []))
         if len(masks_left) < size:
             raise ValueError(f"{size} samples in h5/ but contours for only {len(masks_left)} in jsons/")
 
@@ -202,6 +296,8 @@ class AffRecordsDataset(torch.utils.data.Dataset):
                         rec = {"narration": d["narration"][i - lo], "inpainted": np.asarray(d["inpainted"][i - lo]),
                                "taxonomy": d["taxonomy"][i - lo],
                                "masks": {"original_size": original_size, "aff_left": masks_left[i], "aff_right": masks_right[i]}}
+                        if keep_objects:
+                            rec["masks"]["obj_left"], rec["masks"]["obj_right"] = objs_left[i], objs_right[i]
                         if hasattr(h, "close"):
                             h.close()
                         return rec
@@ -213,7 +309,7 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         ds.records = _LocalRecords()
         ds.cfg, ds.samples_per_epoch, ds.inference = cfg, kw.get("samples_per_epoch", 500 * 8 * 2 * 10), kw.get("inference", False)
         ds.size, ds.original_size, ds.rng = size, tuple(original_size), random.Random(kw.get("seed"))
-        ds._set_augmentation(kw.get("seed"), kw.get("aug_flip", 0.0), kw.get("aug_jitter", 0.0))
+        ds._set_augmentation(kw.get("seed"), kw.get("aug_flip", 0.0), kw.get("aug_jitter", 0.0), kw.get("aug_crop", 0.0))
         return ds
 
     def __len__(self):
@@ -234,7 +330,12 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         left = recreate_mask_from_contours(m.get("aff_left", []), shape)
         right = recreate_mask_from_contours(m.get("aff_right", []), shape)
         aug = self._draw_aug(idx)
-        if aug is not None:                 # before any resize; the masks are mirrored rasters, never fills of mirrored vertices
+        box = self._draw_crop_box(idx, text, m, shape, aug)
+        if box is not None:                 # flip -> crop -> jitter: the jitter's frame mean is the cropped frame's
+            image, left, right, taxonomy = host_crop_sample(image, left, right, taxonomy, aug, box)
+            if aug is not None and aug["jitter"] is not None:
+                image = augment_frame(image, {"flip": False, "jitter": aug["jitter"]})
+        elif aug is not None:               # before any resize; the masks are mirrored rasters, never fills of mirrored vertices
             image = augment_frame(image, aug)
             if aug["flip"]:
                 left, right = np.ascontiguousarray(right[:, ::-1]), np.ascontiguousarray(left[:, ::-1])
@@ -259,7 +360,8 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         """What train_ingest.DeviceIngest builds the sample from on the device: no resize, no normalised tensor, no filled mask, no
         label planes. Draws from self.rng in __getitem__'s order (record, then question, then answer), so a seeded run sees the
         same samples and prompts either way. With an augmentation probability set the dict also carries "aug" (draw_augmentation
-        for this idx): what __getitem__ applies with Pillow, DeviceIngest applies on the device."""
+        for this idx): what __getitem__ applies with Pillow, DeviceIngest applies on the device. With aug_crop set it carries "crop" too
+        (crop_box of a sample that drew the crop, else None), and "crop_skipped" when the draw found no object."""
         item = self.records[self.rng.randint(0, self.size - 1)]
         text = item.get("narration", item.get("text", ""))
         if isinstance(text, bytes):
@@ -283,13 +385,18 @@ class AffRecordsDataset(torch.utils.data.Dataset):
         aug = self._draw_aug(idx)
         if aug is not None:                 # applied by DeviceIngest; frame, contours and taxonomy are the record's own here
             raw["aug"] = aug
+        if self.aug_crop > 0.0:             # the box of the (mirrored) object planes, or None: not drawn, or nothing to centre on
+            skipped = self.crop_skipped
+            raw["crop"] = self._draw_crop_box(idx, text, m, shape, aug)
+            if self.crop_skipped != skipped:
+                raw["crop_skipped"] = True
         return raw
 
 
 class AffValDataset(torch.utils.data.Dataset):
     """AffDatasetVal (aff_dataset.py:350-544): the ActAffordance-style benchmark folders as validation samples."""
 
-    def __init__(self, base_image_dir, cfg, seed=None, aug_flip=0.0, aug_jitter=0.0):
+    def __init__(self, base_image_dir, cfg, seed=None, aug_flip=0.0, aug_jitter=0.0, aug_crop=0.0):
         # the validation set is never augmented: the training set's keywords are accepted and ignored
         self.cfg = cfg
         self.images, self.affs_left, self.affs_right, self.narrations, self.taxonomies = self.load_data_from_nested_folders(base_image_dir)

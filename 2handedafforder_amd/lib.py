@@ -192,6 +192,7 @@ _PROTOS = {
     "haff_jitter_stats_u8": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "haff_augment_u8": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "haff_flip_planes_u8": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "haff_crop_resample_u8": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p],
     "haff_threshold_masks": [c_void_p, c_void_p, c_long, c_float, c_void_p],
     "haff_gate_threshold_masks": [c_void_p, c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p],
     "haff_robot_heatmap": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p],

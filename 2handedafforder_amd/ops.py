@@ -1217,7 +1217,91 @@ def augment_frames(frames, augs):
     return augment_u8(frames, flags, factors, sums)
 
 
-SCORE_FRAME_WORDS = 16                     # haff_score_frame (include/haff_hip.h): 128 bytes as 16 int64 words
+AUG_CROP = 4                           # the crop bit of csrc/frame_crop.hip (beside AUG_FLIP, which it shares)
+CROP_MAX_SCALE = 4                     # per-axis down-scale S / out haff_crop_resample_u8 takes: at most 17 bicubic taps
+_CROP_GEOM = 12                        # descriptor words per sample (include/haff_hip.h)
+_crop_tables = {}                      # (S, out) -> int32 [out, 2 + ksize] rows (first, count, coefficients); filled by the prefetch thread
+
+
+def crop_supported(hw, S):
+    """Whether haff_crop_resample_u8 takes a sample of this (H, W) whose crop square has side S; beyond that the caller crops on
+    the host."""
+    H, W = int(hw[0]), int(hw[1])
+    return H * W <= AUG_MAX_PIXELS and S <= CROP_MAX_SCALE * H and S <= CROP_MAX_SCALE * W
+
+
+def crop_table(S, out):
+    """One axis of Image.resize(BICUBIC) from S to `out` pixels as the crop kernel reads it: int32 [out, 2 + ksize] rows of
+    (first input index, tap count, Pillow's 22-bit coefficients). Built on the host (Pillow normalises in double) and cached per
+    (S, out); DeviceIngest's prefetch thread calls this ahead of the step."""
+    import numpy as np
+    from .preprocess import pil_bicubic_tables_fast
+    key = (int(S), int(out))
+    tab = _crop_tables.get(key)
+    if tab is None:
+        bounds, coeffs = pil_bicubic_tables_fast(*key)
+        tab = np.ascontiguousarray(np.concatenate([bounds, coeffs], 1), dtype=np.int32)
+        if len(_crop_tables) >= 512:       # every S a run meets, times two axes: bounded, oldest first
+            _crop_tables.pop(next(iter(_crop_tables)))
+        _crop_tables[key] = tab
+    return tab
+
+
+def crop_descriptor(boxes, flips, hw):
+    """The pinned int32 descriptor of haff_crop_resample_u8 for samples of one (H, W): boxes[b] is aff_dataset.crop_box's dict or None
+    (the sample is copied), flips[b] its mirror. Samples with one S share their tables."""
+    import numpy as np
+    H, W = int(hw[0]), int(hw[1])
+    B = len(boxes)
+    tabs, where, words = [], {}, B * _CROP_GEOM
+    for box in boxes:
+        if box is not None:
+            for n_out in (W, H):
+                key = (box["S"], n_out)
+                if key not in where:
+                    tab = crop_table(*key)
+                    where[key] = (words, tab.shape[1] - 2)
+                    tabs.append((words, tab))
+                    words += tab.size
+    desc = torch.zeros((words,), dtype=torch.int32, pin_memory=torch.cuda.is_available())
+    d = desc.numpy()
+    for b, (box, flip) in enumerate(zip(boxes, flips)):
+        g = d[b * _CROP_GEOM:(b + 1) * _CROP_GEOM]
+        g[7] = AUG_FLIP if flip else 0
+        if box is not None:
+            g[:7] = [box[k] for k in ("x0", "y0", "cw", "ch", "px", "py", "S")]
+            g[7] |= AUG_CROP
+            g[8:10], g[10:12] = where[(box["S"], W)], where[(box["S"], H)]
+    for off, tab in tabs:
+        d[off:off + tab.size] = tab.reshape(-1)
+    return desc
+
+
+def crop_resample(x, boxes, flips, out=None, desc=None):
+    """haff_crop_resample_u8: uint8 [B,H,W,C] in HBM (C = 3 frames; C = 1 mask planes, non-zero in, 0 / 1 out) with sample b mirrored
+    where flips[b] and then replaced by the object-centred view of boxes[b] (aff_dataset.crop_box of the MIRRORED sample; None: no
+    crop), as aff_dataset.crop_image does it with Pillow. One launch; a new tensor. desc: crop_descriptor(boxes, flips, (H, W)) when
+    the caller built it ahead. A geometry beyond crop_supported is refused (-2) before anything is enqueued."""
+    lib = load_library()
+    _req(x, "x")
+    assert x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] in (1, 3) and x.is_contiguous(), tuple(x.shape)
+    B, H, W, C = x.shape
+    assert len(boxes) == B and len(flips) == B
+    if desc is None:
+        desc = crop_descriptor(boxes, flips, (H, W))
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.device.type == "cpu" and desc.numel() >= B * _CROP_GEOM
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == x.shape and out.device == x.device
+    with torch.cuda.device(x.device):
+        desc_dev = desc.to(x.device, non_blocking=True)
+        rc = lib.haff_crop_resample_u8(x.data_ptr(), out.data_ptr(), B, H, W, C, desc.data_ptr(), desc_dev.data_ptr(), desc.numel(),
+                                       _stream())
+    check(rc, "haff_crop_resample_u8")
+    return out
+
+
+SCORE_FRAME_WORDS = 16                  # haff_score_frame (include/haff_hip.h): 128 bytes as 16 int64 words
 SCORE_MAX_SIDE, SCORE_MAX_THRESHOLDS = 4096, 8
 
 

@@ -19,6 +19,10 @@ ids that one prefetch thread prepares (train_ingest.py) instead of on the main t
 (horizontal_flip.py, apply_jitter.py) drawn per sample from (--seed, sample index): Pillow on the host loader, HIP kernels with
 --device_ingest (csrc/frame_augment.hip), the same augmented samples either way.
 
+--aug_crop P (0 by default; same conditions): the third one, process_cropped_sequences.py's object-centred view, applied between
+the flip and the jitter (csrc/frame_crop.hip with --device_ingest). --aug_flip 0.5 --aug_crop 0.6667 --aug_jitter 0.25 is the
+reference's distribution from un-augmented records.
+
   python -m torch.distributed.run --nproc-per-node 8 2handedafforder_amd/train_ds.py --synthetic 7b --epochs 1 ...
 """
 import argparse
@@ -109,6 +113,12 @@ def parse_args(args):
                    help="probability of Pillow's Brightness -> Contrast -> Color jitter with factors from U(0.4, 1.6) on a training "
                         "frame (2HANDS' apply_jitter.py; its data corresponds to 0.25). With --device_ingest both run in HIP, "
                         "byte for byte what the host loader's Pillow gives for one --seed. Training set only; not with --synthetic")
+    p.add_argument("--aug_crop", default=0.0, type=float,
+                   help="probability of replacing a training sample by its object-centred view: the box of the object masks grown by "
+                        "50 px, pasted centred on a black square and stretched back to the original size (2HANDS' "
+                        "process_cropped_sequences.py; its data corresponds to 0.6667). A narration that says 'something' or 'things' "
+                        "is always cropped. Applied after the flip and before the jitter; the records need obj_left / obj_right "
+                        "contours. Training set only; not with --synthetic")
     return p.parse_args(args)
 
 
@@ -354,7 +364,7 @@ def _main(argv, closers):
     if args.device_ingest and args.synthetic:
         raise SystemExit("--device_ingest cannot be combined with --synthetic: the synthetic dataset yields tensors, not uint8 frames "
                          "and contours (use --sam_records or --dataset_dir)")
-    for flag in ("aug_flip", "aug_jitter"):
+    for flag in ("aug_flip", "aug_jitter", "aug_crop"):
         value = getattr(args, flag)
         if not 0.0 <= value <= 1.0:
             raise SystemExit(f"--{flag} is a probability in [0, 1], not {value}")
@@ -441,6 +451,8 @@ def _main(argv, closers):
     else:
         # AffRecordsDataset = utils/aff_dataset.py:48-346 on the records' HF layout
         aug = {"aug_flip": args.aug_flip, "aug_jitter": args.aug_jitter}   # the training set only: validation is never augmented
+        if args.aug_crop > 0.0:
+            aug["aug_crop"] = args.aug_crop
         if args.sam_records:
             records = torch.load(args.sam_records, weights_only=False)
             train_ds = AffRecordsDataset(records, cfg, seed=args.seed + 1000 * rank, **aug)
@@ -456,8 +468,9 @@ def _main(argv, closers):
         val_ds = AffValDataset(args.benchmark_dir, cfg, seed=777)
         if rank == 0:
             print(f"Training with {len(train_ds)} examples and validating with {len(val_ds)} examples.")
-    if rank == 0 and (args.aug_flip > 0.0 or args.aug_jitter > 0.0):
-        print(f"training augmentation: flip p={args.aug_flip:g}, colour jitter p={args.aug_jitter:g} "
+    if rank == 0 and (args.aug_flip > 0.0 or args.aug_jitter > 0.0 or args.aug_crop > 0.0):
+        crop = f", object crop p={args.aug_crop:g}" if args.aug_crop > 0.0 else ""
+        print(f"training augmentation: flip p={args.aug_flip:g}{crop}, colour jitter p={args.aug_jitter:g} "
               f"({'HIP kernels on the device' if args.device_ingest else 'Pillow on the host'})")
     total_steps = args.epochs * args.steps_per_epoch
     ingest = DeviceIngest(cfg, device, dtype) if args.device_ingest else None
@@ -566,6 +579,12 @@ def _main(argv, closers):
                 print(f"saved checkpoint to {ckpt_dir} (global_step{global_step})")
     if ingest is not None and ingest.host_augments:
         print(f"[rank {rank}] {ingest.host_augments} frames beyond {ops.AUG_MAX_PIXELS} pixels were augmented on the host (Pillow)")
+    if args.aug_crop > 0.0:
+        host_crops = ingest.host_crops if ingest is not None else 0
+        skipped = ingest.crop_skipped if ingest is not None else getattr(train_ds, "crop_skipped", 0)
+        if host_crops or skipped:
+            print(f"[rank {rank}] object crop: {host_crops} samples cropped on the host (Pillow) under --device_ingest, "
+                  f"{skipped} drew the crop and had no object contour")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -8,6 +8,7 @@ of the reference). Here the loader hands over only the uint8 frame, the contour 
   SAM input         LisaTrainable.forward(frames_u8=)  (FrameIngest.sam_frames + haff_patchify_u8, as evaluate(frames_u8=))
   ground-truth masks ops.fill_contours                  (csrc/contour_fill.hip, cvlite-exact)
   augmentation      ops.augment_frames / flip_planes   (csrc/frame_augment.hip, Pillow-exact; only for samples that carry "aug")
+  object crop       ops.crop_resample                  (csrc/frame_crop.hip, Pillow-exact; only for samples that carry a "crop" box)
 
 are made from them in HBM. The text half is train_ds.collate_text, the code collate_fn itself runs. `Prefetcher` is the one
 background thread that calls `raw_item` (decode, HDF5 read, prompt) and the tokeniser ahead of the step loop; the main thread
@@ -21,7 +22,7 @@ import torch
 
 from . import cvlite
 from . import ops
-from .aff_dataset import augment_frame, flip_taxonomy
+from .aff_dataset import augment_frame, flip_taxonomy, host_crop_sample
 from .preprocess import FrameIngest, get_preprocess_shape
 
 
@@ -103,7 +104,11 @@ class DeviceIngest:
     A sample that carries "aug" (aff_dataset.draw_augmentation) is augmented here as AffRecordsDataset.__getitem__ does it on the
     host: the uploaded frame is jittered and / or mirrored before anything is derived from it, the filled planes are mirrored and
     exchanged between the hands, taxonomy entries 0 and 1 are exchanged. `host_augments` counts the frames beyond
-    ops.AUG_MAX_PIXELS, which Pillow augmented before the upload."""
+    ops.AUG_MAX_PIXELS, which Pillow augmented before the upload.
+    A sample that carries a "crop" box (aff_dataset.crop_box of a sample that drew the object crop) is mirrored and cropped in one
+    pass of ops.crop_resample, frames and filled planes alike, before the jitter: flip -> crop -> jitter as on the host. `host_crops`
+    counts the samples the host cropped before the upload (a frame of another size than its planes, which the reference resizes
+    first, or a geometry beyond ops.crop_supported); `crop_skipped` those that drew the crop and had no object to centre on."""
 
     def __init__(self, cfg, device, dtype):
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
@@ -112,10 +117,17 @@ class DeviceIngest:
         self.ingest = FrameIngest(self.device)
         self.host_fills = 0
         self.host_augments = 0
+        self.host_crops = 0
+        self.crop_skipped = 0
 
     def text(self, raw_samples, tokenizer, model_max_length=575, conv_type="llava_v1"):
-        """The text half (host only: what Prefetcher runs in its thread)."""
+        """The text half (host only: what Prefetcher runs in its thread). The crop's coefficient tables are made here too, so the
+        main thread finds them in ops.crop_table's cache."""
         from .train_ds import collate_text
+        for r in raw_samples:
+            if r.get("crop") is not None:
+                for n_out in r["mask_hw"]:
+                    ops.crop_table(r["crop"]["S"], n_out)
         convs, offs = [], [0]
         for r in raw_samples:
             convs.extend(r["conversations"])
@@ -125,9 +137,30 @@ class DeviceIngest:
     def _upload(self, array):
         return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(self.device, non_blocking=True)
 
+    def _host_crops(self, raw_samples):
+        """The samples as the device route takes them: one whose crop the kernel does not take is cropped here with Pillow (mirror
+        included; the jitter stays for the device) and goes on as a frame with finished planes, like a validation sample."""
+        out = []
+        for r in raw_samples:
+            self.crop_skipped += bool(r.get("crop_skipped"))
+            box = r.get("crop")
+            if box is not None and (r["frame"].shape[:2] != tuple(r["mask_hw"]) or not ops.crop_supported(r["mask_hw"], box["S"])):
+                aug = r.get("aug")
+                left, right = (cvlite.draw_contours_filled(tuple(r["mask_hw"]), list(r[k] or []), 1)
+                               for k in ("contours_left", "contours_right"))
+                frame, left, right, taxonomy = host_crop_sample(r["frame"], left, right, r["taxonomy"], aug, box)
+                r = {k: v for k, v in r.items() if k not in ("contours_left", "contours_right", "crop")}
+                r.update(frame=frame, plane_left=left, plane_right=right, taxonomy=taxonomy)
+                if aug is not None:
+                    r["aug"] = {"flip": False, "jitter": aug["jitter"]}
+                self.host_crops += 1
+            out.append(r)
+        return out
+
     def _frames(self, raw_samples):
         """The uploaded frames, augmented: one [B,H,W,3] tensor with per-frame flags, or one call per frame of a list."""
         frames = [r["frame"] for r in raw_samples]
+        boxes = [r.get("crop") for r in raw_samples]
         # None for a sample that drew nothing (or carries no draw: the validation sets)
         augs = [a if a and (a["flip"] or a["jitter"] is not None) else None for a in (r.get("aug") for r in raw_samples)]
         for i, a in enumerate(augs):
@@ -135,6 +168,16 @@ class DeviceIngest:
                 frames[i], augs[i] = augment_frame(frames[i], a), None       # beyond the kernels' limit: Pillow, before the upload
                 self.host_augments += 1
         frames = self._upload_frames(frames)
+        if any(boxes):                     # mirror and crop in one pass; what is left for augment_frames is the jitter
+            flips = [bool(a and a["flip"]) for a in augs]
+            if torch.is_tensor(frames):    # the samples without a box are copied (mirrored where they drew the flip)
+                frames = ops.crop_resample(frames, boxes, flips)
+                cropped = [True] * len(augs)
+            else:
+                frames = [ops.crop_resample(f[None], [b], [fl])[0] if b else f for f, b, fl in zip(frames, boxes, flips)]
+                cropped = [b is not None for b in boxes]
+            augs = [({"flip": False, "jitter": a["jitter"]} if a["jitter"] is not None else None) if a and c else a
+                    for a, c in zip(augs, cropped)]
         if not any(augs):
             return frames
         if torch.is_tensor(frames):
@@ -175,7 +218,11 @@ class DeviceIngest:
                 filled[k].copy_(self._upload(cvlite.draw_contours_filled(hw, contours)), non_blocking=True)
                 self.host_fills += 1
             flips = [bool((raw_samples[i].get("aug") or {}).get("flip")) for i in idxs]
-            if any(flips):                 # flip(fill(contours)), never a fill of mirrored vertices: the scanline fill is not symmetric
+            boxes = [raw_samples[i].get("crop") for i in idxs]
+            if any(boxes):                 # both hands' planes of the group in one launch: mirror, then the crop of the mirrored plane
+                filled = ops.crop_resample(filled[..., None], [b for b in boxes for _ in range(2)],
+                                           [f for f in flips for _ in range(2)])[..., 0]
+            elif any(flips):               # flip(fill(contours)), never a fill of mirrored vertices: the scanline fill is not symmetric
                 flags = torch.tensor([ops.AUG_FLIP * f for f in flips for _ in range(2)], dtype=torch.int32).pin_memory()
                 filled = ops.flip_planes(filled, flags.to(self.device, non_blocking=True))
             filled = filled.float()
@@ -188,6 +235,8 @@ class DeviceIngest:
         cfg = self.cfg
         if text is None:
             text = self.text(raw_samples, tokenizer, model_max_length, conv_type)
+        if any("crop" in r for r in raw_samples):
+            raw_samples = self._host_crops(raw_samples)
         frames = self._frames(raw_samples)
         if torch.is_tensor(frames):
             clip = self.ingest.clip_pixels(frames, cfg.clip.image, self.dtype)

@@ -558,6 +558,23 @@ int haff_jitter_stats_u8(const void* frames, int B, int H, int W, const int* fla
 int haff_augment_u8(const void* in, void* out, int B, int H, int W, const int* flags, const float* factors, const void* sums,
                     void* stream);
 int haff_flip_planes_u8(const void* in, void* out, int P, int H, int W, const int* flags, void* stream);
+/* ---- the object-crop augmentation on the device (train_ds.py --aug_crop; csrc/frame_crop.hip): crop_and_pad of
+ * 2HANDS/scripts/data_augmentation/process_cropped_sequences.py per sample, byte for byte what Pillow gives. in / out u8
+ * [B][H][W][C], C = 3 (frames) or 1 (mask planes: v != 0 is read as 255, result != 0 is written as 1), out of place. The descriptor
+ * is ONE int32 array given twice, as the host copy the call checks and as the device copy the kernel reads:
+ *   words [12 b, 12 b + 12): x0 y0 cw ch px py S flags | htab hks vtab vks        flags: bit 0 mirror, bit 2 crop
+ *   htab / vtab: word offsets of the sample's tables for S -> W and S -> H (preprocess.pil_resample_tables, bicubic), W resp. H rows
+ *   of 2 + hks resp. 2 + vks words: (first input index, tap count, 22-bit coefficients). Samples with one S share their tables.
+ *   Q[sy][sx] = src[y0 + sy - py][x0 + sx - px] inside the cw x ch window pasted at (px, py) on a black S x S square, S = max(cw, ch);
+ *   out = Q.resize((W, H), BICUBIC): horizontal pass, uint8 intermediate (kept in LDS per output tile), vertical pass.
+ * With bit 0 src is the sample with every row reversed (the box is the mirrored sample's); without bit 2 the sample is copied
+ * (mirrored with bit 0) and the rest of its row is not read.
+ * Refused before anything is enqueued: -1 for a NULL or misaligned pointer, a size <= 0, C other than 1 or 3, out overlapping in, a
+ * box outside the sample, S != max(cw, ch), a paste outside the square, a table outside the descriptor or a table row outside
+ * [0, S); -2 for H * W > 2^24, S > 4 W or S > 4 H (more than 17 taps), or a tile of 16 output rows reaching more than 96 source rows
+ * (the caller crops such a sample on the host). */
+int haff_crop_resample_u8(const void* in, void* out, int B, int H, int W, int C, const int* desc_host, const int* desc_dev,
+                          long desc_words, void* stream);
 /* mask > logit_th -> 0/255 bytes (inference.py:294-301 with logit_th = logit(th); chat.py:226 with 0) */
 int haff_threshold_masks(const float* in, void* out, long total, float logit_th, void* stream);
 /* a15 in one pass — the output gating + thresholds of 2Haff/inference.py:276-334 and chat.py:226-253:
