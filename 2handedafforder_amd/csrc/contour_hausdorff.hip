@@ -5,7 +5,11 @@
 //                            CHAIN_APPROX_SIMPLE vertex list of `find_contours_external(plane)[0]`, and for every (bench, pred) pair
 //                            of planes the two directed squared Hausdorff distances between those lists. Integers throughout.
 //
-// Four stages, six launches on the caller's stream, nothing read back:
+//   haff_contour_extract   : for the same batch, ALL of `find_contours_external(plane)`: every contour's vertex list, back to back in
+//                            OpenCV's order, with an offset table (what a 2HANDS contour record holds). The labelling stages are
+//                            shared; its own five follow plan() below.
+//
+// haff_contour_hausdorff: four stages, six launches on the caller's stream, nothing read back:
 //   1 labelling   union-find on int32 parents with a vector atomicMin (Playne-Hawick / Komura). Foreground is 8-connected, background
 //                 4-connected: one pass labels both, a pixel only merges with neighbours of its own class. A background pixel on the
 //                 plane's edge starts with parent -1 = the ring, so "outside" is the background component whose root is -1. Local
@@ -226,14 +230,16 @@ __device__ __forceinline__ bool bit_on(const unsigned long long* bits, int H, in
 }
 
 // cvlite._follow from (x0, y0) on the packed plane, one wavefront: every lane carries the walk's state (it is wave-uniform), lanes
-// 0-7 probe. Returns the vertex count; `flags` collects overflow and fault.
+// 0-7 probe. Returns the vertex count; `flags` collects overflow and fault. kStore = false only counts: nothing is written and
+// nothing overflows (haff_contour_extract's first walk).
+template <bool kStore = true>
 __device__ __forceinline__ int follow(const unsigned long long* bits, int H, int W, int x0, int y0, short2* out, int max_vertices,
                                       int lane, unsigned& flags) {
   // the first foreground neighbour clockwise from "left": s = 3, 2, 1, 0, 7, 6, 5 (4, the left one, is background)
   const int s_probe = (3 - lane) & 7;
   const unsigned long long m0 = __ballot(lane < 7 && bit_on(bits, H, W, x0 + dir_dx(s_probe), y0 + dir_dy(s_probe)));
   if (m0 == 0ull) {                                       // an isolated pixel
-    if (lane == 0) out[0] = make_short2((short)x0, (short)y0);
+    if (kStore && lane == 0) out[0] = make_short2((short)x0, (short)y0);
     return 1;
   }
   int nv = 0;
@@ -249,10 +255,12 @@ __device__ __forceinline__ int follow(const unsigned long long* bits, int H, int
     s = (s + 1 + (__ffsll((long long)m) - 1)) & 7;
     const int x4 = x3 + dir_dx(s), y4 = y3 + dir_dy(s);
     if (s != prev_s) {
-      if (nv < max_vertices) {
-        if (lane == 0) out[nv] = make_short2((short)x3, (short)y3);
-      } else {
-        flags |= kOverflow;
+      if (kStore) {
+        if (nv < max_vertices) {
+          if (lane == 0) out[nv] = make_short2((short)x3, (short)y3);
+        } else {
+          flags |= kOverflow;
+        }
       }
       ++nv;
       prev_s = s;
@@ -384,7 +392,261 @@ int plan(const Plane* pl, int n_planes, int max_vertices, Layout& lay, int& max_
   return HAFF_OK;
 }
 
+// ---- haff_contour_extract: every external contour of every plane (cvlite.find_contours_external, all of it) -------------------
+// Stages 1a-1c above label the planes. Then, each stage a launch of its own, ordered by the stream alone:
+//   starts   a contour starts at every foreground pixel that is its component's root and has x == 0 or an outside left neighbour
+//            (the root of an external component is always such a pixel: tests/contours_ref.py restates the rule): one bit per pixel, by ballot.
+//   number   one workgroup per plane counts the start bits in DESCENDING raster order (OpenCV's order): contour k's start pixel.
+//   count    one wavefront per contour walks it with follow<false>: the contour's vertex count.
+//   offsets  one workgroup per plane: exclusive scan of the counts, the summary row, the flags.
+//   write    the count walk again, storing at the contour's offset; skipped for a flagged plane.
+constexpr int kMaxContours = 1 << 22;
+constexpr unsigned kTooMany = 4u;         // summary flags: kOverflow, kFault, and more contours than max_contours
+constexpr int kWalkGrid = 64;             // workgroups per plane of the two walks: 4 contours each, then strided
+
+__global__ __launch_bounds__(256) void extract_start_kernel(const Plane* planes, const PlaneState* st, const int* labels,
+                                                            unsigned long long* start_bits) {
+  const Plane pl = planes[blockIdx.y];
+  const int n = pl.H * pl.W;
+  const int* L = labels + st[blockIdx.y].label_off;       // final roots: label_root_kernel has run
+  unsigned long long* marks = start_bits + st[blockIdx.y].bits_off;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    bool mark = pl.plane[i] != 0 && L[i] == i;
+    if (mark && i % pl.W != 0) mark = pl.plane[i - 1] == 0 && L[i - 1] == -1;
+    const unsigned long long word = __ballot(mark);       // as in label_root_kernel: a wave's 64 pixels are one word
+    if ((threadIdx.x & 63) == 0) marks[i >> 6] = word;
+  }
+}
+
+// exclusive scan of one value per thread over the workgroup's 256 threads; *total = the sum. All threads call it.
+__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* total) {
+  __shared__ unsigned wave_sum[4];
+  __shared__ unsigned sum_all;
+  const int tid = threadIdx.x, lane = tid & 63;
+  unsigned inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned u = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += u;
+  }
+  __syncthreads();                                        // a second call: the last one's reads are over
+  if (lane == 63) wave_sum[tid >> 6] = inc;
+  __syncthreads();
+  unsigned base = 0u;
+  for (int w = 0; w < (tid >> 6); ++w) base += wave_sum[w];
+  if (tid == 255) sum_all = base + inc;
+  __syncthreads();
+  *total = sum_all;
+  return base + inc - v;
+}
+
+// thread t takes the words [words - 1 - t * per, ...) downwards, `per` of them: descending raster order over the workgroup
+__global__ __launch_bounds__(256) void extract_number_kernel(const Plane* planes, const PlaneState* st,
+                                                             const unsigned long long* start_bits, int* starts, int* n_contours,
+                                                             int max_contours) {
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int words = (planes[p].H * planes[p].W + 63) / 64;
+  const unsigned long long* marks = start_bits + st[p].bits_off;
+  const int per = (words + 255) / 256;
+  const int first = words - 1 - tid * per;                // may be < 0: the thread has no words
+  int last = first - per + 1;
+  last = last < 0 ? 0 : last;
+  unsigned mine = 0u;
+  for (int j = first; j >= last; --j) mine += (unsigned)__popcll(marks[j]);
+  unsigned total;                                         // at most H W <= 2^24
+  int k = (int)block_exclusive_scan(mine, &total);
+  if (tid == 0) n_contours[p] = (int)total;
+  int* out = starts + (long)p * max_contours;
+  for (int j = first; j >= last && k < max_contours; --j) {
+    unsigned long long w = marks[j];
+    while (w != 0ull && k < max_contours) {               // at most 64 rounds: a bit leaves every round
+      const int b = 63 - __clzll((long long)w);
+      out[k++] = 64 * j + b;
+      w &= ~(1ull << b);
+    }
+  }
+}
+
+template <bool kStore>
+__global__ __launch_bounds__(256) void extract_walk_kernel(const Plane* planes, PlaneState* st, const unsigned long long* bits,
+                                                           const int* starts, const int* n_contours, int* counts, const int* offsets,
+                                                           int* summary, short2* verts, int max_contours, int max_vertices,
+                                                           int lds_words) {
+  extern __shared__ unsigned long long lds_bits[];
+  const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  int nc = n_contours[p];                                 // uniform over the workgroup, as is everything up to the barrier
+  if (nc > max_contours) return;                          // kTooMany: nothing of the plane is walked
+  if ((int)blockIdx.x * 4 >= nc) return;
+  if (kStore) {                                           // a flagged plane is the host's. One read for the workgroup: another
+    __shared__ int flagged;                               // workgroup's walk may set the fault bit between two threads' reads
+    if (tid == 0) flagged = summary[4 * p + 2];
+    __syncthreads();
+    if (flagged != 0) return;
+  }
+  const Plane pl = planes[p];
+  const unsigned long long* packed = bits + st[p].bits_off;
+  const int words = (pl.H * pl.W + 63) / 64;
+  const bool in_lds = words <= lds_words;
+  if (in_lds) {
+    for (int j = tid; j < words; j += 256) lds_bits[j] = packed[j];
+    __syncthreads();
+  }
+  const int* start = starts + (long)p * max_contours;
+  int* count = counts + (long)p * max_contours;
+  const int* offs = offsets + (long)p * (max_contours + 1);
+  for (int k = (int)blockIdx.x * 4 + (tid >> 6); k < nc; k += (int)gridDim.x * 4) {   // at most max_contours rounds
+    const int s = start[k], x0 = s % pl.W, y0 = s / pl.W;
+    unsigned flags = 0u;
+    if (kStore) {
+      const int room = count[k];                          // the count walk's: the walk is the same, so nothing overflows
+      short2* out = verts + (long)p * max_vertices + offs[k];
+      const int nv = in_lds ? follow<true>(lds_bits, pl.H, pl.W, x0, y0, out, room, lane, flags)
+                            : follow<true>(packed, pl.H, pl.W, x0, y0, out, room, lane, flags);
+      if (nv != room) flags |= kFault;
+      if (flags && lane == 0) atomicOr(reinterpret_cast<unsigned*>(summary) + 4 * p + 2, kFault);
+    } else {
+      const int nv = in_lds ? follow<false>(lds_bits, pl.H, pl.W, x0, y0, nullptr, 0, lane, flags)
+                            : follow<false>(packed, pl.H, pl.W, x0, y0, nullptr, 0, lane, flags);
+      if (lane == 0) {
+        count[k] = nv;
+        if (flags) atomicOr(&st[p].flags, flags);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void extract_offsets_kernel(const PlaneState* st, const int* n_contours, const int* counts,
+                                                              int* offsets, int* summary, int max_contours, int max_vertices) {
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nc = n_contours[p];
+  unsigned flags = st[p].flags & kFault;
+  if (nc > max_contours) {                                // uniform: the counts were never made
+    if (tid == 0) {
+      summary[4 * p] = nc;
+      summary[4 * p + 1] = 0;
+      summary[4 * p + 2] = (int)(flags | kTooMany);
+      summary[4 * p + 3] = 0;
+    }
+    return;
+  }
+  const int* count = counts + (long)p * max_contours;
+  int* offs = offsets + (long)p * (max_contours + 1);
+  const int per = (nc + 255) / 256;
+  const int lo = tid * per < nc ? tid * per : nc, hi = lo + per < nc ? lo + per : nc;
+  // the contours are disjoint sets of (pixel, direction) states: without a fault the plane's total is at most 8 H W <= 2^27.
+  // A faulted walk's counts may sum past 2^31: unsigned sums, and the plane is flagged whatever they come to.
+  unsigned mine = 0u;
+  for (int k = lo; k < hi; ++k) mine += (unsigned)count[k];
+  unsigned total;
+  unsigned run = block_exclusive_scan(mine, &total);
+  for (int k = lo; k < hi; ++k) {
+    offs[k] = (int)run;
+    run += (unsigned)count[k];
+  }
+  if (tid == 0) {
+    if (total > (unsigned)max_vertices) flags |= kOverflow;
+    offs[nc] = (int)total;
+    summary[4 * p] = nc;
+    summary[4 * p + 1] = (int)total;
+    summary[4 * p + 2] = (int)flags;
+    summary[4 * p + 3] = 0;
+  }
+}
+
+struct ExtractLayout { long start_bits, starts, counts, n_contours, total; };
+
+// plan()'s refusals, max_contours, and the extract stages' areas behind the labelling's (lay.verts is where plan()'s own end)
+int plan_extract(const Plane* pl, int n_planes, int max_contours, int max_vertices, Layout& lay, ExtractLayout& ext, int& max_tiles,
+                 long& max_pixels) {
+  const int rc = plan(pl, n_planes, max_vertices, lay, max_tiles, max_pixels);
+  if (rc != HAFF_OK) return rc;
+  if (max_contours < 1 || max_contours > kMaxContours) return HAFF_ERR_BAD_ARG;
+  long words = 0;
+  for (int i = 0; i < n_planes; ++i) words += ((long)pl[i].H * pl[i].W + 63) / 64;
+  ext.start_bits = lay.verts;
+  ext.starts = align_up(ext.start_bits + words * 8, 16);
+  ext.counts = align_up(ext.starts + (long)n_planes * max_contours * 4, 16);
+  ext.n_contours = align_up(ext.counts + (long)n_planes * max_contours * 4, 16);
+  ext.total = align_up(ext.n_contours + (long)n_planes * 4, 16);
+  return HAFF_OK;
+}
+
 }  // namespace
+
+extern "C" int haff_contour_extract_workspace(const void* planes_host, int n_planes, int max_contours, int max_vertices,
+                                              long* bytes_out) {
+  if (!bytes_out) return HAFF_ERR_BAD_ARG;
+  Layout lay;
+  ExtractLayout ext;
+  int max_tiles;
+  long max_pixels;
+  const int rc = plan_extract(static_cast<const Plane*>(planes_host), n_planes, max_contours, max_vertices, lay, ext, max_tiles,
+                              max_pixels);
+  if (rc != HAFF_OK) return rc;
+  *bytes_out = ext.total;
+  return HAFF_OK;
+}
+
+extern "C" int haff_contour_extract(const void* planes_host, const void* planes_dev, int n_planes, int max_contours, int max_vertices,
+                                    void* workspace, long workspace_bytes, void* verts, void* offsets, void* summary, void* stream) {
+  if (!planes_host || !planes_dev || !workspace || !verts || !offsets || !summary) return HAFF_ERR_BAD_ARG;
+  Layout lay;
+  ExtractLayout ext;
+  int max_tiles;
+  long max_pixels;
+  const Plane* pl = static_cast<const Plane*>(planes_host);
+  const int rc = plan_extract(pl, n_planes, max_contours, max_vertices, lay, ext, max_tiles, max_pixels);
+  if (rc != HAFF_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(planes_dev) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
+      (reinterpret_cast<uintptr_t>(verts) & 3) || (reinterpret_cast<uintptr_t>(offsets) & 3) ||
+      (reinterpret_cast<uintptr_t>(summary) & 3))
+    return HAFF_ERR_BAD_ARG;
+  if (workspace_bytes < ext.total) return HAFF_ERR_BAD_ARG;
+  char* ws = static_cast<char*>(workspace);
+  int* labels = reinterpret_cast<int*>(ws + lay.labels);
+  unsigned long long* bits = reinterpret_cast<unsigned long long*>(ws + lay.bits);
+  PlaneState* st = reinterpret_cast<PlaneState*>(ws + lay.state);
+  unsigned long long* start_bits = reinterpret_cast<unsigned long long*>(ws + ext.start_bits);
+  int* starts = reinterpret_cast<int*>(ws + ext.starts);
+  int* counts = reinterpret_cast<int*>(ws + ext.counts);
+  int* n_contours = reinterpret_cast<int*>(ws + ext.n_contours);
+  const Plane* pd = static_cast<const Plane*>(planes_dev);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int lds_words = 0;
+  for (int i = 0; i < n_planes; ++i) {
+    const long w = ((long)pl[i].H * pl[i].W + 63) / 64;
+    if (w * 8 <= kWalkLdsBytes && w > lds_words) lds_words = (int)w;
+  }
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(extract_walk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          kWalkLdsBytes) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(extract_walk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          kWalkLdsBytes) != hipSuccess)
+    return HAFF_ERR_LAUNCH;
+  const dim3 tiles((unsigned)max_tiles, (unsigned)n_planes);
+  long rb = (max_pixels + 256L * 4 - 1) / (256L * 4);
+  rb = rb > 256 ? 256 : rb;
+  const dim3 roots((unsigned)rb, (unsigned)n_planes);
+  int wg = (max_contours + 3) / 4;
+  wg = wg > kWalkGrid ? kWalkGrid : wg;
+  const dim3 walks((unsigned)wg, (unsigned)n_planes);
+  int* offs = static_cast<int*>(offsets);
+  int* sum = static_cast<int*>(summary);
+  short2* v = static_cast<short2*>(verts);
+  hipLaunchKernelGGL(ch_setup_kernel, dim3((unsigned)((n_planes + 255) / 256)), dim3(256), 0, s, pd, n_planes, st);
+  hipLaunchKernelGGL(label_tile_kernel, tiles, dim3(256), 0, s, pd, st, labels);
+  hipLaunchKernelGGL(label_seam_kernel, tiles, dim3(256), 0, s, pd, st, labels);
+  hipLaunchKernelGGL(label_root_kernel, roots, dim3(256), 0, s, pd, st, labels, bits);
+  hipLaunchKernelGGL(extract_start_kernel, roots, dim3(256), 0, s, pd, st, labels, start_bits);
+  hipLaunchKernelGGL(extract_number_kernel, dim3((unsigned)n_planes), dim3(256), 0, s, pd, st, start_bits, starts, n_contours,
+                     max_contours);
+  hipLaunchKernelGGL(extract_walk_kernel<false>, walks, dim3(256), (size_t)lds_words * 8, s, pd, st, bits, starts, n_contours, counts,
+                     offs, sum, v, max_contours, max_vertices, lds_words);
+  hipLaunchKernelGGL(extract_offsets_kernel, dim3((unsigned)n_planes), dim3(256), 0, s, st, n_contours, counts, offs, sum,
+                     max_contours, max_vertices);
+  hipLaunchKernelGGL(extract_walk_kernel<true>, walks, dim3(256), (size_t)lds_words * 8, s, pd, st, bits, starts, n_contours, counts,
+                     offs, sum, v, max_contours, max_vertices, lds_words);
+  return haff_check_launch();
+}
 
 extern "C" int haff_contour_hausdorff_workspace(const void* planes_host, int n_planes, int max_vertices, long* bytes_out) {
   if (!bytes_out) return HAFF_ERR_BAD_ARG;

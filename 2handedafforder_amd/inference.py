@@ -9,6 +9,9 @@ Images are read/written with PIL (cv2 is not a dependency here); thresholds and 
 
 --score scores the run against the aff_*.png under --benchmark-dir on the device, as `evaluation.py --map` would score the written
 tree (scoring.BenchmarkScorer, one kernel launch per batch, one host read at the end); --score_only writes no PNGs at all.
+
+--write_records PATH also writes the run as 2HANDS contour records (contours.py: one ops.contour_extract call per chunk over the
+planes of --records_threshold, every external contour of each hand), a torch-saved list `train_ds.py --sam_records PATH` loads.
 """
 import argparse
 import json
@@ -21,10 +24,10 @@ import torch
 if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import haff  # noqa: F401
-    from haff import checkpoint, config as hcfg, postprocess, preprocess, prompt as hprompt, scoring
+    from haff import checkpoint, config as hcfg, contours, postprocess, preprocess, prompt as hprompt, scoring
     from haff.lisa import LisaMI355
 else:
-    from . import checkpoint, config as hcfg, postprocess, preprocess, prompt as hprompt, scoring
+    from . import checkpoint, config as hcfg, contours, postprocess, preprocess, prompt as hprompt, scoring
     from .lisa import LisaMI355
 
 
@@ -63,8 +66,15 @@ def parse_args(args):
     parser.add_argument("--score_hausdorff_device", action="store_true", default=False,
                         help="the two Hausdorff distances from the device: contour walk and point-set distance in HIP, nothing read "
                              "back per batch and no host thread")
+    # predictions as 2HANDS contour records (contours.py): off by default
+    parser.add_argument("--write_records", default=None, type=str, metavar="PATH",
+                        help="also torch.save the run as a list of 2HANDS records (narration, image, taxonomy, masks = the contours "
+                             "of both hands at --records_threshold, extracted on the device): what train_ds.py --sam_records loads")
+    parser.add_argument("--records_threshold", default=None, type=float,
+                        help=f"the threshold whose masks --write_records writes: one of {postprocess.THRESHOLDS} (default 0.5)")
     args = parser.parse_args(args)
     check_score_args(args)
+    check_records_args(args)
     return args
 
 
@@ -78,6 +88,18 @@ def check_score_args(args):
         raise SystemExit("--score_hausdorff_device and --score_hausdorff are two routes to the same numbers: pass one of them")
     if args.score and not args.benchmark_dir:
         raise SystemExit("--score needs --benchmark-dir: the ground truth is its aff_{left,right}.png")
+
+
+def check_records_args(args):
+    """--records_threshold modifies --write_records and names one of the thresholds the run computes anyway."""
+    if args.records_threshold is not None and not args.write_records:
+        raise SystemExit("--records_threshold modifies --write_records: pass a path to write to")
+    if args.records_threshold is None:
+        args.records_threshold = 0.5
+    if args.records_threshold not in postprocess.THRESHOLDS:
+        raise SystemExit(f"--records_threshold {args.records_threshold}: one of {postprocess.THRESHOLDS}")
+    if args.write_records and not args.benchmark_dir:
+        raise SystemExit("--write_records needs --benchmark-dir: the frames and narrations come from it")
 
 
 PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -164,6 +186,35 @@ def output_planes(masks_left, masks_right, taxonomies, thresholds=postprocess.TH
     return out
 
 
+def record_planes(masks_left, masks_right, taxonomies, threshold):
+    """The planes output_planes writes for one frame at `threshold`, left on the device: (predicted class index or None without a
+    [SEG], {side: uint8 [H0, W0] of 0 / 255}) under output_planes' own gate; a gated hand has no entry."""
+    out = {}
+    taxonomy = taxonomies[0]
+    if taxonomy.numel() == 0:
+        return None, out
+    t = int(torch.argmax(taxonomy.reshape(-1).float().contiguous()))
+    for side, masks, blank in (("left", masks_left, 1), ("right", masks_right, 0)):
+        if t == blank:
+            continue
+        for pred_mask in masks:
+            if pred_mask.shape[0] == 0:
+                continue
+            out[side] = postprocess.inference_planes(pred_mask[0], None, side, (threshold,))[0]
+    return t, out
+
+
+def chunk_records(reader, narrations, images, masks_left, masks_right, taxonomies, original_size_list, threshold):
+    """One record per frame of a chunk, from ONE ContourReader.read over every open hand's plane. A frame without a [SEG] has no
+    prediction: both hands empty and the records' default class 2."""
+    per_frame = [record_planes(masks_left[b:b + 1], masks_right[b:b + 1], taxonomies[b:b + 1], threshold) for b in range(len(images))]
+    keys = [(b, side) for b, (_, planes) in enumerate(per_frame) for side in planes]
+    found = dict(zip(keys, reader.read([per_frame[b][1][side] for b, side in keys])))
+    return [contours.prediction_record(narrations[b], images[b], 2 if t is None or t > 3 else t, found.get((b, "left"), []),
+                                       found.get((b, "right"), []), original_size_list[b])
+            for b, (t, _) in enumerate(per_frame)]
+
+
 def pad_prompts(id_rows, pad_token_id):
     """collate_fn's rule (utils/dataset.py:90-93,144-150): right-pad with pad_token_id, mask = real positions."""
     L = max(r.numel() for r in id_rows)
@@ -217,12 +268,14 @@ def _main(args, closers):
                                          intersection=args.score_intersection,
                                          hausdorff="device" if args.score_hausdorff_device else args.score_hausdorff)
         closers.append(scorer.close)
+    reader, records = (contours.ContourReader(), []) if args.write_records else (None, None)
     examples = list(iter_examples(args.benchmark_dir))
     for i in range(0, len(examples), max(args.batch_size, 1)):
         chunk = examples[i:i + max(args.batch_size, 1)]
-        frames, resize_list, original_size_list, id_rows = [], [], [], []
+        frames, resize_list, original_size_list, id_rows, images = [], [], [], [], []
         for _, _, image_path, narration in chunk:
-            fr, rs, osz = prepare_frame(load_rgb(image_path), cfg, dtype, device)
+            images.append(load_rgb(image_path))
+            fr, rs, osz = prepare_frame(images[-1], cfg, dtype, device)
             frames.append(fr[0])
             resize_list += rs
             original_size_list += osz
@@ -234,11 +287,18 @@ def _main(args, closers):
             tokenizer=tokenizer, frames_u8=frames, attention_mask=mask)
         if scorer is not None:   # one launch for the chunk; the counts stay on the device until the report
             scorer.add_batch([(d, f) for d, f, _, _ in chunk], masks_left, masks_right, taxonomies, original_size_list)
+        if reader is not None:   # one extraction for the chunk, on the very planes the PNGs below are read back from
+            records += chunk_records(reader, [n for _, _, _, n in chunk], images, masks_left, masks_right, taxonomies,
+                                     original_size_list, args.records_threshold)
         if args.score_only:
             continue
         for b, (dir_name, folder_name, _, _) in enumerate(chunk):   # per frame, exactly the reference's B = 1 rule
             for (side, th), plane in output_planes(masks_left[b:b + 1], masks_right[b:b + 1], taxonomies[b:b + 1]).items():
                 save_mask(os.path.join(args.vis_save_path + str(th), dir_name, folder_name, f"aff_{side}.png"), plane)
+    if reader is not None:
+        contours.save_records(args.write_records, records)
+        print(f"{args.write_records}: {len(records)} records at threshold {args.records_threshold}, {reader.host_walks} planes walked "
+              "on the host")
     if scorer is not None:
         return scorer.report(verbose=True)
     return None

@@ -1386,3 +1386,50 @@ def contour_hausdorff(planes, pairs, max_vertices=65536, return_vertices=False):
         return result
     return (result, verts[:n * max_vertices * 4].view(torch.int16).reshape(n, max_vertices, 2),
             verts[n * max_vertices * 4:n * max_vertices * 4 + 4 * n].view(torch.int32))
+
+
+EXTRACT_MAX_CONTOURS = 1 << 22                            # csrc/contour_hausdorff.hip kMaxContours
+EXTRACT_OVERFLOW, EXTRACT_FAULT, EXTRACT_TOO_MANY = 1, 2, 4   # summary[:, 2]
+
+
+def contour_extract(planes, max_contours=1024, max_vertices=65536, out=None):
+    """haff_contour_extract: planes = uint8 CUDA tensors [H, W] (a list, or one [n, H, W] tensor), on where != 0, of any mix of
+    shapes. Returns (summary, offsets, verts) on the device: int32 [n, 4] = {n_contours, n_vertices, flags, 0}, int32
+    [n, max_contours + 1] (entry k = the first vertex of contour k, entry n_contours = the total) and int16 [n, max_vertices, 2]
+    (x, y): every contour of `cvlite.find_contours_external(plane)`, in its order, back to back. A plane with a flag set
+    (EXTRACT_OVERFLOW / EXTRACT_FAULT / EXTRACT_TOO_MANY) holds nothing of use in offsets and verts; what lies past a plane's
+    n_contours + 1 offsets and n_vertices vertices is left as it was. Only enqueues: no synchronisation, the caller keeps the planes
+    alive until the stream has run. out: the (summary, offsets, verts) tensors to write into."""
+    lib = load_library()
+    planes = list(planes)
+    assert planes, "no planes"
+    for p in planes:
+        _req(p, "planes")
+        assert p.dtype == torch.uint8 and p.dim() == 2 and p.is_contiguous(), (p.dtype, tuple(p.shape), p.is_contiguous())
+        assert p.device == planes[0].device
+    device = planes[0].device
+    n, max_contours, max_vertices = len(planes), int(max_contours), int(max_vertices)
+    host = torch.zeros((2 * n,), dtype=torch.int64, pin_memory=True)    # 16-byte plane descriptors
+    h64 = host.numpy()
+    h32 = h64.view("int32")
+    for i, p in enumerate(planes):
+        h64[2 * i] = p.data_ptr()
+        h32[4 * i + 2], h32[4 * i + 3] = p.shape
+    need = ctypes.c_long(0)
+    check(lib.haff_contour_extract_workspace(host.data_ptr(), n, max_contours, max_vertices, ctypes.addressof(need)),
+          "haff_contour_extract_workspace")
+    if out is None:
+        out = (torch.empty((n, 4), dtype=torch.int32, device=device),
+               torch.empty((n, max_contours + 1), dtype=torch.int32, device=device),
+               torch.empty((n, max_vertices, 2), dtype=torch.int16, device=device))
+    summary, offsets, verts = out
+    for t, dtype, shape in ((summary, torch.int32, (n, 4)), (offsets, torch.int32, (n, max_contours + 1)),
+                            (verts, torch.int16, (n, max_vertices, 2))):
+        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == device, (t.dtype, tuple(t.shape))
+    with torch.cuda.device(device):
+        ws = _workspace(device, need.value)
+        dev = host.to(device, non_blocking=True)
+        rc = lib.haff_contour_extract(host.data_ptr(), dev.data_ptr(), n, max_contours, max_vertices, ws.data_ptr(), ws.numel(),
+                                      verts.data_ptr(), offsets.data_ptr(), summary.data_ptr(), _stream())
+    check(rc, "haff_contour_extract")
+    return summary, offsets, verts

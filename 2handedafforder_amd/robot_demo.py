@@ -14,10 +14,15 @@ img.png, prompt.txt and margins.txt (never the masks). The heat map and the padd
 frame. They go through one evaluate(offset=[0, n]) call; line 0 writes the file names above, line i >= 1 the same set with _<i> in front
 of the extension (aff_left_1.png, aff_left_heat_1.png, cropped_img_1.png, ...).
 
+--contours (off by default): beside each aff_<hand><suffix>.png, aff_<hand><suffix>.json = {"original_size": [H, W], "contours":
+[[[x, y], ...], ...]}: every external contour of that very plane (padded and ANDed), extracted on the device (contours.py) before the
+plane is read back, for a planner that wants polygons instead of a raster.
+
 Offline extras as in inference.py: --synthetic, --sam-checkpoint, --max-new-tokens. Stated deviation: the two waits sleep
 --poll-interval seconds between polls instead of busy-looping. Images are read and written with PIL (cv2 is not a dependency).
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -28,16 +33,18 @@ import torch
 if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import haff  # noqa: F401
-    from haff import postprocess, prompt as hprompt
+    from haff import contours as hcontours, postprocess, prompt as hprompt
     from haff.inference import build_model_and_tokenizer, load_rgb, prepare_frame
 else:
-    from . import postprocess, prompt as hprompt
+    from . import contours as hcontours, postprocess, prompt as hprompt
     from .inference import build_model_and_tokenizer, load_rgb, prepare_frame
 
 
 # Every non-empty line of prompt.txt is an action on the one frame: ONE evaluate(offset=[0, n]) call, so the frame is encoded and the
 # prompt's common head prefilled once. Line 0 writes today's file names, line i >= 1 the same set with _<i> in front of the extension.
 MULTI_PROMPT_FLAG = "--multi_prompt"
+# Also an option of the loop: aff_<hand><suffix>.json with the contours of aff_<hand><suffix>.png beside every such file.
+CONTOURS_FLAG = "--contours"
 
 
 def parse_args(args):
@@ -88,10 +95,11 @@ def read_margins(path):
     return int(m[0]), int(m[1]), int(m[2]), int(m[3])
 
 
-def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, device, suffix=""):
+def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, device, suffix="", contours=False):
     """robot_demo.py:266-327 for a request whose taxonomy is not empty: the hands the --force_* flags select, every non-empty
     entry of pred_masks_<hand> in order (a later one overwrites the files of an earlier one, as there). suffix ("_<i>", --multi_prompt:
-    prompt line i >= 1) goes in front of the file names' extension."""
+    prompt line i >= 1) goes in front of the file names' extension. contours: also aff_<hand><suffix>.json, from the planes while
+    they are still on the device."""
     from PIL import Image
     hands = []
     for side, masks, forced in (("left", masks_left, args.force_left), ("right", masks_right, args.force_right)):
@@ -107,6 +115,7 @@ def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, d
             uploaded[id(m)] = torch.from_numpy(m).to(device)
         and_masks.append(uploaded[id(m)])
     heat, planes = postprocess.robot_planes(torch.stack([x for _, x in hands]), args.th, margins, and_masks)
+    found = hcontours.ContourReader().read(list(planes)) if contours else None
     heat, planes = heat.cpu().numpy(), planes.cpu().numpy()
     for k, (side, _) in enumerate(hands):
         Image.fromarray(heat[k]).save(os.path.join(args.vis_save_path, f"aff_{side}_heat{suffix}.png"))
@@ -114,16 +123,20 @@ def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, d
         os.makedirs(os.path.dirname(mask_save_path), exist_ok=True)
         Image.fromarray(planes[k]).save(mask_save_path)
         print(f"{mask_save_path} has been saved.")
+        if found is not None:
+            with open(os.path.join(args.vis_save_path, f"aff_{side}{suffix}.json"), "w") as f:
+                json.dump({"original_size": list(planes[k].shape), "contours": hcontours.contour_lists(found[k])}, f)
 
 
 def main(argv, max_requests=None):
     """max_requests: return after that many passes that found img.png, prompt.txt and margins.txt (a test hook, like
     chat.main(max_turns=)); None polls forever, as the reference does.
     --multi_prompt is an option of this loop, not one of parse_args' flags (those stay the reference's plus the four offline extras):
-    it is taken out of argv here."""
+    it is taken out of argv here, and so is --contours."""
     from PIL import Image
     multi_prompt = MULTI_PROMPT_FLAG in argv
-    args = parse_args([a for a in argv if a != MULTI_PROMPT_FLAG])
+    contours = CONTOURS_FLAG in argv
+    args = parse_args([a for a in argv if a not in (MULTI_PROMPT_FLAG, CONTOURS_FLAG)])
     os.makedirs(args.vis_save_path, exist_ok=True)
     model, tokenizer, cfg, dtype = build_model_and_tokenizer(args)
     device = model.device
@@ -178,7 +191,8 @@ def main(argv, max_requests=None):
         for i, taxonomy in enumerate(taxonomies):
             suffix = f"_{i}" if i else ""
             if taxonomy.numel() != 0:   # the taxonomy does not gate here (robot_demo.py:268,298 are commented out)
-                write_hands(args, masks_left[i:i + 1], masks_right[i:i + 1], mask_left, mask_right, margins, device, suffix)
+                write_hands(args, masks_left[i:i + 1], masks_right[i:i + 1], mask_left, mask_right, margins, device, suffix,
+                            contours=contours)
             else:
                 print("No taxonomy found!!")
             Image.fromarray(image_np).save(os.path.join(args.vis_save_path, f"cropped_img{suffix}.png"))

@@ -662,6 +662,30 @@ int haff_contour_hausdorff(const void* planes_host, const void* planes_dev, int 
 /* Host only: *bytes_out = the workspace haff_contour_hausdorff needs for these planes (only H and W are read) and max_vertices.
  * The same refusals for the plane table and max_vertices; -1 for a NULL bytes_out. */
 int haff_contour_hausdorff_workspace(const void* planes_host, int n_planes, int max_vertices, long* bytes_out);
+/* ---- predictions as 2HANDS contour records (2HANDS/scripts/utils/compress_masks_to_json.py:60-92: cv2.findContours(mask,
+ * RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), every contour kept; cvlite.find_contours_external restates it) ----
+ * For every plane of the same descriptor table as haff_contour_hausdorff: ALL external contours. A contour starts at every
+ * foreground pixel that is the raster-first pixel of its 8-connected component and has x == 0 or a left neighbour in the outside
+ * background; contours are ordered by DESCENDING raster index of that pixel (OpenCV's order) and each is followed from it as
+ * cvlite._follow does. max_contours and max_vertices are per plane.
+ *   verts    i16 [n_planes][max_vertices][2] (x, y): the contours back to back.
+ *   offsets  i32 [n_planes][max_contours + 1]: entry k the first vertex of contour k, entry n_contours the total.
+ *   summary  i32 [n_planes][4] = {n_contours, n_vertices, flags, 0}, every word written by the call. n_contours is always the true
+ *            number; n_vertices the true total whenever n_contours <= max_contours. flags: 1 more vertices than max_vertices,
+ *            2 fault (a bound of the labelling or of a walk was reached: no input should), 4 more contours than max_contours
+ *            (then no contour is walked: n_vertices is 0 and bit 0 stays clear).
+ *            With a flag set the plane's verts and offsets hold nothing of use and the caller recomputes the plane on the host.
+ * Nothing outside a plane's own rows is written, and inside them nothing past n_vertices vertices and n_contours + 1 offsets.
+ * Nine launches on `stream` (the labelling's four, start marks, numbering, a counting walk, the offsets' scan, the writing walk),
+ * each ordered after the last by the stream alone; nothing is read back; repeat runs are bitwise equal.
+ * Refused before anything is enqueued: what haff_contour_hausdorff refuses for the plane table, max_vertices and the workspace
+ * (sized by haff_contour_extract_workspace); -1 for max_contours outside 1..2^22, a NULL verts, offsets or summary, or one that
+ * is not 4-B aligned; -2 for a side over 4096. */
+int haff_contour_extract(const void* planes_host, const void* planes_dev, int n_planes, int max_contours, int max_vertices,
+                         void* workspace, long workspace_bytes, void* verts, void* offsets, void* summary, void* stream);
+/* Host only: *bytes_out = the workspace haff_contour_extract needs. The same refusals for the plane table, max_contours and
+ * max_vertices; -1 for a NULL bytes_out. */
+int haff_contour_extract_workspace(const void* planes_host, int n_planes, int max_contours, int max_vertices, long* bytes_out);
 
 
 /* ==== training path (LoRA fine-tune: train_ds.py:489-622 driving model_forward, LISA.py:175-430) ==================
