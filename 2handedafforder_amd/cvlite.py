@@ -192,3 +192,31 @@ def find_contours_external(mask):
             traced[vy, vx] = True
         found.append(np.array([(px - 1, py - 1) for px, py in pts], dtype=np.int32).reshape(-1, 1, 2))
     return found[::-1]
+
+
+_GAUSS7 = (8, 28, 56, 72, 56, 28, 8)   # OpenCV's small_gaussian_tab[3] = {0.03125, 0.109375, 0.21875, 0.28125, ...} times 256
+
+
+def _reflect101(p, n):
+    """borderInterpolate(p, n, BORDER_REFLECT_101) for an index array, any overshoot"""
+    if n == 1:
+        return np.zeros_like(p)
+    period = 2 * n - 2
+    p = np.mod(p, period)
+    return np.where(p >= n, period - p, p)
+
+
+def gaussian_blur7_u8(img):
+    """cv2.GaussianBlur(img, (7, 7), 0) of a 2-D uint8 image (ActAffordance/scripts/utils/gaussian.py:16): OpenCV's bit-exact 8-bit
+    path. sigma = 0 with ksize 7 takes the built-in table above, which is exact in 8.8 fixed point; BORDER_REFLECT_101; both passes
+    in integers, out = (sum c[dy] c[dx] p + 2^15) >> 16. Unpinned against cv2 itself, as everything in this module."""
+    img = np.asarray(img)
+    if img.ndim != 2 or img.dtype != np.uint8:
+        raise ValueError("gaussian_blur7_u8 takes a 2-D uint8 image")
+    h, w = img.shape
+    a = img.astype(np.int64)
+    cols = [_reflect101(np.arange(w) + k - 3, w) for k in range(7)]
+    rows = [_reflect101(np.arange(h) + k - 3, h) for k in range(7)]
+    hor = sum(c * a[:, ix] for c, ix in zip(_GAUSS7, cols))
+    ver = sum(c * hor[iy] for c, iy in zip(_GAUSS7, rows))
+    return ((ver + 32768) >> 16).astype(np.uint8)

@@ -12,6 +12,10 @@ tree (scoring.BenchmarkScorer, one kernel launch per batch, one host read at the
 
 --write_records PATH also writes the run as 2HANDS contour records (contours.py: one ops.contour_extract call per chunk over the
 planes of --records_threshold, every external contour of each hand), a torch-saved list `train_ds.py --sam_records PATH` loads.
+
+--smooth_masks applies ActAffordance's scripts/utils/gaussian.py (7x7 Gaussian blur of each written plane, then `> --smooth_threshold`)
+to the fp32 masks on the device, once for all thresholds (postprocess.smooth_mask_lists, csrc/mask_smooth.hip): the PNGs, --score /
+--score_only and --write_records then equal what that script would leave behind on the unsmoothed run's tree.
 """
 import argparse
 import json
@@ -72,9 +76,15 @@ def parse_args(args):
                              "of both hands at --records_threshold, extracted on the device): what train_ds.py --sam_records loads")
     parser.add_argument("--records_threshold", default=None, type=float,
                         help=f"the threshold whose masks --write_records writes: one of {postprocess.THRESHOLDS} (default 0.5)")
+    # gaussian.py, step 2 of the benchmark workflow, on the logits (postprocess.smooth_mask_lists): off by default
+    parser.add_argument("--smooth_masks", action="store_true", default=False,
+                        help="smooth every mask as ActAffordance's scripts/utils/gaussian.py smooths the written PNGs (7x7 Gaussian blur, "
+                             "then --smooth_threshold), once on the device before anything is written, scored or traced")
+    parser.add_argument("--smooth_threshold", default=None, type=float, help="gaussian.py --threshold, in [0, 1) (default 0.5)")
     args = parser.parse_args(args)
     check_score_args(args)
     check_records_args(args)
+    check_smooth_args(args)
     return args
 
 
@@ -100,6 +110,18 @@ def check_records_args(args):
         raise SystemExit(f"--records_threshold {args.records_threshold}: one of {postprocess.THRESHOLDS}")
     if args.write_records and not args.benchmark_dir:
         raise SystemExit("--write_records needs --benchmark-dir: the frames and narrations come from it")
+
+
+def check_smooth_args(args):
+    """--smooth_threshold modifies --smooth_masks and is a gaussian.py threshold."""
+    if args.smooth_threshold is not None and not args.smooth_masks:
+        raise SystemExit("--smooth_threshold modifies --smooth_masks: pass it too")
+    if args.smooth_threshold is None:
+        args.smooth_threshold = 0.5
+    try:
+        postprocess.smooth_need(args.smooth_threshold)
+    except ValueError as e:
+        raise SystemExit(f"--smooth_threshold: {e}")
 
 
 PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -285,6 +307,8 @@ def _main(args, closers):
         output_ids, masks_left, masks_right, taxonomies = model.evaluate(
             None, None, input_ids.to(device), resize_list, original_size_list, max_new_tokens=args.max_new_tokens,
             tokenizer=tokenizer, frames_u8=frames, attention_mask=mask)
+        if args.smooth_masks:    # once, for all five thresholds and every consumer below
+            masks_left, masks_right = postprocess.smooth_mask_lists(masks_left, masks_right, args.smooth_threshold)
         if scorer is not None:   # one launch for the chunk; the counts stay on the device until the report
             scorer.add_batch([(d, f) for d, f, _, _ in chunk], masks_left, masks_right, taxonomies, original_size_list)
         if reader is not None:   # one extraction for the chunk, on the very planes the PNGs below are read back from

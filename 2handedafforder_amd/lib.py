@@ -198,6 +198,7 @@ _PROTOS = {
     "haff_robot_heatmap": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p, c_void_p],
     "haff_robot_mask": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p,
                         c_void_p],
+    "haff_mask_quantile7": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "haff_score_masks": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "haff_contour_hausdorff": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p,
                                c_void_p],

@@ -1041,6 +1041,20 @@ def robot_mask(logits, th, margins, mask=None, on_value=255, out=None):
     return out
 
 
+def mask_quantile7(logits, need):
+    """fp32 [n, H, W] mask logits -> fp32 [n, H, W]: per pixel the weighted upper quantile of its 7x7 neighbourhood (reflect-101,
+    weights of OpenCV's 7-tap Gaussian table, total 65536): the largest tap with weight{taps >= it} >= need. `out > lt` is then
+    gaussian.py's smoothing of the plane `logits > lt`, for every lt (postprocess.smooth_need gives need for its --threshold)."""
+    lib = load_library()
+    _req(logits, "logits")
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 3
+    n, H, W = logits.shape
+    out = torch.empty_like(logits)
+    rc = lib.haff_mask_quantile7(logits.data_ptr(), n, H, W, int(need), out.data_ptr(), _stream())
+    check(rc, "haff_mask_quantile7")
+    return out
+
+
 def resample_u8(frames, out_hw, axis, bounds, coeffs):
     """One axis of Pillow's antialiased resampling on uint8 NHWC frames [B,H,W,3]; bounds/coeffs = device int32 tables."""
     lib = load_library()

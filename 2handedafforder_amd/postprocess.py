@@ -126,3 +126,34 @@ def robot_planes(logits, th, margins, and_masks, on_value=255):
     for k in range(n):
         ops.robot_mask(logits[k], t, margins, and_masks[k], on_value, out=buf[k, :Ho * Wo].view(Ho, Wo))
     return heat, buf[:, :Ho * Wo].view(n, Ho, Wo)
+
+
+# ---- ActAffordance/scripts/utils/gaussian.py: the benchmark workflow's mask smoothing, on the logits (csrc/mask_smooth.hip) ----
+
+def smooth_need(threshold=0.5):
+    """The weight (of 65536) a pixel's "on" taps must reach for gaussian.py --threshold `threshold` to keep it on. The 8-bit blur of
+    a 0/255 plane is (255 M + 32768) >> 16 with M the weight of the on taps, and `blurred / 255.0 > threshold` (in double, as numpy
+    divides) holds from b = min{b in 0..255 : b / 255.0 > threshold} on: need = ceil((65536 b - 32768) / 255). 0.5 -> 32768."""
+    t = float(threshold)
+    if not 0.0 <= t < 1.0:       # NaN fails both
+        raise ValueError(f"smoothing threshold {threshold}: must lie in [0, 1)")
+    b = next(b for b in range(256) if b / 255.0 > t)
+    return -((32768 - 65536 * b) // 255)
+
+
+def smooth_mask_lists(masks_left, masks_right, threshold=0.5):
+    """The two mask lists evaluate() returns (per frame fp32 [k, H0, W0] logits, k possibly 0) -> the same structure with every plane
+    smoothed as gaussian.py smooths the PNGs written from it: `smoothed > x*(th)` is the 7x7 blur + threshold of `mask > x*(th)` for
+    every th at once (ops.mask_quantile7). Both hands of a frame go through one launch; empty entries pass through."""
+    need = smooth_need(threshold)
+    out_left, out_right = list(masks_left), list(masks_right)
+    for b, (ml, mr) in enumerate(zip(masks_left, masks_right)):
+        if ml.shape[0] + mr.shape[0] == 0:
+            continue
+        # both hands of a frame have the frame's size; torch.cat of one non-empty and one empty entry is the non-empty one
+        smoothed = ops.mask_quantile7(torch.cat([ml, mr]).float().contiguous(), need)
+        if ml.shape[0]:
+            out_left[b] = smoothed[:ml.shape[0]]
+        if mr.shape[0]:
+            out_right[b] = smoothed[ml.shape[0]:]
+    return out_left, out_right

@@ -599,6 +599,19 @@ int haff_robot_heatmap(const float* logits, int n, int H, int W, const void* jet
  * on_value. -1 when mask's size is not the padded size (cv2.bitwise_and raises) or the padded size is empty. */
 int haff_robot_mask(const float* logits, int H0, int W0, int left, int top, int right, int bottom, float th, const void* mask,
                     int mask_h, int mask_w, int on_value, void* out, void* stream);
+/* ---- the benchmark workflow's mask smoothing (ActAffordance/scripts/utils/gaussian.py: cv2.GaussianBlur(img, (7, 7), 0), then
+ * `blurred / 255.0 > tau`; csrc/mask_smooth.hip) on the f32 logits, for every threshold at once ----
+ * n contiguous f32 planes logits [n][H][W] -> out [n][H][W] (out != logits): every output is the weighted upper quantile of the
+ * pixel's 49 taps under BORDER_REFLECT_101 (any overshoot; a side of 1 maps every tap to index 0), weights c[dy] c[dx] with
+ * c = {8, 28, 56, 72, 56, 28, 8} (OpenCV's 7-tap table times 256; total 65536): the largest tap value v with
+ * weight{taps >= v} >= need, need in 1..65536. The output is one of the inputs, bit for bit (but -0.0 and +0.0 compare equal and
+ * either may be returned). A NaN tap counts as -inf; a pixel whose weight of taps above -inf is below need gets -inf; no NaN is
+ * written. For a 0/255 plane p = 255 [logits > lt] of ANY lt, 255 [out > lt] is the 8-bit bit-exact blur of p followed by
+ * `blurred / 255.0 > tau` when need = ceil((65536 b - 32768) / 255), b = min{b in 0..255 : b / 255.0 > tau} (tau = 0.5: 32768).
+ * Both pointers 4-B aligned; a 16-B aligned logits with W % 4 == 0 takes the float4 path. One launch, no atomics, no workspace:
+ * deterministic. -1 for a NULL or misaligned pointer, out == logits, n < 1, a side < 1, need outside 1..65536; -2 for a side over
+ * 4096; nothing is written in either case. */
+int haff_mask_quantile7(const float* logits, int n, int H, int W, int need, float* out, void* stream);
 /* ---- benchmark scoring and validation metrics on the device (calculate_iou.py:117-337 as evaluation.py restates it,
  * 2Haff/train_ds.py:625-796; csrc/mask_score.hip) ----
  * One frame of a haff_score_masks batch: 128 bytes, every pointer a DEVICE pointer. */
