@@ -220,3 +220,73 @@ def gaussian_blur7_u8(img):
     hor = sum(c * a[:, ix] for c, ix in zip(_GAUSS7, cols))
     ver = sum(c * hor[iy] for c, iy in zip(_GAUSS7, rows))
     return ((ver + 32768) >> 16).astype(np.uint8)
+
+
+def pad_to_square(img):
+    """pad_image (2HANDS/scripts/affordance_extraction_preparation.py:53-61): cv2.copyMakeBorder with zeros up to the square of the
+    longer side; a portrait image (h > w) is padded on the LEFT, any other on the TOP."""
+    img = np.asarray(img)
+    h, w = img.shape[:2]
+    out = np.zeros((max(h, w), max(h, w)) + img.shape[2:], dtype=img.dtype)
+    if h > w:
+        out[:, h - w:] = img
+    else:
+        out[w - h:, :] = img
+    return out
+
+
+def resize_nearest(img, size):
+    """cv2.resize(img, (w, h), interpolation=cv2.INTER_NEAREST). Restated from OpenCV's resizeNN (modules/imgproc/src/resize.cpp):
+    per axis the source index is min(cvFloor(x * ifx), n_src - 1) with ifx = 1. / ((double)n_dst / n_src), in IEEE double exactly
+    in that order, which is not the exact rational floor (34 columns from 6: column 17 reads 2, not 3). Unpinned against cv2."""
+    img = np.asarray(img)
+    w, h = int(size[0]), int(size[1])
+    sh, sw = img.shape[:2]
+    xs = np.minimum(np.floor(np.arange(w, dtype=np.float64) * (1.0 / (w / sw))), sw - 1).astype(np.int64)
+    ys = np.minimum(np.floor(np.arange(h, dtype=np.float64) * (1.0 / (h / sh))), sh - 1).astype(np.int64)
+    return img[ys][:, xs]
+
+
+def dilate_rect(img, k):
+    """cv2.dilate(img, np.ones((k, k), np.uint8), iterations=1) of a 2-D uint8 image: the grey maximum over the k x k rectangle.
+    Restated from OpenCV's morphology (modules/imgproc/src/morph.dispatch.cpp): the default anchor (-1, -1) is the centre
+    (k // 2, k // 2), so the window of pixel x is [x - k // 2, x + k - 1 - k // 2] (not symmetric for even k), and the default
+    border, morphologyDefaultBorderValue, is the minimum for a dilation: taps outside the image stay out of the maximum.
+    Unpinned against cv2."""
+    img = np.asarray(img)
+    if img.ndim != 2 or img.dtype != np.uint8:
+        raise ValueError("dilate_rect takes a 2-D uint8 image")
+    k = int(k)
+    if k < 1:
+        raise ValueError("dilate_rect: k >= 1")
+    h, w = img.shape
+    lo = k // 2
+    pad = np.zeros((h + k - 1, w + k - 1), dtype=np.uint8)
+    pad[lo:lo + h, lo:lo + w] = img
+    hor = pad[:, 0:w].copy()
+    for s in range(1, k):
+        np.maximum(hor, pad[:, s:s + w], out=hor)
+    out = hor[0:h].copy()
+    for s in range(1, k):
+        np.maximum(out, hor[s:s + h], out=out)
+    return out
+
+
+def extract_affordance(completed, hand):
+    """extract_affordances' arithmetic (affordance_extraction_preparation.py:284-292, misc/determine_mask_overlap.py): the hand mask
+    padded to a square, resized nearest to the completed mask when the shapes differ, then cv2.bitwise_and: the AND of the grey
+    VALUES bit by bit (1 & 2 is 0), not of `!= 0`."""
+    completed, hand = np.asarray(completed), np.asarray(hand)
+    hand = pad_to_square(hand)
+    if completed.shape != hand.shape:
+        hand = resize_nearest(hand, (completed.shape[1], completed.shape[0]))
+    return np.bitwise_and(completed, hand)
+
+
+def process_affordance(mask, k):
+    """process_affordances on one mask (affordance_extraction_preparation.py:298-304): None for a mask delete_empty_masks removes
+    (all zero, tested BEFORE the dilation), else dilate_rect(mask, k) with every non-zero pixel recoloured to 255."""
+    mask = np.asarray(mask)
+    if not mask.any():
+        return None
+    return np.where(dilate_rect(mask, k) != 0, 255, 0).astype(np.uint8)

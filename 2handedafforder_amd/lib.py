@@ -205,6 +205,7 @@ _PROTOS = {
     "haff_contour_hausdorff_workspace": [c_void_p, c_int, c_int, c_void_p],
     "haff_contour_extract": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p],
     "haff_contour_extract_workspace": [c_void_p, c_int, c_int, c_int, c_void_p],
+    "haff_affordance_extract": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     # ---- training path (csrc/train.hip + batched GEMMs) ----
     "haff_gemm_bf16_batched": [c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_long,
                                c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],

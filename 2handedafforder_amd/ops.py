@@ -1447,3 +1447,117 @@ def contour_extract(planes, max_contours=1024, max_vertices=65536, out=None):
                                       verts.data_ptr(), offsets.data_ptr(), summary.data_ptr(), _stream())
     check(rc, "haff_contour_extract")
     return summary, offsets, verts
+
+
+AFF_EXTRACT_ITEM_WORDS = 8              # haff_extract_item (include/haff_hip.h): 64 bytes as 8 int64 words
+AFF_EXTRACT_MAX_SIDE, AFF_EXTRACT_MAX_K = 4096, 31
+AFF_EXTRACT_HAND, AFF_EXTRACT_GREY = 1, 2   # stats[:, 7]: a hand was ANDed in / `a` holds a value other than 0 and 255
+AFF_EXTRACT_STATS = ("nonzero_a", "nonzero_out", "sum_a", "min_row", "max_row", "min_col", "max_col", "flags")
+
+
+def nearest_pad_tables(hand_hw, out_hw, device=None):
+    """The gather tables of `cv2.resize(pad_image(hand), (W, H), interpolation=INTER_NEAREST)` for a hand mask of shape hand_hw and a
+    plane of shape out_hw = (H, W): int32 (col [W], row [H]), the hand's own column / row each output column / row reads, -1 for
+    the padding. pad_image (affordance_extraction_preparation.py:53-61) pads to the square of side S = max(Hh, Wh): a portrait
+    mask (Hh > Wh) on the LEFT, any other on the TOP. resizeNN computes its indices in double, and not as the exact rational floor:
+    p = min(floor(x * (1.0 / (D / S))), S - 1) with the division and the reciprocal in IEEE double in that order (D = 34, S = 6,
+    x = 17 reads 2, not 17 * 6 // 34 = 3). The reference skips the resize when the padded hand already has the plane's shape: the
+    formula gives the identity for D == S, which is asserted here. CPU tensors, or on `device`."""
+    import numpy as np
+    Hh, Wh = int(hand_hw[0]), int(hand_hw[1])
+    H, W = int(out_hw[0]), int(out_hw[1])
+    assert Hh >= 1 and Wh >= 1 and H >= 1 and W >= 1, (hand_hw, out_hw)
+    S = max(Hh, Wh)
+
+    def axis(D, pad):
+        inv = 1.0 / (D / S)                                   # Python floats are IEEE doubles
+        p = np.minimum(np.floor(np.arange(D, dtype=np.float64) * inv), S - 1).astype(np.int64)
+        if D == S:
+            assert np.array_equal(p, np.arange(S)), "the nearest table of an unchanged length is the identity"
+        p = p - pad
+        p[p < 0] = -1
+        return torch.from_numpy(p.astype(np.int32))
+
+    col, row = axis(W, S - Wh if Hh > Wh else 0), axis(H, 0 if Hh > Wh else S - Hh)
+    if device is not None:
+        col, row = col.to(device), row.to(device)
+    return col, row
+
+
+def affordance_extract(items, k, stats=None):
+    """haff_affordance_extract on a batch of any mix of shapes. items: a list of (plane, hand, tables, out): plane = uint8 CUDA [H, W];
+    hand = None or uint8 CUDA [Hh, Wh] with tables = (col int32 [W], row int32 [H]) on the device as nearest_pad_tables builds them
+    (items of one geometry may share them); out = None (statistics only) or uint8 CUDA [H, W]. k: the dilation's side, 1..31.
+    a = plane & hand[row][:, col] (bitwise; 0 in the padding), out = 255 where the k x k window (anchor k // 2) holds a non-zero a.
+    Returns int64 [n, 8] on the device, columns AFF_EXTRACT_STATS, zeroed by the call itself. Only enqueues: no synchronisation, the
+    caller keeps the tensors alive until the stream has run. Every refusal is raised before anything is written."""
+    lib = load_library()
+    items = list(items)
+    if not items:
+        raise ValueError("affordance_extract: no items")
+    k = int(k)
+    if not 1 <= k <= AFF_EXTRACT_MAX_K:
+        raise ValueError(f"affordance_extract: k = {k} is outside 1..{AFF_EXTRACT_MAX_K}")
+
+    def u8(t, name, i):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"affordance_extract: item {i}: {name} must live in HBM (cuda tensor); there is no CPU fallback")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"affordance_extract: item {i}: {name} is {t.dtype}, not uint8")
+        if t.dim() != 2 or t.numel() == 0:
+            raise ValueError(f"affordance_extract: item {i}: {name} has shape {tuple(t.shape)}, not [H, W]")
+        if not t.is_contiguous():
+            raise ValueError(f"affordance_extract: item {i}: {name} is not contiguous")
+        if max(t.shape) > AFF_EXTRACT_MAX_SIDE:
+            raise ValueError(f"affordance_extract: item {i}: {name} has a side over {AFF_EXTRACT_MAX_SIDE}")
+
+    def table(t, name, i, length):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"affordance_extract: item {i}: {name} table must live in HBM (cuda tensor)")
+        if t.dtype != torch.int32:
+            raise TypeError(f"affordance_extract: item {i}: {name} table is {t.dtype}, not int32")
+        if not t.is_contiguous():
+            raise ValueError(f"affordance_extract: item {i}: {name} table is not contiguous")
+        if t.dim() != 1 or t.numel() != length:
+            raise ValueError(f"affordance_extract: item {i}: {name} table has shape {tuple(t.shape)}, not [{length}]")
+
+    n = len(items)
+    host = torch.zeros((n, AFF_EXTRACT_ITEM_WORDS), dtype=torch.int64, pin_memory=True)
+    h64 = host.numpy()
+    h32 = h64.view("int32")
+    device = None
+    for i, (plane, hand, tables, out) in enumerate(items):
+        u8(plane, "plane", i)
+        device = plane.device if device is None else device
+        H, W = plane.shape
+        Hh = Wh = 0
+        if hand is not None:
+            u8(hand, "hand", i)
+            if tables is None or len(tables) != 2:
+                raise ValueError(f"affordance_extract: item {i}: a hand needs its (col, row) tables")
+            table(tables[0], "col", i, W)
+            table(tables[1], "row", i, H)
+            Hh, Wh = hand.shape
+        if out is not None:
+            u8(out, "out", i)
+            if tuple(out.shape) != (H, W):
+                raise ValueError(f"affordance_extract: item {i}: out has shape {tuple(out.shape)}, the plane {(H, W)}")
+        for t in (hand, out) + (tuple(tables) if hand is not None else ()):
+            if t is not None and t.device != device:
+                raise RuntimeError(f"affordance_extract: item {i}: tensors on {t.device} and {device}")
+        if plane.device != device:
+            raise RuntimeError(f"affordance_extract: item {i}: tensors on {plane.device} and {device}")
+        h64[i, 0] = plane.data_ptr()
+        h64[i, 1] = _p(hand)
+        h64[i, 2] = tables[0].data_ptr() if hand is not None else 0
+        h64[i, 3] = tables[1].data_ptr() if hand is not None else 0
+        h64[i, 4] = _p(out)
+        h32[i, 10:14] = (H, W, Hh, Wh)
+    if stats is None:
+        stats = torch.empty((n, 8), dtype=torch.int64, device=device)
+    assert stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (n, 8) and stats.device == device
+    with torch.cuda.device(device):
+        dev = host.to(device, non_blocking=True)
+        rc = lib.haff_affordance_extract(host.data_ptr(), dev.data_ptr(), n, k, stats.data_ptr(), _stream())
+    check(rc, "haff_affordance_extract")
+    return stats

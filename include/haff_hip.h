@@ -699,6 +699,36 @@ int haff_contour_extract(const void* planes_host, const void* planes_dev, int n_
 /* Host only: *bytes_out = the workspace haff_contour_extract needs. The same refusals for the plane table, max_contours and
  * max_vertices; -1 for a NULL bytes_out. */
 int haff_contour_extract_workspace(const void* planes_host, int n_planes, int max_contours, int max_vertices, long* bytes_out);
+/* ---- 2HANDS records from hand and object masks (2HANDS/scripts/affordance_extraction_preparation.py:256-304: pad_image,
+ * cv2.resize(INTER_NEAREST), cv2.bitwise_and, delete_empty_masks, cv2.dilate, recolor_masks_white, as cvlite.extract_affordance and
+ * cvlite.process_affordance restate them; csrc/affordance_extract.hip) ----
+ * One item of a haff_affordance_extract batch: 64 bytes, every pointer a DEVICE pointer. */
+typedef struct haff_extract_item {
+  const unsigned char* in;        /* u8 [H][W] at any address: the completed mask, or any plane to process */
+  const unsigned char* hand;      /* u8 [Hh][Wh] at any address; NULL = no AND */
+  const int* col;                 /* i32 [W]: the hand's source column of every column, -1 (or anything outside 0..Wh-1) = padding */
+  const int* row;                 /* i32 [H]: the same for rows; both tables are read only with a hand and may be shared by items */
+  unsigned char* out;             /* u8 [H][W] at any address, not `in`; NULL = statistics only */
+  int H, W, Hh, Wh;
+  int pad[2];
+} haff_extract_item;
+/* a(y, x) = in(y, x) & hand[row[y]][col[x]], BITWISE as cv2.bitwise_and (1 & 2 = 0), 0 where either index is padding; in(y, x)
+ * without a hand. out(y, x) = 255 when any a(y', x') != 0 with x' in [x - k/2, x + k - 1 - k/2] and y' in [y - k/2, y + k - 1 - k/2]
+ * inside the image, else 0: cv2.dilate with np.ones((k, k)), the default anchor (k/2, k/2) and the default border, which keeps
+ * taps outside the image out of the maximum, followed by recolor_masks_white. For even k the window is not symmetric: a lone pixel
+ * at column 5 turns on columns 4..7 for k = 4, one at column 0 columns 0..2. k = 1 is the recolour alone.
+ *   stats  i64 [n_items][8], every word written by the call (a kernel in front of the main launch, same stream):
+ *          {non-zero pixels of a (delete_empty_masks' test, BEFORE the dilation), non-zero pixels of out, sum of the values of a,
+ *           min row, max row, min column, max column of out's on pixels (H, -1, W, -1 for an empty plane), flags}.
+ *          flags: 1 a hand was ANDed in, 2 a holds a value other than 0 and 255 (its sum / 255 is then no pixel count).
+ * Two launches over grid (16 x 64 tiles of the largest item, items); integer atomics on order-independent values only: repeat runs
+ * are bitwise equal. items_host is the HOST copy of the descriptors, checked here and never read by a kernel; items_dev the
+ * caller's DEVICE copy, uploaded in stream order before the call. The tables' lengths are the caller's to check; their values are
+ * bounds-checked by the kernel.
+ * Refused before anything is enqueued: -1 for a NULL table or stats, one that is not 8-B aligned, n_items outside 1..65535, a NULL
+ * in, out == in, a side <= 0, a hand without both tables or with one that is not 4-B aligned; -2 for k outside 1..31 or a side
+ * (of the plane or the hand) over 4096. */
+int haff_affordance_extract(const void* items_host, const void* items_dev, int n_items, int k, void* stats, void* stream);
 
 
 /* ==== training path (LoRA fine-tune: train_ds.py:489-622 driving model_forward, LISA.py:175-430) ==================
