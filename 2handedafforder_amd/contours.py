@@ -11,6 +11,12 @@ import torch
 from . import cvlite, ops
 
 
+def host_walk(counter, walk, *planes):
+    """The one rule for planes the device flagged or does not take: counted in counter.host_walks, read back, walked on the host."""
+    counter.host_walks += 1
+    return walk(*(p.cpu().numpy() for p in planes))
+
+
 class ContourReader:
     """read(planes) -> per plane the list of int32 [n, 1, 2] arrays `cvlite.find_contours_external(plane)` returns, element for
     element. planes: uint8 CUDA tensors [H, W] (a list, or one [n, H, W] tensor), on where != 0. max_contours / max_vertices are
@@ -33,8 +39,7 @@ class ContourReader:
         for i, plane in enumerate(planes):
             n_contours, n_vertices, flags = (int(v) for v in summary[i, :3])
             if flags:
-                self.host_walks += 1
-                out.append(cvlite.find_contours_external(plane.cpu().numpy()))
+                out.append(host_walk(self, cvlite.find_contours_external, plane))
                 continue
             if n_contours == 0:
                 out.append([])

@@ -184,9 +184,7 @@ __global__ __launch_bounds__(256) void affordance_extract_kernel(const ExtractIt
 
 extern "C" int haff_affordance_extract(const void* items_host, const void* items_dev, int n_items, int k, void* stats, void* stream) {
   if (!items_host || !items_dev || !stats || n_items <= 0 || n_items > 65535) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(items_host) & 7) || (reinterpret_cast<uintptr_t>(items_dev) & 7) ||
-      (reinterpret_cast<uintptr_t>(stats) & 7))
-    return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(items_host, 8) || !haff_aligned(items_dev, 8) || !haff_aligned(stats, 8)) return HAFF_ERR_BAD_ARG;
   if (k < 1 || k > kMaxK) return HAFF_ERR_UNSUPPORTED;
   const ExtractItem* items = static_cast<const ExtractItem*>(items_host);
   long tiles = 1;
@@ -195,7 +193,7 @@ extern "C" int haff_affordance_extract(const void* items_host, const void* items
     if (!it.in || it.H <= 0 || it.W <= 0 || it.in == it.out) return HAFF_ERR_BAD_ARG;
     if (it.hand) {
       if (!it.col || !it.row || it.Hh <= 0 || it.Wh <= 0) return HAFF_ERR_BAD_ARG;
-      if ((reinterpret_cast<uintptr_t>(it.col) & 3) || (reinterpret_cast<uintptr_t>(it.row) & 3)) return HAFF_ERR_BAD_ARG;
+      if (!haff_aligned(it.col, 4) || !haff_aligned(it.row, 4)) return HAFF_ERR_BAD_ARG;
       if (it.Hh > kMaxSide || it.Wh > kMaxSide) return HAFF_ERR_UNSUPPORTED;
     }
     if (it.H > kMaxSide || it.W > kMaxSide) return HAFF_ERR_UNSUPPORTED;

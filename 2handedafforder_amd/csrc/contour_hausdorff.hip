@@ -362,34 +362,63 @@ __global__ __launch_bounds__(256) void hausdorff_d2_kernel(const int* pairs, con
   }
 }
 
-struct Layout { long labels, bits, state, verts, counts, total; };
+// the workspace's areas (byte offsets) and what the launches need of the plane table
+struct Layout {
+  long labels, bits, state, verts, counts, total;
+  long words;                             // 64-pixel words of all packed planes
+  int max_tiles, rb;                      // the labelling grids' x: tiles of the largest plane, label_root_kernel's workgroups
+  int lds_words;                          // the walk's LDS: the largest packed plane of the batch that fits kWalkLdsBytes
+};
 
 // 0, or the refusal code of the plane table / max_vertices
-int plan(const Plane* pl, int n_planes, int max_vertices, Layout& lay, int& max_tiles, long& max_pixels) {
-  long words = 0;
+int plan(const Plane* pl, int n_planes, int max_vertices, Layout& lay) {
   if (!pl || n_planes <= 0 || n_planes > kMaxPlanes) return HAFF_ERR_BAD_ARG;
-  if (reinterpret_cast<uintptr_t>(pl) & 7) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(pl, 8)) return HAFF_ERR_BAD_ARG;
   if (max_vertices < 1 || max_vertices > kMaxVertices) return HAFF_ERR_BAD_ARG;
-  long ints = 0;
-  max_tiles = 1;
-  max_pixels = 1;
+  long ints = 0, max_pixels = 1;
+  lay.words = 0;
+  lay.max_tiles = 1;
+  lay.lds_words = 0;
   for (int i = 0; i < n_planes; ++i) {
     if (pl[i].H <= 0 || pl[i].W <= 0) return HAFF_ERR_BAD_ARG;
     if (pl[i].H > kMaxSide || pl[i].W > kMaxSide) return HAFF_ERR_UNSUPPORTED;
-    const long n = (long)pl[i].H * pl[i].W;
+    const long n = (long)pl[i].H * pl[i].W, w = (n + 63) / 64;
     ints += align_up(n, 4);
-    words += (n + 63) / 64;
+    lay.words += w;
+    if (w * 8 <= kWalkLdsBytes && w > lay.lds_words) lay.lds_words = (int)w;
     const int t = ((pl[i].W + kTile - 1) / kTile) * ((pl[i].H + kTile - 1) / kTile);
-    max_tiles = t > max_tiles ? t : max_tiles;
+    lay.max_tiles = t > lay.max_tiles ? t : lay.max_tiles;
     max_pixels = n > max_pixels ? n : max_pixels;
   }
+  const long rb = (max_pixels + 256L * 4 - 1) / (256L * 4);
+  lay.rb = rb > 256 ? 256 : (int)rb;
   lay.labels = 0;
   lay.bits = align_up(ints * 4, 16);
-  lay.state = align_up(lay.bits + words * 8, 16);
+  lay.state = align_up(lay.bits + lay.words * 8, 16);
   lay.verts = align_up(lay.state + (long)n_planes * (long)sizeof(PlaneState), 16);
   lay.counts = lay.verts + (long)n_planes * max_vertices * 4;
   lay.total = align_up(lay.counts + (long)n_planes * 4, 16);
   return HAFF_OK;
+}
+
+struct Labelled { int* labels; unsigned long long* bits; PlaneState* st; };
+
+// stages 1a-1c (and 2) on the caller's stream: the three areas both entry points share, labelled and packed
+Labelled launch_labelling(const Layout& lay, char* ws, const Plane* pd, int n_planes, hipStream_t s) {
+  const Labelled l{reinterpret_cast<int*>(ws + lay.labels), reinterpret_cast<unsigned long long*>(ws + lay.bits),
+                   reinterpret_cast<PlaneState*>(ws + lay.state)};
+  const dim3 tiles((unsigned)lay.max_tiles, (unsigned)n_planes);
+  hipLaunchKernelGGL(ch_setup_kernel, dim3((unsigned)((n_planes + 255) / 256)), dim3(256), 0, s, pd, n_planes, l.st);
+  hipLaunchKernelGGL(label_tile_kernel, tiles, dim3(256), 0, s, pd, l.st, l.labels);
+  hipLaunchKernelGGL(label_seam_kernel, tiles, dim3(256), 0, s, pd, l.st, l.labels);
+  hipLaunchKernelGGL(label_root_kernel, dim3((unsigned)lay.rb, (unsigned)n_planes), dim3(256), 0, s, pd, l.st, l.labels, l.bits);
+  return l;
+}
+
+// a walk kernel may take kWalkLdsBytes of dynamic LDS
+template <typename K> bool allow_walk_lds(K kernel) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kWalkLdsBytes) ==
+         hipSuccess;
 }
 
 // ---- haff_contour_extract: every external contour of every plane (cvlite.find_contours_external, all of it) -------------------
@@ -556,15 +585,12 @@ __global__ __launch_bounds__(256) void extract_offsets_kernel(const PlaneState* 
 struct ExtractLayout { long start_bits, starts, counts, n_contours, total; };
 
 // plan()'s refusals, max_contours, and the extract stages' areas behind the labelling's (lay.verts is where plan()'s own end)
-int plan_extract(const Plane* pl, int n_planes, int max_contours, int max_vertices, Layout& lay, ExtractLayout& ext, int& max_tiles,
-                 long& max_pixels) {
-  const int rc = plan(pl, n_planes, max_vertices, lay, max_tiles, max_pixels);
+int plan_extract(const Plane* pl, int n_planes, int max_contours, int max_vertices, Layout& lay, ExtractLayout& ext) {
+  const int rc = plan(pl, n_planes, max_vertices, lay);
   if (rc != HAFF_OK) return rc;
   if (max_contours < 1 || max_contours > kMaxContours) return HAFF_ERR_BAD_ARG;
-  long words = 0;
-  for (int i = 0; i < n_planes; ++i) words += ((long)pl[i].H * pl[i].W + 63) / 64;
   ext.start_bits = lay.verts;
-  ext.starts = align_up(ext.start_bits + words * 8, 16);
+  ext.starts = align_up(ext.start_bits + lay.words * 8, 16);
   ext.counts = align_up(ext.starts + (long)n_planes * max_contours * 4, 16);
   ext.n_contours = align_up(ext.counts + (long)n_planes * max_contours * 4, 16);
   ext.total = align_up(ext.n_contours + (long)n_planes * 4, 16);
@@ -578,10 +604,7 @@ extern "C" int haff_contour_extract_workspace(const void* planes_host, int n_pla
   if (!bytes_out) return HAFF_ERR_BAD_ARG;
   Layout lay;
   ExtractLayout ext;
-  int max_tiles;
-  long max_pixels;
-  const int rc = plan_extract(static_cast<const Plane*>(planes_host), n_planes, max_contours, max_vertices, lay, ext, max_tiles,
-                              max_pixels);
+  const int rc = plan_extract(static_cast<const Plane*>(planes_host), n_planes, max_contours, max_vertices, lay, ext);
   if (rc != HAFF_OK) return rc;
   *bytes_out = ext.total;
   return HAFF_OK;
@@ -592,68 +615,45 @@ extern "C" int haff_contour_extract(const void* planes_host, const void* planes_
   if (!planes_host || !planes_dev || !workspace || !verts || !offsets || !summary) return HAFF_ERR_BAD_ARG;
   Layout lay;
   ExtractLayout ext;
-  int max_tiles;
-  long max_pixels;
-  const Plane* pl = static_cast<const Plane*>(planes_host);
-  const int rc = plan_extract(pl, n_planes, max_contours, max_vertices, lay, ext, max_tiles, max_pixels);
+  const int rc = plan_extract(static_cast<const Plane*>(planes_host), n_planes, max_contours, max_vertices, lay, ext);
   if (rc != HAFF_OK) return rc;
-  if ((reinterpret_cast<uintptr_t>(planes_dev) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
-      (reinterpret_cast<uintptr_t>(verts) & 3) || (reinterpret_cast<uintptr_t>(offsets) & 3) ||
-      (reinterpret_cast<uintptr_t>(summary) & 3))
+  if (!haff_aligned(planes_dev, 8) || !haff_aligned(workspace, 16) || !haff_aligned(verts, 4) || !haff_aligned(offsets, 4) ||
+      !haff_aligned(summary, 4))
     return HAFF_ERR_BAD_ARG;
   if (workspace_bytes < ext.total) return HAFF_ERR_BAD_ARG;
   char* ws = static_cast<char*>(workspace);
-  int* labels = reinterpret_cast<int*>(ws + lay.labels);
-  unsigned long long* bits = reinterpret_cast<unsigned long long*>(ws + lay.bits);
-  PlaneState* st = reinterpret_cast<PlaneState*>(ws + lay.state);
   unsigned long long* start_bits = reinterpret_cast<unsigned long long*>(ws + ext.start_bits);
   int* starts = reinterpret_cast<int*>(ws + ext.starts);
   int* counts = reinterpret_cast<int*>(ws + ext.counts);
   int* n_contours = reinterpret_cast<int*>(ws + ext.n_contours);
   const Plane* pd = static_cast<const Plane*>(planes_dev);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int lds_words = 0;
-  for (int i = 0; i < n_planes; ++i) {
-    const long w = ((long)pl[i].H * pl[i].W + 63) / 64;
-    if (w * 8 <= kWalkLdsBytes && w > lds_words) lds_words = (int)w;
-  }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(extract_walk_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          kWalkLdsBytes) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(extract_walk_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          kWalkLdsBytes) != hipSuccess)
-    return HAFF_ERR_LAUNCH;
-  const dim3 tiles((unsigned)max_tiles, (unsigned)n_planes);
-  long rb = (max_pixels + 256L * 4 - 1) / (256L * 4);
-  rb = rb > 256 ? 256 : rb;
-  const dim3 roots((unsigned)rb, (unsigned)n_planes);
+  if (!allow_walk_lds(extract_walk_kernel<false>) || !allow_walk_lds(extract_walk_kernel<true>)) return HAFF_ERR_LAUNCH;
+  const dim3 roots((unsigned)lay.rb, (unsigned)n_planes);
   int wg = (max_contours + 3) / 4;
   wg = wg > kWalkGrid ? kWalkGrid : wg;
   const dim3 walks((unsigned)wg, (unsigned)n_planes);
+  const size_t lds = (size_t)lay.lds_words * 8;
   int* offs = static_cast<int*>(offsets);
   int* sum = static_cast<int*>(summary);
   short2* v = static_cast<short2*>(verts);
-  hipLaunchKernelGGL(ch_setup_kernel, dim3((unsigned)((n_planes + 255) / 256)), dim3(256), 0, s, pd, n_planes, st);
-  hipLaunchKernelGGL(label_tile_kernel, tiles, dim3(256), 0, s, pd, st, labels);
-  hipLaunchKernelGGL(label_seam_kernel, tiles, dim3(256), 0, s, pd, st, labels);
-  hipLaunchKernelGGL(label_root_kernel, roots, dim3(256), 0, s, pd, st, labels, bits);
-  hipLaunchKernelGGL(extract_start_kernel, roots, dim3(256), 0, s, pd, st, labels, start_bits);
-  hipLaunchKernelGGL(extract_number_kernel, dim3((unsigned)n_planes), dim3(256), 0, s, pd, st, start_bits, starts, n_contours,
+  const Labelled l = launch_labelling(lay, ws, pd, n_planes, s);
+  hipLaunchKernelGGL(extract_start_kernel, roots, dim3(256), 0, s, pd, l.st, l.labels, start_bits);
+  hipLaunchKernelGGL(extract_number_kernel, dim3((unsigned)n_planes), dim3(256), 0, s, pd, l.st, start_bits, starts, n_contours,
                      max_contours);
-  hipLaunchKernelGGL(extract_walk_kernel<false>, walks, dim3(256), (size_t)lds_words * 8, s, pd, st, bits, starts, n_contours, counts,
-                     offs, sum, v, max_contours, max_vertices, lds_words);
-  hipLaunchKernelGGL(extract_offsets_kernel, dim3((unsigned)n_planes), dim3(256), 0, s, st, n_contours, counts, offs, sum,
+  hipLaunchKernelGGL(extract_walk_kernel<false>, walks, dim3(256), lds, s, pd, l.st, l.bits, starts, n_contours, counts, offs, sum, v,
+                     max_contours, max_vertices, lay.lds_words);
+  hipLaunchKernelGGL(extract_offsets_kernel, dim3((unsigned)n_planes), dim3(256), 0, s, l.st, n_contours, counts, offs, sum,
                      max_contours, max_vertices);
-  hipLaunchKernelGGL(extract_walk_kernel<true>, walks, dim3(256), (size_t)lds_words * 8, s, pd, st, bits, starts, n_contours, counts,
-                     offs, sum, v, max_contours, max_vertices, lds_words);
+  hipLaunchKernelGGL(extract_walk_kernel<true>, walks, dim3(256), lds, s, pd, l.st, l.bits, starts, n_contours, counts, offs, sum, v,
+                     max_contours, max_vertices, lay.lds_words);
   return haff_check_launch();
 }
 
 extern "C" int haff_contour_hausdorff_workspace(const void* planes_host, int n_planes, int max_vertices, long* bytes_out) {
   if (!bytes_out) return HAFF_ERR_BAD_ARG;
   Layout lay;
-  int max_tiles;
-  long max_pixels;
-  const int rc = plan(static_cast<const Plane*>(planes_host), n_planes, max_vertices, lay, max_tiles, max_pixels);
+  const int rc = plan(static_cast<const Plane*>(planes_host), n_planes, max_vertices, lay);
   if (rc != HAFF_OK) return rc;
   *bytes_out = lay.total;
   return HAFF_OK;
@@ -665,14 +665,11 @@ extern "C" int haff_contour_hausdorff(const void* planes_host, const void* plane
   if (!planes_host || !planes_dev || !pairs_host || !pairs_dev || !result || !workspace) return HAFF_ERR_BAD_ARG;
   if (n_pairs <= 0 || n_pairs > kMaxPairs) return HAFF_ERR_BAD_ARG;
   Layout lay;
-  int max_tiles;
-  long max_pixels;
   const Plane* pl = static_cast<const Plane*>(planes_host);
-  const int rc = plan(pl, n_planes, max_vertices, lay, max_tiles, max_pixels);
+  const int rc = plan(pl, n_planes, max_vertices, lay);
   if (rc != HAFF_OK) return rc;
-  if ((reinterpret_cast<uintptr_t>(planes_dev) & 7) || (reinterpret_cast<uintptr_t>(pairs_host) & 3) ||
-      (reinterpret_cast<uintptr_t>(pairs_dev) & 3) || (reinterpret_cast<uintptr_t>(result) & 3) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(verts_out) & 3))
+  if (!haff_aligned(planes_dev, 8) || !haff_aligned(pairs_host, 4) || !haff_aligned(pairs_dev, 4) || !haff_aligned(result, 4) ||
+      !haff_aligned(workspace, 16) || !haff_aligned(verts_out, 4))
     return HAFF_ERR_BAD_ARG;
   if (workspace_bytes < lay.total) return HAFF_ERR_BAD_ARG;
   for (int i = 0; i < n_pairs; ++i) {
@@ -681,31 +678,15 @@ extern "C" int haff_contour_hausdorff(const void* planes_host, const void* plane
     if (pl[b].H != pl[p].H || pl[b].W != pl[p].W) return HAFF_ERR_BAD_ARG;
   }
   char* ws = static_cast<char*>(workspace);
-  int* labels = reinterpret_cast<int*>(ws + lay.labels);
-  unsigned long long* bits = reinterpret_cast<unsigned long long*>(ws + lay.bits);
-  PlaneState* st = reinterpret_cast<PlaneState*>(ws + lay.state);
   short2* verts = reinterpret_cast<short2*>(verts_out ? static_cast<char*>(verts_out) : ws + lay.verts);
   int* counts = reinterpret_cast<int*>(verts_out ? static_cast<char*>(verts_out) + (long)n_planes * max_vertices * 4 : ws + lay.counts);
   const Plane* pd = static_cast<const Plane*>(planes_dev);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // the walk's LDS: the largest packed plane of the batch that fits kWalkLdsBytes
-  int lds_words = 0;
-  for (int i = 0; i < n_planes; ++i) {
-    const long w = ((long)pl[i].H * pl[i].W + 63) / 64;
-    if (w * 8 <= kWalkLdsBytes && w > lds_words) lds_words = (int)w;
-  }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(contour_walk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          kWalkLdsBytes) != hipSuccess)
-    return HAFF_ERR_LAUNCH;
-  const dim3 tiles((unsigned)max_tiles, (unsigned)n_planes);
-  long rb = (max_pixels + 256L * 4 - 1) / (256L * 4);
-  rb = rb > 256 ? 256 : rb;
-  hipLaunchKernelGGL(ch_setup_kernel, dim3((unsigned)((n_planes + 255) / 256)), dim3(256), 0, s, pd, n_planes, st);
-  hipLaunchKernelGGL(label_tile_kernel, tiles, dim3(256), 0, s, pd, st, labels);
-  hipLaunchKernelGGL(label_seam_kernel, tiles, dim3(256), 0, s, pd, st, labels);
-  hipLaunchKernelGGL(label_root_kernel, dim3((unsigned)rb, (unsigned)n_planes), dim3(256), 0, s, pd, st, labels, bits);
-  hipLaunchKernelGGL(contour_walk_kernel, dim3((unsigned)n_planes), dim3(256), (size_t)lds_words * 8, s, pd, st, bits, verts, counts,
-                     max_vertices, lds_words);
-  hipLaunchKernelGGL(hausdorff_d2_kernel, dim3((unsigned)n_pairs, 2u), dim3(256), 0, s, pairs_dev, st, verts, max_vertices, static_cast<unsigned*>(result));
+  if (!allow_walk_lds(contour_walk_kernel)) return HAFF_ERR_LAUNCH;
+  const Labelled l = launch_labelling(lay, ws, pd, n_planes, s);
+  hipLaunchKernelGGL(contour_walk_kernel, dim3((unsigned)n_planes), dim3(256), (size_t)lay.lds_words * 8, s, pd, l.st, l.bits, verts,
+                     counts, max_vertices, lay.lds_words);
+  hipLaunchKernelGGL(hausdorff_d2_kernel, dim3((unsigned)n_pairs, 2u), dim3(256), 0, s, pairs_dev, l.st, verts, max_vertices,
+                     static_cast<unsigned*>(result));
   return haff_check_launch();
 }

@@ -218,6 +218,13 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// OpenCV's borderInterpolate for BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), any overshoot
+__device__ __forceinline__ int reflect101(int p, int len) {
+  if (len == 1) return 0;
+  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
+  return p;
+}
+
 static inline int haff_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? HAFF_OK : HAFF_ERR_LAUNCH;

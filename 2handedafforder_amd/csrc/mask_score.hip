@@ -202,9 +202,7 @@ extern "C" int haff_score_masks(const void* frames_host, const void* frames_dev,
                                 int n_th, void* counts, void* stream) {
   if (!frames_host || !frames_dev || !thresholds_host || !counts || n_frames <= 0 || n_frames > 65535) return HAFF_ERR_BAD_ARG;
   if (n_th < 1 || n_th > kMaxTh) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(frames_host) & 7) || (reinterpret_cast<uintptr_t>(frames_dev) & 7) ||
-      (reinterpret_cast<uintptr_t>(counts) & 3))
-    return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(frames_host, 8) || !haff_aligned(frames_dev, 8) || !haff_aligned(counts, 4)) return HAFF_ERR_BAD_ARG;
   const ScoreFrame* fr = static_cast<const ScoreFrame*>(frames_host);
   long blocks = 1;
   for (int i = 0; i < n_frames; ++i) {
@@ -212,9 +210,7 @@ extern "C" int haff_score_masks(const void* frames_host, const void* frames_dev,
     if (f.Hs <= 0 || f.Ws <= 0 || f.Hb <= 0 || f.Wb <= 0) return HAFF_ERR_BAD_ARG;
     if (f.Hs > kMaxSide || f.Ws > kMaxSide || f.Hb > kMaxSide || f.Wb > kMaxSide) return HAFF_ERR_UNSUPPORTED;
     if (f.tax && (f.n_tax < 1 || f.n_tax > kMaxTax)) return HAFF_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(f.logit[0]) & 3) || (reinterpret_cast<uintptr_t>(f.logit[1]) & 3) ||
-        (reinterpret_cast<uintptr_t>(f.tax) & 3))
-      return HAFF_ERR_BAD_ARG;
+    if (!haff_aligned(f.logit[0], 4) || !haff_aligned(f.logit[1], 4) || !haff_aligned(f.tax, 4)) return HAFF_ERR_BAD_ARG;
     for (int h = 0; h < 2; ++h) {
       if (f.gt[h] && (f.gt_hw[h][0] != f.Hb || f.gt_hw[h][1] != f.Wb)) return HAFF_ERR_BAD_ARG;
       if (f.obj[h] && (f.obj_hw[h][0] != f.Hb || f.obj_hw[h][1] != f.Wb)) return HAFF_ERR_BAD_ARG;

@@ -26,13 +26,6 @@ constexpr int kR = 3;                          // 7 taps per axis
 constexpr int kHaloW = kTileW + 2 * kR, kHaloH = kTileH + 2 * kR;
 constexpr unsigned kKeyNegInf = 0x007fffffu;   // key(-inf) = ~0xff800000
 
-// OpenCV's borderInterpolate for BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), any overshoot
-__device__ __forceinline__ int reflect101(int p, int len) {
-  if (len == 1) return 0;
-  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
-  return p;
-}
-
 // float -> uint32 with a < b <=> key(a) < key(b); -0.0 joins +0.0 and NaN joins -inf
 __device__ __forceinline__ unsigned to_key(float x) {
   if (x != x) return kKeyNegInf;
@@ -115,9 +108,9 @@ __global__ __launch_bounds__(256) void mask_quantile7_kernel(const float* logits
 
 extern "C" int haff_mask_quantile7(const float* logits, int n, int H, int W, int need, float* out, void* stream) {
   if (!logits || !out || logits == out || n < 1 || H < 1 || W < 1 || need < 1 || need > 65536) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(logits) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(logits, 4) || !haff_aligned(out, 4)) return HAFF_ERR_BAD_ARG;
   if (H > 4096 || W > 4096) return HAFF_ERR_UNSUPPORTED;
-  const int vec = (W % 4 == 0) && !(reinterpret_cast<uintptr_t>(logits) & 15);
+  const int vec = (W % 4 == 0) && haff_aligned(logits);
   const dim3 grid((unsigned)((W + kTileW - 1) / kTileW), (unsigned)((H + kTileH - 1) / kTileH), (unsigned)(n < 65535 ? n : 65535));
   hipLaunchKernelGGL(mask_quantile7_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits, out, n, H, W, need,
                      vec);

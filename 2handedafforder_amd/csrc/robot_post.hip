@@ -24,13 +24,6 @@ constexpr int kParts = 256;                    // max min/max partials per plane
 constexpr int kTileW = 64, kTileH = 16;        // heatmap output tile per 256-thread workgroup (4 pixels per thread)
 constexpr int kHaloW = kTileW + 4, kHaloH = kTileH + 4;
 
-// OpenCV's borderInterpolate for BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba), any overshoot
-__device__ __forceinline__ int reflect101(int p, int len) {
-  if (len == 1) return 0;
-  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
-  return p;
-}
-
 // min / max over a 256-thread workgroup; every thread gets the result
 __device__ __forceinline__ void block_minmax(float& mn, float& mx, float* red /* [8] */) {
 #pragma unroll
@@ -224,10 +217,10 @@ __global__ __launch_bounds__(256) void robot_mask_kernel(RobotMaskArgs p) {
 extern "C" int haff_robot_heatmap(const float* logits, int n, int H, int W, const void* jet_rgb, float* workspace,
                                   long workspace_floats, void* out, void* stream) {
   if (!logits || !jet_rgb || !workspace || !out || n <= 0 || H <= 0 || W <= 0 || n > 65535) return HAFF_ERR_BAD_ARG;
-  if (workspace_floats < (long)n * kParts * 2 || (reinterpret_cast<uintptr_t>(logits) & 3)) return HAFF_ERR_BAD_ARG;
+  if (workspace_floats < (long)n * kParts * 2 || !haff_aligned(logits, 4)) return HAFF_ERR_BAD_ARG;
   const long hw = (long)H * W;
   if ((H + kTileH - 1) / kTileH > 65535) return HAFF_ERR_UNSUPPORTED;
-  const int vec = (hw % 4 == 0) && !(reinterpret_cast<uintptr_t>(logits) & 15);
+  const int vec = (hw % 4 == 0) && haff_aligned(logits);
   long parts = (hw + 8191) / 8192;                      // >= 8192 elements (8 float4 per thread) per part
   if (parts > kParts) parts = kParts;
   const long chunk = ((hw + parts - 1) / parts + 3) & ~3L;
@@ -247,7 +240,7 @@ extern "C" int haff_robot_mask(const float* logits, int H0, int W0, int left, in
   const long Ho = (long)H0 + top + bottom, Wo = (long)W0 + left + right;
   if (Ho <= 0 || Wo <= 0 || Ho > INT32_MAX || Wo > INT32_MAX) return HAFF_ERR_BAD_ARG;
   if (mask && (mask_h != Ho || mask_w != Wo)) return HAFF_ERR_BAD_ARG;   // cv2.bitwise_and raises on a size mismatch
-  if ((reinterpret_cast<uintptr_t>(out) & 3) || (reinterpret_cast<uintptr_t>(mask) & 3)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(out, 4) || !haff_aligned(mask, 4)) return HAFF_ERR_BAD_ARG;
   RobotMaskArgs p{logits, (const unsigned char*)mask, (unsigned char*)out, H0, W0, (int)Ho, (int)Wo, left, top, th,
                   (unsigned)on_value};
   long g = ((Ho * Wo + 3) / 4 + 255) / 256;

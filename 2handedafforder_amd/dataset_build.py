@@ -55,7 +55,6 @@ from . import cvlite
 
 SIDES = ("left", "right")
 INVALID_VERB_CLASSES = ("eat", "look", "search", "feel", "transition", "wait", "smell", "finish", "unfreeze")
-MAX_SIDE = 4096
 PHASES = ("decode", "kernels", "contours", "writes")
 
 
@@ -146,7 +145,7 @@ class DeviceRoute(_Route):
         torch = self.torch
         res, call, where = [None] * len(items), [], []
         for i, (plane, hand) in enumerate(items):
-            if max(plane.shape) > MAX_SIDE or (hand is not None and max(hand.shape) > MAX_SIDE):
+            if max(plane.shape + (hand.shape if hand is not None else ())) > self.ops.AFF_EXTRACT_MAX_SIDE:
                 self.host_extracts += 1                       # past the kernel's limits: cvlite, counted
                 out, stats = self.host_item(plane, hand, k)
                 res[i] = (torch.from_numpy(out).to(self.device) if want_out else None, stats)
@@ -164,15 +163,16 @@ class DeviceRoute(_Route):
         return res
 
     def contours(self, handles):
-        small = [h for h in handles if max(h.shape) <= MAX_SIDE]
+        from .contours import host_walk
+        max_side = self.ops.HAUSDORFF_MAX_SIDE                # ops.contour_extract's
+        small = [h for h in handles if max(h.shape) <= max_side]
         found = iter(self.reader.read(small)) if small else iter(())
         out = []
         for h in handles:
-            if max(h.shape) <= MAX_SIDE:
+            if max(h.shape) <= max_side:
                 out.append(next(found))
             else:
-                self.reader.host_walks += 1
-                out.append(cvlite.find_contours_external(h.cpu().numpy()))
+                out.append(host_walk(self.reader, cvlite.find_contours_external, h))
         self.host_walks = self.reader.host_walks
         return out
 

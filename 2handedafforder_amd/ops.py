@@ -7,6 +7,7 @@ fp16 inference mode (f16 MFMA, fp32 accumulate: the *_f16 instances of the 16-bi
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from .lib import check, load_library
@@ -63,6 +64,19 @@ def _workspace(device, nbytes):
     if buf is None or buf.numel() < nbytes:
         buf = _WORKSPACES[key] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
     return buf
+
+
+def _out(out, shape, dtype, device):
+    """A wrapper's output: a new tensor, or the caller's, which must be exactly that one (and contiguous)."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=dtype, device=device)
+    assert out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == tuple(shape) and out.device == device, (out.dtype, out.shape)
+    return out
+
+
+def upload_pinned(array, device):
+    """A numpy array as a device tensor, through a pinned staging copy: the upload does not block the host."""
+    return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(device, non_blocking=True)
 
 
 def row_stats(x, eps, rms=False):
@@ -781,7 +795,6 @@ def patchify_nchw(x, P, gh, gw, Kp, out_dtype):
 
 def patchify_u8(frames, P, gh, gw, Kp, mean3, std3, out_dtype):
     """frames uint8 NHWC [B,Hf,Wf,3]; mean3/std3 host sequences of 3 floats (0..255 scale)."""
-    import ctypes
     lib = load_library()
     _req(frames, "frames")
     assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.shape[3] == 3
@@ -967,8 +980,9 @@ def resize_bilinear(x, crop_hw, out_hw):
     assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
     N, Hs, Ws = x.shape
     out = torch.empty((N, out_hw[0], out_hw[1]), dtype=torch.float32, device=x.device)
-    rc = lib.haff_resize_bilinear(x.data_ptr(), out.data_ptr(), N, Hs, Ws, int(crop_hw[0]), int(crop_hw[1]),
-                                  int(out_hw[0]), int(out_hw[1]), _stream())
+    with torch.cuda.device(x.device):
+        rc = lib.haff_resize_bilinear(x.data_ptr(), out.data_ptr(), N, Hs, Ws, int(crop_hw[0]), int(crop_hw[1]),
+                                      int(out_hw[0]), int(out_hw[1]), _stream())
     check(rc, "haff_resize_bilinear")
     return out
 
@@ -978,14 +992,14 @@ def threshold_masks(x, logit_th=0.0):
     _req(x, "x")
     assert x.dtype == torch.float32 and x.is_contiguous()
     out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-    rc = lib.haff_threshold_masks(x.data_ptr(), out.data_ptr(), x.numel(), float(logit_th), _stream())
+    with torch.cuda.device(x.device):
+        rc = lib.haff_threshold_masks(x.data_ptr(), out.data_ptr(), x.numel(), float(logit_th), _stream())
     check(rc, "haff_threshold_masks")
     return out
 
 
 def gate_threshold_masks(x, logit_ths, on_value=255, taxonomy=None, blank_class=-1):
     """x fp32 [...] mask logits of ONE prompt -> uint8 [n_th, ...]: (argmax(taxonomy) != blank_class and x > th) ? on_value : 0."""
-    import ctypes
     lib = load_library()
     _req(x, "x")
     assert x.dtype == torch.float32 and x.is_contiguous()
@@ -996,8 +1010,9 @@ def gate_threshold_masks(x, logit_ths, on_value=255, taxonomy=None, blank_class=
     ths = (ctypes.c_float * n_th)(*[float(v) for v in logit_ths])
     if taxonomy is not None:
         assert taxonomy.dtype == torch.float32 and taxonomy.is_cuda and taxonomy.numel() == 4 and taxonomy.is_contiguous()
-    rc = lib.haff_gate_threshold_masks(x.data_ptr(), buf.data_ptr(), total, stride, ctypes.cast(ths, ctypes.c_void_p), n_th,
-                                       int(on_value), _p(taxonomy), int(blank_class), _stream())
+    with torch.cuda.device(x.device):
+        rc = lib.haff_gate_threshold_masks(x.data_ptr(), buf.data_ptr(), total, stride, ctypes.cast(ths, ctypes.c_void_p), n_th,
+                                           int(on_value), _p(taxonomy), int(blank_class), _stream())
     check(rc, "haff_gate_threshold_masks")
     return buf[:, :total].reshape((n_th,) + tuple(x.shape))
 
@@ -1012,7 +1027,8 @@ def robot_heatmap(logits, jet):
     n, H, W = logits.shape
     ws = torch.empty((n * 512,), dtype=torch.float32, device=logits.device)
     out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=logits.device)
-    rc = lib.haff_robot_heatmap(logits.data_ptr(), n, H, W, jet.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream())
+    with torch.cuda.device(logits.device):
+        rc = lib.haff_robot_heatmap(logits.data_ptr(), n, H, W, jet.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream())
     check(rc, "haff_robot_heatmap")
     return out
 
@@ -1031,12 +1047,10 @@ def robot_mask(logits, th, margins, mask=None, on_value=255, out=None):
         _req(mask, "mask")
         assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 2
         mh, mw = mask.shape
-    shape = (max(H0 + top + bottom, 0), max(W0 + left + right, 0))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=logits.device)
-    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape and out.device == logits.device
-    rc = lib.haff_robot_mask(logits.data_ptr(), H0, W0, left, top, right, bottom, float(th), _p(mask), mh, mw, int(on_value),
-                             out.data_ptr(), _stream())
+    out = _out(out, (max(H0 + top + bottom, 0), max(W0 + left + right, 0)), torch.uint8, logits.device)
+    with torch.cuda.device(logits.device):
+        rc = lib.haff_robot_mask(logits.data_ptr(), H0, W0, left, top, right, bottom, float(th), _p(mask), mh, mw, int(on_value),
+                                 out.data_ptr(), _stream())
     check(rc, "haff_robot_mask")
     return out
 
@@ -1050,7 +1064,8 @@ def mask_quantile7(logits, need):
     assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 3
     n, H, W = logits.shape
     out = torch.empty_like(logits)
-    rc = lib.haff_mask_quantile7(logits.data_ptr(), n, H, W, int(need), out.data_ptr(), _stream())
+    with torch.cuda.device(logits.device):
+        rc = lib.haff_mask_quantile7(logits.data_ptr(), n, H, W, int(need), out.data_ptr(), _stream())
     check(rc, "haff_mask_quantile7")
     return out
 
@@ -1066,8 +1081,9 @@ def resample_u8(frames, out_hw, axis, bounds, coeffs):
     n_out = ow if axis == 0 else oh
     assert bounds.shape == (n_out, 2) and coeffs.shape[0] == n_out and bounds.is_contiguous() and coeffs.is_contiguous()
     out = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=frames.device)
-    rc = lib.haff_resample_u8(frames.data_ptr(), out.data_ptr(), B, H, W, oh, ow, axis, bounds.data_ptr(), coeffs.data_ptr(),
-                              coeffs.shape[1], _stream())
+    with torch.cuda.device(frames.device):
+        rc = lib.haff_resample_u8(frames.data_ptr(), out.data_ptr(), B, H, W, oh, ow, axis, bounds.data_ptr(), coeffs.data_ptr(),
+                                  coeffs.shape[1], _stream())
     check(rc, "haff_resample_u8")
     return out
 
@@ -1080,8 +1096,9 @@ def clip_normalize_u8(frames, top, left, size, lut, out_dtype):
     assert lut.dtype == torch.float32 and lut.is_cuda and lut.shape == (3, 256) and lut.is_contiguous()
     B, H, W, _ = frames.shape
     out = torch.empty((B, 3, size, size), dtype=out_dtype, device=frames.device)
-    rc = lib.haff_clip_normalize_u8(frames.data_ptr(), out.data_ptr(), B, H, W, int(top), int(left), int(size), lut.data_ptr(),
-                                    _dt(out), _stream())
+    with torch.cuda.device(frames.device):
+        rc = lib.haff_clip_normalize_u8(frames.data_ptr(), out.data_ptr(), B, H, W, int(top), int(left), int(size), lut.data_ptr(),
+                                        _dt(out), _stream())
     check(rc, "haff_clip_normalize_u8")
     return out
 
@@ -1091,7 +1108,6 @@ FILL_MAX_VERTS, FILL_MAX_COORD = 4096, 32768   # haff_fill_contours_u8's host-ch
 
 def contour_points(contour):
     """One OpenCV-style contour ([n,2] or [n,1,2], any number type) as cvlite.draw_contours_filled reads it: int32 [n,2]."""
-    import numpy as np
     return np.ascontiguousarray(np.asarray(contour, dtype=np.int32).reshape(-1, 2))
 
 
@@ -1104,7 +1120,6 @@ def fill_contours_supported(contour):
 def fill_contours(planes, hw, device, out=None):
     """cvlite.draw_contours_filled for a batch of planes in one launch. planes: one list of contours per output plane;
     returns uint8 [len(planes), H, W] of 0 / 1 (zeroed by the call itself: `out` may hold anything)."""
-    import numpy as np
     lib = load_library()
     device = torch.device(device)
     if device.type != "cuda":
@@ -1128,13 +1143,12 @@ def fill_contours(planes, hw, device, out=None):
     d[n_poly + 1:2 * n_poly + 1] = plane_of
     if n_pts:
         d[2 * n_poly + 1:] = np.concatenate(polys, 0).reshape(-1)
-    if out is None:
-        out = torch.empty((n_planes, H, W), dtype=torch.uint8, device=device)
-    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n_planes, H, W) and out.device == device
-    desc_dev = desc.to(device, non_blocking=True)
+    out = _out(out, (n_planes, H, W), torch.uint8, device)
     host = desc.data_ptr()
-    rc = lib.haff_fill_contours_u8(host + 4 * (2 * n_poly + 1), host, host + 4 * (n_poly + 1), desc_dev.data_ptr(), n_poly, n_planes,
-                                   out.data_ptr(), H, W, _stream())
+    with torch.cuda.device(device):
+        dev = desc.to(device, non_blocking=True)
+        rc = lib.haff_fill_contours_u8(host + 4 * (2 * n_poly + 1), host, host + 4 * (n_poly + 1), dev.data_ptr(), n_poly, n_planes,
+                                       out.data_ptr(), H, W, _stream())
     check(rc, "haff_fill_contours_u8")
     return out
 
@@ -1163,9 +1177,7 @@ def jitter_stats(frames, flags, factors, out=None):
     carry AUG_JITTER, 0 for the others (zeroed by the call itself: `out` may hold anything)."""
     lib = load_library()
     B, H, W = _aug_args(frames, flags, factors)
-    if out is None:
-        out = torch.empty((B,), dtype=torch.int64, device=frames.device)
-    assert out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (B,) and out.device == frames.device
+    out = _out(out, (B,), torch.int64, frames.device)
     with torch.cuda.device(frames.device):
         rc = lib.haff_jitter_stats_u8(frames.data_ptr(), B, H, W, flags.data_ptr(), factors.data_ptr(), out.data_ptr(), _stream())
     check(rc, "haff_jitter_stats_u8")
@@ -1177,9 +1189,7 @@ def augment_u8(frames, flags, factors, sums, out=None):
     lib = load_library()
     B, H, W = _aug_args(frames, flags, factors)
     assert sums.dtype == torch.int64 and sums.is_contiguous() and tuple(sums.shape) == (B,) and sums.device == frames.device
-    if out is None:
-        out = torch.empty_like(frames)
-    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == frames.shape and out.device == frames.device
+    out = _out(out, frames.shape, torch.uint8, frames.device)
     with torch.cuda.device(frames.device):
         rc = lib.haff_augment_u8(frames.data_ptr(), out.data_ptr(), B, H, W, flags.data_ptr(), factors.data_ptr(), sums.data_ptr(),
                                  _stream())
@@ -1194,9 +1204,7 @@ def flip_planes(planes, flags, out=None):
     assert planes.dtype == torch.uint8 and planes.dim() == 3 and planes.is_contiguous(), tuple(planes.shape)
     P, H, W = planes.shape
     assert flags.dtype == torch.int32 and flags.is_contiguous() and tuple(flags.shape) == (P,) and flags.device == planes.device
-    if out is None:
-        out = torch.empty_like(planes)
-    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == planes.shape and out.device == planes.device
+    out = _out(out, planes.shape, torch.uint8, planes.device)
     with torch.cuda.device(planes.device):
         rc = lib.haff_flip_planes_u8(planes.data_ptr(), out.data_ptr(), P, H, W, flags.data_ptr(), _stream())
     check(rc, "haff_flip_planes_u8")
@@ -1206,7 +1214,6 @@ def flip_planes(planes, flags, out=None):
 def augment_table(augs, device):
     """The device arrays of the augment kernels from one `aug` dict per frame ({"flip": bool, "jitter": None | (fb, fc, fs)}, or None):
     int32 [B] flags and float32 [B,3] factors, uploaded together from one pinned buffer."""
-    import numpy as np
     B = len(augs)
     host = torch.zeros((4 * B,), dtype=torch.float32, pin_memory=True)      # [flags B | factors 3 B]
     h = host.numpy()
@@ -1248,7 +1255,6 @@ def crop_table(S, out):
     """One axis of Image.resize(BICUBIC) from S to `out` pixels as the crop kernel reads it: int32 [out, 2 + ksize] rows of
     (first input index, tap count, Pillow's 22-bit coefficients). Built on the host (Pillow normalises in double) and cached per
     (S, out); DeviceIngest's prefetch thread calls this ahead of the step."""
-    import numpy as np
     from .preprocess import pil_bicubic_tables_fast
     key = (int(S), int(out))
     tab = _crop_tables.get(key)
@@ -1264,7 +1270,6 @@ def crop_table(S, out):
 def crop_descriptor(boxes, flips, hw):
     """The pinned int32 descriptor of haff_crop_resample_u8 for samples of one (H, W): boxes[b] is aff_dataset.crop_box's dict or None
     (the sample is copied), flips[b] its mirror. Samples with one S share their tables."""
-    import numpy as np
     H, W = int(hw[0]), int(hw[1])
     B = len(boxes)
     tabs, where, words = [], {}, B * _CROP_GEOM
@@ -1304,19 +1309,17 @@ def crop_resample(x, boxes, flips, out=None, desc=None):
     if desc is None:
         desc = crop_descriptor(boxes, flips, (H, W))
     assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.device.type == "cpu" and desc.numel() >= B * _CROP_GEOM
-    if out is None:
-        out = torch.empty_like(x)
-    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == x.shape and out.device == x.device
+    out = _out(out, x.shape, torch.uint8, x.device)
     with torch.cuda.device(x.device):
-        desc_dev = desc.to(x.device, non_blocking=True)
-        rc = lib.haff_crop_resample_u8(x.data_ptr(), out.data_ptr(), B, H, W, C, desc.data_ptr(), desc_dev.data_ptr(), desc.numel(),
-                                       _stream())
+        dev = desc.to(x.device, non_blocking=True)
+        rc = lib.haff_crop_resample_u8(x.data_ptr(), out.data_ptr(), B, H, W, C, desc.data_ptr(), dev.data_ptr(), desc.numel(), _stream())
     check(rc, "haff_crop_resample_u8")
     return out
 
 
 SCORE_FRAME_WORDS = 16                  # haff_score_frame (include/haff_hip.h): 128 bytes as 16 int64 words
-SCORE_MAX_SIDE, SCORE_MAX_THRESHOLDS = 4096, 8
+MAX_SIDE = 4096                         # kMaxSide of csrc/mask_score.hip, contour_hausdorff.hip and affordance_extract.hip
+SCORE_MAX_SIDE, SCORE_MAX_THRESHOLDS = MAX_SIDE, 8
 
 
 def score_masks(frames, logit_ths, device, out_counts=None):
@@ -1324,7 +1327,6 @@ def score_masks(frames, logit_ths, device, out_counts=None):
     scoring.pack_frames builds it; every pointer in it a device pointer the caller keeps alive until the call returns).
     Returns int32 [n, n_th, 4] on the device = {intersection, union, predicted area, ground-truth area} per frame and LOGIT
     threshold (zeroed by the call itself; the values are below 2^25). out_counts: a contiguous int32 [n, n_th, 4] to write into."""
-    import ctypes
     lib = load_library()
     device = torch.device(device)
     if device.type != "cuda":
@@ -1340,15 +1342,38 @@ def score_masks(frames, logit_ths, device, out_counts=None):
     assert out_counts.device.type == "cuda"
     ths = (ctypes.c_float * max(n_th, 1))(*[float(v) for v in logit_ths])
     with torch.cuda.device(out_counts.device):
-        dev_copy = host.to(out_counts.device, non_blocking=True)
-        rc = lib.haff_score_masks(host.data_ptr(), dev_copy.data_ptr(), n, ctypes.cast(ths, ctypes.c_void_p), n_th,
+        dev = host.to(out_counts.device, non_blocking=True)
+        rc = lib.haff_score_masks(host.data_ptr(), dev.data_ptr(), n, ctypes.cast(ths, ctypes.c_void_p), n_th,
                                   out_counts.data_ptr(), _stream())
     check(rc, "haff_score_masks")
     return out_counts
 
 
-HAUSDORFF_MAX_SIDE, HAUSDORFF_MAX_PLANES, HAUSDORFF_MAX_VERTICES = 4096, 4096, 1 << 22   # csrc/contour_hausdorff.hip
+HAUSDORFF_MAX_SIDE, HAUSDORFF_MAX_PLANES, HAUSDORFF_MAX_VERTICES = MAX_SIDE, 4096, 1 << 22   # csrc/contour_hausdorff.hip
 HAUSDORFF_OVERFLOW, HAUSDORFF_FAULT = 0b0101, 0b1010     # result[:, 4]: either plane of the pair ran past max_vertices / hit a bound
+
+
+def _u8_planes(planes):
+    """The planes of a contour call as a list, checked (uint8 [H, W], contiguous, in HBM, on one device), and that device."""
+    planes = list(planes)
+    assert planes, "no planes"
+    for p in planes:
+        _req(p, "planes")
+        assert p.dtype == torch.uint8 and p.dim() == 2 and p.is_contiguous(), (p.dtype, tuple(p.shape), p.is_contiguous())
+        assert p.device == planes[0].device
+    return planes, planes[0].device
+
+
+def _plane_table(planes, extra_words=0):
+    """The pinned int64 table of 16-byte haff_contour_plane descriptors {pointer, H, W} (include/haff_hip.h), with `extra_words`
+    zeroed int64 words behind them."""
+    host = torch.zeros((2 * len(planes) + extra_words,), dtype=torch.int64, pin_memory=True)
+    h64 = host.numpy()
+    h32 = h64.view(np.int32)
+    for i, p in enumerate(planes):
+        h64[2 * i] = p.data_ptr()
+        h32[4 * i + 2], h32[4 * i + 3] = p.shape
+    return host
 
 
 def contour_hausdorff(planes, pairs, max_vertices=65536, return_vertices=False):
@@ -1359,26 +1384,13 @@ def contour_hausdorff(planes, pairs, max_vertices=65536, return_vertices=False):
     synchronisation, the caller keeps the planes alive until the stream has run. return_vertices: also int16 [n, max_vertices, 2]
     (x, y) in walk order (rows past a plane's count hold whatever the buffer held) and the int32 [n] vertex counts; True, or the
     uint8 CUDA buffer of at least 4 n max_vertices + 4 n bytes they are to be views of."""
-    import numpy as np
     lib = load_library()
-    planes = list(planes)
-    assert planes, "no planes"
-    for p in planes:
-        _req(p, "planes")
-        assert p.dtype == torch.uint8 and p.dim() == 2 and p.is_contiguous(), (p.dtype, tuple(p.shape), p.is_contiguous())
-        assert p.device == planes[0].device
-    device = planes[0].device
+    planes, device = _u8_planes(planes)
     n, max_vertices = len(planes), int(max_vertices)
     pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
     n_pairs = len(pairs)
-    words = 2 * n + n_pairs                                  # int64 words: 16-byte plane descriptors, then the int32 pairs
-    host = torch.zeros((words,), dtype=torch.int64, pin_memory=True)
-    h64 = host.numpy()
-    h32 = h64.view(np.int32)
-    for i, p in enumerate(planes):
-        h64[2 * i] = p.data_ptr()
-        h32[4 * i + 2], h32[4 * i + 3] = p.shape
-    h32[4 * n:4 * n + 2 * n_pairs] = pairs.reshape(-1)
+    host = _plane_table(planes, extra_words=n_pairs)         # the int32 pairs lie behind the plane descriptors
+    host.numpy().view(np.int32)[4 * n:4 * n + 2 * n_pairs] = pairs.reshape(-1)
     need = ctypes.c_long(0)
     check(lib.haff_contour_hausdorff_workspace(host.data_ptr(), n, max_vertices, ctypes.addressof(need)),
           "haff_contour_hausdorff_workspace")
@@ -1415,31 +1427,16 @@ def contour_extract(planes, max_contours=1024, max_vertices=65536, out=None):
     n_contours + 1 offsets and n_vertices vertices is left as it was. Only enqueues: no synchronisation, the caller keeps the planes
     alive until the stream has run. out: the (summary, offsets, verts) tensors to write into."""
     lib = load_library()
-    planes = list(planes)
-    assert planes, "no planes"
-    for p in planes:
-        _req(p, "planes")
-        assert p.dtype == torch.uint8 and p.dim() == 2 and p.is_contiguous(), (p.dtype, tuple(p.shape), p.is_contiguous())
-        assert p.device == planes[0].device
-    device = planes[0].device
+    planes, device = _u8_planes(planes)
     n, max_contours, max_vertices = len(planes), int(max_contours), int(max_vertices)
-    host = torch.zeros((2 * n,), dtype=torch.int64, pin_memory=True)    # 16-byte plane descriptors
-    h64 = host.numpy()
-    h32 = h64.view("int32")
-    for i, p in enumerate(planes):
-        h64[2 * i] = p.data_ptr()
-        h32[4 * i + 2], h32[4 * i + 3] = p.shape
+    host = _plane_table(planes)
     need = ctypes.c_long(0)
     check(lib.haff_contour_extract_workspace(host.data_ptr(), n, max_contours, max_vertices, ctypes.addressof(need)),
           "haff_contour_extract_workspace")
-    if out is None:
-        out = (torch.empty((n, 4), dtype=torch.int32, device=device),
-               torch.empty((n, max_contours + 1), dtype=torch.int32, device=device),
-               torch.empty((n, max_vertices, 2), dtype=torch.int16, device=device))
-    summary, offsets, verts = out
-    for t, dtype, shape in ((summary, torch.int32, (n, 4)), (offsets, torch.int32, (n, max_contours + 1)),
-                            (verts, torch.int16, (n, max_vertices, 2))):
-        assert t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == device, (t.dtype, tuple(t.shape))
+    summary, offsets, verts = out if out is not None else (None, None, None)
+    summary = _out(summary, (n, 4), torch.int32, device)
+    offsets = _out(offsets, (n, max_contours + 1), torch.int32, device)
+    verts = _out(verts, (n, max_vertices, 2), torch.int16, device)
     with torch.cuda.device(device):
         ws = _workspace(device, need.value)
         dev = host.to(device, non_blocking=True)
@@ -1450,7 +1447,7 @@ def contour_extract(planes, max_contours=1024, max_vertices=65536, out=None):
 
 
 AFF_EXTRACT_ITEM_WORDS = 8              # haff_extract_item (include/haff_hip.h): 64 bytes as 8 int64 words
-AFF_EXTRACT_MAX_SIDE, AFF_EXTRACT_MAX_K = 4096, 31
+AFF_EXTRACT_MAX_SIDE, AFF_EXTRACT_MAX_K = MAX_SIDE, 31
 AFF_EXTRACT_HAND, AFF_EXTRACT_GREY = 1, 2   # stats[:, 7]: a hand was ANDed in / `a` holds a value other than 0 and 255
 AFF_EXTRACT_STATS = ("nonzero_a", "nonzero_out", "sum_a", "min_row", "max_row", "min_col", "max_col", "flags")
 
@@ -1463,7 +1460,6 @@ def nearest_pad_tables(hand_hw, out_hw, device=None):
     p = min(floor(x * (1.0 / (D / S))), S - 1) with the division and the reciprocal in IEEE double in that order (D = 34, S = 6,
     x = 17 reads 2, not 17 * 6 // 34 = 3). The reference skips the resize when the padded hand already has the plane's shape: the
     formula gives the identity for D == S, which is asserted here. CPU tensors, or on `device`."""
-    import numpy as np
     Hh, Wh = int(hand_hw[0]), int(hand_hw[1])
     H, W = int(out_hw[0]), int(out_hw[1])
     assert Hh >= 1 and Wh >= 1 and H >= 1 and W >= 1, (hand_hw, out_hw)
@@ -1524,7 +1520,7 @@ def affordance_extract(items, k, stats=None):
     n = len(items)
     host = torch.zeros((n, AFF_EXTRACT_ITEM_WORDS), dtype=torch.int64, pin_memory=True)
     h64 = host.numpy()
-    h32 = h64.view("int32")
+    h32 = h64.view(np.int32)
     device = None
     for i, (plane, hand, tables, out) in enumerate(items):
         u8(plane, "plane", i)
@@ -1553,9 +1549,7 @@ def affordance_extract(items, k, stats=None):
         h64[i, 3] = tables[1].data_ptr() if hand is not None else 0
         h64[i, 4] = _p(out)
         h32[i, 10:14] = (H, W, Hh, Wh)
-    if stats is None:
-        stats = torch.empty((n, 8), dtype=torch.int64, device=device)
-    assert stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (n, 8) and stats.device == device
+    stats = _out(stats, (n, 8), torch.int64, device)
     with torch.cuda.device(device):
         dev = host.to(device, non_blocking=True)
         rc = lib.haff_affordance_extract(host.data_ptr(), dev.data_ptr(), n, k, stats.data_ptr(), _stream())

@@ -28,6 +28,7 @@ import torch
 
 from . import ops
 from . import postprocess
+from .contours import host_walk
 
 BENCHMARK_HW = (855, 855)                  # calculate_iou.py:139: the uncropped benchmark resolution
 
@@ -172,9 +173,6 @@ class BenchmarkScorer:
     def __exit__(self, *exc):
         self.close()
 
-    def _upload(self, plane):
-        return torch.from_numpy(plane).pin_memory().to(self.device, non_blocking=True)
-
     def _frame(self, dir_name, folder_name, masks_left, masks_right, taxonomy, frame_hw):
         """The descriptor dict of one frame, or None when the frame rules skip it on the host's knowledge alone."""
         if taxonomy.numel() == 0:                              # no [SEG]: inference.py writes nothing
@@ -196,7 +194,7 @@ class BenchmarkScorer:
                 if g.shape != target_hw:
                     return None
                 f["gt_host"][side] = g
-                f[f"gt_{side}"] = self._upload(g)
+                f[f"gt_{side}"] = ops.upload_pinned(g, self.device)
         if not f["gt_host"]:
             return None
         if self.intersection:
@@ -206,7 +204,7 @@ class BenchmarkScorer:
                 if o is None or o.shape != target_hw:
                     f["obj_missing"].append(side)              # skipped iff this hand is written: the gate decides
                 else:
-                    f[f"obj_{side}"] = self._upload(o)
+                    f[f"obj_{side}"] = ops.upload_pinned(o, self.device)
         return f
 
     def add_batch(self, keys, masks_left, masks_right, taxonomies, frame_hws):
@@ -293,8 +291,7 @@ class BenchmarkScorer:
                 if flags & ops.HAUSDORFF_FAULT:
                     print(f"warning: the device contour walk reported a fault on frame {label} (flags {flags:#x}); "
                           "its Hausdorff distances are recomputed on the host", file=sys.stderr)
-                self.host_walks += 1
-                out.append(_hausdorff_planes(bench.cpu().numpy() > 0, pred.cpu().numpy()))
+                out.append(host_walk(self, lambda b, p: _hausdorff_planes(b > 0, p), bench, pred))
                 continue
             h, w = bench.shape
             row = []

@@ -17,7 +17,6 @@ only uploads and launches.
 import queue
 import threading
 
-import numpy as np
 import torch
 
 from . import cvlite
@@ -134,9 +133,6 @@ class DeviceIngest:
             offs.append(offs[-1] + len(r["conversations"]))
         return collate_text(convs, tokenizer, model_max_length, True, conv_type, inference=raw_samples[0]["inference"], offsets=offs)
 
-    def _upload(self, array):
-        return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(self.device, non_blocking=True)
-
     def _host_crops(self, raw_samples):
         """The samples as the device route takes them: one whose crop the kernel does not take is cropped here with Pillow (mirror
         included; the jitter stays for the device) and goes on as a frame with finished planes, like a validation sample."""
@@ -190,7 +186,7 @@ class DeviceIngest:
             for i, f in enumerate(frames):
                 host[i].copy_(torch.from_numpy(f))
             return host.to(self.device, non_blocking=True)
-        return [self._upload(f) for f in frames]
+        return [ops.upload_pinned(f, self.device) for f in frames]
 
     def _masks(self, raw_samples):
         """float [1,H,W] per sample and hand. Samples of one mask size share one launch of the fill kernel."""
@@ -200,7 +196,7 @@ class DeviceIngest:
         for i, r in enumerate(raw_samples):
             if "plane_left" in r:          # validation set: the PNG planes are the ground truth
                 for dst, key in ((left, "plane_left"), (right, "plane_right")):
-                    dst[i] = (self._upload(r[key]) > 0).float()[None]
+                    dst[i] = (ops.upload_pinned(r[key], self.device) > 0).float()[None]
             else:
                 groups.setdefault(tuple(r["mask_hw"]), []).append(i)
         for hw, idxs in groups.items():
@@ -215,7 +211,7 @@ class DeviceIngest:
                         redo.append((len(planes) - 1, contours))
             filled = ops.fill_contours(planes, hw, self.device)
             for k, contours in redo:
-                filled[k].copy_(self._upload(cvlite.draw_contours_filled(hw, contours)), non_blocking=True)
+                filled[k].copy_(ops.upload_pinned(cvlite.draw_contours_filled(hw, contours), self.device), non_blocking=True)
                 self.host_fills += 1
             flips = [bool((raw_samples[i].get("aug") or {}).get("flip")) for i in idxs]
             boxes = [raw_samples[i].get("crop") for i in idxs]
