@@ -21,6 +21,11 @@ def _s():
     return ops._stream()
 
 
+def _call(name, *args):
+    """The library's entry point `name` on the current stream (its last argument), checked under that name."""
+    check(getattr(load_library(), name)(*args, _s()), name)
+
+
 def _pad8(n):
     return (n + 7) // 8 * 8
 
@@ -38,7 +43,6 @@ def _fn16(lib, name, dtype):
 def scale_dev(a, alpha, per_row=False):
     """a * alpha with alpha a DEVICE fp32 scalar (or one value per row of the 2-D a): the multiply runs in fp32 inside the kernel —
     a torch multiply would first round the 0-dim upstream gradient to a's dtype (bf16)."""
-    lib = load_library()
     a = a.contiguous()
     if a.numel() == 0:   # empty in, empty out (the torch multiply this replaced accepted it; the kernel entry refuses cols = 0)
         return a.clone()
@@ -46,7 +50,7 @@ def scale_dev(a, alpha, per_row=False):
     rows, cols = (a.shape[0], a.numel() // a.shape[0]) if per_row else (1, a.numel())
     assert alpha.numel() == (rows if per_row else 1) and alpha.device == a.device
     out = torch.empty_like(a)
-    check(lib.haff_scale_dev(a.data_ptr(), out.data_ptr(), rows, cols, alpha.data_ptr(), 1 if per_row else 0, _dt(a), _s()), "haff_scale_dev")
+    _call("haff_scale_dev", a.data_ptr(), out.data_ptr(), rows, cols, alpha.data_ptr(), 1 if per_row else 0, _dt(a))
     return out
 
 
@@ -55,7 +59,6 @@ def scale_dev(a, alpha, per_row=False):
 # ------------------------------------------------------------------------------------------------------------------
 def transpose(x, Rp=None, Cp=None):
     """x [..., R, C] (any batch strides, unit inner stride) -> [Z, Cp, Rp] contiguous, zero padded."""
-    lib = load_library()
     if x.dim() == 2:
         x = x.unsqueeze(0)
     lead = x.shape[:-2]
@@ -70,8 +73,7 @@ def transpose(x, Rp=None, Cp=None):
     else:
         raise ValueError("transpose supports at most two batch dims")
     out = torch.empty((nbo * nbi, Cp, Rp), dtype=x.dtype, device=x.device)
-    check(lib.haff_transpose(x.data_ptr(), x.stride(-2), so, si, out.data_ptr(), R, C, Rp, Cp, nbo, nbi, _dt(x), _s()),
-          "haff_transpose")
+    _call("haff_transpose", x.data_ptr(), x.stride(-2), so, si, out.data_ptr(), R, C, Rp, Cp, nbo, nbi, _dt(x))
     return out
 
 
@@ -127,8 +129,7 @@ ORDERED_REDUCTIONS = True   # False: the fp32-atomic forms of rounds 1-3 (A/B; r
 
 
 def _reduce_partials(partials, out, n_out, n_parts, out_inner, part_stride, group_stride, accumulate):
-    check(load_library().haff_reduce_partials(partials.data_ptr(), out.data_ptr(), n_out, n_parts, out_inner, part_stride, group_stride,
-                                              1 if accumulate else 0, _s()), "haff_reduce_partials")
+    _call("haff_reduce_partials", partials.data_ptr(), out.data_ptr(), n_out, n_parts, out_inner, part_stride, group_stride, 1 if accumulate else 0)
 
 
 def colsum(x2d):
@@ -140,33 +141,31 @@ def colsum(x2d):
         return torch.zeros((C,), dtype=torch.float32, device=x2d.device)
     if not ORDERED_REDUCTIONS:
         out = torch.zeros((C,), dtype=torch.float32, device=x2d.device)
-        check(lib.haff_colsum(x2d.data_ptr(), out.data_ptr(), R, C, _dt(x2d), _s()), "haff_colsum")
+        _call("haff_colsum", x2d.data_ptr(), out.data_ptr(), R, C, _dt(x2d))
         return out
     parts = lib.haff_colsum_parts(R)
     partials = torch.empty((parts, C), dtype=torch.float32, device=x2d.device)
-    check(lib.haff_colsum_partials(x2d.data_ptr(), partials.data_ptr(), R, C, _dt(x2d), _s()), "haff_colsum_partials")
+    _call("haff_colsum_partials", x2d.data_ptr(), partials.data_ptr(), R, C, _dt(x2d))
     out = torch.empty((C,), dtype=torch.float32, device=x2d.device)
     _reduce_partials(partials, out, C, parts, C, C, 0, False)
     return out
 
 
 def _mul(a, b):
-    lib = load_library()
     a, b = a.contiguous(), b.contiguous()
     out = torch.empty_like(a)
-    check(lib.haff_mul(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _dt(a), _s()), "haff_mul")
+    _call("haff_mul", a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _dt(a))
     return out
 
 
 def axpby(a, b, alpha, beta):
-    lib = load_library()
     a = a.contiguous()
     out = torch.empty_like(a)
     bp = 0
     if b is not None:
         b = b.contiguous()
         bp = b.data_ptr()
-    check(lib.haff_axpby(a.data_ptr(), bp, out.data_ptr(), a.numel(), float(alpha), float(beta), _dt(a), _s()), "haff_axpby")
+    _call("haff_axpby", a.data_ptr(), bp, out.data_ptr(), a.numel(), float(alpha), float(beta), _dt(a))
     return out
 
 
@@ -278,21 +277,19 @@ def linear(x, w, bias=None, resid=None, w_t=None):
 class ActFn(Function):
     @staticmethod
     def forward(ctx, x, act):
-        lib = load_library()
         x = x.contiguous()
         y = torch.empty_like(x)
-        check(lib.haff_act_fwd(x.data_ptr(), y.data_ptr(), x.numel(), act, _dt(x), _s()), "haff_act_fwd")
+        _call("haff_act_fwd", x.data_ptr(), y.data_ptr(), x.numel(), act, _dt(x))
         ctx.save_for_backward(x)
         ctx.act = act
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         (x,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        check(lib.haff_act_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), ctx.act, _dt(x), _s()), "haff_act_bwd")
+        _call("haff_act_bwd", x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), ctx.act, _dt(x))
         return dx, None
 
 
@@ -305,22 +302,19 @@ class SwigluFn(Function):
 
     @staticmethod
     def forward(ctx, gu):
-        lib = load_library()
         gu = gu.contiguous()
         M, F2 = gu.shape
         y = torch.empty((M, F2 // 2), dtype=gu.dtype, device=gu.device)
-        check(lib.haff_swiglu_fwd(gu.data_ptr(), y.data_ptr(), M, F2 // 2, _dt(gu), _s()), "haff_swiglu_fwd")
+        _call("haff_swiglu_fwd", gu.data_ptr(), y.data_ptr(), M, F2 // 2, _dt(gu))
         ctx.save_for_backward(gu)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         (gu,) = ctx.saved_tensors
         dy = dy.contiguous()
         dgu = torch.empty_like(gu)
-        check(lib.haff_swiglu_bwd(gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(), gu.shape[0], gu.shape[1] // 2, _dt(gu), _s()),
-              "haff_swiglu_bwd")
+        _call("haff_swiglu_bwd", gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(), gu.shape[0], gu.shape[1] // 2, _dt(gu))
         return dgu
 
 
@@ -379,14 +373,13 @@ class LayerNormFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(x)
         need_w = ctx.needs_input_grad[1]
         dyx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_w else None
-        check(lib.haff_norm_bwd(x.data_ptr(), dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0 if dyx is None else dyx.data_ptr(),
-                                x.shape[0], x.shape[1], float(ctx.eps), 0, _dt(x), _s()), "haff_norm_bwd")
+        _call("haff_norm_bwd", x.data_ptr(), dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0 if dyx is None else dyx.data_ptr(),
+              x.shape[0], x.shape[1], float(ctx.eps), 0, _dt(x))
         dw = colsum(dyx) if need_w else None
         db = colsum(dy) if ctx.needs_input_grad[2] else None
         return dx, dw, db, None
@@ -405,12 +398,10 @@ class RMSNormFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        check(lib.haff_norm_bwd(x.data_ptr(), dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0, x.shape[0], x.shape[1],
-                                float(ctx.eps), 1, _dt(x), _s()), "haff_norm_bwd")
+        _call("haff_norm_bwd", x.data_ptr(), dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0, x.shape[0], x.shape[1], float(ctx.eps), 1, _dt(x))
         return dx, None, None
 
 
@@ -432,19 +423,17 @@ class ResidRMSNormFn(Function):
 
     @staticmethod
     def backward(ctx, g_x, g_h):
-        lib = load_library()
         x, w = ctx.saved_tensors
         if g_h is None:
             return g_x, None, None
         g_h = g_h.contiguous()
         dx = torch.empty_like(x)
         if g_x is None:
-            check(lib.haff_norm_bwd(x.data_ptr(), g_h.data_ptr(), w.data_ptr(), dx.data_ptr(), 0, x.shape[0], x.shape[1], float(ctx.eps), 1,
-                                    _dt(x), _s()), "haff_norm_bwd")
+            _call("haff_norm_bwd", x.data_ptr(), g_h.data_ptr(), w.data_ptr(), dx.data_ptr(), 0, x.shape[0], x.shape[1], float(ctx.eps), 1, _dt(x))
         else:
             g_x = g_x.contiguous()
-            check(lib.haff_norm_bwd_add(x.data_ptr(), g_h.data_ptr(), w.data_ptr(), g_x.data_ptr(), dx.data_ptr(), 0, x.shape[0], x.shape[1],
-                                        float(ctx.eps), 1, _dt(x), _s()), "haff_norm_bwd_add")
+            _call("haff_norm_bwd_add", x.data_ptr(), g_h.data_ptr(), w.data_ptr(), g_x.data_ptr(), dx.data_ptr(), 0, x.shape[0], x.shape[1],
+                  float(ctx.eps), 1, _dt(x))
         return dx, None, None
 
 
@@ -457,24 +446,20 @@ class RopeFn(Function):
 
     @staticmethod
     def forward(ctx, x, cos_sin, T, H, d):
-        lib = load_library()
         x = x.contiguous()
         y = torch.empty_like(x)
-        check(lib.haff_rope(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), cos_sin.data_ptr(), x.shape[0], T, H, d, 0, 0,
-                            _dt(x), _s()), "haff_rope")
+        _call("haff_rope", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), cos_sin.data_ptr(), x.shape[0], T, H, d, 0, 0, _dt(x))
         ctx.save_for_backward(cos_sin)
         ctx.dims = (T, H, d)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         (cos_sin,) = ctx.saved_tensors
         T, H, d = ctx.dims
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        check(lib.haff_rope(dy.data_ptr(), dy.stride(0), dx.data_ptr(), dx.stride(0), cos_sin.data_ptr(), dy.shape[0], T, H, d, 0, 1,
-                            _dt(dy), _s()), "haff_rope")
+        _call("haff_rope", dy.data_ptr(), dy.stride(0), dx.data_ptr(), dx.stride(0), cos_sin.data_ptr(), dy.shape[0], T, H, d, 0, 1, _dt(dy))
         return dx, None, None, None, None
 
 
@@ -487,7 +472,6 @@ class AttentionFn(Function):
 
     @staticmethod
     def forward(ctx, q, k, v, H, scale_, causal):
-        lib = load_library()
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         B, Nq, HD = q.shape
         Nk = k.shape[1]
@@ -498,8 +482,7 @@ class AttentionFn(Function):
         Nkp = _pad8(Nk)
         s = bgemm(q4, k4, out_dtype=torch.float32)                       # [B,H,Nq,Nk]
         p = torch.empty((B, H, Nq, Nkp), dtype=q.dtype, device=q.device)
-        check(lib.haff_softmax_fwd(s.data_ptr(), Nk, p.data_ptr(), Nkp, B * H * Nq, Nq, Nk, float(scale_), 1 if causal else 0,
-                                   Nk - Nq, _dt(q), _s()), "haff_softmax_fwd")
+        _call("haff_softmax_fwd", s.data_ptr(), Nk, p.data_ptr(), Nkp, B * H * Nq, Nq, Nk, float(scale_), 1 if causal else 0, Nk - Nq, _dt(q))
         vt = transpose(v4, Rp=Nkp).view(B, H, d, Nkp)                    # [B,H,d,Nkp]
         out = torch.empty((B, Nq, HD), dtype=q.dtype, device=q.device)
         bgemm(p, vt, out=out.view(B, Nq, H, d).permute(0, 2, 1, 3))
@@ -509,7 +492,6 @@ class AttentionFn(Function):
 
     @staticmethod
     def backward(ctx, do):
-        lib = load_library()
         q, k, v, p = ctx.saved_tensors
         H, scale_, Nk = ctx.cfg
         do = do.contiguous()
@@ -522,8 +504,7 @@ class AttentionFn(Function):
         do4 = do.view(B, Nq, H, d).permute(0, 2, 1, 3)
         dp = bgemm(do4, v4, out_dtype=torch.float32)                     # [B,H,Nq,Nk]
         ds = torch.empty_like(p)
-        check(lib.haff_softmax_bwd(p.data_ptr(), Nkp, dp.data_ptr(), Nk, ds.data_ptr(), B * H * Nq, Nk, scale_, _dt(p), _s()),
-              "haff_softmax_bwd")
+        _call("haff_softmax_bwd", p.data_ptr(), Nkp, dp.data_ptr(), Nk, ds.data_ptr(), B * H * Nq, Nk, scale_, _dt(p))
         kt = transpose(k4, Rp=Nkp).view(B, H, d, Nkp)
         dq = torch.empty_like(q)
         bgemm(ds, kt, out=dq.view(B, Nq, H, d).permute(0, 2, 1, 3))
@@ -866,7 +847,7 @@ class LoraGateUpSwigluFn(Function):
         dev, dt_ = xg.device, xg.dtype
         dy = dy.contiguous()
         dgu = torch.empty_like(gu)
-        check(lib.haff_swiglu_bwd(gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(), M, F, _dt(gu), _s()), "haff_swiglu_bwd")
+        _call("haff_swiglu_bwd", gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(), M, F, _dt(gu))
         # dt^T [16][M] = Bblk^T . dgu'^T in one weight-streaming launch: Bblk^T [16][2F] holds Bg^T on the gate columns (rows 0-7)
         # and Bu^T on the up columns (rows 8-15), zeros elsewhere
         blk = torch.zeros((16, F // 16, 2, 16), dtype=dt_, device=dev)
@@ -946,18 +927,16 @@ class EmbedFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         (ids,) = ctx.saved_tensors
         dy = dy.contiguous()
         acc = torch.zeros(ctx.shape, dtype=torch.float32, device=dy.device)
         flat = ids.reshape(-1).contiguous()
         if ORDERED_REDUCTIONS:   # rows that share an id are added in row order (stable sort on the device: no host read)
             sorted_ids, order = torch.sort(flat, stable=True)
-            check(lib.haff_scatter_add_rows_sorted(sorted_ids.data_ptr(), order.data_ptr(), dy.data_ptr(), acc.data_ptr(), flat.numel(),
-                                                   ctx.shape[1], _dt(dy), _s()), "haff_scatter_add_rows_sorted")
+            _call("haff_scatter_add_rows_sorted", sorted_ids.data_ptr(), order.data_ptr(), dy.data_ptr(), acc.data_ptr(), flat.numel(),
+                  ctx.shape[1], _dt(dy))
         else:
-            check(lib.haff_scatter_add_rows(flat.data_ptr(), dy.data_ptr(), acc.data_ptr(), flat.numel(), ctx.shape[1], _dt(dy), _s()),
-                  "haff_scatter_add_rows")
+            _call("haff_scatter_add_rows", flat.data_ptr(), dy.data_ptr(), acc.data_ptr(), flat.numel(), ctx.shape[1], _dt(dy))
         return acc.to(ctx.wdtype), None
 
 
@@ -969,7 +948,6 @@ class CrossEntropyFn(Function):
 
     @staticmethod
     def forward(ctx, logits, labels, n_valid=None):
-        lib = load_library()
         logits = logits.contiguous()
         labels = labels.contiguous()
         R, V = logits.shape
@@ -981,8 +959,8 @@ class CrossEntropyFn(Function):
         # fp16: the kernel writes softmax - onehot unscaled and the 1 / n_valid joins the upstream (loss-scaled) gradient in backward:
         # softmax / n_valid itself would fall below fp16's subnormals for a 32003-word vocabulary before the loss scale reaches it
         ctx.post = n_valid if logits.dtype == torch.float16 else None
-        check(lib.haff_cross_entropy(logits.data_ptr(), logits.stride(0), labels.data_ptr(), row_loss.data_ptr(), dlogits.data_ptr(),
-                                     R, V, 1.0 if ctx.post else 1.0 / n_valid, _dt(logits), _s()), "haff_cross_entropy")
+        _call("haff_cross_entropy", logits.data_ptr(), logits.stride(0), labels.data_ptr(), row_loss.data_ptr(), dlogits.data_ptr(), R, V,
+              1.0 if ctx.post else 1.0 / n_valid, _dt(logits))
         ctx.save_for_backward(dlogits)
         # sum of R floats / n_valid: reduction of a tiny vector (torch sum as plumbing of a scalar)
         return (row_loss.sum() / n_valid).to(torch.float32)
@@ -1004,7 +982,6 @@ class MaskLossFn(Function):
 
     @staticmethod
     def forward(ctx, x, t, wgts):
-        lib = load_library()
         x, t = x.contiguous(), t.contiguous()
         n, hw = x.shape
         stats = torch.zeros((n, 4), dtype=torch.float32, device=x.device)
@@ -1021,15 +998,14 @@ class MaskLossFn(Function):
             partials = torch.empty((n, SLOTS, 4), dtype=torch.float32, device=x.device)
             n_parts = ctypes.c_int(0)
             for i in range(n):  # per-sample weight is a host scalar (taxonomy one-hot sums)
-                check(lib.haff_mask_loss_stats_partials(x[i].data_ptr(), t[i].data_ptr(), partials[i].data_ptr(), 1, hw, float(wgts[i]),
-                                                        ctypes.byref(n_parts), _s()), "haff_mask_loss_stats_partials")
+                _call("haff_mask_loss_stats_partials", x[i].data_ptr(), t[i].data_ptr(), partials[i].data_ptr(), 1, hw, float(wgts[i]),
+                      ctypes.byref(n_parts))
                 assert 0 < n_parts.value <= SLOTS, n_parts.value
             # stats[i][k] = sum over the parts of sample i, in index order (one launch for all samples)
             _reduce_partials(partials, stats, 4 * n, n_parts.value, 4, 4, SLOTS * 4, False)
         else:
             for i in range(n):
-                check(lib.haff_mask_loss_stats(x[i].data_ptr(), t[i].data_ptr(), stats[i].data_ptr(), 1, hw, float(wgts[i]), _s()),
-                      "haff_mask_loss_stats")
+                _call("haff_mask_loss_stats", x[i].data_ptr(), t[i].data_ptr(), stats[i].data_ptr(), 1, hw, float(wgts[i]))
         ctx.save_for_backward(x, t, stats)
         ctx.wgts = [float(w) for w in wgts]
         # four sums per sample -> {bce, dice}: a handful of n-element device ops (scalar plumbing; a host round trip here
@@ -1041,7 +1017,6 @@ class MaskLossFn(Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = load_library()
         x, t, stats = ctx.saved_tensors
         n, hw = x.shape
         coef = g.to(torch.float32).contiguous()   # [n, 2] upstream gradients of {bce, dice}: read by the kernel, not by the host
@@ -1049,8 +1024,8 @@ class MaskLossFn(Function):
         if n == 0 or hw == 0:
             return dx, None, None
         for i in range(n):
-            check(lib.haff_mask_loss_grad_dev(x[i].data_ptr(), t[i].data_ptr(), stats[i].data_ptr(), dx[i].data_ptr(), 1, hw,
-                                              ctx.wgts[i], coef[i].data_ptr(), _s()), "haff_mask_loss_grad_dev")
+            _call("haff_mask_loss_grad_dev", x[i].data_ptr(), t[i].data_ptr(), stats[i].data_ptr(), dx[i].data_ptr(), 1, hw, ctx.wgts[i],
+                  coef[i].data_ptr())
         return dx, None, None
 
 
@@ -1066,11 +1041,10 @@ class BilinearFn(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         (N, Hs, Ws), (Hc, Wc), (Ho, Wo) = ctx.geom
         dy = dy.contiguous()
         dx = torch.zeros((N, Hs, Ws), dtype=torch.float32, device=dy.device)
-        check(lib.haff_resize_bilinear_bwd(dy.data_ptr(), dx.data_ptr(), N, Hs, Ws, Hc, Wc, Ho, Wo, _s()), "haff_resize_bilinear_bwd")
+        _call("haff_resize_bilinear_bwd", dy.data_ptr(), dx.data_ptr(), N, Hs, Ws, Hc, Wc, Ho, Wo)
         return dx, None, None
 
 
@@ -1098,14 +1072,12 @@ class TaxonomyCEFn(Function):
 
     @staticmethod
     def forward(ctx, z, t):
-        lib = load_library()
         z, t = z.contiguous(), t.contiguous().float()
         R, C = z.shape
         loss = torch.empty((R,), dtype=torch.float32, device=z.device)
         dz = torch.empty_like(z)
         probs = torch.empty_like(z)
-        check(lib.haff_taxonomy_ce(z.data_ptr(), t.data_ptr(), probs.data_ptr(), loss.data_ptr(), dz.data_ptr(), R, C, _s()),
-              "haff_taxonomy_ce")
+        _call("haff_taxonomy_ce", z.data_ptr(), t.data_ptr(), probs.data_ptr(), loss.data_ptr(), dz.data_ptr(), R, C)
         ctx.save_for_backward(dz)
         ctx.mark_non_differentiable(probs)
         return loss, probs

@@ -239,37 +239,30 @@ __global__ void softmax_rows_kernel(const T* x, float* out, int rows, int C) {
   for (int c = 0; c < C; ++c) out[(long)r * C + c] = expf(elem<T>::ld(x + (long)r * C + c) - m) / s;
 }
 
-inline int grid_for(long total, int block) {
-  long g = (total + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
+inline int grid_for(long total, int block) { return haff_grid(total, block, 8192); }
 
 }  // namespace
 
-#define HAFF_STREAM(s) reinterpret_cast<hipStream_t>(s)
-
 // in_dtype/out_dtype: 0 = bf16, 1 = f32, 3 = f16 (dtype codes of include/haff_hip.h; below, too). Any other code is refused
-// with HAFF_ERR_BAD_ARG: no entry point treats "anything else" as f32.
+// with HAFF_ERR_BAD_ARG: no entry point treats "anything else" as f32. The six (in, out) pairs that have a kernel are the table.
 extern "C" int haff_patchify_nchw(const void* x, void* out, int B, int Cin, int Hin, int Win, int P, int gh, int gw,
                                   int Kp, int in_dtype, int out_dtype, void* stream) {
   if (B <= 0 || P <= 0 || gh * P > Hin || gw * P > Win || Kp < Cin * P * P) return HAFF_ERR_BAD_ARG;
   const long total = (long)B * gh * gw * Kp;
   dim3 g(grid_for(total, 256)), b(256);
-  hipStream_t s = HAFF_STREAM(stream);
-  if (in_dtype == 0 && out_dtype == 0)
-    hipLaunchKernelGGL((patchify_nchw_kernel<bf16_t, bf16_t>), g, b, 0, s, (const bf16_t*)x, (bf16_t*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
-  else if (in_dtype == 1 && out_dtype == 0)
-    hipLaunchKernelGGL((patchify_nchw_kernel<float, bf16_t>), g, b, 0, s, (const float*)x, (bf16_t*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
-  else if (in_dtype == 1 && out_dtype == 1)
-    hipLaunchKernelGGL((patchify_nchw_kernel<float, float>), g, b, 0, s, (const float*)x, (float*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
-  else if (in_dtype == 0 && out_dtype == 1)
-    hipLaunchKernelGGL((patchify_nchw_kernel<bf16_t, float>), g, b, 0, s, (const bf16_t*)x, (float*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
-  else if (in_dtype == 3 && out_dtype == 3)
-    hipLaunchKernelGGL((patchify_nchw_kernel<f16_t, f16_t>), g, b, 0, s, (const f16_t*)x, (f16_t*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
-  else if (in_dtype == 1 && out_dtype == 3)
-    hipLaunchKernelGGL((patchify_nchw_kernel<float, f16_t>), g, b, 0, s, (const float*)x, (f16_t*)out, B, Cin, Hin, Win, P, gh, gw, Kp);
-  else return HAFF_ERR_BAD_ARG;
-  return haff_check_launch();
+#define HAFF_PATCHIFY_PAIR(in_, TI_, out_, TO_)                                                                                  \
+  if (in_dtype == in_ && out_dtype == out_) {                                                                                    \
+    hipLaunchKernelGGL((patchify_nchw_kernel<TI_, TO_>), g, b, 0, haff_stream(stream), (const TI_*)x, (TO_*)out, B, Cin, Hin, Win, P, gh, gw, Kp); \
+    return haff_check_launch();                                                                                                  \
+  }
+  HAFF_PATCHIFY_PAIR(0, bf16_t, 0, bf16_t)
+  HAFF_PATCHIFY_PAIR(1, float, 0, bf16_t)
+  HAFF_PATCHIFY_PAIR(1, float, 1, float)
+  HAFF_PATCHIFY_PAIR(0, bf16_t, 1, float)
+  HAFF_PATCHIFY_PAIR(3, f16_t, 3, f16_t)
+  HAFF_PATCHIFY_PAIR(1, float, 3, f16_t)
+#undef HAFF_PATCHIFY_PAIR
+  return HAFF_ERR_BAD_ARG;
 }
 
 extern "C" int haff_patchify_u8(const void* frames, void* out, int B, int Hf, int Wf, int P, int gh, int gw, int Kp,
@@ -277,17 +270,8 @@ extern "C" int haff_patchify_u8(const void* frames, void* out, int B, int Hf, in
   if (B <= 0 || P <= 0 || Kp < 3 * P * P || !mean3 || !std3) return HAFF_ERR_BAD_ARG;
   const long total = (long)B * gh * gw * Kp;
   dim3 g(grid_for(total, 256)), b(256);
-  hipStream_t s = HAFF_STREAM(stream);
-  if (out_dtype == 0)
-    hipLaunchKernelGGL((patchify_u8_kernel<bf16_t>), g, b, 0, s, (const unsigned char*)frames, (bf16_t*)out, B, Hf, Wf, P, gh, gw, Kp,
-                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  else if (out_dtype == 3)
-    hipLaunchKernelGGL((patchify_u8_kernel<f16_t>), g, b, 0, s, (const unsigned char*)frames, (f16_t*)out, B, Hf, Wf, P, gh, gw, Kp,
-                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  else if (out_dtype == 1)
-    hipLaunchKernelGGL((patchify_u8_kernel<float>), g, b, 0, s, (const unsigned char*)frames, (float*)out, B, Hf, Wf, P, gh, gw, Kp,
-                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-  else return HAFF_ERR_BAD_ARG;
+  HAFF_DISPATCH(out_dtype, hipLaunchKernelGGL((patchify_u8_kernel<T>), g, b, 0, haff_stream(stream), (const unsigned char*)frames, (T*)out, B, Hf, Wf,
+                                              P, gh, gw, Kp, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]));
   return haff_check_launch();
 }
 
@@ -295,10 +279,7 @@ extern "C" int haff_im2col3x3(const void* x, void* out, int B, int H, int W, int
   if (B <= 0 || (C & 7)) return HAFF_ERR_BAD_ARG;
   const long total = (long)B * H * W * 9 * (C / 8);
   dim3 g(grid_for(total, 256)), b(256);
-  if (dtype == 0) hipLaunchKernelGGL((im2col3x3_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (const bf16_t*)x, (bf16_t*)out, B, H, W, C);
-  else if (dtype == 3) hipLaunchKernelGGL((im2col3x3_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (const f16_t*)x, (f16_t*)out, B, H, W, C);
-  else if (dtype == 1) hipLaunchKernelGGL((im2col3x3_kernel<float>), g, b, 0, HAFF_STREAM(stream), (const float*)x, (float*)out, B, H, W, C);
-  else return HAFF_ERR_BAD_ARG;
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((im2col3x3_kernel<T>), g, b, 0, haff_stream(stream), (const T*)x, (T*)out, B, H, W, C));
   return haff_check_launch();
 }
 
@@ -306,23 +287,23 @@ extern "C" int haff_embed_splice(const long* ids, const int* img_pos, const void
                                  int B, int L, int n_img, int Hd, int dtype, void* stream) {
   if (B <= 0 || L <= 0 || n_img <= 0 || (Hd & 7)) return HAFF_ERR_BAD_ARG;
   dim3 g(B * (L + n_img - 1)), b(128);
-  if (dtype == 0) hipLaunchKernelGGL((embed_splice_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const bf16_t*)embed, (const bf16_t*)img, (bf16_t*)out, L, n_img, Hd);
-  else if (dtype == 3) hipLaunchKernelGGL((embed_splice_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const f16_t*)embed, (const f16_t*)img, (f16_t*)out, L, n_img, Hd);
-  else if (dtype == 1) hipLaunchKernelGGL((embed_splice_kernel<float>), g, b, 0, HAFF_STREAM(stream), ids, img_pos, (const float*)embed, (const float*)img, (float*)out, L, n_img, Hd);
-  else return HAFF_ERR_BAD_ARG;
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((embed_splice_kernel<T>), g, b, 0, haff_stream(stream), ids, img_pos, (const T*)embed, (const T*)img, (T*)out, L, n_img, Hd));
+  return haff_check_launch();
+}
+
+// the two RoPE + cache-append entry points after their own checks: one shared pos0, or pos0_rows (then pos0 is 0)
+static int rope_cache_launch(void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, int B, int Tq, int Hq, int Hkv,
+                             int d, int pos0, int Tmax, const int* pos0_rows, int dtype, void* stream) {
+  const long total = (long)B * Tq * (Hq + 2 * Hkv) * (d / 16);
+  dim3 g(grid_for(total, 256)), b(256);
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((rope_cache_kernel<T>), g, b, 0, haff_stream(stream), (T*)qkv, ld, (T*)kcache, (T*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, pos0_rows));
   return haff_check_launch();
 }
 
 extern "C" int haff_rope_cache(void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, int B, int Tq,
                                int Hq, int Hkv, int d, int pos0, int Tmax, int dtype, void* stream) {
   if (B <= 0 || Tq <= 0 || (d & 15) || (ld & 7) || pos0 < 0 || pos0 + Tq > Tmax) return HAFF_ERR_BAD_ARG;
-  const long total = (long)B * Tq * (Hq + 2 * Hkv) * (d / 16);
-  dim3 g(grid_for(total, 256)), b(256);
-  if (dtype == 0) hipLaunchKernelGGL((rope_cache_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (bf16_t*)qkv, ld, (bf16_t*)kcache, (bf16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
-  else if (dtype == 3) hipLaunchKernelGGL((rope_cache_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (f16_t*)qkv, ld, (f16_t*)kcache, (f16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
-  else if (dtype == 1) hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr);
-  else return HAFF_ERR_BAD_ARG;
-  return haff_check_launch();
+  return rope_cache_launch(qkv, ld, kcache, vcache, cos_sin, B, Tq, Hq, Hkv, d, pos0, Tmax, nullptr, dtype, stream);
 }
 
 // Ragged batches: row b's Tq new positions start at pos0_rows[b] (device int32 [B], each with pos0_rows[b] + Tq <= Tmax —
@@ -330,18 +311,12 @@ extern "C" int haff_rope_cache(void* qkv, long ld, void* kcache, void* vcache, c
 extern "C" int haff_rope_cache_rows(void* qkv, long ld, void* kcache, void* vcache, const float* cos_sin, int B, int Tq,
                                     int Hq, int Hkv, int d, const int* pos0_rows, int Tmax, int dtype, void* stream) {
   if (B <= 0 || Tq <= 0 || (d & 15) || (ld & 7) || !pos0_rows || Tq > Tmax) return HAFF_ERR_BAD_ARG;
-  const long total = (long)B * Tq * (Hq + 2 * Hkv) * (d / 16);
-  dim3 g(grid_for(total, 256)), b(256);
-  if (dtype == 0) hipLaunchKernelGGL((rope_cache_kernel<bf16_t>), g, b, 0, HAFF_STREAM(stream), (bf16_t*)qkv, ld, (bf16_t*)kcache, (bf16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
-  else if (dtype == 3) hipLaunchKernelGGL((rope_cache_kernel<f16_t>), g, b, 0, HAFF_STREAM(stream), (f16_t*)qkv, ld, (f16_t*)kcache, (f16_t*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
-  else if (dtype == 1) hipLaunchKernelGGL((rope_cache_kernel<float>), g, b, 0, HAFF_STREAM(stream), (float*)qkv, ld, (float*)kcache, (float*)vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows);
-  else return HAFF_ERR_BAD_ARG;
-  return haff_check_launch();
+  return rope_cache_launch(qkv, ld, kcache, vcache, cos_sin, B, Tq, Hq, Hkv, d, 0, Tmax, pos0_rows, dtype, stream);
 }
 
 extern "C" int haff_argmax_rows(const float* x, long ld, long* out, int rows, int V, void* stream) {
   if (rows <= 0 || V <= 0) return HAFF_ERR_BAD_ARG;
-  hipLaunchKernelGGL(argmax_rows_kernel, dim3(rows), dim3(1024), 0, HAFF_STREAM(stream), x, ld, out, V);
+  hipLaunchKernelGGL(argmax_rows_kernel, dim3(rows), dim3(1024), 0, haff_stream(stream), x, ld, out, V);
   return haff_check_launch();
 }
 
@@ -355,11 +330,10 @@ extern "C" int haff_decode_book(const long* nxt_raw, const long* forced, long fo
                                 long pad, long eos, int B, void* stream) {
   if (B <= 0 || !nxt_raw || !use_forced || !steps || !finished || !out_ids || !lens || !t_rows || !tok || !pos || !nk)
     return HAFF_ERR_BAD_ARG;
-  if (h1 && ((row_bytes & 15) || (hid_sb & 15) || (reinterpret_cast<uintptr_t>(h1) & 15) || (reinterpret_cast<uintptr_t>(hidden) & 15)))
-    return HAFF_ERR_BAD_ARG;
+  if (h1 && ((row_bytes & 15) || (hid_sb & 15) || !haff_aligned(h1) || !haff_aligned(hidden))) return HAFF_ERR_BAD_ARG;
   DecodeBookArgs p{nxt_raw, forced, forced_ld, use_forced, steps, finished, out_ids, out_ld, lens, t_rows, tok, pos, nk,
                    reinterpret_cast<const char*>(h1), reinterpret_cast<char*>(hidden), hid_sb, row_bytes, pad, eos};
-  hipLaunchKernelGGL(decode_book_kernel, dim3(B), dim3(256), 0, HAFF_STREAM(stream), p);
+  hipLaunchKernelGGL(decode_book_kernel, dim3(B), dim3(256), 0, haff_stream(stream), p);
   return haff_check_launch();
 }
 
@@ -367,19 +341,13 @@ extern "C" int haff_add_bcast(const void* a, const void* b, void* out, long rows
                               void* stream) {
   if (rows <= 0 || (C & 7) || mod <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(rows * (C / 8), 256)), blk(256);
-  if (dtype == 0) hipLaunchKernelGGL((add_bcast_kernel<bf16_t>), g, blk, 0, HAFF_STREAM(stream), (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, rows, C, mod);
-  else if (dtype == 3) hipLaunchKernelGGL((add_bcast_kernel<f16_t>), g, blk, 0, HAFF_STREAM(stream), (const f16_t*)a, (const f16_t*)b, (f16_t*)out, rows, C, mod);
-  else if (dtype == 1) hipLaunchKernelGGL((add_bcast_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)a, (const float*)b, (float*)out, rows, C, mod);
-  else return HAFF_ERR_BAD_ARG;
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((add_bcast_kernel<T>), g, blk, 0, haff_stream(stream), (const T*)a, (const T*)b, (T*)out, rows, C, mod));
   return haff_check_launch();
 }
 
 extern "C" int haff_softmax_rows(const void* x, float* out, int rows, int C, int dtype, void* stream) {
   if (rows <= 0 || C <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g((rows + 63) / 64), blk(64);
-  if (dtype == 0) hipLaunchKernelGGL((softmax_rows_kernel<bf16_t>), g, blk, 0, HAFF_STREAM(stream), (const bf16_t*)x, out, rows, C);
-  else if (dtype == 3) hipLaunchKernelGGL((softmax_rows_kernel<f16_t>), g, blk, 0, HAFF_STREAM(stream), (const f16_t*)x, out, rows, C);
-  else if (dtype == 1) hipLaunchKernelGGL((softmax_rows_kernel<float>), g, blk, 0, HAFF_STREAM(stream), (const float*)x, out, rows, C);
-  else return HAFF_ERR_BAD_ARG;
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((softmax_rows_kernel<T>), g, blk, 0, haff_stream(stream), (const T*)x, out, rows, C));
   return haff_check_launch();
 }

@@ -69,10 +69,7 @@ __global__ __launch_bounds__(256) void clip_normalize_kernel(const unsigned char
   }
 }
 
-inline unsigned grid_1d(long total) {
-  long g = (total + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
-}
+inline unsigned grid_1d(long total) { return (unsigned)haff_grid(total, 256, 65536); }
 
 }  // namespace
 
@@ -83,7 +80,7 @@ inline unsigned grid_1d(long total) {
 extern "C" int haff_resample_u8(const void* in, void* out, int B, int Hin, int Win, int Hout, int Wout, int axis,
                                 const int* bounds, const int* coeffs, int ksize, void* stream) {
   if (B <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || ksize <= 0 || !bounds || !coeffs) return HAFF_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t s = haff_stream(stream);
   if (axis == 0) {
     if (Hout != Hin) return HAFF_ERR_BAD_ARG;
     const long rows = (long)B * Hin;
@@ -105,15 +102,7 @@ extern "C" int haff_resample_u8(const void* in, void* out, int B, int Hin, int W
 extern "C" int haff_clip_normalize_u8(const void* in, void* out, int B, int Hin, int Win, int top, int left, int S,
                                       const float* lut, int out_dtype, void* stream) {
   if (B <= 0 || S <= 0 || top < 0 || left < 0 || top + S > Hin || left + S > Win || !lut) return HAFF_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const unsigned g = grid_1d((long)B * 3 * S * S);
-  if (out_dtype == 0)
-    hipLaunchKernelGGL((clip_normalize_kernel<bf16_t>), dim3(g), dim3(256), 0, s, (const unsigned char*)in, (bf16_t*)out, B, Hin, Win, top, left, S, lut);
-  else if (out_dtype == 3)
-    hipLaunchKernelGGL((clip_normalize_kernel<f16_t>), dim3(g), dim3(256), 0, s, (const unsigned char*)in, (f16_t*)out, B, Hin, Win, top, left, S, lut);
-  else if (out_dtype == 1)
-    hipLaunchKernelGGL((clip_normalize_kernel<float>), dim3(g), dim3(256), 0, s, (const unsigned char*)in, (float*)out, B, Hin, Win, top, left, S, lut);
-  else
-    return HAFF_ERR_BAD_ARG;
+  HAFF_DISPATCH(out_dtype, hipLaunchKernelGGL((clip_normalize_kernel<T>), dim3(g), dim3(256), 0, haff_stream(stream), (const unsigned char*)in, (T*)out, B, Hin, Win, top, left, S, lut));
   return haff_check_launch();
 }

@@ -229,6 +229,32 @@ static inline int haff_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? HAFF_OK : HAFF_ERR_LAUNCH;
 }
+static inline hipStream_t haff_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+// host side: blocks of `block` threads that cover `total` items, at least 1 and at most `cap` (the grid-stride kernels take the rest)
+static inline int haff_grid(long total, int block, long cap) {
+  const long g = (total + block - 1) / block;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+// host side, storage-type dispatch: runs the statement with T = the element type of dtype code 0 (bf16), 1 (f32) or 3 (f16) and
+// RETURNS HAFF_ERR_BAD_ARG from the calling function for any other code, before a launch (code 2 is the norms' mixed form, a
+// special case of norm.hip). HAFF_DISPATCH_16 serves the 16-bit-only vector paths: codes 0 and 3.
+#define HAFF_DISPATCH_CASE_(code, type, ...) case code: { using T = type; __VA_ARGS__; } break;
+#define HAFF_DISPATCH(dtype, ...) \
+  do { switch (dtype) { \
+    HAFF_DISPATCH_CASE_(0, bf16_t, __VA_ARGS__) \
+    HAFF_DISPATCH_CASE_(1, float, __VA_ARGS__) \
+    HAFF_DISPATCH_CASE_(3, f16_t, __VA_ARGS__) \
+    default: return HAFF_ERR_BAD_ARG; \
+  } } while (0)
+#define HAFF_DISPATCH_16(dtype, ...) \
+  do { switch (dtype) { \
+    HAFF_DISPATCH_CASE_(0, bf16_t, __VA_ARGS__) \
+    HAFF_DISPATCH_CASE_(3, f16_t, __VA_ARGS__) \
+    default: return HAFF_ERR_BAD_ARG; \
+  } } while (0)
+// the statement with the compile-time constant NAME = (cond), true first
+#define HAFF_DISPATCH_BOOL(cond, NAME, ...) \
+  do { if (cond) { constexpr bool NAME = true; __VA_ARGS__; } else { constexpr bool NAME = false; __VA_ARGS__; } } while (0)
 // host side: p sits on a `bytes` boundary (a power of two; 16 = one dwordx4 access). A null pointer passes.
 static inline bool haff_aligned(const void* p, unsigned bytes = 16) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 // host side: the (batch, head, token) strides of q / k / v are multiples of in_mask + 1 elements, those of the output of out_mask + 1

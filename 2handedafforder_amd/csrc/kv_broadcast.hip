@@ -59,8 +59,8 @@ __global__ __launch_bounds__(kThreads) void kv_prefix_broadcast_kernel(const uni
 extern "C" int haff_kv_prefix_broadcast(const void* k_src, const void* v_src, long src_row_stride, void* k_dst, void* v_dst,
                                         long dst_row_stride, const int* frame_of, int B, int F, int P, int H, int dtype, void* stream) {
   if (!k_src || !v_src || !k_dst || !v_dst || !frame_of || B < 1 || F < 1 || P < 1 || H < 1) return HAFF_ERR_BAD_ARG;
-  const long elem = dtype == 1 ? 4 : ((dtype == 0 || dtype == 3) ? 2 : 0);
-  if (!elem) return HAFF_ERR_BAD_ARG;
+  long elem = 0;                                          // bytes per element: the kernel never sees the type
+  HAFF_DISPATCH(dtype, elem = sizeof(T));
   const long row_bytes = (long)H * elem;
   const long run = (long)P * H;                           // elements of one row's prefix
   if (row_bytes % 16 || src_row_stride < run || dst_row_stride < run || (src_row_stride * elem) % 16 || (dst_row_stride * elem) % 16)
@@ -70,7 +70,7 @@ extern "C" int haff_kv_prefix_broadcast(const void* k_src, const void* v_src, lo
   const long units = run * elem / 16;
   const long chunks = (units + kChunkUnits - 1) / kChunkUnits;
   if (chunks * B > INT_MAX) return HAFF_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(kv_prefix_broadcast_kernel, dim3((unsigned)(chunks * B)), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(kv_prefix_broadcast_kernel, dim3((unsigned)(chunks * B)), dim3(kThreads), 0, haff_stream(stream),
                      (const unit_t*)k_src, (const unit_t*)v_src, src_row_stride * elem / 16, (unit_t*)k_dst, (unit_t*)v_dst,
                      dst_row_stride * elem / 16, frame_of, B, F, units);
   return haff_check_launch();

@@ -254,6 +254,15 @@ int launch_stats(const void* x, long ldx, float* stats, int rows, int C, float e
   return HAFF_ERR_UNSUPPORTED;
 }
 
+// the norms' four-way type choice: code 2 is theirs alone, the other codes are the common three
+template <bool RMS>
+int launch_norm_dtype(const void* x, long ldx, void* y, long ldy, const float* w, const float* b, const int* in_map, int rows, int C,
+                      float eps, int dtype, void* stream) {
+  if (dtype == 2) return launch_norm<float, RMS, bf16_t>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, haff_stream(stream));
+  HAFF_DISPATCH(dtype, return launch_norm<T, RMS>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, haff_stream(stream)));
+  return HAFF_ERR_BAD_ARG;   // not reached: every case above returns
+}
+
 }  // namespace
 
 // dtype: 0 = bf16, 1 = f32 (x and y), 2 = f32 x -> bf16 y (an fp32 residual stream feeding a bf16 product: one rounding, of the
@@ -261,21 +270,13 @@ int launch_stats(const void* x, long ldx, float* stats, int rows, int C, float e
 extern "C" int haff_layernorm(const void* x, long ldx, void* y, long ldy, const float* w, const float* b,
                               const int* in_map, int rows, int C, float eps, int dtype, void* stream) {
   if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || (ldy & 7) || !w || !b || dtype < 0 || dtype > 3) return HAFF_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == 2) return launch_norm<float, false, bf16_t>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s);
-  if (dtype == 3) return launch_norm<f16_t, false>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s);
-  return dtype == 0 ? launch_norm<bf16_t, false>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s)
-                    : launch_norm<float, false>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, s);
+  return launch_norm_dtype<false>(x, ldx, y, ldy, w, b, in_map, rows, C, eps, dtype, stream);
 }
 
 extern "C" int haff_rmsnorm(const void* x, long ldx, void* y, long ldy, const float* w, int rows, int C,
                             float eps, int dtype, void* stream) {
   if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || (ldy & 7) || !w || dtype < 0 || dtype > 3) return HAFF_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == 2) return launch_norm<float, true, bf16_t>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s);   // (as haff_layernorm)
-  if (dtype == 3) return launch_norm<f16_t, true>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s);
-  return dtype == 0 ? launch_norm<bf16_t, true>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s)
-                    : launch_norm<float, true>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, s);
+  return launch_norm_dtype<true>(x, ldx, y, ldy, w, nullptr, nullptr, rows, C, eps, dtype, stream);
 }
 
 // {mean, rstd} from the per-wave partial sums haff_gemm_bf16_rowstats left: partials f32 [rows][slots][2] = {sum, sum of squares}
@@ -307,7 +308,7 @@ __global__ __launch_bounds__(256) void row_stats_finalize_kernel(const float* pa
 
 extern "C" int haff_row_stats_finalize(const float* partials, float* stats, int rows, int slots, int C, float eps, void* stream) {
   if (rows <= 0 || slots <= 0 || C <= 0 || !partials || !stats) return HAFF_ERR_BAD_ARG;
-  hipLaunchKernelGGL(row_stats_finalize_kernel, dim3((rows + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(row_stats_finalize_kernel, dim3((rows + 255) / 256), dim3(256), 0, haff_stream(stream),
                      partials, stats, rows, slots, C, eps);
   return haff_check_launch();
 }
@@ -317,9 +318,6 @@ extern "C" int haff_row_stats_finalize(const float* partials, float* stats, int 
 extern "C" int haff_row_stats(const void* x, long ldx, float* stats, int rows, int C, float eps, int rms, int dtype,
                               void* stream) {
   if (rows <= 0 || C <= 0 || (C & 7) || (ldx & 7) || !stats) return HAFF_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == 0) return rms ? launch_stats<bf16_t, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<bf16_t, false>(x, ldx, stats, rows, C, eps, s);
-  if (dtype == 3) return rms ? launch_stats<f16_t, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<f16_t, false>(x, ldx, stats, rows, C, eps, s);
-  if (dtype != 1) return HAFF_ERR_BAD_ARG;
-  return rms ? launch_stats<float, true>(x, ldx, stats, rows, C, eps, s) : launch_stats<float, false>(x, ldx, stats, rows, C, eps, s);
+  HAFF_DISPATCH(dtype, HAFF_DISPATCH_BOOL(rms, RMS, return launch_stats<T, RMS>(x, ldx, stats, rows, C, eps, haff_stream(stream))));
+  return HAFF_ERR_BAD_ARG;   // not reached: every case above returns
 }

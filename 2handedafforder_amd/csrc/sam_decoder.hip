@@ -163,11 +163,7 @@ extern "C" int haff_upscale_mask(const void* up1, const float* ln_w, const float
   if (n_prompts <= 0 || h <= 0 || w <= 0) return HAFF_ERR_BAD_ARG;
   const long total = (long)n_prompts * h * w * 4;
   dim3 g((unsigned)((total + 255) / 256)), b(256);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == 0) hipLaunchKernelGGL((upscale_mask_kernel<bf16_t>), g, b, 0, s, (const bf16_t*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps);
-  else if (dtype == 3) hipLaunchKernelGGL((upscale_mask_kernel<f16_t>), g, b, 0, s, (const f16_t*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps);
-  else if (dtype == 1) hipLaunchKernelGGL((upscale_mask_kernel<float>), g, b, 0, s, (const float*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps);
-  else return HAFF_ERR_BAD_ARG;
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((upscale_mask_kernel<T>), g, b, 0, haff_stream(stream), (const T*)up1, ln_w, ln_b, w2, b2, hyper, out, n_prompts, h, w, eps));
   return haff_check_launch();
 }
 
@@ -175,18 +171,15 @@ extern "C" int haff_upscale_mask(const void* up1, const float* ln_w, const float
 extern "C" int haff_resize_bilinear(const float* in, float* out, int N, int Hs, int Ws, int Hc, int Wc, int Ho, int Wo,
                                     void* stream) {
   if (N <= 0 || Hc <= 0 || Wc <= 0 || Hc > Hs || Wc > Ws || Ho <= 0 || Wo <= 0) return HAFF_ERR_BAD_ARG;
-  const long total = (long)N * Ho * Wo;
-  long g = (total + 255) / 256;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(resize_bilinear_kernel, dim3((unsigned)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), in, out, N, Hs, Ws, Hc, Wc, Ho, Wo);
+  const dim3 g(haff_grid((long)N * Ho * Wo, 256, 16384));   // N, Ho, Wo >= 1: the floor of 1 never applies
+  hipLaunchKernelGGL(resize_bilinear_kernel, g, dim3(256), 0, haff_stream(stream), in, out, N, Hs, Ws, Hc, Wc, Ho, Wo);
   return haff_check_launch();
 }
 
 extern "C" int haff_threshold_masks(const float* in, void* out, long total, float logit_th, void* stream) {
   if (total <= 0) return HAFF_ERR_BAD_ARG;
-  long g = (total + 255) / 256;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL(threshold_masks_kernel, dim3((unsigned)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), in, (unsigned char*)out, total, logit_th);
+  const dim3 g(haff_grid(total, 256, 16384));               // total >= 1: likewise
+  hipLaunchKernelGGL(threshold_masks_kernel, g, dim3(256), 0, haff_stream(stream), in, (unsigned char*)out, total, logit_th);
   return haff_check_launch();
 }
 
@@ -198,14 +191,9 @@ extern "C" int haff_gate_threshold_masks(const float* logits, void* planes, long
                                          const float* thresholds_host, int n_th, int on_value, const float* taxonomy,
                                          int blank_class, void* stream) {
   if (total <= 0 || n_th <= 0 || n_th > 8 || on_value < 0 || on_value > 255 || !thresholds_host) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(logits) & 15) || (reinterpret_cast<uintptr_t>(planes) & 3) || plane_stride < total ||
-      (plane_stride & 3))
-    return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(logits) || !haff_aligned(planes, 4) || plane_stride < total || (plane_stride & 3)) return HAFF_ERR_BAD_ARG;
   GateArgs p{logits, (unsigned char*)planes, total, plane_stride, taxonomy, blank_class, n_th, on_value, {}};
   for (int t = 0; t < n_th; ++t) p.th[t] = thresholds_host[t];
-  long g = ((total >> 2) + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(gate_threshold_kernel, dim3((unsigned)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(gate_threshold_kernel, dim3(haff_grid(total >> 2, 256, 8192)), dim3(256), 0, haff_stream(stream), p);
   return haff_check_launch();
 }

@@ -10,10 +10,7 @@
 
 namespace {
 
-inline int grid_for(long total, int block) {
-  long g = (total + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
+inline int grid_for(long total, int block, long cap = 16384) { return haff_grid(total, block, cap); }
 
 // ---- batched 2-D transpose: in [nb][R][ld_in] (C valid columns) -> out [nb][Cp][Rp], zero padded ---------------
 template <typename T>
@@ -673,68 +670,53 @@ __global__ void adamw_kernel(float* master, float* m, float* v, const TG* g, TP*
 
 }  // namespace
 
-#define HS(s) reinterpret_cast<hipStream_t>(s)
-// storage-type dispatch: T = the element type of dtype code 0 (bf16), 1 (f32) or 3 (f16); any other code is refused before a
-// launch (code 2 is the norms' mixed form, which none of these kernels has)
-#define DISPATCH_T(dtype, ...) \
-  do { \
-    switch (dtype) { \
-      case 0: { using T = bf16_t; __VA_ARGS__; } break; \
-      case 1: { using T = float; __VA_ARGS__; } break; \
-      case 3: { using T = f16_t; __VA_ARGS__; } break; \
-      default: return HAFF_ERR_BAD_ARG; \
-    } \
-  } while (0)
-
 extern "C" int haff_transpose(const void* in, long ld_in, long s_in_o, long s_in_i, void* out, int R, int C, int Rp, int Cp,
                               int nb_outer, int nb_inner, int dtype, void* stream) {
   if (R <= 0 || C <= 0 || Rp < R || Cp < C || nb_outer <= 0 || nb_inner <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g((Cp + 31) / 32, (Rp + 31) / 32, nb_outer * nb_inner), b(32, 8);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((transpose_kernel<T>), g, b, 0, HS(stream), (const T*)in, ld_in, s_in_o, s_in_i, (T*)out, R, C, Rp, Cp, nb_inner));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((transpose_kernel<T>), g, b, 0, haff_stream(stream), (const T*)in, ld_in, s_in_o, s_in_i, (T*)out, R, C, Rp, Cp, nb_inner));
   return haff_check_launch();
 }
 
 extern "C" int haff_act_fwd(const void* x, void* y, long n, int act, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((act_fwd_kernel<T>), g, b, 0, HS(stream), (const T*)x, (T*)y, n, act));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((act_fwd_kernel<T>), g, b, 0, haff_stream(stream), (const T*)x, (T*)y, n, act));
   return haff_check_launch();
 }
 extern "C" int haff_act_bwd(const void* x, const void* dy, void* dx, long n, int act, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((act_bwd_kernel<T>), g, b, 0, HS(stream), (const T*)x, (const T*)dy, (T*)dx, n, act));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((act_bwd_kernel<T>), g, b, 0, haff_stream(stream), (const T*)x, (const T*)dy, (T*)dx, n, act));
   return haff_check_launch();
 }
 extern "C" int haff_swiglu_fwd(const void* gu, void* y, long M, int F, int dtype, void* stream) {
   if (M <= 0 || F <= 0 || (F & 15)) return HAFF_ERR_BAD_ARG;
-  if ((dtype == 0 || dtype == 3) && ((reinterpret_cast<uintptr_t>(gu) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
+  if ((dtype == 0 || dtype == 3) && haff_aligned(gu) && haff_aligned(y)) {
     const dim3 g(grid_for(M * F / 8, 256)), b(256);
-    if (dtype == 0) hipLaunchKernelGGL((swiglu_fwd_vec_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)gu, (bf16_t*)y, M, F);
-    else hipLaunchKernelGGL((swiglu_fwd_vec_kernel<f16_t>), g, b, 0, HS(stream), (const f16_t*)gu, (f16_t*)y, M, F);
+    HAFF_DISPATCH_16(dtype, hipLaunchKernelGGL((swiglu_fwd_vec_kernel<T>), g, b, 0, haff_stream(stream), (const T*)gu, (T*)y, M, F));
     return haff_check_launch();
   }
   dim3 g(grid_for(M * F, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_fwd_kernel<T>), g, b, 0, HS(stream), (const T*)gu, (T*)y, M, F));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((swiglu_fwd_kernel<T>), g, b, 0, haff_stream(stream), (const T*)gu, (T*)y, M, F));
   return haff_check_launch();
 }
 extern "C" int haff_swiglu_bwd(const void* gu, const void* dy, void* dgu, long M, int F, int dtype, void* stream) {
   if (M <= 0 || F <= 0 || (F & 15)) return HAFF_ERR_BAD_ARG;
-  if ((dtype == 0 || dtype == 3) && ((reinterpret_cast<uintptr_t>(gu) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dgu)) & 15) == 0) {
+  if ((dtype == 0 || dtype == 3) && haff_aligned(gu) && haff_aligned(dy) && haff_aligned(dgu)) {
     const dim3 g(grid_for(M * F / 8, 256)), b(256);
-    if (dtype == 0) hipLaunchKernelGGL((swiglu_bwd_vec_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)gu, (const bf16_t*)dy, (bf16_t*)dgu, M, F);
-    else hipLaunchKernelGGL((swiglu_bwd_vec_kernel<f16_t>), g, b, 0, HS(stream), (const f16_t*)gu, (const f16_t*)dy, (f16_t*)dgu, M, F);
+    HAFF_DISPATCH_16(dtype, hipLaunchKernelGGL((swiglu_bwd_vec_kernel<T>), g, b, 0, haff_stream(stream), (const T*)gu, (const T*)dy, (T*)dgu, M, F));
     return haff_check_launch();
   }
   dim3 g(grid_for(M * F, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_bwd_kernel<T>), g, b, 0, HS(stream), (const T*)gu, (const T*)dy, (T*)dgu, M, F));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((swiglu_bwd_kernel<T>), g, b, 0, haff_stream(stream), (const T*)gu, (const T*)dy, (T*)dgu, M, F));
   return haff_check_launch();
 }
 // out = alpha*a + beta*b (b may be null)
 extern "C" int haff_axpby(const void* a, const void* b, void* out, long n, float alpha, float beta, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), blk(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((axpby_kernel<T>), g, blk, 0, HS(stream), (const T*)a, (const T*)b, (T*)out, n, alpha, beta));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((axpby_kernel<T>), g, blk, 0, haff_stream(stream), (const T*)a, (const T*)b, (T*)out, n, alpha, beta));
   return haff_check_launch();
 }
 // out = a * alpha with alpha an fp32 scalar (alpha_stride = 0) or one fp32 value per row (alpha_stride = 1) in DEVICE memory: the
@@ -745,14 +727,14 @@ extern "C" int haff_scale_dev(const void* a, void* out, long rows, long cols, co
                               void* stream) {
   if (rows <= 0 || cols <= 0 || !alpha || (alpha_stride != 0 && alpha_stride != 1)) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(rows * cols, 256)), blk(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((scale_dev_kernel<T>), g, blk, 0, HS(stream), (const T*)a, (T*)out, rows, cols, alpha, alpha_stride));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((scale_dev_kernel<T>), g, blk, 0, haff_stream(stream), (const T*)a, (T*)out, rows, cols, alpha, alpha_stride));
   return haff_check_launch();
 }
 // out = a * b elementwise (LoRA dropout mask, peft lora_dropout, train_ds.py:224)
 extern "C" int haff_mul(const void* a, const void* b, void* out, long n, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(n, 256)), blk(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((mul_kernel<T>), g, blk, 0, HS(stream), (const T*)a, (const T*)b, (T*)out, n));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((mul_kernel<T>), g, blk, 0, haff_stream(stream), (const T*)a, (const T*)b, (T*)out, n));
   return haff_check_launch();
 }
 // rms != 0: RMSNorm adjoint (dx only). dyx (f32 [rows][C], may be null) receives dy*xhat for the weight gradient.
@@ -760,23 +742,14 @@ static int norm_bwd_launch(const void* x, const void* dy, const float* w, const 
                            float eps, int rms, int dtype, void* stream) {
   if (rows <= 0 || C <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g((rows + 3) / 4), b(256);
-  const bool al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) |
-                    reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(dyx) | reinterpret_cast<uintptr_t>(add)) & 15) == 0;
-  if ((dtype == 0 || dtype == 3) && al && (C == 4096 || C == 5120)) {   // Llama 7B / 13B rows: one pass, the row in registers
-#define HAFF_NBV(T_, R_, NV_) hipLaunchKernelGGL((norm_bwd_vec_kernel<T_, R_, NV_>), g, b, 0, HS(stream), (const T_*)x, (const T_*)dy, w, (T_*)dx, dyx, rows, eps, (const T_*)add)
-    if (dtype == 0) {
-      if (C == 4096) { if (rms) HAFF_NBV(bf16_t, true, 8); else HAFF_NBV(bf16_t, false, 8); }
-      else { if (rms) HAFF_NBV(bf16_t, true, 10); else HAFF_NBV(bf16_t, false, 10); }
-    } else {
-      if (C == 4096) { if (rms) HAFF_NBV(f16_t, true, 8); else HAFF_NBV(f16_t, false, 8); }
-      else { if (rms) HAFF_NBV(f16_t, true, 10); else HAFF_NBV(f16_t, false, 10); }
-    }
-#undef HAFF_NBV
+  const bool al = haff_aligned(x) && haff_aligned(dy) && haff_aligned(dx) && haff_aligned(w) && haff_aligned(dyx) && haff_aligned(add);
+  if ((dtype == 0 || dtype == 3) && al && (C == 4096 || C == 5120)) {   // Llama 7B / 13B rows: one pass, the row in registers (8 / 10 vectors per lane)
+    HAFF_DISPATCH_16(dtype, HAFF_DISPATCH_BOOL(C == 4096, NV8, HAFF_DISPATCH_BOOL(rms, RMS,
+        hipLaunchKernelGGL((norm_bwd_vec_kernel<T, RMS, NV8 ? 8 : 10>), g, b, 0, haff_stream(stream), (const T*)x, (const T*)dy, w, (T*)dx, dyx, rows, eps, (const T*)add))));
     return haff_check_launch();
   }
-  DISPATCH_T(dtype,
-             if (rms) hipLaunchKernelGGL((norm_bwd_kernel<T, true>), g, b, 0, HS(stream), (const T*)x, (const T*)dy, w, (T*)dx, dyx, rows, C, eps, (const T*)add);
-             else hipLaunchKernelGGL((norm_bwd_kernel<T, false>), g, b, 0, HS(stream), (const T*)x, (const T*)dy, w, (T*)dx, dyx, rows, C, eps, (const T*)add));
+  HAFF_DISPATCH(dtype, HAFF_DISPATCH_BOOL(rms, RMS,
+      hipLaunchKernelGGL((norm_bwd_kernel<T, RMS>), g, b, 0, haff_stream(stream), (const T*)x, (const T*)dy, w, (T*)dx, dyx, rows, C, eps, (const T*)add)));
   return haff_check_launch();
 }
 
@@ -797,31 +770,30 @@ extern "C" int haff_norm_bwd_add(const void* x, const void* dy, const float* w, 
 extern "C" int haff_colsum(const void* x, float* out, long R, int C, int dtype, void* stream) {
   if (R <= 0 || C <= 0) return HAFF_ERR_BAD_ARG;
   if ((dtype == 0 || dtype == 3) && (C & 7) == 0 && C >= 8 && C <= 2048 && ((C >> 3) & ((C >> 3) - 1)) == 0 &&
-      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && R >= 1024) {
+      haff_aligned(x) && R >= 1024) {
     const long rpp = 1024 / (C >> 3);
     long rpb_v = ((R + 63) / 64 + 8 * rpp - 1) / (8 * rpp) * (8 * rpp);   // <= 64 blocks, whole 8-row steps
     const dim3 g((unsigned)((R + rpb_v - 1) / rpb_v)), b(1024);
-    if (dtype == 0) hipLaunchKernelGGL((colsum_vec_kernel<bf16_t>), g, b, 0, HS(stream), (const bf16_t*)x, out, R, C, rpb_v);
-    else hipLaunchKernelGGL((colsum_vec_kernel<f16_t>), g, b, 0, HS(stream), (const f16_t*)x, out, R, C, rpb_v);
+    HAFF_DISPATCH_16(dtype, hipLaunchKernelGGL((colsum_vec_kernel<T>), g, b, 0, haff_stream(stream), (const T*)x, out, R, C, rpb_v));
     return haff_check_launch();
   }
   const long rpb = 256;
   dim3 g((C + 63) / 64, (unsigned)((R + rpb - 1) / rpb)), b(64);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<T>), g, b, 0, HS(stream), (const T*)x, out, R, C, rpb));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((colsum_kernel<T>), g, b, 0, haff_stream(stream), (const T*)x, out, R, C, rpb));
   return haff_check_launch();
 }
 extern "C" int haff_softmax_fwd(const float* s, long ld, void* p, long ldp, long rows, int Nq, int Nk, float scale, int causal,
                                 int q_pos0, int dtype, void* stream) {
   if (rows <= 0 || Nq <= 0 || Nk <= 0 || ldp < Nk || ld < Nk) return HAFF_ERR_BAD_ARG;   // the kernel takes row % Nq
   dim3 g((unsigned)((rows + 3) / 4)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_fwd_kernel<T>), g, b, 0, HS(stream), s, ld, (T*)p, ldp, rows, Nq, Nk, scale, causal, q_pos0));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((softmax_fwd_kernel<T>), g, b, 0, haff_stream(stream), s, ld, (T*)p, ldp, rows, Nq, Nk, scale, causal, q_pos0));
   return haff_check_launch();
 }
 extern "C" int haff_softmax_bwd(const void* p, long ldp, const float* dp, long ld, void* ds, long rows, int Nk, float scale,
                                 int dtype, void* stream) {
   if (rows <= 0 || Nk <= 0 || ldp < Nk || ld < Nk) return HAFF_ERR_BAD_ARG;   // rows shorter than Nk would overlap
   dim3 g((unsigned)((rows + 3) / 4)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_bwd_kernel<T>), g, b, 0, HS(stream), (const T*)p, ldp, dp, ld, (T*)ds, rows, Nk, scale));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((softmax_bwd_kernel<T>), g, b, 0, haff_stream(stream), (const T*)p, ldp, dp, ld, (T*)ds, rows, Nk, scale));
   return haff_check_launch();
 }
 extern "C" int haff_rope(const void* x, long ldx, void* y, long ldy, const float* cos_sin, long rows, int Tlen, int H, int d,
@@ -829,71 +801,74 @@ extern "C" int haff_rope(const void* x, long ldx, void* y, long ldy, const float
   if (rows <= 0 || Tlen <= 0 || H <= 0 || d <= 0 || (d & 1)) return HAFF_ERR_BAD_ARG;   // the kernel divides by each of them
   dim3 g(grid_for(rows * H * (d / 2), 256)), b(256);
   const float sign = adjoint ? -1.f : 1.f;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((rope_kernel<T>), g, b, 0, HS(stream), (const T*)x, ldx, (T*)y, ldy, cos_sin, rows, Tlen, H, d, pos0, sign));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((rope_kernel<T>), g, b, 0, haff_stream(stream), (const T*)x, ldx, (T*)y, ldy, cos_sin, rows, Tlen, H, d, pos0, sign));
   return haff_check_launch();
 }
 extern "C" int haff_cross_entropy(const void* logits, long ld, const long* labels, float* row_loss, void* dlogits, long rows,
                                   int V, float gscale, int dtype, void* stream) {
   if (rows <= 0 || V <= 0 || ld < V) return HAFF_ERR_BAD_ARG;   // ld < V: a row's gradient would be written over the next row
   dim3 g((unsigned)rows), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((cross_entropy_kernel<T>), g, b, 0, HS(stream), (const T*)logits, ld, labels, row_loss, (T*)dlogits, V, gscale));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((cross_entropy_kernel<T>), g, b, 0, haff_stream(stream), (const T*)logits, ld, labels, row_loss, (T*)dlogits, V, gscale));
   return haff_check_launch();
 }
 extern "C" int haff_mask_loss_stats(const float* x, const float* t, float* stats, int n_samples, long n, float wgt, void* stream) {
   if (n_samples <= 0 || n <= 0) return HAFF_ERR_BAD_ARG;
-  dim3 g(grid_for(n, 256) > 256 ? 256 : grid_for(n, 256), n_samples), b(256);
-  hipLaunchKernelGGL(mask_loss_stats_kernel, g, b, 0, HS(stream), x, t, stats, n, wgt);
+  dim3 g(grid_for(n, 256, 256), n_samples), b(256);
+  hipLaunchKernelGGL(mask_loss_stats_kernel, g, b, 0, haff_stream(stream), x, t, stats, n, wgt);
+  return haff_check_launch();
+}
+// the coefficients as host values (coef null) or as a device pair coef (then c_bce = c_dice = 1)
+static int mask_loss_grad_launch(const float* x, const float* t, const float* stats, float* dx, int n_samples, long n, float wgt,
+                                 float c_bce, float c_dice, const float* coef, void* stream) {
+  if (n_samples <= 0 || n <= 0) return HAFF_ERR_BAD_ARG;
+  dim3 g(grid_for(n, 256, 256), n_samples), b(256);
+  hipLaunchKernelGGL(mask_loss_grad_kernel, g, b, 0, haff_stream(stream), x, t, stats, dx, n, wgt, c_bce, c_dice, coef);
   return haff_check_launch();
 }
 extern "C" int haff_mask_loss_grad(const float* x, const float* t, const float* stats, float* dx, int n_samples, long n, float wgt,
                                    float c_bce, float c_dice, void* stream) {
-  if (n_samples <= 0 || n <= 0) return HAFF_ERR_BAD_ARG;
-  dim3 g(grid_for(n, 256) > 256 ? 256 : grid_for(n, 256), n_samples), b(256);
-  hipLaunchKernelGGL(mask_loss_grad_kernel, g, b, 0, HS(stream), x, t, stats, dx, n, wgt, c_bce, c_dice, (const float*)nullptr);
-  return haff_check_launch();
+  return mask_loss_grad_launch(x, t, stats, dx, n_samples, n, wgt, c_bce, c_dice, nullptr, stream);
 }
 extern "C" int haff_mask_loss_grad_dev(const float* x, const float* t, const float* stats, float* dx, int n_samples, long n, float wgt,
                                        const float* coef, void* stream) {
-  if (n_samples <= 0 || n <= 0 || !coef) return HAFF_ERR_BAD_ARG;
-  dim3 g(grid_for(n, 256) > 256 ? 256 : grid_for(n, 256), n_samples), b(256);
-  hipLaunchKernelGGL(mask_loss_grad_kernel, g, b, 0, HS(stream), x, t, stats, dx, n, wgt, 1.f, 1.f, coef);
-  return haff_check_launch();
+  if (!coef) return HAFF_ERR_BAD_ARG;
+  return mask_loss_grad_launch(x, t, stats, dx, n_samples, n, wgt, 1.f, 1.f, coef, stream);
 }
 extern "C" int haff_resize_bilinear_bwd(const float* dout, float* din, int N, int Hs, int Ws, int Hc, int Wc, int Ho, int Wo,
                                         void* stream) {
   if (N <= 0 || Hc <= 0 || Wc <= 0 || Hc > Hs || Wc > Ws || Ho <= 0 || Wo <= 0) return HAFF_ERR_BAD_ARG;   // the scales divide by Ho / Wo
-  hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(grid_for((long)N * Hc * Wc, 256)), dim3(256), 0, HS(stream), dout, din, N, Hs, Ws, Hc, Wc, Ho, Wo);
+  hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(grid_for((long)N * Hc * Wc, 256)), dim3(256), 0, haff_stream(stream), dout, din, N, Hs, Ws, Hc, Wc, Ho, Wo);
   return haff_check_launch();
 }
 extern "C" int haff_scatter_add_rows(const long* ids, const void* dx, float* dE, long rows, int C, int dtype, void* stream) {
   if (rows <= 0 || C <= 0) return HAFF_ERR_BAD_ARG;
   dim3 g(grid_for(rows * C, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((scatter_add_rows_kernel<T>), g, b, 0, HS(stream), ids, (const T*)dx, dE, rows, C));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((scatter_add_rows_kernel<T>), g, b, 0, haff_stream(stream), ids, (const T*)dx, dE, rows, C));
   return haff_check_launch();
 }
 // ---- ordered (atomic-free, bitwise repeatable) forms; partial buffers are caller-provided DEVICE fp32 ----
 extern "C" int haff_reduce_partials(const float* partials, float* out, int n_out, int n_parts, int out_inner, long part_stride,
                                     long group_stride, int accumulate, void* stream) {
   if (!partials || !out || n_out <= 0 || n_parts <= 0 || out_inner <= 0) return HAFF_ERR_BAD_ARG;
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3(n_out), dim3(64), 0, HS(stream), partials, out, n_out, n_parts, out_inner, part_stride,
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3(n_out), dim3(64), 0, haff_stream(stream), partials, out, n_out, n_parts, out_inner, part_stride,
                      group_stride, accumulate);
   return haff_check_launch();
 }
 // partials: >= 1024 floats; *n_parts (host) = how many were written
 extern "C" int haff_sumsq_partials(const void* g, float* partials, long n, int dtype, int* n_parts, void* stream) {
   if (n <= 0 || !partials || !n_parts) return HAFF_ERR_BAD_ARG;
-  const int nb = grid_for(n, 256) > 1024 ? 1024 : grid_for(n, 256);
+  const int nb = grid_for(n, 256, 1024);
   *n_parts = nb;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((sumsq_partials_kernel<T>), dim3(nb), dim3(256), 0, HS(stream), (const T*)g, partials, n));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((sumsq_partials_kernel<T>), dim3(nb), dim3(256), 0, haff_stream(stream), (const T*)g, partials, n));
   return haff_check_launch();
 }
 // partials: >= n_samples * 256 * 4 floats, laid out [sample][part][4]; *n_parts = parts per sample
 extern "C" int haff_mask_loss_stats_partials(const float* x, const float* t, float* partials, int n_samples, long n, float wgt,
                                              int* n_parts, void* stream) {
   if (n_samples <= 0 || n <= 0 || !partials || !n_parts) return HAFF_ERR_BAD_ARG;
-  const int nb = grid_for(n, 256) > 256 ? 256 : grid_for(n, 256);
+  const int nb = grid_for(n, 256, 256);
   *n_parts = nb;
-  hipLaunchKernelGGL(mask_loss_stats_partials_kernel, dim3(nb, n_samples), dim3(256), 0, HS(stream), x, t, partials, n, wgt);
+  hipLaunchKernelGGL(mask_loss_stats_partials_kernel, dim3(nb, n_samples), dim3(256), 0, haff_stream(stream), x, t, partials, n, wgt);
   return haff_check_launch();
 }
 // row blocks of the column sums: haff_colsum_parts(R) blocks, partials [parts][C]
@@ -907,20 +882,20 @@ extern "C" int haff_colsum_partials(const void* x, float* partials, long R, int 
   const int parts = haff_colsum_parts(R);
   const long rpb = (R + parts - 1) / parts;
   dim3 g((C + 63) / 64, parts), b(64);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_partials_kernel<T>), g, b, 0, HS(stream), (const T*)x, partials, R, C, rpb));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((colsum_partials_kernel<T>), g, b, 0, haff_stream(stream), (const T*)x, partials, R, C, rpb));
   return haff_check_launch();
 }
 // sorted_ids / order: a STABLE ascending sort of the rows' ids and the permutation that produced it (DEVICE int64 [rows])
 extern "C" int haff_scatter_add_rows_sorted(const long* sorted_ids, const long* order, const void* dx, float* dE, long rows, int C,
                                             int dtype, void* stream) {
   if (rows <= 0 || C <= 0 || !sorted_ids || !order) return HAFF_ERR_BAD_ARG;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((scatter_add_rows_sorted_kernel<T>), dim3((unsigned)rows), dim3(256), 0, HS(stream), sorted_ids, order, (const T*)dx, dE, rows, C));
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((scatter_add_rows_sorted_kernel<T>), dim3((unsigned)rows), dim3(256), 0, haff_stream(stream), sorted_ids, order, (const T*)dx, dE, rows, C));
   return haff_check_launch();
 }
 extern "C" int haff_sumsq(const void* g, float* out, long n, int dtype, void* stream) {
   if (n <= 0) return HAFF_ERR_BAD_ARG;
-  dim3 gr(grid_for(n, 256) > 1024 ? 1024 : grid_for(n, 256)), b(256);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((sumsq_kernel<T>), gr, b, 0, HS(stream), (const T*)g, out, n));
+  dim3 gr(grid_for(n, 256, 1024)), b(256);
+  HAFF_DISPATCH(dtype, hipLaunchKernelGGL((sumsq_kernel<T>), gr, b, 0, haff_stream(stream), (const T*)g, out, n));
   return haff_check_launch();
 }
 // g_dtype: gradient storage (0 bf16 / 1 f32 / 3 f16); lp_dtype: -1 none, 0 bf16 / 3 f16 copy of the updated parameter
@@ -933,7 +908,7 @@ static int adamw_launch(float* master, float* m, float* v, const void* g, void* 
   dim3 gr(grid_for(n, 256)), b(256);
   // the copy's type is a template parameter: an f16 copy is f16_rn(master), a bf16 one bf16_rn(master) (lp_dtype -1: no copy)
 #define HAFF_ADAMW(TP_) \
-  DISPATCH_T(g_dtype, hipLaunchKernelGGL((adamw_kernel<T, TP_>), gr, b, 0, HS(stream), master, m, v, (const T*)g, \
+  HAFF_DISPATCH(g_dtype, hipLaunchKernelGGL((adamw_kernel<T, TP_>), gr, b, 0, haff_stream(stream), master, m, v, (const T*)g, \
                                          lp_dtype == -1 ? nullptr : (TP_*)param_lp, n, lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gscale_dev, norm))
   if (lp_dtype == 3) HAFF_ADAMW(f16_t);
   else HAFF_ADAMW(bf16_t);
@@ -966,6 +941,6 @@ extern "C" int haff_adamw_step_skip(float* master, float* m, float* v, const voi
 // z, t f32 [rows][C<=8]; probs (may be null) = softmax(z); loss f32[rows]; dz (may be null) = d loss / d z
 extern "C" int haff_taxonomy_ce(const float* z, const float* t, float* probs, float* loss, float* dz, int rows, int C, void* stream) {
   if (rows <= 0 || C <= 0 || C > 8) return HAFF_ERR_BAD_ARG;
-  hipLaunchKernelGGL(taxonomy_ce_kernel, dim3((rows + 63) / 64), dim3(64), 0, HS(stream), z, t, probs, loss, dz, rows, C);
+  hipLaunchKernelGGL(taxonomy_ce_kernel, dim3((rows + 63) / 64), dim3(64), 0, haff_stream(stream), z, t, probs, loss, dz, rows, C);
   return haff_check_launch();
 }

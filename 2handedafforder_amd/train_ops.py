@@ -6,7 +6,7 @@ import math
 
 import torch
 
-from .autograd import _dt, _s
+from .autograd import _call, _dt, _s
 from .lib import check, load_library
 
 
@@ -23,12 +23,23 @@ class AdamWState:
 _LP_DT = {torch.bfloat16: 0, torch.float16: 3}   # the kernel's code of a 16-bit parameter copy (bf16_rn / f16_rn of the master)
 
 
+def _adamw(master, m, v, grad, lp_ptr, lp_dt, n, lr, betas, eps, wd, step, gscale, gscale_dev, skip_norm):
+    """The adamw entry point that gscale_dev / skip_norm (device fp32 scalars or None) select, on the 13 arguments all three share."""
+    args = (master.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), lp_ptr, n, float(lr), float(betas[0]), float(betas[1]),
+            float(eps), float(wd), step, float(gscale))
+    if skip_norm is not None:
+        _call("haff_adamw_step_skip", *args, 0 if gscale_dev is None else gscale_dev.data_ptr(), skip_norm.data_ptr(), _dt(grad), lp_dt)
+    elif gscale_dev is not None:
+        _call("haff_adamw_step_dev", *args, gscale_dev.data_ptr(), _dt(grad), lp_dt)
+    else:
+        _call("haff_adamw_step", *args, _dt(grad), lp_dt)
+
+
 def adamw_step(state, grad, lr, betas=(0.9, 0.95), eps=1e-8, wd=0.0, gscale=1.0, param_lp=None, gscale_dev=None, skip_norm=None):
     """One fused AdamW update (torch.optim.AdamW semantics); optionally refreshes a bf16 / fp16 copy of the parameter.
     gscale_dev: device fp32 scalar multiplied into gscale inside the kernel (clip_coef_device: no host read of the norm).
     skip_norm: device fp32 gradient norm; the kernel leaves every bit of the state and the copy alone when it is not finite (the
     fp16 mode's overflow). The host does not know the outcome: the caller undoes `state.step += 1` after reading the norm."""
-    lib = load_library()
     state.step += 1
     grad = grad.contiguous()
     lp_ptr, lp_dt = 0, -1
@@ -36,19 +47,10 @@ def adamw_step(state, grad, lr, betas=(0.9, 0.95), eps=1e-8, wd=0.0, gscale=1.0,
         lp_ptr, lp_dt = param_lp.data_ptr(), _LP_DT[param_lp.dtype]
     if skip_norm is not None:
         assert skip_norm.dtype == torch.float32 and skip_norm.numel() == 1
-        check(lib.haff_adamw_step_skip(state.master.data_ptr(), state.m.data_ptr(), state.v.data_ptr(), grad.data_ptr(), lp_ptr,
-                                       state.master.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(wd),
-                                       state.step, float(gscale), 0 if gscale_dev is None else gscale_dev.data_ptr(),
-                                       skip_norm.data_ptr(), _dt(grad), lp_dt, _s()), "haff_adamw_step_skip")
     elif gscale_dev is not None:
         assert gscale_dev.dtype == torch.float32 and gscale_dev.numel() == 1
-        check(lib.haff_adamw_step_dev(state.master.data_ptr(), state.m.data_ptr(), state.v.data_ptr(), grad.data_ptr(), lp_ptr,
-                                      state.master.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(wd),
-                                      state.step, float(gscale), gscale_dev.data_ptr(), _dt(grad), lp_dt, _s()), "haff_adamw_step_dev")
-    else:
-        check(lib.haff_adamw_step(state.master.data_ptr(), state.m.data_ptr(), state.v.data_ptr(), grad.data_ptr(), lp_ptr,
-                                  state.master.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), float(wd),
-                                  state.step, float(gscale), _dt(grad), lp_dt, _s()), "haff_adamw_step")
+    _adamw(state.master, state.m, state.v, grad, lp_ptr, lp_dt, state.master.numel(), lr, betas, eps, wd, state.step, gscale, gscale_dev,
+           skip_norm)
     if param_lp is not None and param_lp.dtype == torch.float32:
         param_lp.copy_(state.master)  # fp32 parameters alias the master values (plain copy)
 
@@ -287,20 +289,11 @@ class BucketAdamW:
         """skip_norm (device fp32 gradient norm, fp16 mode): every bucket's update is skipped on the device when it is not finite.
         The step count advances here; the caller reads the norm once and calls unstep() on an overflow (the skipped step then
         does not count: DeepSpeed's fp16 optimizer neither steps Adam nor the LR scheduler on an overflow)."""
-        lib = load_library()
         self.step_count += 1
         for b in self.buckets:
-            g = b["grad"]
             lp_ptr, lp_dt = (b["lp"].data_ptr(), _LP_DT[b["lp"].dtype]) if b["lp"] is not None else (0, -1)
-            args = (b["master"].data_ptr(), b["m"].data_ptr(), b["v"].data_ptr(), g.data_ptr(), lp_ptr, g.numel(), float(lr),
-                    float(betas[0]), float(betas[1]), float(eps), float(wd), self.step_count, float(gscale))
-            if skip_norm is not None:
-                check(lib.haff_adamw_step_skip(*args, 0 if gscale_dev is None else gscale_dev.data_ptr(), skip_norm.data_ptr(), _dt(g),
-                                               lp_dt, _s()), "haff_adamw_step_skip")
-            elif gscale_dev is not None:
-                check(lib.haff_adamw_step_dev(*args, gscale_dev.data_ptr(), _dt(g), lp_dt, _s()), "haff_adamw_step_dev")
-            else:
-                check(lib.haff_adamw_step(*args, _dt(g), lp_dt, _s()), "haff_adamw_step")
+            _adamw(b["master"], b["m"], b["v"], b["grad"], lp_ptr, lp_dt, b["grad"].numel(), lr, betas, eps, wd, self.step_count, gscale,
+                   gscale_dev, skip_norm)
 
     def unstep(self):
         """The last step() was skipped on the device (non-finite gradient norm): its step number is handed to the next one."""
