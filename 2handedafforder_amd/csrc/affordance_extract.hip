@@ -41,6 +41,17 @@ struct ExtractItem {                // == haff_extract_item (include/haff_hip.h)
   int pad[2];
 };
 static_assert(sizeof(ExtractItem) == 64, "descriptor layout");
+HAFF_SAME_SIZE(ExtractItem, haff_extract_item);
+HAFF_SAME_FIELD(ExtractItem, in, haff_extract_item, in);
+HAFF_SAME_FIELD(ExtractItem, hand, haff_extract_item, hand);
+HAFF_SAME_FIELD(ExtractItem, col, haff_extract_item, col);
+HAFF_SAME_FIELD(ExtractItem, row, haff_extract_item, row);
+HAFF_SAME_FIELD(ExtractItem, out, haff_extract_item, out);
+HAFF_SAME_FIELD(ExtractItem, H, haff_extract_item, H);
+HAFF_SAME_FIELD(ExtractItem, W, haff_extract_item, W);
+HAFF_SAME_FIELD(ExtractItem, Hh, haff_extract_item, Hh);
+HAFF_SAME_FIELD(ExtractItem, Wh, haff_extract_item, Wh);
+HAFF_SAME_FIELD(ExtractItem, pad, haff_extract_item, pad);
 
 typedef unsigned long long u64;
 

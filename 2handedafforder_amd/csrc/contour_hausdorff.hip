@@ -47,6 +47,10 @@ struct Plane {                            // == haff_contour_plane (include/haff
   int H, W;
 };
 static_assert(sizeof(Plane) == 16, "descriptor layout");
+HAFF_SAME_SIZE(Plane, haff_contour_plane);
+HAFF_SAME_FIELD(Plane, plane, haff_contour_plane, plane);
+HAFF_SAME_FIELD(Plane, H, haff_contour_plane, H);
+HAFF_SAME_FIELD(Plane, W, haff_contour_plane, W);
 
 struct PlaneState {                       // workspace, one per plane
   long label_off;                         // first label of the plane, in ints from the label area's base

@@ -583,8 +583,6 @@ __global__ __launch_bounds__(64 * CH_KW) void decode_chain_kernel(ChainArgs a) {
 //   last word is a sticky error flag (a wait ran out of patience: haff_decode_chain_status).
 //   per_stage_launches != 0: the same kernel as n_layers * 5 launches, one per stage (tests / A-B: identical arithmetic, no chaining).
 // hidden % 256 == 0, ffn % 256 == 0, hidden == heads * 128, hidden / 16 <= 512, M <= 8, n_layers <= 48; 16-B aligned pointers.
-struct haff_chain_layer { const void *wqkv, *wo, *wgu, *wd; void *kcache, *vcache; };
-
 extern "C" int haff_decode_chain_bf16(const haff_chain_layer* layers, int n_layers, int M, int hidden, int ffn, int heads, void* x,
                                       void* qkv, void* att, void* g, float* ssq_a, float* ssq_b, float* ws, const float* stats0, float eps,
                                       const float* cos_sin, const int* nk_rows, int tmax, float scale, unsigned* sync,

@@ -3,11 +3,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// the public declarations (and the return codes): every extern "C" definition in csrc/ is compiled against its declaration
+#include "haff_hip.h"
+#include <cstddef>
 
-#define HAFF_OK 0
-#define HAFF_ERR_BAD_ARG (-1)
-#define HAFF_ERR_UNSUPPORTED (-2)
-#define HAFF_ERR_LAUNCH (-3)
+// A kernel-side struct K mirrors a public descriptor P of haff_hip.h (the kernels keep their own names: a rename would change the
+// mangled kernel names). HAFF_SAME_SIZE once per pair, HAFF_SAME_FIELD for every field.
+#define HAFF_SAME_SIZE(K, P) static_assert(sizeof(K) == sizeof(P), #K " and " #P " differ in size")
+#define HAFF_SAME_FIELD(K, kf, P, pf) \
+  static_assert(offsetof(K, kf) == offsetof(P, pf) && sizeof(K::kf) == sizeof(P::pf), #K "::" #kf " is not " #P "::" #pf)
 
 typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(8))) short bf16x8;

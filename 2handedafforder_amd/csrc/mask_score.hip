@@ -40,6 +40,20 @@ struct ScoreFrame {                 // == haff_score_frame (include/haff_hip.h)
   int pad[3];
 };
 static_assert(sizeof(ScoreFrame) == 128, "descriptor layout");
+HAFF_SAME_SIZE(ScoreFrame, haff_score_frame);
+HAFF_SAME_FIELD(ScoreFrame, logit, haff_score_frame, logit);
+HAFF_SAME_FIELD(ScoreFrame, tax, haff_score_frame, taxonomy);
+HAFF_SAME_FIELD(ScoreFrame, gt, haff_score_frame, gt);
+HAFF_SAME_FIELD(ScoreFrame, obj, haff_score_frame, obj);
+HAFF_SAME_FIELD(ScoreFrame, out, haff_score_frame, out);
+HAFF_SAME_FIELD(ScoreFrame, Hs, haff_score_frame, Hs);
+HAFF_SAME_FIELD(ScoreFrame, Ws, haff_score_frame, Ws);
+HAFF_SAME_FIELD(ScoreFrame, Hb, haff_score_frame, Hb);
+HAFF_SAME_FIELD(ScoreFrame, Wb, haff_score_frame, Wb);
+HAFF_SAME_FIELD(ScoreFrame, n_tax, haff_score_frame, n_tax);
+HAFF_SAME_FIELD(ScoreFrame, gt_hw, haff_score_frame, gt_hw);
+HAFF_SAME_FIELD(ScoreFrame, obj_hw, haff_score_frame, obj_hw);
+HAFF_SAME_FIELD(ScoreFrame, pad, haff_score_frame, pad);
 
 struct ScoreTh { float v[kMaxTh]; };
 

@@ -24,6 +24,12 @@
 #ifndef HAFF_HIP_H
 #define HAFF_HIP_H
 
+/* return codes of every entry point */
+#define HAFF_OK 0
+#define HAFF_ERR_BAD_ARG (-1)
+#define HAFF_ERR_UNSUPPORTED (-2)
+#define HAFF_ERR_LAUNCH (-3)
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -4,7 +4,7 @@
 // `attr` line and every entry-point call an `rc` line, over a sweep of all 18 entry points. Nothing is launched and no GPU is needed.
 // The four files' anonymous namespaces clash in one unit, so build it once per file (-DDUMP_TU=1..4) and concatenate the outputs; two
 // builds against two versions of the sources must print identical output when the host dispatch is unchanged:
-//   for t in 1 2 3 4; do hipcc -std=c++17 -x hip --cuda-host-only -DDUMP_TU=$t -I<csrc dir to dump> tools/attn_dispatch_dump.cpp -o dump$t; done
+//   for t in 1 2 3 4; do hipcc -std=c++17 -x hip --cuda-host-only -DDUMP_TU=$t -I<csrc dir to dump> -Iinclude tools/attn_dispatch_dump.cpp -o dump$t; done
 //   (./dump1; ./dump2; ./dump3; ./dump4) | sha256sum
 // A record does not depend on which host function launches: the kernel expression as written at the launch has the launching
 // function's template arguments (from __PRETTY_FUNCTION__) substituted into it.

@@ -7,7 +7,7 @@
 // The files' anonymous namespaces clash in one unit, so build it once per file (-DDUMP_TU=1..7) and concatenate the outputs; two
 // builds against two versions of the sources must print identical output when the host dispatch is unchanged:
 //   for t in 1 2 3 4 5 6 7; do hipcc -std=c++17 -x hip --cuda-host-only -Wl,--unresolved-symbols=ignore-all -DDUMP_TU=$t \
-//       -I<csrc dir to dump> tools/data_dispatch_dump.cpp -o dump$t; done
+//       -I<csrc dir to dump> -Iinclude tools/data_dispatch_dump.cpp -o dump$t; done
 //   (for t in 1 2 3 4 5 6 7; do ./dump$t; done) | sha256sum
 // A kernel is named by the text at its launch; the kernel of an `attr` line by its address, so a helper may pass it on. Taking a
 // kernel's address makes the host-only unit refer to a device binary that is never built: hence the linker flag.

@@ -2,7 +2,7 @@
 // written at the launch plus the launching function's template arguments, grid, block, every GemmArgs field), over a sweep of all
 // its entry points. Nothing is launched and no GPU is needed. Two builds of
 // this file against two versions of gemm_bf16.hip must print identical output when the host dispatch is unchanged:
-//   hipcc -std=c++17 -x hip --cuda-host-only -I<dir with the gemm_bf16.hip to dump> tools/gemm_dispatch_dump.cpp -o dump && ./dump | sha256sum
+//   hipcc -std=c++17 -x hip --cuda-host-only -I<dir with the gemm_bf16.hip to dump> -Iinclude tools/gemm_dispatch_dump.cpp -o dump && ./dump | sha256sum
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>

@@ -7,7 +7,7 @@
 // ahead behind ONE counted wait and ONE workgroup barrier per K-tile; 64 v_mfma_f32_16x16x32_bf16 per K-tile and wave in four
 // quadrants of 16, every quadrant reloading ONE 64-row operand half (4 ds_read_b128) for a later quadrant ("snake": 64 fragment
 // registers instead of 128 for a double buffer).
-// hipcc --offload-arch=gfx950 -O3 -o gemm_w4 gemm_w4.hip && ./gemm_w4 [M N K]
+// hipcc --offload-arch=gfx950 -O3 -I../../include -o gemm_w4 gemm_w4.hip && ./gemm_w4 [M N K]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

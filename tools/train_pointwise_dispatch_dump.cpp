@@ -7,7 +7,7 @@
 // GPU is needed. The files' anonymous namespaces clash in one unit, so build it once per file (-DDUMP_TU=1..6) and concatenate the
 // outputs; two builds against two versions of the sources must print identical output when the host dispatch is unchanged:
 //   for t in 1 2 3 4 5 6; do hipcc -std=c++17 -x hip --cuda-host-only -Wl,--unresolved-symbols=ignore-all -DDUMP_TU=$t \
-//       -I<csrc dir to dump> tools/train_pointwise_dispatch_dump.cpp -o dump$t; done
+//       -I<csrc dir to dump> -Iinclude tools/train_pointwise_dispatch_dump.cpp -o dump$t; done
 //   (for t in 1 2 3 4 5 6; do ./dump$t; done) | sha256sum
 // A kernel is named by its INSTANCE, not by the text at its launch: the launch macro hands the kernel to dump_launch as a template
 // argument and the record carries its mangled name (..._GLOBAL__N_116transpose_kernelItEEv...: the name, its template arguments, its
