@@ -19,6 +19,13 @@
 // plane, one 4-B store per threshold where the address allows; bytes otherwise). The 256 KB source planes stay in L2; the
 // target-side bytes are the traffic. Counts: ballot + popcount per wave into wave-uniform registers, one LDS slot per wave, one
 // integer atomicAdd per counter and workgroup. Integer sums do not depend on arrival order: repeat runs are bitwise equal.
+//
+//   overlays (calculate_iou.py:43-95, create_overlay): a frame whose descriptor has vis = k draws through ScoreVis record k - 1
+//   behind the frame table. A third launch, grid (blocks, records), 256 threads, 4 consecutive pixels of one frame row per thread:
+//   the frame pixel's target pixel through the nearest-index tables, the hands' bits there by the SAME device functions the scoring
+//   kernel counts with (taxonomy_gate, axis_taps, tap_sums, the 510 S rule, obj > 0) at the one threshold that is drawn, the
+//   ground-truth bits, then two unfused fp32 blends with round-half-even and saturation in between: cv2.addWeighted twice on uint8.
+//   12 bytes per canvas and thread, as three words where the canvas row allows; no atomics, no workspace.
 #include "haff_common.h"
 
 namespace {
@@ -37,7 +44,8 @@ struct ScoreFrame {                 // == haff_score_frame (include/haff_hip.h)
   unsigned char* out;               // [T][Hb][Wb] or null
   int Hs, Ws, Hb, Wb, n_tax;
   int gt_hw[2][2], obj_hw[2][2];    // the planes' own shapes, checked on the host against (Hb, Wb)
-  int pad[3];
+  int vis;                          // 0, or 1 + the index of the frame's ScoreVis behind the frame table
+  int pad[2];
 };
 static_assert(sizeof(ScoreFrame) == 128, "descriptor layout");
 HAFF_SAME_SIZE(ScoreFrame, haff_score_frame);
@@ -53,7 +61,35 @@ HAFF_SAME_FIELD(ScoreFrame, Wb, haff_score_frame, Wb);
 HAFF_SAME_FIELD(ScoreFrame, n_tax, haff_score_frame, n_tax);
 HAFF_SAME_FIELD(ScoreFrame, gt_hw, haff_score_frame, gt_hw);
 HAFF_SAME_FIELD(ScoreFrame, obj_hw, haff_score_frame, obj_hw);
+HAFF_SAME_FIELD(ScoreFrame, vis, haff_score_frame, vis);
 HAFF_SAME_FIELD(ScoreFrame, pad, haff_score_frame, pad);
+
+struct ScoreVis {                   // == haff_score_vis (include/haff_hip.h)
+  const unsigned char* rgb;         // [Hf][Wf][3]
+  const int* row;                   // [Hf] -> target row, or null with col: the identity
+  const int* col;                   // [Wf] -> target column
+  unsigned char* out[2];            // benchmark, prediction overlay; null = not drawn
+  long stride[2];                   // bytes per canvas row
+  int Hf, Wf, t;
+  float alpha[2], beta[2], gamma;
+  int color[2][3];
+  int pad[4];
+};
+static_assert(sizeof(ScoreVis) == sizeof(ScoreFrame), "the vis records continue the frame table");
+HAFF_SAME_SIZE(ScoreVis, haff_score_vis);
+HAFF_SAME_FIELD(ScoreVis, rgb, haff_score_vis, rgb);
+HAFF_SAME_FIELD(ScoreVis, row, haff_score_vis, row);
+HAFF_SAME_FIELD(ScoreVis, col, haff_score_vis, col);
+HAFF_SAME_FIELD(ScoreVis, out, haff_score_vis, out);
+HAFF_SAME_FIELD(ScoreVis, stride, haff_score_vis, stride);
+HAFF_SAME_FIELD(ScoreVis, Hf, haff_score_vis, Hf);
+HAFF_SAME_FIELD(ScoreVis, Wf, haff_score_vis, Wf);
+HAFF_SAME_FIELD(ScoreVis, t, haff_score_vis, t);
+HAFF_SAME_FIELD(ScoreVis, alpha, haff_score_vis, alpha);
+HAFF_SAME_FIELD(ScoreVis, beta, haff_score_vis, beta);
+HAFF_SAME_FIELD(ScoreVis, gamma, haff_score_vis, gamma);
+HAFF_SAME_FIELD(ScoreVis, color, haff_score_vis, color);
+HAFF_SAME_FIELD(ScoreVis, pad, haff_score_vis, pad);
 
 struct ScoreTh { float v[kMaxTh]; };
 
@@ -71,6 +107,38 @@ __device__ __forceinline__ Taps axis_taps(int o, int n_in, int n_out) {
   t.w0 = (unsigned)den - t.w1;
   return t;
 }
+
+// argmax of the frame's taxonomy vector, first maximum by strict > (a NaN never wins); -1 without one: both hands open
+__device__ __forceinline__ int taxonomy_gate(const ScoreFrame& f) {
+  int best = -1;
+  if (f.tax) {
+    best = 0;
+    float bv = f.tax[0];
+    for (int c = 1; c < f.n_tax; ++c) {
+      const float v = f.tax[c];
+      if (v > bv) { bv = v; best = c; }
+    }
+  }
+  return best;
+}
+
+// S[t] += wy wx over the taps whose logit is above threshold t, for the first n_th of NT thresholds
+template <int NT>
+__device__ __forceinline__ void tap_sums(const float* src, int Ws, const Taps& ty, const Taps& tx, const float (&th)[NT], int n_th,
+                                         unsigned (&S)[NT]) {
+#pragma unroll
+  for (int tap = 0; tap < 4; ++tap) {
+    const unsigned w = ((tap & 2) ? ty.w1 : ty.w0) * ((tap & 1) ? tx.w1 : tx.w0);
+    if (w == 0) continue;   // the clamped edge and the equal-size identity read one tap
+    const float v = src[(long)((tap & 2) ? ty.i1 : ty.i0) * Ws + ((tap & 1) ? tx.i1 : tx.i0)];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (t < n_th && v > th[t]) S[t] += w;
+  }
+}
+
+// the resampled byte round-half-even(255 S / half) is above 0
+__device__ __forceinline__ bool coverage_on(unsigned S, unsigned long long half) { return 510ull * S > half; }
 
 // 4 bytes at p + b as one word when the address allows, the bytes below `total` otherwise
 __device__ __forceinline__ unsigned load_quad(const unsigned char* p, long b, long total) {
@@ -98,18 +166,7 @@ __global__ __launch_bounds__(256) void score_masks_kernel(const ScoreFrame* fram
   if ((long)blockIdx.x * 256 >= n4) return;   // a smaller frame of the batch: the whole workgroup leaves, before any barrier
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-  if (tid == 0) {
-    int best = -1;
-    if (f.tax) {
-      best = 0;
-      float bv = f.tax[0];
-      for (int c = 1; c < f.n_tax; ++c) {
-        const float v = f.tax[c];
-        if (v > bv) { bv = v; best = c; }
-      }
-    }
-    gate = best;
-  }
+  if (tid == 0) gate = taxonomy_gate(f);
   __syncthreads();
   const int best = gate;
   const bool open[2] = {f.logit[0] != nullptr && best != 1, f.logit[1] != nullptr && best != 0};
@@ -144,18 +201,10 @@ __global__ __launch_bounds__(256) void score_masks_kernel(const ScoreFrame* fram
           if ((ob >> k) & 1u) {
             const Taps tx = axis_taps(x, f.Ws, f.Wb);
             unsigned S[kMaxTh] = {};
-#pragma unroll
-            for (int tap = 0; tap < 4; ++tap) {
-              const unsigned w = ((tap & 2) ? ty.w1 : ty.w0) * ((tap & 1) ? tx.w1 : tx.w0);
-              if (w == 0) continue;   // the clamped edge and the equal-size identity read one tap
-              const float v = src[(long)((tap & 2) ? ty.i1 : ty.i0) * f.Ws + ((tap & 1) ? tx.i1 : tx.i0)];
-#pragma unroll
-              for (int t = 0; t < kMaxTh; ++t)
-                if (t < n_th && v > th.v[t]) S[t] += w;
-            }
+            tap_sums(src, f.Ws, ty, tx, th.v, n_th, S);
 #pragma unroll
             for (int t = 0; t < kMaxTh; ++t)
-              if (t < n_th && 510ull * S[t] > half) pm[t] |= 1u << k;
+              if (t < n_th && coverage_on(S[t], half)) pm[t] |= 1u << k;
           }
           if (++x == f.Wb) {
             x = 0;
@@ -210,6 +259,115 @@ __global__ __launch_bounds__(256) void score_masks_kernel(const ScoreFrame* fram
   }
 }
 
+// cv2.addWeighted on uint8, one channel: a * alpha + b * beta + gamma in fp32, unfused, then cvRound (half to even) and saturation
+__device__ __forceinline__ float add_weighted(float a, float alpha, float b, float beta, float gamma) {
+  float pa = __fmul_rn(a, alpha), pb = __fmul_rn(b, beta);
+  asm volatile("" : "+v"(pa), "+v"(pb));   // the build contracts across statements (-ffp-contract=fast): keep both products' roundings
+  const float v = rintf(__fadd_rn(__fadd_rn(pa, pb), gamma));
+  return v < 0.f ? 0.f : (v > 255.f ? 255.f : v);   // a NaN weight lands on 255 by the compares, never outside a byte
+}
+
+constexpr int kVisPixels = 4;       // consecutive pixels of one frame row per thread: 12 bytes, three words
+constexpr int kVisMaxBlocks = 1024; // per record; the rest is grid-strided
+
+// Record blockIdx.y of the ScoreVis table behind the n_frames frame descriptors. The frame that names it is found by a scan of the
+// descriptors' vis fields (the host refuses a record named twice, so at most one thread finds one).
+__global__ __launch_bounds__(256) void score_vis_kernel(const ScoreFrame* frames, int n_frames, ScoreTh th) {
+  __shared__ int owner, gate;
+  const int tid = threadIdx.x;
+  if (tid == 0) owner = -1;
+  __syncthreads();
+  for (int i = tid; i < n_frames; i += 256)
+    if (frames[i].vis == (int)blockIdx.y + 1) owner = i;
+  __syncthreads();
+  if (owner < 0) return;            // a record no frame names: nothing to draw (uniform over the workgroup)
+  const ScoreFrame f = frames[owner];
+  const ScoreVis v = reinterpret_cast<const ScoreVis*>(frames + n_frames)[blockIdx.y];
+  const int qw = (v.Wf + kVisPixels - 1) / kVisPixels;   // threads per frame row
+  const long items = (long)v.Hf * qw;
+  if ((long)blockIdx.x * 256 >= items) return;            // a smaller frame of the batch, before the gate's barrier
+  if (tid == 0) gate = taxonomy_gate(f);
+  __syncthreads();
+  const int best = gate;
+  const bool open[2] = {f.logit[0] != nullptr && best != 1, f.logit[1] != nullptr && best != 0};
+  const unsigned long long half = 4ull * (unsigned long long)f.Hb * (unsigned long long)f.Wb;
+  float th1[1] = {0.f};
+#pragma unroll
+  for (int k = 0; k < kMaxTh; ++k)
+    if (k == v.t) th1[0] = th.v[k];
+
+  for (long item = (long)blockIdx.x * 256 + tid; item < items; item += (long)gridDim.x * 256) {
+    const int y = (int)(item / qw), x0 = (int)(item % qw) * kVisPixels;
+    const int n = v.Wf - x0 < kVisPixels ? v.Wf - x0 : kVisPixels;
+    int yb = v.row ? v.row[y] : y;
+    yb = yb < 0 ? 0 : (yb > f.Hb - 1 ? f.Hb - 1 : yb);
+    const Taps ty = axis_taps(yb, f.Hs, f.Hb);
+
+    // the frame's 12 bytes: three words where the address allows
+    const unsigned char* src = v.rgb + ((long)y * v.Wf + x0) * 3;
+    unsigned char px[3 * kVisPixels] = {};
+    if (n == kVisPixels && (reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+#pragma unroll
+      for (int w = 0; w < 3; ++w) {
+        const unsigned m = reinterpret_cast<const unsigned*>(src)[w];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) px[4 * w + b] = (unsigned char)(m >> (8 * b));
+      }
+    } else {
+#pragma unroll
+      for (int b = 0; b < 3 * kVisPixels; ++b)
+        if (b < 3 * n) px[b] = src[b];
+    }
+
+    // layer bits per pixel: bit 0 / 1 = left / right ground truth, bit 2 / 3 = left / right prediction
+    unsigned bits[kVisPixels] = {};
+#pragma unroll
+    for (int k = 0; k < kVisPixels; ++k) {
+      if (k >= n) continue;
+      int xb = v.col ? v.col[x0 + k] : x0 + k;
+      xb = xb < 0 ? 0 : (xb > f.Wb - 1 ? f.Wb - 1 : xb);
+      const long at = (long)yb * f.Wb + xb;
+      const Taps tx = axis_taps(xb, f.Ws, f.Wb);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (f.gt[h] && f.gt[h][at] > 0) bits[k] |= 1u << h;
+        if (!open[h]) continue;
+        if (f.obj[h] && !(f.obj[h][at] > 0)) continue;
+        unsigned S[1] = {0u};
+        tap_sums(f.logit[h], f.Ws, ty, tx, th1, 1, S);
+        if (coverage_on(S[0], half)) bits[k] |= 4u << h;
+      }
+    }
+
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {         // canvas 0: benchmark layers, canvas 1: prediction layers
+      if (!v.out[c]) continue;
+      unsigned char res[3 * kVisPixels];
+#pragma unroll
+      for (int k = 0; k < kVisPixels; ++k) {
+        const bool L = (bits[k] >> (2 * c)) & 1u, R = (bits[k] >> (2 * c + 1)) & 1u;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const float t1 = add_weighted((float)px[3 * k + ch], v.alpha[0], L ? (float)v.color[0][ch] : 0.f, v.beta[0], v.gamma);
+          const float t2 = add_weighted(t1, v.alpha[1], R ? (float)v.color[1][ch] : 0.f, v.beta[1], v.gamma);
+          res[3 * k + ch] = (unsigned char)t2;
+        }
+      }
+      unsigned char* dst = v.out[c] + (long)y * v.stride[c] + (long)x0 * 3;
+      if (n == kVisPixels && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+          reinterpret_cast<unsigned*>(dst)[w] = (unsigned)res[4 * w] | ((unsigned)res[4 * w + 1] << 8) | ((unsigned)res[4 * w + 2] << 16) |
+                                                ((unsigned)res[4 * w + 3] << 24);
+      } else {
+#pragma unroll
+        for (int b = 0; b < 3 * kVisPixels; ++b)
+          if (b < 3 * n) dst[b] = res[b];
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int haff_score_masks(const void* frames_host, const void* frames_dev, int n_frames, const float* thresholds_host,
@@ -218,7 +376,9 @@ extern "C" int haff_score_masks(const void* frames_host, const void* frames_dev,
   if (n_th < 1 || n_th > kMaxTh) return HAFF_ERR_BAD_ARG;
   if (!haff_aligned(frames_host, 8) || !haff_aligned(frames_dev, 8) || !haff_aligned(counts, 4)) return HAFF_ERR_BAD_ARG;
   const ScoreFrame* fr = static_cast<const ScoreFrame*>(frames_host);
-  long blocks = 1;
+  long blocks = 1, vis_blocks = 1;
+  int n_vis = 0;                                  // overlay records behind the table: the largest vis of the batch
+  unsigned long long vis_seen[1024] = {};         // one bit per record (n_frames <= 65535): a record draws for one frame
   for (int i = 0; i < n_frames; ++i) {
     const ScoreFrame& f = fr[i];
     if (f.Hs <= 0 || f.Ws <= 0 || f.Hb <= 0 || f.Wb <= 0) return HAFF_ERR_BAD_ARG;
@@ -233,6 +393,26 @@ extern "C" int haff_score_masks(const void* frames_host, const void* frames_dev,
     long g = (n4 + 256L * kQuadsPerThread - 1) / (256L * kQuadsPerThread);
     g = g > kMaxBlocks ? kMaxBlocks : g;
     blocks = g > blocks ? g : blocks;
+    if (f.vis == 0) continue;
+    // the frame's overlay record, behind the frame table
+    if (f.vis < 1 || f.vis > n_frames) return HAFF_ERR_BAD_ARG;
+    if (vis_seen[(f.vis - 1) >> 6] >> ((f.vis - 1) & 63) & 1ull) return HAFF_ERR_BAD_ARG;
+    vis_seen[(f.vis - 1) >> 6] |= 1ull << ((f.vis - 1) & 63);
+    const ScoreVis& v = reinterpret_cast<const ScoreVis*>(fr + n_frames)[f.vis - 1];
+    if (v.Hf < 1 || v.Wf < 1) return HAFF_ERR_BAD_ARG;
+    if (v.Hf > kMaxSide || v.Wf > kMaxSide) return HAFF_ERR_UNSUPPORTED;
+    if (!v.rgb || (!v.out[0] && !v.out[1])) return HAFF_ERR_BAD_ARG;
+    if ((v.row == nullptr) != (v.col == nullptr)) return HAFF_ERR_BAD_ARG;
+    if (!v.row && (v.Hf != f.Hb || v.Wf != f.Wb)) return HAFF_ERR_BAD_ARG;
+    if (!haff_aligned(v.row, 4) || !haff_aligned(v.col, 4)) return HAFF_ERR_BAD_ARG;
+    if (v.t < 0 || v.t >= n_th) return HAFF_ERR_BAD_ARG;
+    for (int c = 0; c < 2; ++c)
+      if (v.out[c] && v.stride[c] < 3L * v.Wf) return HAFF_ERR_BAD_ARG;
+    const long items = (long)v.Hf * ((v.Wf + kVisPixels - 1) / kVisPixels);
+    long vg = (items + 255) / 256;
+    vg = vg > kVisMaxBlocks ? kVisMaxBlocks : vg;
+    vis_blocks = vg > vis_blocks ? vg : vis_blocks;
+    n_vis = f.vis > n_vis ? f.vis : n_vis;
   }
   ScoreTh th{};
   for (int t = 0; t < n_th; ++t) th.v[t] = thresholds_host[t];
@@ -241,5 +421,8 @@ extern "C" int haff_score_masks(const void* frames_host, const void* frames_dev,
   hipLaunchKernelGGL(score_zero_kernel, dim3((unsigned)((n_counts + 255) / 256)), dim3(256), 0, s, (unsigned*)counts, n_counts);
   hipLaunchKernelGGL(score_masks_kernel, dim3((unsigned)blocks, (unsigned)n_frames), dim3(256), 0, s,
                      static_cast<const ScoreFrame*>(frames_dev), th, n_th, (unsigned*)counts);
+  if (n_vis)
+    hipLaunchKernelGGL(score_vis_kernel, dim3((unsigned)vis_blocks, (unsigned)n_vis), dim3(256), 0, s,
+                       static_cast<const ScoreFrame*>(frames_dev), n_frames, th);
   return haff_check_launch();
 }

@@ -235,6 +235,13 @@ def pad_to_square(img):
     return out
 
 
+def nearest_indices(n_dst, n_src):
+    """The source index of every destination index along one axis of cv2.resize(..., interpolation=cv2.INTER_NEAREST), int64
+    [n_dst]: min(cvFloor(x * ifx), n_src - 1) with ifx = 1. / ((double)n_dst / n_src), in IEEE double in that order (resizeNN)."""
+    n_dst, n_src = int(n_dst), int(n_src)
+    return np.minimum(np.floor(np.arange(n_dst, dtype=np.float64) * (1.0 / (n_dst / n_src))), n_src - 1).astype(np.int64)
+
+
 def resize_nearest(img, size):
     """cv2.resize(img, (w, h), interpolation=cv2.INTER_NEAREST). Restated from OpenCV's resizeNN (modules/imgproc/src/resize.cpp):
     per axis the source index is min(cvFloor(x * ifx), n_src - 1) with ifx = 1. / ((double)n_dst / n_src), in IEEE double exactly
@@ -242,9 +249,7 @@ def resize_nearest(img, size):
     img = np.asarray(img)
     w, h = int(size[0]), int(size[1])
     sh, sw = img.shape[:2]
-    xs = np.minimum(np.floor(np.arange(w, dtype=np.float64) * (1.0 / (w / sw))), sw - 1).astype(np.int64)
-    ys = np.minimum(np.floor(np.arange(h, dtype=np.float64) * (1.0 / (h / sh))), sh - 1).astype(np.int64)
-    return img[ys][:, xs]
+    return img[nearest_indices(h, sh)][:, nearest_indices(w, sw)]
 
 
 def dilate_rect(img, k):

@@ -16,6 +16,10 @@ planes of --records_threshold, every external contour of each hand), a torch-sav
 --smooth_masks applies ActAffordance's scripts/utils/gaussian.py (7x7 Gaussian blur of each written plane, then `> --smooth_threshold`)
 to the fp32 masks on the device, once for all thresholds (postprocess.smooth_mask_lists, csrc/mask_smooth.hip): the PNGs, --score /
 --score_only and --write_records then equal what that script would leave behind on the unsmoothed run's tree.
+
+--visualize DIR (with --score / --score_only) writes the panels of `calculate_iou.py --visualize`: ground truth and prediction over the
+frame, side by side, captioned with the IoU of the scored counts. The scoring call draws them (haff_score_vis, csrc/mask_score.hip)
+from the per-pixel decisions it counts, so smoothing, --score_cropped and --score_intersection show as they are scored.
 """
 import argparse
 import json
@@ -70,6 +74,16 @@ def parse_args(args):
     parser.add_argument("--score_hausdorff_device", action="store_true", default=False,
                         help="the two Hausdorff distances from the device: contour walk and point-set distance in HIP, nothing read "
                              "back per batch and no host thread")
+    # calculate_iou.py --visualize on the device (scoring.BenchmarkScorer(visualize=)): off by default
+    parser.add_argument("--visualize", default=None, type=str, metavar="DIR",
+                        help="with --score / --score_only: also write the benchmark's overlay panels (ground truth | prediction over the "
+                             "frame, captioned with the frame's IoU) into DIR, drawn on the device from the pixels that are scored")
+    parser.add_argument("--visualize_threshold", default=None, type=float,
+                        help=f"the threshold whose prediction is drawn: one of {postprocess.THRESHOLDS} (default 0.5)")
+    parser.add_argument("--visualize_caption", default=None, type=str,
+                        help='the caption on the prediction half (default Aff-Ex); "." writes the prediction overlay alone, for frames '
+                             "above IoU 0.2")
+    parser.add_argument("--visualize_examples", default=None, type=int, help="panels to write (default 20; 0 = every scored frame)")
     # predictions as 2HANDS contour records (contours.py): off by default
     parser.add_argument("--write_records", default=None, type=str, metavar="PATH",
                         help="also torch.save the run as a list of 2HANDS records (narration, image, taxonomy, masks = the contours "
@@ -83,6 +97,7 @@ def parse_args(args):
     parser.add_argument("--smooth_threshold", default=None, type=float, help="gaussian.py --threshold, in [0, 1) (default 0.5)")
     args = parser.parse_args(args)
     check_score_args(args)
+    check_visualize_args(args)
     check_records_args(args)
     check_smooth_args(args)
     return args
@@ -98,6 +113,25 @@ def check_score_args(args):
         raise SystemExit("--score_hausdorff_device and --score_hausdorff are two routes to the same numbers: pass one of them")
     if args.score and not args.benchmark_dir:
         raise SystemExit("--score needs --benchmark-dir: the ground truth is its aff_{left,right}.png")
+
+
+def check_visualize_args(args):
+    """--visualize modifies --score / --score_only, and its own modifiers mean nothing without it."""
+    if args.visualize and not args.score:
+        raise SystemExit("--visualize modifies --score / --score_only: pass one of them")
+    for flag in ("visualize_threshold", "visualize_caption", "visualize_examples"):
+        if getattr(args, flag) is not None and not args.visualize:
+            raise SystemExit(f"--{flag} modifies --visualize: pass a directory to write to")
+    if args.visualize_threshold is None:
+        args.visualize_threshold = 0.5
+    if args.visualize_threshold not in postprocess.THRESHOLDS:
+        raise SystemExit(f"--visualize_threshold {args.visualize_threshold}: one of {postprocess.THRESHOLDS}")
+    if args.visualize_caption is None:
+        args.visualize_caption = "Aff-Ex"
+    if args.visualize_examples is None:
+        args.visualize_examples = 20
+    if args.visualize_examples < 0:
+        raise SystemExit("--visualize_examples: 0 (every scored frame) or a count")
 
 
 def check_records_args(args):
@@ -288,7 +322,10 @@ def _main(args, closers):
         scorer = scoring.BenchmarkScorer(args.benchmark_dir, device, postprocess.THRESHOLDS,
                                          names=[stem + str(th) for th in postprocess.THRESHOLDS], cropped=args.score_cropped,
                                          intersection=args.score_intersection,
-                                         hausdorff="device" if args.score_hausdorff_device else args.score_hausdorff)
+                                         hausdorff="device" if args.score_hausdorff_device else args.score_hausdorff,
+                                         visualize=None if not args.visualize else {
+                                             "dir": args.visualize, "threshold": args.visualize_threshold,
+                                             "caption": args.visualize_caption, "examples": args.visualize_examples})
         closers.append(scorer.close)
     reader, records = (contours.ContourReader(), []) if args.write_records else (None, None)
     examples = list(iter_examples(args.benchmark_dir))
@@ -310,7 +347,8 @@ def _main(args, closers):
         if args.smooth_masks:    # once, for all five thresholds and every consumer below
             masks_left, masks_right = postprocess.smooth_mask_lists(masks_left, masks_right, args.smooth_threshold)
         if scorer is not None:   # one launch for the chunk; the counts stay on the device until the report
-            scorer.add_batch([(d, f) for d, f, _, _ in chunk], masks_left, masks_right, taxonomies, original_size_list)
+            scorer.add_batch([(d, f) for d, f, _, _ in chunk], masks_left, masks_right, taxonomies, original_size_list,
+                             frames_u8=frames if args.visualize else None)
         if reader is not None:   # one extraction for the chunk, on the very planes the PNGs below are read back from
             records += chunk_records(reader, [n for _, _, _, n in chunk], images, masks_left, masks_right, taxonomies,
                                      original_size_list, args.records_threshold)

@@ -1322,11 +1322,14 @@ MAX_SIDE = 4096                         # kMaxSide of csrc/mask_score.hip, conto
 SCORE_MAX_SIDE, SCORE_MAX_THRESHOLDS = MAX_SIDE, 8
 
 
-def score_masks(frames, logit_ths, device, out_counts=None):
+def score_masks(frames, logit_ths, device, out_counts=None, vis=None):
     """haff_score_masks on a packed descriptor table. frames: int64 [n, SCORE_FRAME_WORDS] (numpy or a CPU tensor, as
     scoring.pack_frames builds it; every pointer in it a device pointer the caller keeps alive until the call returns).
     Returns int32 [n, n_th, 4] on the device = {intersection, union, predicted area, ground-truth area} per frame and LOGIT
-    threshold (zeroed by the call itself; the values are below 2^25). out_counts: a contiguous int32 [n, n_th, 4] to write into."""
+    threshold (zeroed by the call itself; the values are below 2^25). out_counts: a contiguous int32 [n, n_th, 4] to write into.
+    vis: int64 [m, SCORE_FRAME_WORDS], the haff_score_vis records of scoring.pack_vis, appended to the same upload: a frame whose
+    descriptor names record k (pack_frames' "vis" key) has its overlays drawn by a further launch behind the scoring one. None:
+    the bytes uploaded and the launches of a call without overlays."""
     lib = load_library()
     device = torch.device(device)
     if device.type != "cuda":
@@ -1334,8 +1337,17 @@ def score_masks(frames, logit_ths, device, out_counts=None):
     frames = torch.as_tensor(frames)
     assert frames.dtype == torch.int64 and frames.dim() == 2 and frames.shape[1] == SCORE_FRAME_WORDS and frames.shape[0] >= 1
     n, n_th = frames.shape[0], len(logit_ths)
-    host = torch.empty((n, SCORE_FRAME_WORDS), dtype=torch.int64, pin_memory=True)
-    host.copy_(frames)
+    m = 0
+    if vis is not None:
+        vis = torch.as_tensor(vis)
+        assert vis.dtype == torch.int64 and vis.dim() == 2 and vis.shape[1] == SCORE_FRAME_WORDS and vis.shape[0] >= 1
+        m = vis.shape[0]
+    host = torch.empty((n + m, SCORE_FRAME_WORDS), dtype=torch.int64, pin_memory=True)
+    host[:n].copy_(frames)
+    if m:
+        host[n:].copy_(vis)
+    named = int(host[:n].numpy().view(np.int32)[:, 29].max())   # the library reads record `named - 1` behind the frames: it must be there
+    assert named <= m, f"a frame names overlay record {named} of {m}"
     if out_counts is None:
         out_counts = torch.empty((n, n_th, 4), dtype=torch.int32, device=device)
     assert out_counts.dtype == torch.int32 and out_counts.is_contiguous() and tuple(out_counts.shape) == (n, n_th, 4)

@@ -44,8 +44,9 @@ def _plane(t, dtype, name):
 
 def pack_frames(frames):
     """frames: dicts with the keys left, right (fp32 [Hs, Ws] logits or None), taxonomy (fp32, 4 n values, or None: gate open),
-    gt_left, gt_right, obj_left, obj_right (uint8 2-D planes or None), out (uint8 [T, Hb, Wb] or None), target_hw and, when
-    both hands are None, src_hw. Returns the int64 [n, 16] descriptor table of ops.score_masks; the caller keeps the tensors alive
+    gt_left, gt_right, obj_left, obj_right (uint8 2-D planes or None), out (uint8 [T, Hb, Wb] or None), target_hw, when
+    both hands are None, src_hw, and optionally vis (k >= 1: the frame's overlays are drawn through record k - 1 of pack_vis's
+    table; 0 or absent: nothing is drawn). Returns the int64 [n, 16] descriptor table of ops.score_masks; the caller keeps the tensors alive
     until the launch is enqueued. Shapes are recorded as the tensors have them: the library refuses a ground-truth or object plane
     whose shape is not the target's, and sizes it does not take."""
     table = np.zeros((len(frames), ops.SCORE_FRAME_WORDS), dtype=np.int64)
@@ -70,6 +71,42 @@ def pack_frames(frames):
         ptrs.append(out)
         table[i, :8] = [0 if p is None else p.data_ptr() for p in ptrs]
         ints[i, 16:29] = [hs, ws, hb, wb, 0 if tax is None else tax.numel()] + shapes
+        ints[i, 29] = int(f.get("vis") or 0)
+    return table
+
+
+OVERLAY_ALPHA, OVERLAY_BETA, OVERLAY_GAMMA = (0.5, 1.0), (0.5, 0.5), 0.0   # calculate_iou.py:81-82: the two cv2.addWeighted calls
+OVERLAY_COLORS = ((255, 0, 0), (0, 255, 0))   # RGB, left and right: green as the code at :77-78 does, not blue as its comment says
+
+
+def pack_vis(records):
+    """The overlay records of ops.score_masks (haff_score_vis, include/haff_hip.h) as an int64 [m, 16] table. records: dicts with
+    rgb (uint8 [Hf, Wf, 3], the frame as loaded), row / col (int32 [Hf] / [Wf] nearest indices into the frame's target grid, as
+    cvlite.nearest_indices gives them; both None for the identity), out = (benchmark overlay, prediction overlay), each a uint8
+    view [Hf, Wf, 3] whose pixels are contiguous and whose rows may be strided (the two halves of one [Hf, 2 Wf, 3] canvas, say) or
+    None (not drawn), t (index of the threshold that is drawn) and optionally alpha, beta, gamma, colors (create_overlay's by
+    default). Everything lives in HBM and is kept alive by the caller until the launch is enqueued."""
+    table = np.zeros((len(records), ops.SCORE_FRAME_WORDS), dtype=np.int64)
+    ints = table.view(np.int32).reshape(len(records), 2 * ops.SCORE_FRAME_WORDS)
+    floats = table.view(np.float32).reshape(len(records), 2 * ops.SCORE_FRAME_WORDS)
+    for i, r in enumerate(records):
+        rgb = _plane(r["rgb"], torch.uint8, "rgb")
+        assert rgb.dim() == 3 and rgb.shape[2] == 3
+        hf, wf = rgb.shape[:2]
+        row, col = _plane(r.get("row"), torch.int32, "row"), _plane(r.get("col"), torch.int32, "col")
+        assert row is None or tuple(row.shape) == (hf,)
+        assert col is None or tuple(col.shape) == (wf,)
+        table[i, :3] = [rgb.data_ptr(), 0 if row is None else row.data_ptr(), 0 if col is None else col.data_ptr()]
+        for k, o in enumerate(r["out"]):
+            if o is None:
+                continue
+            if not o.is_cuda:
+                raise RuntimeError("out must live in HBM (cuda tensor); the hot path has no CPU fallback")
+            assert o.dtype == torch.uint8 and tuple(o.shape) == (hf, wf, 3) and o.stride(2) == 1 and o.stride(1) == 3
+            table[i, 3 + k], table[i, 5 + k] = o.data_ptr(), o.stride(0) if hf > 1 else max(o.stride(0), 3 * wf)
+        ints[i, 14:17] = [hf, wf, int(r["t"])]
+        floats[i, 17:22] = [*r.get("alpha", OVERLAY_ALPHA), *r.get("beta", OVERLAY_BETA), r.get("gamma", OVERLAY_GAMMA)]
+        ints[i, 22:28] = np.asarray(r.get("colors", OVERLAY_COLORS), dtype=np.int32).reshape(6)
     return table
 
 
@@ -142,10 +179,18 @@ class BenchmarkScorer:
     frame; the integers are read back with the counts, and no thread exists. The planes (T + 1 per frame, 0.7 MB each at 855 x 855)
     stay in HBM until report(): a frame whose result carries a flag (a contour of more than `max_vertices` vertices, or a kernel
     bound that no input should reach) is read back and recomputed by `evaluation.calculate_hausdorff` there, and counted in
-    `host_walks`. Without hausdorff the two fields of the report are None."""
+    `host_walks`. Without hausdorff the two fields of the report are None.
+
+    visualize: None, or a dict {"dir", "threshold" (one of thresholds, default 0.5), "caption" (default "Aff-Ex"), "examples"
+    (default 20, 0 = all)}: `evaluation.py --visualize` on the tree the run would write at that
+    threshold, drawn by the scoring call itself (haff_score_vis) from the very per-pixel decisions it counts. The first `examples`
+    scored frames, in the benchmark's sorted order (the reference shuffles), get a canvas and an overlay record; after the batch's
+    launch its canvases, its slice of the counts and the argmax of its frames with a missing object plane are read back in one copy,
+    the captions are drawn (the IoU is that of the counts) and the PNGs written. A frame the rules above drop is neither drawn nor
+    counted. add_batch then needs frames_u8, the frames as loaded (uint8 [H0, W0, 3] in HBM)."""
 
     def __init__(self, benchmark_dir, device, thresholds=postprocess.THRESHOLDS, names=None, cropped=False, intersection=False,
-                 hausdorff=False, max_vertices=65536):
+                 hausdorff=False, max_vertices=65536, visualize=None):
         self.benchmark_dir, self.device = benchmark_dir, torch.device(device)
         self.thresholds = tuple(thresholds)
         self.names = list(names) if names is not None else [str(t) for t in self.thresholds]
@@ -158,6 +203,15 @@ class BenchmarkScorer:
         self._labels, self._counts, self._gates, self._needs_gate, self._hd = [], [], [], [], []
         self._hd_results, self._hd_planes = [], []
         self._pool = None
+        self.visualize, self.panels = None, []       # panels: (label, iou, path or None) of every frame drawn
+        if visualize is not None:
+            v = {"threshold": 0.5, "caption": "Aff-Ex", "examples": 20, **visualize}
+            if v["threshold"] not in self.thresholds:
+                raise ValueError(f"visualize threshold {v['threshold']}: one of {self.thresholds}")
+            os.makedirs(v["dir"], exist_ok=True)
+            v["t"] = self.thresholds.index(v["threshold"])
+            v["left"] = int(v["examples"]) if int(v["examples"]) > 0 else float("inf")
+            self.visualize, self._vis_tables = v, {}
         if self.hausdorff and not self.hausdorff_device:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="haff-hausdorff")
@@ -207,9 +261,63 @@ class BenchmarkScorer:
                     f[f"obj_{side}"] = ops.upload_pinned(o, self.device)
         return f
 
-    def add_batch(self, keys, masks_left, masks_right, taxonomies, frame_hws):
-        """One evaluate() call: keys = [(dir_name, folder_name)], the three lists evaluate() returns, the frames' (H0, W0)."""
-        frames = []
+    def _vis_record(self, f, key, frame_u8):
+        """The overlay record of one frame that is about to be scored (pack_vis's dict), with its canvas: [Hf, 2 Wf, 3] for the
+        side-by-side panel, [Hf, Wf, 3] (the prediction overlay alone) with the caption "."."""
+        from . import cvlite
+        if frame_u8 is None or not frame_u8.is_cuda:
+            raise RuntimeError("visualize needs frames_u8: the frames as loaded, uint8 [H0, W0, 3] in HBM")
+        hf, wf = int(frame_u8.shape[0]), int(frame_u8.shape[1])
+        hb, wb = f["target_hw"]
+        row = col = None
+        if (hf, wf) != (hb, wb):          # one table pair per distinct geometry, uploaded once
+            if (hb, wb, hf, wf) not in self._vis_tables:
+                self._vis_tables[hb, wb, hf, wf] = tuple(ops.upload_pinned(cvlite.nearest_indices(n, m).astype(np.int32), self.device)
+                                                         for n, m in ((hf, hb), (wf, wb)))
+            row, col = self._vis_tables[hb, wb, hf, wf]
+        both = self.visualize["caption"] != "."
+        canvas = torch.empty((hf, (2 if both else 1) * wf, 3), dtype=torch.uint8, device=self.device)
+        return {"rgb": frame_u8.contiguous(), "row": row, "col": col, "t": self.visualize["t"], "canvas": canvas, "key": key,
+                "out": (canvas[:, :wf], canvas[:, wf:]) if both else (None, canvas)}
+
+    def _write_panels(self, frames, records, counts):
+        """Behind the batch's launch: ONE device -> host copy of the canvases, the batch's counts and the argmax of its frames with
+        a missing object plane; then the captions and the PNGs."""
+        from . import evaluation
+        v, T = self.visualize, len(self.thresholds)
+        drawn = [f for f in frames if f.get("vis")]
+        gates = [torch.argmax(f["taxonomy"]).to(torch.int32).reshape(1) for f in drawn if f["obj_missing"]]
+        parts = [r["canvas"].reshape(-1) for r in records] + [torch.cat([counts.reshape(-1)] + gates).view(torch.uint8)]
+        flat = torch.cat(parts).cpu().numpy()
+        n_canvas = sum(r["canvas"].numel() for r in records)
+        ints = flat[n_canvas:].view(np.int32)
+        counts_host = ints[:len(frames) * T * 4].reshape(len(frames), T, 4)
+        gate_vals = iter(ints[len(frames) * T * 4:].tolist())
+        at = 0
+        for i, f in enumerate(frames):
+            if not f.get("vis"):
+                continue
+            r = records[f["vis"] - 1]
+            canvas = flat[at:at + r["canvas"].numel()].reshape(tuple(r["canvas"].shape))
+            at += r["canvas"].numel()
+            if f["obj_missing"]:
+                t = next(gate_vals)
+                if any(t != (1 if side == "left" else 0) for side in f["obj_missing"]):
+                    continue                                   # report() drops this frame: not drawn, not counted
+            if v["left"] <= 0:
+                continue
+            v["left"] -= 1
+            sub, leaf = r["key"]
+            iou, _ = counts_to_iou(*counts_host[i][v["t"]][:3])
+            wf = r["rgb"].shape[1]
+            bench = canvas[:, :wf] if v["caption"] != "." else None
+            path = evaluation.write_panel(v["dir"], sub, leaf, v["caption"], iou, bench, canvas[:, -wf:])
+            self.panels.append((f["label"], iou, path))
+
+    def add_batch(self, keys, masks_left, masks_right, taxonomies, frame_hws, frames_u8=None):
+        """One evaluate() call: keys = [(dir_name, folder_name)], the three lists evaluate() returns, the frames' (H0, W0), and with
+        visualize the frames themselves."""
+        frames, records, sure = [], [], 0
         for b, (dir_name, folder_name) in enumerate(keys):
             f = self._frame(dir_name, folder_name, masks_left[b], masks_right[b], taxonomies[b], frame_hws[b])
             if f is None:
@@ -217,11 +325,18 @@ class BenchmarkScorer:
             if self.hausdorff:
                 f["out"] = torch.empty((len(self.thresholds),) + f["target_hw"], dtype=torch.uint8, device=self.device)
             f["label"] = f"{dir_name}/{folder_name}"
+            v = self.visualize
+            if v is not None and sure < v["left"]:
+                records.append(self._vis_record(f, (dir_name, folder_name), None if frames_u8 is None else frames_u8[b]))
+                f["vis"] = len(records)
+                sure += not f["obj_missing"]                   # a frame the gate may still drop does not use up the quota
             frames.append(f)
         if not frames:
             return
-        counts = ops.score_masks(pack_frames(frames), self.logit_ths, self.device)
+        counts = ops.score_masks(pack_frames(frames), self.logit_ths, self.device, **({"vis": pack_vis(records)} if records else {}))
         self._counts.append(counts.reshape(-1))
+        if records:
+            self._write_panels(frames, records, counts)
         for f in frames:
             self._labels.append(f["label"])
             self._needs_gate.append(f["obj_missing"])

@@ -629,8 +629,29 @@ typedef struct haff_score_frame {
   unsigned char* out;             /* u8 [T][Hb][Wb]: the predicted two-hand union per threshold, 0/1; NULL = not written */
   int Hs, Ws, Hb, Wb, n_tax;
   int gt_hw[2][2], obj_hw[2][2];  /* (rows, columns) of each gt / obj plane as the caller holds it: checked against (Hb, Wb) */
-  int pad[3];
+  int vis;                        /* 0 = nothing drawn; k in 1..n_frames = record n_frames + k - 1 of the SAME tables, a haff_score_vis */
+  int pad[2];
 } haff_score_frame;
+/* One overlay record of a haff_score_masks batch (calculate_iou.py:43-95, create_overlay): 128 bytes, every pointer a DEVICE pointer.
+ * It sits behind the n_frames frame descriptors of the host and the device table; the frame whose vis names it supplies the logits,
+ * gate, planes and (Hb, Wb). Per frame pixel (y, x): the target pixel is (row[y], col[x]) (clamped into the target grid); a hand's
+ * prediction layer is on where the scoring rule above turns the hand on at threshold t (gate, resample, obj AND), its benchmark layer
+ * where gt > 0; per channel c, in fp32 with every product and sum rounded on its own (never fused),
+ * t1 = rgb * alpha[0] + (L ? color[0][c] : 0) * beta[0] + gamma,
+ * u1 = saturate(round-half-even(t1)), t2 = u1 * alpha[1] + (R ? color[1][c] : 0) * beta[1] + gamma, byte = saturate(round-half-even(t2)):
+ * two cv2.addWeighted calls on uint8. Both blends always run. out[0] takes the benchmark layers, out[1] the prediction layers. */
+typedef struct haff_score_vis {
+  const unsigned char* rgb;       /* u8 [Hf][Wf][3]: the frame as loaded (RGB) */
+  const int* row;                 /* int32 [Hf]: nearest source row in the target grid (Hb, Wb) of every frame row */
+  const int* col;                 /* int32 [Wf]: the same for columns; row and col both NULL = identity, needs (Hf, Wf) == (Hb, Wb) */
+  unsigned char* out[2];          /* benchmark overlay, prediction overlay: pixel (y, x) at out[k] + y * stride[k] + 3 x; NULL = not drawn */
+  long stride[2];                 /* bytes per canvas row, >= 3 Wf. Side by side: one canvas [Hf][2 Wf][3], out[1] = out[0] + 3 Wf, both 6 Wf */
+  int Hf, Wf;
+  int t;                          /* index of the threshold that is drawn */
+  float alpha[2], beta[2], gamma; /* create_overlay: (0.5, 1), (0.5, 0.5), 0: every product and sum exact in fp32 */
+  int color[2][3];                /* RGB of the left and the right hand, 0..255: (255, 0, 0) and (0, 255, 0) */
+  int pad[4];
+} haff_score_vis;
 /* counts u32 [n_frames][n_th][4] = {intersection, union, predicted area, ground-truth area} of the two-hand unions of every frame
  * and LOGIT threshold, zeroed by the call itself (a kernel in front of the scoring launch, same stream), then one launch over
  * grid (blocks per frame, frames). Per target pixel and hand: the bilinear resample (half-pixel centres, no antialiasing) of the
@@ -641,10 +662,16 @@ typedef struct haff_score_frame {
  * maximum); index 1 blanks the left hand, index 0 the right one, any other neither. Integer atomics only: repeat runs are bitwise
  * equal. frames_host is the HOST copy of the n_frames descriptors, checked here and never read by a kernel; frames_dev the caller's
  * DEVICE copy, uploaded in stream order before the call. thresholds_host: HOST array of n_th floats.
+ * When any frame has vis != 0 a third launch follows the scoring launch, grid (blocks, max vis), 256 threads, four consecutive
+ * pixels of a frame row per thread, word stores where the canvas row allows and bytes otherwise, no atomics and no workspace: the
+ * overlays of haff_score_vis, from the same per-pixel decisions that were counted. Both tables then hold n_frames + max(vis) records.
  * Refused before anything is enqueued: -1 for n_th outside 1..8, n_frames outside 1..65535, a side <= 0, a gt / obj plane whose
  * shape is not (Hb, Wb), n_tax outside 1..1024 with a taxonomy, a logit or taxonomy pointer that is not 4-B aligned, a descriptor
  * table that is not 8-B aligned, counts not 4-B aligned, a NULL table, thresholds or counts; -2 for a side over 4096. The u8
- * planes may sit at any address (4-B aligned quads move as words, the rest as bytes). */
+ * planes may sit at any address (4-B aligned quads move as words, the rest as bytes). After a frame's own checks, when its vis != 0:
+ * -1 for vis outside 1..n_frames or named by an earlier frame too, a NULL rgb, both out NULL, only one of row / col, no tables with
+ * (Hf, Wf) != (Hb, Wb), a row / col that is not 4-B aligned, t outside 0..n_th-1, a stride of a drawn canvas below 3 Wf, Hf < 1 or
+ * Wf < 1; -2 for Hf or Wf over 4096. rgb and the canvases may sit at any address. Nothing is launched on a refusal. */
 int haff_score_masks(const void* frames_host, const void* frames_dev, int n_frames, const float* thresholds_host, int n_th,
                      void* counts, void* stream);
 /* ---- the benchmark's Hausdorff distances on the device (calculate_iou.py:9-24 as evaluation.calculate_hausdorff and
