@@ -17,6 +17,11 @@ planes of --records_threshold, every external contour of each hand), a torch-sav
 to the fp32 masks on the device, once for all thresholds (postprocess.smooth_mask_lists, csrc/mask_smooth.hip): the PNGs, --score /
 --score_only and --write_records then equal what that script would leave behind on the unsmoothed run's tree.
 
+--device_png makes the mask files on the device (png.py, csrc/png_encode.hip): the planes of a chunk stay in HBM, one measure and one
+emit call turn them into PNG streams of run tokens, and the host reads those few KB back instead of ten planes per frame and runs no
+encoder. Same names, order and pixels as the default route; the files are a few times the size of Pillow's. Not with --score_only, which
+writes no files.
+
 --visualize DIR (with --score / --score_only) writes the panels of `calculate_iou.py --visualize`: ground truth and prediction over the
 frame, side by side, captioned with the IoU of the scored counts. The scoring call draws them (haff_score_vis, csrc/mask_score.hip)
 from the per-pixel decisions it counts, so smoothing, --score_cropped and --score_intersection show as they are scored.
@@ -32,10 +37,10 @@ import torch
 if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import haff  # noqa: F401
-    from haff import checkpoint, config as hcfg, contours, postprocess, preprocess, prompt as hprompt, scoring
+    from haff import checkpoint, config as hcfg, contours, png, postprocess, preprocess, prompt as hprompt, scoring
     from haff.lisa import LisaMI355
 else:
-    from . import checkpoint, config as hcfg, contours, postprocess, preprocess, prompt as hprompt, scoring
+    from . import checkpoint, config as hcfg, contours, png, postprocess, preprocess, prompt as hprompt, scoring
     from .lisa import LisaMI355
 
 
@@ -95,8 +100,13 @@ def parse_args(args):
                         help="smooth every mask as ActAffordance's scripts/utils/gaussian.py smooths the written PNGs (7x7 Gaussian blur, "
                              "then --smooth_threshold), once on the device before anything is written, scored or traced")
     parser.add_argument("--smooth_threshold", default=None, type=float, help="gaussian.py --threshold, in [0, 1) (default 0.5)")
+    # the mask files as PNG streams made on the device (png.py): off by default
+    parser.add_argument("--device_png", action="store_true", default=False,
+                        help="encode the mask PNGs on the device, one call pair per chunk: the host reads back the compressed streams, "
+                             "not the planes (same pixels, files a few times the size of Pillow's)")
     args = parser.parse_args(args)
     check_score_args(args)
+    check_png_args(args)
     check_visualize_args(args)
     check_records_args(args)
     check_smooth_args(args)
@@ -113,6 +123,12 @@ def check_score_args(args):
         raise SystemExit("--score_hausdorff_device and --score_hausdorff are two routes to the same numbers: pass one of them")
     if args.score and not args.benchmark_dir:
         raise SystemExit("--score needs --benchmark-dir: the ground truth is its aff_{left,right}.png")
+
+
+def check_png_args(args):
+    """--device_png is a route to the mask files; --score_only writes none."""
+    if getattr(args, "device_png", False) and args.score_only:
+        raise SystemExit("--device_png makes the mask files and --score_only writes none: pass one of them")
 
 
 def check_visualize_args(args):
@@ -221,9 +237,18 @@ def save_mask(path, plane_u8):
     print(f"{path} has been saved.")
 
 
-def output_planes(masks_left, masks_right, taxonomies, thresholds=postprocess.THRESHOLDS):
+def save_png_bytes(path, data):
+    """save_mask for a file that is already encoded (--device_png)."""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(data)
+    print(f"{path} has been saved.")
+
+
+def output_planes(masks_left, masks_right, taxonomies, thresholds=postprocess.THRESHOLDS, on_device=False):
     """inference.py:276-334 on the device: {(side, th): uint8 [H0,W0] 0/255} — gating from taxonomies[0] (one host read of
-    its argmax decides which files exist), all five thresholds of a hand from ONE pass over its fp32 mask."""
+    its argmax decides which files exist), all five thresholds of a hand from ONE pass over its fp32 mask. on_device: the planes
+    stay CUDA tensors (--device_png encodes them there)."""
     out = {}
     taxonomy = taxonomies[0]
     if taxonomy.numel() == 0:
@@ -236,7 +261,9 @@ def output_planes(masks_left, masks_right, taxonomies, thresholds=postprocess.TH
         for pred_mask in masks:
             if pred_mask.shape[0] == 0:
                 continue
-            planes = postprocess.inference_planes(pred_mask[0], None, side, thresholds).cpu().numpy()
+            planes = postprocess.inference_planes(pred_mask[0], None, side, thresholds)
+            if not on_device:
+                planes = planes.cpu().numpy()
             for k, th in enumerate(thresholds):
                 out[(side, th)] = planes[k]
     return out
@@ -328,6 +355,7 @@ def _main(args, closers):
                                              "caption": args.visualize_caption, "examples": args.visualize_examples})
         closers.append(scorer.close)
     reader, records = (contours.ContourReader(), []) if args.write_records else (None, None)
+    encoder = png.PngEncoder() if args.device_png else None
     examples = list(iter_examples(args.benchmark_dir))
     for i in range(0, len(examples), max(args.batch_size, 1)):
         chunk = examples[i:i + max(args.batch_size, 1)]
@@ -354,6 +382,14 @@ def _main(args, closers):
                                      original_size_list, args.records_threshold)
         if args.score_only:
             continue
+        if encoder is not None:  # the chunk's planes stay on the device: one encode makes all its files, written in the usual order
+            named = [(os.path.join(args.vis_save_path + str(th), dir_name, folder_name, f"aff_{side}.png"), plane)
+                     for b, (dir_name, folder_name, _, _) in enumerate(chunk)
+                     for (side, th), plane in output_planes(masks_left[b:b + 1], masks_right[b:b + 1], taxonomies[b:b + 1],
+                                                            on_device=True).items()]
+            for (path, _), data in zip(named, encoder.encode([plane for _, plane in named])):
+                save_png_bytes(path, data)
+            continue
         for b, (dir_name, folder_name, _, _) in enumerate(chunk):   # per frame, exactly the reference's B = 1 rule
             for (side, th), plane in output_planes(masks_left[b:b + 1], masks_right[b:b + 1], taxonomies[b:b + 1]).items():
                 save_mask(os.path.join(args.vis_save_path + str(th), dir_name, folder_name, f"aff_{side}.png"), plane)
@@ -361,6 +397,7 @@ def _main(args, closers):
         contours.save_records(args.write_records, records)
         print(f"{args.write_records}: {len(records)} records at threshold {args.records_threshold}, {reader.host_walks} planes walked "
               "on the host")
+    png.report_host_encodes(encoder)
     if scorer is not None:
         return scorer.report(verbose=True)
     return None

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HAFF_LIB_PATH") or os.path.join(_HERE, "lib", "libhaff_hip.so")   # override: A/B builds in tools/
 CSRC_DIR = os.path.join(_HERE, "csrc")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "haff_hip.h")
+IO_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "haff_io.h")   # file-format helpers, beside the frozen hot-path ABI
 
 c_void_p, c_int, c_long, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -50,12 +51,13 @@ def parse_header(text):
     return protos
 
 
-def _read_header():
+def _read_header(path=None):
+    path = HEADER_PATH if path is None else path
     try:
-        with open(HEADER_PATH) as fh:
+        with open(path) as fh:
             return fh.read()
     except OSError as e:
-        raise HaffLibraryError(f"{HEADER_PATH} not readable: the prototypes of libhaff_hip.so are derived from it") from e
+        raise HaffLibraryError(f"{path} not readable: the prototypes of libhaff_hip.so are derived from it") from e
 
 
 # name -> argtypes ; every entry point returns int (0 ok, <0 error). include/haff_hip.h is the one declaration: this table is read
@@ -63,6 +65,10 @@ def _read_header():
 _PROTOS = parse_header(_read_header())
 
 EXPORTED_SYMBOLS = tuple(sorted(_PROTOS))
+
+# the same for include/haff_io.h, in a table of its own: the hot-path ABI above stays as it is locked
+_IO_PROTOS = parse_header(_read_header(IO_HEADER_PATH))
+IO_SYMBOLS = tuple(sorted(_IO_PROTOS))
 
 _lib = None
 
@@ -102,7 +108,7 @@ def load_library():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU or eager fallback for the hot path)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in _PROTOS.items():
+    for name, argtypes in list(_PROTOS.items()) + list(_IO_PROTOS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

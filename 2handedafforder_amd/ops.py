@@ -1567,3 +1567,52 @@ def affordance_extract(items, k, stats=None):
         rc = lib.haff_affordance_extract(host.data_ptr(), dev.data_ptr(), n, k, stats.data_ptr(), _stream())
     check(rc, "haff_affordance_extract")
     return stats
+
+
+PNG_MAX_SIDE, PNG_MAX_PLANES = MAX_SIDE, 4096            # csrc/png_encode.hip
+
+
+def png_block_bound(H, W):
+    """The most bytes the block of an H x W plane can take (include/haff_io.h): every byte a 9-bit literal."""
+    return (10 + 9 * (W + 1) * H + 7) // 8
+
+
+def png_measure(planes):
+    """haff_png_measure: planes = uint8 CUDA tensors [H, W] of any mix of shapes (a list, or one [n, H, W] tensor), any values.
+    Returns (table, job): table int32 [n, 4] on the device, to be read as uint32 = {byte offset of the plane's DEFLATE block in
+    png_emit's output, its byte length, the Adler-32 of the plane's scanlines, 0}; job = what png_emit needs beside the table as the
+    host read it (the descriptors, the workspace with every scanline's bit offset). Only enqueues."""
+    lib = load_library()
+    planes, device = _u8_planes(planes)
+    n = len(planes)
+    host = _plane_table(planes)                          # haff_png_plane = haff_contour_plane's layout: {pointer, H, W}
+    need = ctypes.c_long(0)
+    check(lib.haff_png_workspace(host.data_ptr(), n, ctypes.addressof(need)), "haff_png_workspace")
+    table = torch.empty((n, 4), dtype=torch.int32, device=device)
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=device)   # its own: it lives until png_emit has run
+    with torch.cuda.device(device):
+        dev = host.to(device, non_blocking=True)
+        rc = lib.haff_png_measure(host.data_ptr(), dev.data_ptr(), n, ws.data_ptr(), ws.numel(), table.data_ptr(), _stream())
+    check(rc, "haff_png_measure")
+    return table, (planes, host, dev, ws, table)
+
+
+def png_emit(job, table_host, out=None):
+    """haff_png_emit: job = png_measure's, table_host = its table as a uint32 numpy array [n, 4] read back by the caller. Returns the
+    uint8 CUDA tensor of exactly the size the table implies (the last plane's offset + length, rounded up to 4), or `out` (uint8,
+    contiguous, at least that size; only that many bytes are written): every plane's block at its offset, zeros between a block's end
+    and the next offset. Only enqueues."""
+    lib = load_library()
+    planes, host, dev, ws, table = job
+    th = np.ascontiguousarray(table_host, dtype=np.uint32)
+    assert th.shape == (len(planes), 4), th.shape
+    total = int(th[-1, 0]) + (int(th[-1, 1]) + 3) // 4 * 4
+    device = table.device
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == device
+    with torch.cuda.device(device):
+        rc = lib.haff_png_emit(host.data_ptr(), dev.data_ptr(), len(planes), ws.data_ptr(), ws.numel(), th.ctypes.data, table.data_ptr(),
+                               out.data_ptr(), out.numel(), _stream())
+    check(rc, "haff_png_emit")
+    return out

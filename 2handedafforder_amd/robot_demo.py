@@ -18,6 +18,10 @@ of the extension (aff_left_1.png, aff_left_heat_1.png, cropped_img_1.png, ...).
 [[[x, y], ...], ...]}: every external contour of that very plane (padded and ANDed), extracted on the device (contours.py) before the
 plane is read back, for a planner that wants polygons instead of a raster.
 
+--device_png (off by default): the aff_<hand><suffix>.png masks are encoded on the device (png.py, csrc/png_encode.hip) from the padded
+and ANDed planes, and the host reads back the PNG streams instead of the planes: same pixels, no encoder in the request's latency. The
+heat maps and cropped_img.png are RGB and stay on Pillow.
+
 Offline extras as in inference.py: --synthetic, --sam-checkpoint, --max-new-tokens. Stated deviation: the two waits sleep
 --poll-interval seconds between polls instead of busy-looping. Images are read and written with PIL (cv2 is not a dependency).
 """
@@ -33,10 +37,10 @@ import torch
 if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import haff  # noqa: F401
-    from haff import contours as hcontours, postprocess, prompt as hprompt
+    from haff import contours as hcontours, png as hpng, postprocess, prompt as hprompt
     from haff.inference import build_model_and_tokenizer, load_rgb, prepare_frame
 else:
-    from . import contours as hcontours, postprocess, prompt as hprompt
+    from . import contours as hcontours, png as hpng, postprocess, prompt as hprompt
     from .inference import build_model_and_tokenizer, load_rgb, prepare_frame
 
 
@@ -45,6 +49,8 @@ else:
 MULTI_PROMPT_FLAG = "--multi_prompt"
 # Also an option of the loop: aff_<hand><suffix>.json with the contours of aff_<hand><suffix>.png beside every such file.
 CONTOURS_FLAG = "--contours"
+# Also an option of the loop: the aff_<hand><suffix>.png masks leave the device as PNG streams (png.PngEncoder).
+DEVICE_PNG_FLAG = "--device_png"
 
 
 def parse_args(args):
@@ -95,11 +101,11 @@ def read_margins(path):
     return int(m[0]), int(m[1]), int(m[2]), int(m[3])
 
 
-def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, device, suffix="", contours=False):
+def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, device, suffix="", contours=False, encoder=None):
     """robot_demo.py:266-327 for a request whose taxonomy is not empty: the hands the --force_* flags select, every non-empty
     entry of pred_masks_<hand> in order (a later one overwrites the files of an earlier one, as there). suffix ("_<i>", --multi_prompt:
     prompt line i >= 1) goes in front of the file names' extension. contours: also aff_<hand><suffix>.json, from the planes while
-    they are still on the device."""
+    they are still on the device. encoder: a png.PngEncoder that makes the aff_<hand><suffix>.png files there too."""
     from PIL import Image
     hands = []
     for side, masks, forced in (("left", masks_left, args.force_left), ("right", masks_right, args.force_right)):
@@ -116,12 +122,17 @@ def write_hands(args, masks_left, masks_right, mask_left, mask_right, margins, d
         and_masks.append(uploaded[id(m)])
     heat, planes = postprocess.robot_planes(torch.stack([x for _, x in hands]), args.th, margins, and_masks)
     found = hcontours.ContourReader().read(list(planes)) if contours else None
-    heat, planes = heat.cpu().numpy(), planes.cpu().numpy()
+    files = encoder.encode(list(planes)) if encoder is not None else None
+    heat, planes = heat.cpu().numpy(), planes.cpu().numpy() if files is None else planes
     for k, (side, _) in enumerate(hands):
         Image.fromarray(heat[k]).save(os.path.join(args.vis_save_path, f"aff_{side}_heat{suffix}.png"))
         mask_save_path = os.path.join(args.vis_save_path, f"aff_{side}{suffix}.png")
         os.makedirs(os.path.dirname(mask_save_path), exist_ok=True)
-        Image.fromarray(planes[k]).save(mask_save_path)
+        if files is None:
+            Image.fromarray(planes[k]).save(mask_save_path)
+        else:
+            with open(mask_save_path, "wb") as f:
+                f.write(files[k])
         print(f"{mask_save_path} has been saved.")
         if found is not None:
             with open(os.path.join(args.vis_save_path, f"aff_{side}{suffix}.json"), "w") as f:
@@ -132,11 +143,12 @@ def main(argv, max_requests=None):
     """max_requests: return after that many passes that found img.png, prompt.txt and margins.txt (a test hook, like
     chat.main(max_turns=)); None polls forever, as the reference does.
     --multi_prompt is an option of this loop, not one of parse_args' flags (those stay the reference's plus the four offline extras):
-    it is taken out of argv here, and so is --contours."""
+    it is taken out of argv here, and so are --contours and --device_png."""
     from PIL import Image
     multi_prompt = MULTI_PROMPT_FLAG in argv
     contours = CONTOURS_FLAG in argv
-    args = parse_args([a for a in argv if a not in (MULTI_PROMPT_FLAG, CONTOURS_FLAG)])
+    encoder = hpng.PngEncoder() if DEVICE_PNG_FLAG in argv else None
+    args = parse_args([a for a in argv if a not in (MULTI_PROMPT_FLAG, CONTOURS_FLAG, DEVICE_PNG_FLAG)])
     os.makedirs(args.vis_save_path, exist_ok=True)
     model, tokenizer, cfg, dtype = build_model_and_tokenizer(args)
     device = model.device
@@ -192,13 +204,14 @@ def main(argv, max_requests=None):
             suffix = f"_{i}" if i else ""
             if taxonomy.numel() != 0:   # the taxonomy does not gate here (robot_demo.py:268,298 are commented out)
                 write_hands(args, masks_left[i:i + 1], masks_right[i:i + 1], mask_left, mask_right, margins, device, suffix,
-                            contours=contours)
+                            contours=contours, encoder=encoder)
             else:
                 print("No taxonomy found!!")
             Image.fromarray(image_np).save(os.path.join(args.vis_save_path, f"cropped_img{suffix}.png"))
         os.remove(image_path)
         os.remove(prompt_path)
         os.remove(margins_path)
+    hpng.report_host_encodes(encoder)
 
 
 if __name__ == "__main__":
