@@ -584,10 +584,27 @@ def decode_case(B, H, Tmax, nks, seed, dtype, pair=False, nan=False):
     return ragged_poison(c, nan)
 
 
-def rope_case(B, H, Tmax, nks, seed, dtype):
+def chain_choice(B, H, nks, shift=0):
+    """The chained decode step's attention stage (one workgroup per (row, head), four waves that take every fourth trip of 16 keys,
+    256 keys requested before the wait): (row, head) pair i takes turn (i + shift) % 10 of key 0, the new row nk - 1, the last cached
+    row nk - 2, keys 16, 32 and 48 (the first key of waves 1 to 3), keys 255, 256, 257 (both sides of the pre-wait registers) and
+    300; a turn whose key the row does not see passes to the next one (key 0 is always seen)."""
+    ch = torch.empty((B, H, 1), dtype=torch.long)
+    for b in range(B):
+        cand = [0, nks[b] - 1, nks[b] - 2, 16, 32, 48, 255, 256, 257, 300]
+        for h in range(H):
+            t = (b * H + h + shift) % len(cand)
+            while not 0 <= cand[t] < nks[b]:
+                t = (t + 1) % len(cand)
+            ch[b, h, 0] = cand[t]
+    return ch
+
+
+def rope_case(B, H, Tmax, nks, seed, dtype, choice=None):
     """The fused-RoPE decode step: -> (Case of the ROTATED problem (what the kernel attends), qkv_raw [B, 3, H, d], caches before the
     step k0, v0 [B,H,Tmax,d] with NaN from row nk - 1 on, cos_sin). q_raw = r16(rope_inv(GAIN * kcache[choice])) for an old key,
-    GAIN * k_new for the new row; the Case's q is r16(rope(q_raw)), its k row nk - 1 is r16(rope(k_new))."""
+    GAIN * k_new for the new row; the Case's q is r16(rope(q_raw)), its k row nk - 1 is r16(rope(k_new)). choice [B, H, 1]: the key
+    every (row, head) answers with (default: decode_choice)."""
     d = DEC_D
     cs = cos_sin_table(Tmax, d)
     pos = torch.tensor([n - 1 for n in nks])
@@ -595,7 +612,7 @@ def rope_case(B, H, Tmax, nks, seed, dtype):
     v = rand((B, H, Tmax, d), seed + 1).to(dtype)
     k_new = unit_rows((B, H, d), seed + 2, dtype, amp_of(d))
     v_new = rand((B, H, d), seed + 3).to(dtype)
-    choice = decode_choice(B, H, nks)
+    choice = decode_choice(B, H, nks) if choice is None else choice
     rot = lambda x: rope(x, pos[:, None], cs).to(dtype)   # noqa: E731
     k_rot = rot(k_new)
     is_new = choice[..., 0] == pos[:, None]

@@ -9,7 +9,9 @@ replaces (haff_gemm_bf16_rms x 4 + haff_decode_attention_rope_rows_bf16 per tran
   * ragged rows (every row at its own position), repeated launches equal bit for bit, the sticky timeout word stays 0;
   * through a hipGraph (the form generate() replays) the chained step equals its eager self.
 Against the CPU oracle the chain is covered by test_configs_gpu.py::test_decode_rows_carrying_rmsnorm_matches_oracle (it is the
-default path of LlamaHip.decode_rows at <= 8 rows)."""
+default path of LlamaHip.decode_rows at <= 8 rows). This module pins the CHAINING (the waits, the hand-offs, the graph replay); the
+ARITHMETIC of the kernel's own product and attention statements is pinned by tests/test_chain_edge_kernels_gpu.py against the float64
+restatement tests/chain_ref.py, at the narrowest geometries the entry point admits."""
 import pytest
 import torch
 
