@@ -16,6 +16,7 @@
 // outlier columns into its mask. The masks (uint32 [S][K/32]) are ORed into, never cleared here: the caller zeroes them for a
 // fresh call and keeps them across a frame's decode steps (sticky masks: a decode row sees the whole prefix's columns).
 #include "haff_common.h"
+#include "gemm_quant.h"
 
 #pragma clang fp contract(off)
 
@@ -291,12 +292,10 @@ __device__ __forceinline__ void i8_epilogue(const I8Args& p, int m, int nt, int 
 // workgroup per 16 * NT weight rows, KW waves splitting K into contiguous ranges of 64-byte blocks. Lane (fr, fh) holds weight row
 // fr and activation row fr, bytes 16 fh .. 16 fh + 15 of a block: one 16-byte load each feeds v_mfma_i32_16x16x64_i8 directly
 // (D[n = 4 fh + r][m = fr]). The KW int32 partial tiles are summed in LDS (exact).
-template <int MT> constexpr int i8_batch() { return MT == 1 ? 4 : (MT == 2 ? 2 : 1); }
-
 template <int MT, int NT, bool SWIGLU, int KW>
 __global__ __launch_bounds__(64 * KW) void gemm_i8_skinny_kernel(I8Args p) {
   static_assert(!SWIGLU || (NT % 2) == 0, "SwiGLU pairs a gate tile with an up tile");
-  constexpr int U = i8_batch<MT>();
+  constexpr int U = quant_batch<MT>();
   __shared__ int red[KW][MT][64][4];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -430,17 +429,14 @@ __global__ __launch_bounds__(256) void gemm_i8_tiled_kernel(I8Args p) {
   }
 }
 
-constexpr int kI8Waves = 8;
-
 template <int MT>
 void launch_i8_skinny(const I8Args& p, int swiglu, hipStream_t s) {
-  const int tiles = (p.N + 15) / 16;
-  const dim3 b(64 * kI8Waves);
-  if (swiglu) hipLaunchKernelGGL((gemm_i8_skinny_kernel<MT, 2, true, kI8Waves>), dim3((tiles + 1) / 2), b, 0, s, p);
-  else if (MT >= 2 && tiles / 2 >= 192) hipLaunchKernelGGL((gemm_i8_skinny_kernel<MT, 2, false, kI8Waves>), dim3((tiles + 1) / 2), b, 0, s, p);
-  else hipLaunchKernelGGL((gemm_i8_skinny_kernel<MT, 1, false, kI8Waves>), dim3(tiles), b, 0, s, p);
+  const int nt = quant_raster_nt(p.N, MT, swiglu);
+  const dim3 g = quant_grid(p.N, nt), b(64 * kQuantWaves);
+  if (swiglu) hipLaunchKernelGGL((gemm_i8_skinny_kernel<MT, 2, true, kQuantWaves>), g, b, 0, s, p);
+  else if (nt == 2) hipLaunchKernelGGL((gemm_i8_skinny_kernel<MT, 2, false, kQuantWaves>), g, b, 0, s, p);
+  else hipLaunchKernelGGL((gemm_i8_skinny_kernel<MT, 1, false, kQuantWaves>), g, b, 0, s, p);
 }
-
 
 }  // namespace
 
@@ -489,9 +485,7 @@ extern "C" int haff_gemm_int8_f16(const void* A, long lda, const void* CA, long 
            reinterpret_cast<const signed char*>(CB), SCB, cols, ncols, seg_rows, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (f == 1) {
-    if (M <= 16) launch_i8_skinny<1>(p, swiglu, s);
-    else if (M <= 32) launch_i8_skinny<2>(p, swiglu, s);
-    else launch_i8_skinny<4>(p, swiglu, s);
+    HAFF_DISPATCH_MT(M, launch_i8_skinny<MT>(p, swiglu, s));
   } else {
     const dim3 g((M + kTM - 1) / kTM, (N + kTN - 1) / kTN);
     if (swiglu) hipLaunchKernelGGL(gemm_i8_tiled_kernel<true>, g, dim3(256), 0, s, p);

@@ -16,6 +16,7 @@
 // a 256-entry LDS table of fp32 pairs {NF4[hi], NF4[lo]} (one ds_read_b64 per two weights), scaled by absmax with one packed
 // multiply and rounded to f16 with one packed convert.
 #include "haff_common.h"
+#include "gemm_quant.h"
 
 #include <type_traits>
 
@@ -327,9 +328,7 @@ struct Nf4LoraArgs : Nf4Args {
   float scale;
 };
 
-// Activation 16-B fragments per 64-block per tile row of 16: two k-steps. Blocks per batch of loads (two register sets).
-template <int MT> constexpr int nf4_batch() { return MT == 1 ? 4 : (MT == 2 ? 2 : 1); }
-
+// Activation 16-B fragments per 64-block per tile row of 16: two k-steps (quant_batch blocks per batch of loads).
 // LORA: the rank update s * sum_j t[m][8 seg + j] * B[n][j] joins the reduced sums before bias, activation, SwiGLU and residual,
 // as ONE MFMA per 16 x 16 tile (the trick of lora_qkv_rope_fwd_kernel): the weight operand of lane (fr, fh) holds row fr's 8
 // coefficients where fh is the row tile's segment and zeros elsewhere, the activation operand t[m][8 fh .. 8 fh + 7].
@@ -337,7 +336,7 @@ template <int MT, int NT, bool SWIGLU, int KW, bool LORA = false>
 __global__ __launch_bounds__(64 * KW) void gemm_nf4_kernel(std::conditional_t<LORA, Nf4LoraArgs, Nf4Args> p) {
   using E = h16<true>;
   static_assert(!SWIGLU || (NT % 2) == 0, "SwiGLU pairs a gate tile with an up tile");
-  constexpr int U = nf4_batch<MT>();
+  constexpr int U = quant_batch<MT>();
   __shared__ nf4_f2 lut[256];                 // byte -> {NF4[byte >> 4], NF4[byte & 15]} (element order in memory: even k first)
   __shared__ float red[KW][MT][64][4];
   for (int b = threadIdx.x; b < 256; b += 64 * KW) lut[b] = nf4_f2{kNF4[b >> 4], kNF4[b & 15]};
@@ -500,47 +499,57 @@ __global__ __launch_bounds__(64 * KW) void gemm_nf4_kernel(std::conditional_t<LO
   }
 }
 
-constexpr int kNf4Waves = 8;
-
 template <int MT, bool LORA, typename Args>
 void launch_nf4(const Args& p, int swiglu, hipStream_t s) {
-  // 16 weight rows per workgroup while that leaves >= 192 workgroups (SwiGLU: a gate and an up tile), wider otherwise
-  const int tiles = (p.N + 15) / 16;
-  const dim3 b(64 * kNf4Waves);
-  if (swiglu) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, true, kNf4Waves, LORA>), dim3((tiles + 1) / 2), b, 0, s, p);
-  else if (MT >= 2 && tiles / 2 >= 192) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, false, kNf4Waves, LORA>), dim3((tiles + 1) / 2), b, 0, s, p);
-  else hipLaunchKernelGGL((gemm_nf4_kernel<MT, 1, false, kNf4Waves, LORA>), dim3(tiles), b, 0, s, p);
+  const int nt = quant_raster_nt(p.N, MT, swiglu);
+  const dim3 g = quant_grid(p.N, nt), b(64 * kQuantWaves);
+  if (swiglu) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, true, kQuantWaves, LORA>), g, b, 0, s, p);
+  else if (nt == 2) hipLaunchKernelGGL((gemm_nf4_kernel<MT, 2, false, kQuantWaves, LORA>), g, b, 0, s, p);
+  else hipLaunchKernelGGL((gemm_nf4_kernel<MT, 1, false, kQuantWaves, LORA>), g, b, 0, s, p);
 }
 
-// the host-side refusals of haff_gemm_nf4_f16 (0: go on)
+// The host-side rules the entry points below share, one function each (haff_aligned: on that many bytes, or null).
+// The stored rows of a weight: whole 64-blocks, both tables present, the absmax on a float, the codes on the kernel's widest access to
+// them: 4 bytes in the quantiser and the row-major dequantisers (a thread's word of 8 codes), 8 in the products, 16 transposed
+bool nf4_rows_bad(const void* packed, unsigned packed_align, const float* absmax, int N, int K) {
+  return N <= 0 || K <= 0 || (K & 63) || !packed || !absmax || !haff_aligned(packed, packed_align) || !haff_aligned(absmax, 4);
+}
+// f16 rows read or written 8 elements at a time: present, on 16 bytes, a stride of whole chunks that holds `cols` elements
+bool nf4_f16_rows_bad(const void* p, long ld, long cols) { return !p || !haff_aligned(p) || (ld & 7) || ld < cols; }
+
+// the refusals of both products (0: go on); -2 comes right after the zero dimensions, ahead of every other -1 rule
 int nf4_gemm_args_bad(const void* A, long lda, const void* Wq, const float* absmax, const void* C, const void* resid, int M, int N, int K,
                       int swiglu) {
   if (M <= 0 || N <= 0 || K <= 0) return HAFF_ERR_BAD_ARG;
   if (M > 64) return HAFF_ERR_UNSUPPORTED;   // decode-sized products only: prefill dequantises and runs haff_gemm_f16
-  if ((K & 63) || (lda & 7) || lda < K || !A || !Wq || !absmax || !C) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(Wq) & 7) || (reinterpret_cast<uintptr_t>(absmax) & 3))
-    return HAFF_ERR_BAD_ARG;
+  if (nf4_rows_bad(Wq, 8, absmax, N, K) || nf4_f16_rows_bad(A, lda, K) || !C) return HAFF_ERR_BAD_ARG;
   if (swiglu && ((N & 31) || resid)) return HAFF_ERR_BAD_ARG;
   return 0;
 }
 
 // ... and of the adapters' layout, shared by both LoRA entry points
 bool nf4_lora_layout_bad(const void* B, int nseg, int seg_rows) {
-  return nseg < 1 || nseg > 4 || seg_rows <= 0 || (seg_rows & 15) || !B || (reinterpret_cast<uintptr_t>(B) & 15);
+  return nseg < 1 || nseg > 4 || seg_rows <= 0 || (seg_rows & 15) || !B || !haff_aligned(B);
+}
+
+// The argument block of both products, every field BY NAME (Nf4LoraArgs adds its own to it)
+void nf4_args(Nf4Args& p, const void* A, long lda, const void* Wq, const float* absmax, void* C, long ldc, const float* bias,
+              const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32) {
+  p.A = reinterpret_cast<const bf16_t*>(A); p.lda = lda;
+  p.Wq = reinterpret_cast<const unsigned char*>(Wq); p.absmax = absmax;
+  p.C = C; p.ldc = ldc; p.bias = bias; p.resid = resid; p.ldr = ldr; p.row_map = row_map;
+  p.M = M; p.N = N; p.K = K; p.act = act; p.out_f32 = out_f32;
 }
 
 }  // namespace
 
 extern "C" int haff_nf4_quantize_f16(const void* W, long ldw, int N, int K, int double_quant, const int* row_map, void* packed,
                                      float* absmax, float* offset, void* workspace, long workspace_bytes, void* stream) {
-  if (N <= 0 || K <= 0 || (K & 63) || (ldw & 7) || ldw < K || (double_quant != 0 && double_quant != 1)) return HAFF_ERR_BAD_ARG;
-  if (!W || !packed || !absmax || !offset || !workspace) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(W) & 15) || (reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(absmax) & 3) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 3))
-    return HAFF_ERR_BAD_ARG;
+  if (nf4_rows_bad(packed, 4, absmax, N, K) || nf4_f16_rows_bad(W, ldw, K) || (double_quant != 0 && double_quant != 1)) return HAFF_ERR_BAD_ARG;
+  if (!offset || !workspace || !haff_aligned(workspace, 4)) return HAFF_ERR_BAD_ARG;
   const long nb = (long)N * (K >> 6);
   if (workspace_bytes < 4 * nb) return HAFF_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t s = haff_stream(stream);
   float* amax_src = reinterpret_cast<float*>(workspace);
   const long thr = (long)N * (K >> 3);
   hipLaunchKernelGGL(nf4_codes_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(W), ldw, N,
@@ -553,23 +562,20 @@ extern "C" int haff_nf4_quantize_f16(const void* W, long ldw, int N, int K, int 
 
 extern "C" int haff_nf4_dequant_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out, long ldo,
                                     void* stream) {
-  if (N <= 0 || K <= 0 || (K & 63) || (ldo & 7) || ldo < K || !packed || !absmax || !out) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(absmax) & 3) || (reinterpret_cast<uintptr_t>(out) & 15))
-    return HAFF_ERR_BAD_ARG;
+  if (nf4_rows_bad(packed, 4, absmax, N, K) || nf4_f16_rows_bad(out, ldo, K)) return HAFF_ERR_BAD_ARG;
   const long thr = (long)N * (K >> 3);
-  hipLaunchKernelGGL(nf4_dequant_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(nf4_dequant_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, haff_stream(stream),
                      reinterpret_cast<const unsigned char*>(packed), absmax, N, K, row_map, reinterpret_cast<bf16_t*>(out), ldo);
   return haff_check_launch();
 }
 
 extern "C" int haff_nf4_dequant_t_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out_t, long ldo,
                                       void* stream) {
-  if (N <= 0 || K <= 0 || (K & 63) || (ldo & 7) || ldo < ((N + 7) & ~7) || !packed || !absmax || !out_t) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(absmax) & 3) || (reinterpret_cast<uintptr_t>(out_t) & 15) ||
-      (reinterpret_cast<uintptr_t>(row_map) & 3))
-    return HAFF_ERR_BAD_ARG;
+  // unlike the row-major forms: the fill reads 16-byte code chunks (packed on 16 bytes, not 4), an output row holds the stored rows
+  // padded to whole 8-column chunks (ldo >= roundup(N, 8), not K), and the row map's alignment is asked for
+  if (nf4_rows_bad(packed, 16, absmax, N, K) || nf4_f16_rows_bad(out_t, ldo, (N + 7) & ~7) || !haff_aligned(row_map, 4)) return HAFF_ERR_BAD_ARG;
   hipLaunchKernelGGL(nf4_dequant_t_kernel, dim3((unsigned)((K + kT_K - 1) / kT_K), (unsigned)((N + kT_N - 1) / kT_N)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const unsigned char*>(packed), absmax, N, K, row_map,
+                     haff_stream(stream), reinterpret_cast<const unsigned char*>(packed), absmax, N, K, row_map,
                      reinterpret_cast<f16_t*>(out_t), ldo);
   return haff_check_launch();
 }
@@ -578,12 +584,9 @@ extern "C" int haff_gemm_nf4_f16(const void* A, long lda, const void* Wq, const 
                                  const void* resid, long ldr, const int* row_map, int M, int N, int K, int act, int out_f32, int swiglu,
                                  void* stream) {
   if (const int bad = nf4_gemm_args_bad(A, lda, Wq, absmax, C, resid, M, N, K, swiglu)) return bad;
-  Nf4Args p{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const unsigned char*>(Wq), absmax, C, ldc, bias, resid, ldr,
-            row_map, M, N, K, act, out_f32};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (M <= 16) launch_nf4<1, false>(p, swiglu, s);
-  else if (M <= 32) launch_nf4<2, false>(p, swiglu, s);
-  else launch_nf4<4, false>(p, swiglu, s);
+  Nf4Args p;
+  nf4_args(p, A, lda, Wq, absmax, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32);
+  HAFF_DISPATCH_MT(M, launch_nf4<MT, false>(p, swiglu, haff_stream(stream)));
   return haff_check_launch();
 }
 
@@ -592,28 +595,22 @@ extern "C" int haff_gemm_nf4_lora_f16(const void* A, long lda, const void* Wq, c
                                       int swiglu, const void* t, long ldt, const void* B, int nseg, int seg_rows, float scale,
                                       void* stream) {
   if (const int bad = nf4_gemm_args_bad(A, lda, Wq, absmax, C, resid, M, N, K, swiglu)) return bad;
-  if (nf4_lora_layout_bad(B, nseg, seg_rows) || !t || (reinterpret_cast<uintptr_t>(t) & 15) || ldt < 8 * nseg || (ldt & 7))
-    return HAFF_ERR_BAD_ARG;
-  Nf4LoraArgs p{{reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const unsigned char*>(Wq), absmax, C, ldc, bias, resid, ldr,
-                 row_map, M, N, K, act, out_f32},
-                reinterpret_cast<const bf16_t*>(t), ldt, reinterpret_cast<const bf16_t*>(B), nseg, seg_rows, scale};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (M <= 16) launch_nf4<1, true>(p, swiglu, s);
-  else if (M <= 32) launch_nf4<2, true>(p, swiglu, s);
-  else launch_nf4<4, true>(p, swiglu, s);
+  if (nf4_lora_layout_bad(B, nseg, seg_rows) || nf4_f16_rows_bad(t, ldt, 8 * nseg)) return HAFF_ERR_BAD_ARG;
+  Nf4LoraArgs p;
+  nf4_args(p, A, lda, Wq, absmax, C, ldc, bias, resid, ldr, row_map, M, N, K, act, out_f32);
+  p.t = reinterpret_cast<const bf16_t*>(t); p.ldt = ldt; p.B = reinterpret_cast<const bf16_t*>(B);
+  p.nseg = nseg; p.seg_rows = seg_rows; p.scale = scale;
+  HAFF_DISPATCH_MT(M, launch_nf4<MT, true>(p, swiglu, haff_stream(stream)));
   return haff_check_launch();
 }
 
 extern "C" int haff_nf4_dequant_lora_f16(const void* packed, const float* absmax, int N, int K, const int* row_map, void* out, long ldo,
                                          const void* A_cat, long lda, const void* B, int nseg, int seg_rows, float scale,
                                          void* stream) {
-  if (N <= 0 || K <= 0 || (K & 63) || (ldo & 7) || ldo < K || !packed || !absmax || !out) return HAFF_ERR_BAD_ARG;
-  if ((reinterpret_cast<uintptr_t>(packed) & 3) || (reinterpret_cast<uintptr_t>(absmax) & 3) || (reinterpret_cast<uintptr_t>(out) & 15))
-    return HAFF_ERR_BAD_ARG;
-  if (nf4_lora_layout_bad(B, nseg, seg_rows) || !A_cat || (reinterpret_cast<uintptr_t>(A_cat) & 15) || lda < K || (lda & 7))
-    return HAFF_ERR_BAD_ARG;
+  if (nf4_rows_bad(packed, 4, absmax, N, K) || nf4_f16_rows_bad(out, ldo, K)) return HAFF_ERR_BAD_ARG;
+  if (nf4_lora_layout_bad(B, nseg, seg_rows) || nf4_f16_rows_bad(A_cat, lda, K)) return HAFF_ERR_BAD_ARG;
   const long thr = (long)((N + 7) >> 3) * (K >> 3);
-  hipLaunchKernelGGL(nf4_dequant_lora_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(nf4_dequant_lora_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, haff_stream(stream),
                      reinterpret_cast<const unsigned char*>(packed), absmax, N, K, row_map, reinterpret_cast<f16_t*>(out), ldo,
                      reinterpret_cast<const f16_t*>(A_cat), lda, reinterpret_cast<const f16_t*>(B), nseg, seg_rows, scale);
   return haff_check_launch();

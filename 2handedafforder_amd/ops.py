@@ -74,6 +74,28 @@ def _out(out, shape, dtype, device):
     return out
 
 
+def _linear_out(x, M, N, swiglu, out, out_rows, out_dtype, resid, bias, row_map):
+    """The output of a linear*(): the caller's `out`, or a new [out_rows or M, N (SwiGLU: N / 2)] tensor of out_dtype (None: x's), and
+    the epilogue's operands checked against it: resid like out, bias fp32 [N], row_map int32 [M]."""
+    n_out = N // 2 if swiglu else N
+    if out is None:
+        out = torch.empty((M if out_rows is None else out_rows, n_out), dtype=x.dtype if out_dtype is None else out_dtype, device=x.device)
+    assert out.stride(1) == 1 and out.shape[1] == n_out
+    if resid is not None:
+        assert resid.dtype == out.dtype and resid.stride(1) == 1
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == N
+    if row_map is not None:
+        assert row_map.dtype == torch.int32 and row_map.numel() == M
+    return out
+
+
+def _epilogue_args(out, bias, resid, row_map, M, N, K, act, swiglu):
+    """The ten arguments `bias, resid, ldr, row_map, M, N, K, act, out_f32, swiglu` that follow `C, ldc` in every product's C signature"""
+    return (_p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
+            1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0)
+
+
 def upload_pinned(array, device):
     """A numpy array as a device tensor, through a pinned staging copy: the upload does not block the host."""
     return torch.from_numpy(np.ascontiguousarray(array)).pin_memory().to(device, non_blocking=True)
@@ -231,18 +253,7 @@ def linear(x, w, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, ou
         M = a_map.numel()
     N = w.shape[0]
     assert w.shape[1] == K, (x.shape, w.shape)
-    n_out = N // 2 if swiglu else N
-    if out_dtype is None:
-        out_dtype = x.dtype
-    if out is None:
-        out = torch.empty((out_rows if out_rows is not None else M, n_out), dtype=out_dtype, device=x.device)
-    assert out.stride(1) == 1 and out.shape[1] == n_out
-    if resid is not None:
-        assert resid.dtype == out.dtype and resid.stride(1) == 1
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == N
-    if row_map is not None:
-        assert row_map.dtype == torch.int32 and row_map.numel() == M
+    out = _linear_out(x, M, N, swiglu, out, out_rows, out_dtype, resid, bias, row_map)
     if (SPLIT_ROW_TAIL and x.dtype in (torch.bfloat16, torch.float16) and M > 4096 and 0 < (M & 255) <= 64 and row_map is None and a_map is None
             and ln_stats is None and not swiglu and not tile_cfg and out_rows is None and N >= 256):
         # A short row tail that costs the persistent 256 x 256 tile a whole extra round (CLIP at 64 frames: 16448 rows = 64.25
@@ -254,40 +265,29 @@ def linear(x, w, bias=None, act=ACT_NONE, resid=None, row_map=None, out=None, ou
             _LINEAR(x[:m0], w, bias, act, None if resid is None else resid[:m0], out=out[:m0])
             _LINEAR(x[m0:], w, bias, act, None if resid is None else resid[m0:], out=out[m0:])
             return out
+    xa, wc = (x.data_ptr(), x.stride(0)), (w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0))
+    epi = _epilogue_args(out, bias, resid, row_map, M, N, K, act, swiglu)
     if ln_stats is not None:
         assert x.dtype in (torch.bfloat16, torch.float16) and w.dtype == x.dtype and a_map is None
         assert ln_stats.dtype == torch.float32 and ln_stats.shape == (M, 2) and ln_stats.is_contiguous()
         if ln_colsum is not None:
             assert ln_colsum.dtype == torch.float32 and ln_colsum.numel() == N
-        rc = _fn(lib, "haff_gemm_bf16_ln", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
-                                   out.stride(0), _p(bias), _p(resid), 0 if resid is None else resid.stride(0),
-                                   _p(row_map), ln_stats.data_ptr(), _p(ln_colsum), M, N, K, act,
-                                   1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, _stream())
+        rc = _fn(lib, "haff_gemm_bf16_ln", x.dtype)(*xa, *wc, *epi[:4], ln_stats.data_ptr(), _p(ln_colsum), *epi[4:], _stream())
     elif a_map is not None:
         assert w.dtype == x.dtype
-        rc = _fn(lib, "haff_gemm_bf16_gather", x.dtype)(x.data_ptr(), x.stride(0), a_map.data_ptr(), x.shape[0], w.data_ptr(),
-                                       w.stride(0), out.data_ptr(), out.stride(0), _p(bias), _p(resid),
-                                       0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
-                                       1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, _stream())
+        rc = _fn(lib, "haff_gemm_bf16_gather", x.dtype)(*xa, a_map.data_ptr(), x.shape[0], *wc, *epi, _stream())
     elif x.dtype in (torch.bfloat16, torch.float16) and 32 < M <= 1024 and not tile_cfg:
         # few output tiles (decode at batch 33..64 on narrow weights, prefill / CLIP at one frame): the library may split K
         # over workgroups through a per-stream fp32 workspace (partials summed in a fixed order)
         assert w.dtype == x.dtype
         ws = _workspace(x.device, 64 << 20)
-        rc = _fn(lib, "haff_gemm_bf16_ws", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
-                                   _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
-                                   1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, ws.data_ptr(), ws.numel(), _stream())
+        rc = _fn(lib, "haff_gemm_bf16_ws", x.dtype)(*xa, *wc, *epi, ws.data_ptr(), ws.numel(), _stream())
     elif x.dtype in (torch.bfloat16, torch.float16):
         assert w.dtype == x.dtype
-        rc = _fn(lib, "haff_gemm_bf16_cfg", x.dtype)(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(),
-                                    out.stride(0), _p(bias), _p(resid), 0 if resid is None else resid.stride(0),
-                                    _p(row_map), M, N, K, act, 1 if out.dtype == torch.float32 else 0,
-                                    1 if swiglu else 0, tile_cfg, _stream())
+        rc = _fn(lib, "haff_gemm_bf16_cfg", x.dtype)(*xa, *wc, *epi, tile_cfg, _stream())
     else:
         assert w.dtype == torch.float32 and out.dtype == torch.float32
-        rc = lib.haff_gemm_f32(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
-                               _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map),
-                               M, N, K, act, 1 if swiglu else 0, _stream())
+        rc = lib.haff_gemm_f32(*xa, *wc, *epi[:8], epi[9], _stream())   # (fp32 out only: the signature has no out_f32)
     check(rc, "haff_gemm")
     return out
 
@@ -318,13 +318,19 @@ def nf4_quantize(w, double_quant=True, row_map=None, packed=None, absmax=None):
     return packed, absmax, offset
 
 
-def nf4_dequant(packed, absmax, row_map=None, out=None):
-    """f16 [N, K] = f16_rn(NF4[code] * absmax) of the stored rows; row_map (int32 [N]): stored row n goes to out row row_map[n]."""
-    lib = load_library()
+def _nf4_operands(packed, absmax):
+    """(N, K) of an NF4 weight's stored rows: packed uint8 [N, K/2] and absmax f32 [N, K/64], both contiguous, in HBM"""
     _req(packed, "packed")
     N, K = packed.shape[0], packed.shape[1] * 2
     assert packed.dtype == torch.uint8 and packed.is_contiguous() and absmax.dtype == torch.float32 and absmax.is_contiguous()
     assert absmax.shape == (N, K // 64)
+    return N, K
+
+
+def nf4_dequant(packed, absmax, row_map=None, out=None):
+    """f16 [N, K] = f16_rn(NF4[code] * absmax) of the stored rows; row_map (int32 [N]): stored row n goes to out row row_map[n]."""
+    lib = load_library()
+    N, K = _nf4_operands(packed, absmax)
     if out is None:
         out = torch.empty((N, K), dtype=torch.float16, device=packed.device)
     assert out.dtype == torch.float16 and out.stride(1) == 1 and out.shape[1] == K
@@ -346,10 +352,7 @@ def nf4_dequant_lora(packed, absmax, lora, row_map=None, out=None):
     """nf4_dequant with unmerged LoRA adapters folded in (haff_nf4_dequant_lora_f16): f16 [N, K] = f16_rn(NF4[code] * absmax +
     scale * (B A_cat)[n, k]), each stored row against its own segment's 8 rank rows of A_cat; same row_map contract."""
     lib = load_library()
-    _req(packed, "packed")
-    N, K = packed.shape[0], packed.shape[1] * 2
-    assert packed.dtype == torch.uint8 and packed.is_contiguous() and absmax.dtype == torch.float32 and absmax.is_contiguous()
-    assert absmax.shape == (N, K // 64)
+    N, K = _nf4_operands(packed, absmax)
     _check_nf4_lora(lora, N, K)
     if out is None:
         out = torch.empty((N, K), dtype=torch.float16, device=packed.device)
@@ -367,11 +370,8 @@ def nf4_dequant_t(packed, absmax, row_map=None, out=None):
     columns zero: the layout autograd.transpose(w, Rp=_pad8(N)) gives a frozen weight's resident W^T (haff_nf4_dequant_t_f16).
     out: f16 [K, >= Np] with unit inner stride; its columns from Np on are left alone."""
     lib = load_library()
-    _req(packed, "packed")
-    N, K = packed.shape[0], packed.shape[1] * 2
+    N, K = _nf4_operands(packed, absmax)
     Np = (N + 7) // 8 * 8
-    assert packed.dtype == torch.uint8 and packed.is_contiguous() and absmax.dtype == torch.float32 and absmax.is_contiguous()
-    assert absmax.shape == (N, K // 64)
     if out is None:
         out = torch.empty((K, Np), dtype=torch.float16, device=packed.device)
     assert out.dtype == torch.float16 and out.stride(1) == 1 and out.shape[0] == K and out.shape[1] >= Np
@@ -392,34 +392,21 @@ def linear_nf4(x, packed, absmax, bias=None, act=ACT_NONE, resid=None, row_map=N
     _req(x, "x")
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float16
     M, K = x.shape
-    N = packed.shape[0]
-    assert packed.dtype == torch.uint8 and packed.shape[1] * 2 == K and absmax.shape == (N, K // 64)
-    n_out = N // 2 if swiglu else N
-    if out_dtype is None:
-        out_dtype = x.dtype
-    if out is None:
-        out = torch.empty((M, n_out), dtype=out_dtype, device=x.device)
-    assert out.stride(1) == 1 and out.shape[1] == n_out and out.dtype in (torch.float16, torch.float32)
-    if resid is not None:
-        assert resid.dtype == out.dtype and resid.stride(1) == 1
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == N
-    if row_map is not None:
-        assert row_map.dtype == torch.int32 and row_map.numel() == M
+    N = _nf4_operands(packed, absmax)[0]
+    assert packed.shape[1] * 2 == K
+    out = _linear_out(x, M, N, swiglu, out, None, out_dtype, resid, bias, row_map)
+    assert out.dtype in (torch.float16, torch.float32)
+    head = (x.data_ptr(), x.stride(0), packed.data_ptr(), absmax.data_ptr(), out.data_ptr(), out.stride(0))
+    epi = _epilogue_args(out, bias, resid, row_map, M, N, K, act, swiglu)
     if lora is not None:
         _check_nf4_lora(lora, N, K)
         t = linear(x, lora.a_cat) if lora_t is None else lora_t
         assert t.dtype == torch.float16 and t.stride(1) == 1 and t.shape == (M, 8 * lora.nseg)
-        rc = lib.haff_gemm_nf4_lora_f16(x.data_ptr(), x.stride(0), packed.data_ptr(), absmax.data_ptr(), out.data_ptr(), out.stride(0),
-                                        _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
-                                        1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, t.data_ptr(), t.stride(0),
-                                        lora.b.data_ptr(), lora.nseg, lora.seg_rows, float(lora.scale), _stream())
+        rc = lib.haff_gemm_nf4_lora_f16(*head, *epi, t.data_ptr(), t.stride(0), lora.b.data_ptr(), lora.nseg, lora.seg_rows,
+                                        float(lora.scale), _stream())
         check(rc, "haff_gemm_nf4_lora_f16")
         return out
-    rc = lib.haff_gemm_nf4_f16(x.data_ptr(), x.stride(0), packed.data_ptr(), absmax.data_ptr(), out.data_ptr(), out.stride(0),
-                               _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
-                               1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, _stream())
-    check(rc, "haff_gemm_nf4_f16")
+    check(lib.haff_gemm_nf4_f16(*head, *epi, _stream()), "haff_gemm_nf4_f16")
     return out
 
 
@@ -497,22 +484,11 @@ def linear_int8(q, cb, scb, bias=None, act=ACT_NONE, resid=None, row_map=None, o
     M, K = x.shape
     N = cb.shape[0]
     assert cb.dtype == torch.int8 and cb.is_contiguous() and cb.shape[1] == K and scb.numel() == N
-    n_out = N // 2 if swiglu else N
-    if out_dtype is None:
-        out_dtype = x.dtype
-    if out is None:
-        out = torch.empty((M, n_out), dtype=out_dtype, device=x.device)
-    assert out.stride(1) == 1 and out.shape[1] == n_out and out.dtype in (torch.float16, torch.float32)
-    if resid is not None:
-        assert resid.dtype == out.dtype and resid.stride(1) == 1
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == N
-    if row_map is not None:
-        assert row_map.dtype == torch.int32 and row_map.numel() == M
+    out = _linear_out(x, M, N, swiglu, out, None, out_dtype, resid, bias, row_map)
+    assert out.dtype in (torch.float16, torch.float32)
     rc = lib.haff_gemm_int8_f16(x.data_ptr(), x.stride(0), q.ca.data_ptr(), q.ca.stride(0), q.sca.data_ptr(), cb.data_ptr(),
                                 scb.data_ptr(), q.cols.data_ptr(), q.ncols.data_ptr(), q.seg_rows, out.data_ptr(), out.stride(0),
-                                _p(bias), _p(resid), 0 if resid is None else resid.stride(0), _p(row_map), M, N, K, act,
-                                1 if out.dtype == torch.float32 else 0, 1 if swiglu else 0, int(form), _stream())
+                                *_epilogue_args(out, bias, resid, row_map, M, N, K, act, swiglu), int(form), _stream())
     check(rc, "haff_gemm_int8_f16")
     return out
 
@@ -570,12 +546,8 @@ def linear_rms(x, w, resid=None, out=None, swiglu=False, ssq_in=None, ssq_out=No
     M, K = x.shape
     N = w.shape[0]
     assert x.dtype in (torch.bfloat16, torch.float16) and w.dtype == x.dtype and x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K
-    n_out = N // 2 if swiglu else N
-    if out is None:
-        out = torch.empty((M, n_out), dtype=x.dtype, device=x.device)
-    assert out.dtype == x.dtype and out.stride(1) == 1 and out.shape == (M, n_out)
-    if resid is not None:
-        assert resid.dtype == out.dtype and resid.stride(1) == 1
+    out = _linear_out(x, M, N, swiglu, out, None, None, resid, None, None)
+    assert out.dtype == x.dtype and out.shape[0] == M
     if ssq_in is not None:
         assert ssq_in.dtype == torch.float32 and ssq_in.is_contiguous() and ssq_in.shape[1] == 16
     if ssq_out is not None:

@@ -1,5 +1,6 @@
 """The LLM.int8 8-bit mode's host side (no GPU): hand cases of the independent restatement (tests/int8_ref.py), haff.quant's
-restatement against it, the option refusals, and the three entry points' declarations and host-side refusals."""
+restatement against it, the option refusals, and the three entry points' declarations (their host-side refusals:
+tests/test_quant_contract_cpu.py)."""
 import ctypes
 import os
 import re
@@ -190,22 +191,12 @@ def test_load_in_8bit_option_refusals():
         LisaMI355(cfg, {}, dtype=torch.float16, load_in_8bit=True, llm_int8_threshold=-1.0)
 
 
-def test_int8_entry_points_declared_and_refuse_bad_shapes_on_the_host():
+def test_int8_entry_points_declared():
+    """(their host-side refusals: tests/test_quant_contract_cpu.py)"""
     text = open(os.path.join(ROOT, "include", "haff_hip.h")).read()
     for name in ENTRY:
         assert re.search(r"^int %s\(" % name, text, flags=re.M), name
         assert name in haff.EXPORTED_SYMBOLS
     if not os.path.exists(haff.LIB_PATH):
         haff.build_library()
-    lib = haff.load_library()
-    buf = (ctypes.c_char * 4096)()
-    p = ctypes.addressof(buf)
-    p16 = (p + 15) & ~15
-    # K % 64, threshold < 0, misaligned operands: refused before anything is launched
-    assert lib.haff_int8_quantize_weight_f16(p16, 96, 4, 96, None, p16, p16, None) == -1
-    assert lib.haff_int8_quantize_act_f16(p16, 64, 1, 64, -1.0, 1, None, p16, p16, 64, p16, p16, p16, None) == -1
-    assert lib.haff_int8_quantize_act_f16(p16, 64, 1, 64, 6.0, 1, None, None, p16, 64, p16, p16, p16, None) == -1
-    assert lib.haff_gemm_int8_f16(p16, 64, p16 + 1, 64, p16, p16, p16, None, None, 1, p16, 64, None, None, 0, None,
-                                  1, 64, 64, 0, 0, 0, 0, None) == -1
-    assert lib.haff_gemm_int8_f16(p16, 64, p16, 64, p16, p16, p16, None, None, 1, p16, 64, None, None, 0, None,
-                                  65, 64, 64, 0, 0, 0, 1, None) == -2        # the weight-streaming form serves M <= 64 only
+    assert all(hasattr(ctypes.CDLL(haff.LIB_PATH), n) for n in ENTRY)

@@ -1,5 +1,5 @@
-"""Serving LoRA adapters unmerged on the NF4 base, host side (no GPU): the two entry points' declarations and host-side refusals,
-LisaMI355's option refusals, the adapter layout quant.lora_pack builds, the CPU restatement (tests/lora_serve_ref.py) by hand, and
+"""Serving LoRA adapters unmerged on the NF4 base, host side (no GPU): the two entry points' declarations (their host-side refusals:
+tests/test_quant_contract_cpu.py), LisaMI355's option refusals, the adapter layout quant.lora_pack builds, the CPU restatement (tests/lora_serve_ref.py) by hand, and
 what the GPU comparisons' tolerance can and cannot pass."""
 import ctypes
 import os
@@ -33,35 +33,6 @@ def test_declarations_equal_the_ctypes_prototypes():
     # each is its parent's argument list with the adapters' arguments in front of the stream
     assert hlib._PROTOS[NAMES[0]][:7] + hlib._PROTOS[NAMES[0]][-1:] == hlib._PROTOS["haff_nf4_dequant_f16"]
     assert hlib._PROTOS[NAMES[1]][:16] + hlib._PROTOS[NAMES[1]][-1:] == hlib._PROTOS["haff_gemm_nf4_f16"]
-
-
-def test_host_side_refusals_before_any_launch():
-    """Never-dereferenced pointers, no GPU: a refusal has to come from the host checks."""
-    if not os.path.exists(haff.LIB_PATH):
-        haff.build_library()
-    lib = haff.load_library()
-    f = 0x1000   # 16-B aligned, never dereferenced
-
-    def gemm(M=1, N=64, K=64, lda=None, A=f, Wq=f, swiglu=0, resid=None, t=f, ldt=None, B=f, nseg=1, seg_rows=16):
-        return int(lib.haff_gemm_nf4_lora_f16(A, K if lda is None else lda, Wq, f, f, N, None, resid, N, None, M, N, K, 0, 0, swiglu,
-                                              t, 8 * nseg if ldt is None else ldt, B, nseg, seg_rows, 2.0, None))
-    # the parent's refusals
-    assert gemm(M=65) == -2 and gemm(M=0) == -1 and gemm(K=96) == -1 and gemm(lda=60) == -1
-    assert gemm(A=f + 8) == -1 and gemm(Wq=f + 4) == -1
-    assert gemm(N=48, swiglu=1, nseg=2) == -1 and gemm(swiglu=1, nseg=2, resid=f) == -1
-    # the adapters'
-    assert gemm(nseg=0) == -1 and gemm(nseg=5, ldt=40) == -1
-    assert gemm(seg_rows=0) == -1 and gemm(seg_rows=-16) == -1 and gemm(seg_rows=24) == -1
-    assert gemm(t=None) == -1 and gemm(t=f + 8) == -1 and gemm(B=None) == -1 and gemm(B=f + 8) == -1
-    assert gemm(nseg=3, ldt=16) == -1 and gemm(nseg=1, ldt=12) == -1
-
-    def deq(N=16, K=64, ldo=None, out=f, A=f, lda=None, B=f, nseg=1, seg_rows=16):
-        return int(lib.haff_nf4_dequant_lora_f16(f, f, N, K, None, out, K if ldo is None else ldo, A, K if lda is None else lda, B,
-                                                 nseg, seg_rows, 2.0, None))
-    assert deq(K=100) == -1 and deq(ldo=60) == -1 and deq(out=f + 8) == -1 and deq(N=0) == -1          # the parent's
-    assert deq(nseg=0) == -1 and deq(nseg=5) == -1 and deq(seg_rows=0) == -1 and deq(seg_rows=40) == -1
-    assert deq(A=None) == -1 and deq(A=f + 8) == -1 and deq(B=None) == -1 and deq(B=f + 4) == -1
-    assert deq(lda=56) == -1
 
 
 def _state(cfg, modules, r=8):

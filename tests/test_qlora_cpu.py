@@ -1,5 +1,6 @@
 """NF4 fine-tuning (QLoRA), host side (no GPU): train_ds.py's --load_in_4bit / --load_in_8bit flags and their exits, LisaTrainable's
-option refusals, and the declaration, ctypes prototype and host-side refusals of haff_nf4_dequant_t_f16."""
+option refusals, and the declaration and ctypes prototype of haff_nf4_dequant_t_f16 (its host-side refusals:
+tests/test_quant_contract_cpu.py)."""
 import ctypes
 import os
 import re
@@ -82,26 +83,6 @@ def test_dequant_t_declared_with_the_same_signature_in_header_and_ctypes_table()
     # ... and it is haff_nf4_dequant_f16's signature: the same arguments, the output transposed
     m0 = re.search(r"^int haff_nf4_dequant_f16\(([^)]*)\);", text, flags=re.M)
     assert _c_args(m0.group(1)) == _c_args(m.group(1)) == lib._PROTOS["haff_nf4_dequant_f16"]
-
-
-def test_dequant_t_refuses_bad_arguments_on_the_host():
-    if not os.path.exists(haff.LIB_PATH):
-        haff.build_library()
-    lib = haff.load_library()
-    f = 0x1000   # 16-B aligned, never dereferenced: every call below returns before a launch
-
-    def d(N, K, ldo, packed=f, absmax=f, out=f, row_map=None):
-        return int(lib.haff_nf4_dequant_t_f16(packed, absmax, N, K, row_map, out, ldo, None))
-    assert d(16, 100, 16) == -1                  # K % 64
-    assert d(16, 0, 16) == -1 and d(0, 64, 16) == -1
-    assert d(16, 64, 8) == -1                    # ldo < roundup(N, 8)
-    assert d(13, 64, 13) == -1                   # ldo % 8
-    assert d(13, 64, 8) == -1                    # roundup(13, 8) = 16 > 8
-    assert d(16, 64, 16, out=f + 8) == -1        # out misaligned
-    assert d(16, 64, 16, packed=f + 4) == -1     # packed misaligned (16-B loads)
-    assert d(16, 64, 16, absmax=f + 2) == -1
-    assert d(16, 64, 16, row_map=f + 2) == -1
-    assert d(16, 64, 16, packed=None) == -1 and d(16, 64, 16, absmax=None) == -1 and d(16, 64, 16, out=None) == -1
 
 
 def test_nf4_weight_has_dequant_t():
