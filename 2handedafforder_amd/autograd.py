@@ -40,6 +40,18 @@ def _fn16(lib, name, dtype):
     return getattr(lib, name)
 
 
+def _call16(name, dtype, *args):
+    """_call for a 16-bit training kernel: the entry point `name` for bf16, its *_f16 sibling for fp16 (_fn16)."""
+    check(_fn16(load_library(), name, dtype)(*args, _s()), name)
+
+
+def _f32_workspace(fn, dev, *shape):
+    """The f32 partials of a product contracted over rows: as many values as the library's fn(*shape) asks for."""
+    n_ws = getattr(load_library(), fn)(*shape)
+    assert n_ws > 0
+    return torch.empty((n_ws,), dtype=torch.float32, device=dev)
+
+
 def scale_dev(a, alpha, per_row=False):
     """a * alpha with alpha a DEVICE fp32 scalar (or one value per row of the 2-D a): the multiply runs in fp32 inside the kernel —
     a torch multiply would first round the 0-dim upstream gradient to a's dtype (bf16)."""
@@ -80,7 +92,6 @@ def transpose(x, Rp=None, Cp=None):
 def bgemm(a, w, out=None, out_dtype=None):
     """Batched NT product: a [Zo,Zi,M,K], w [Zo,Zi,N,K] (strided views, unit inner stride) -> out [Zo,Zi,M,N]
     (contiguous unless `out` is a strided view with unit inner stride)."""
-    lib = load_library()
     Zo, Zi, M, K = a.shape
     N = w.shape[2]
     assert w.shape[0] == Zo and w.shape[1] == Zi and w.shape[3] == K and a.stride(3) == 1 and w.stride(3) == 1
@@ -89,17 +100,14 @@ def bgemm(a, w, out=None, out_dtype=None):
     if out is None:
         out = torch.empty((Zo, Zi, M, N), dtype=out_dtype, device=a.device)
     assert out.stride(3) == 1
+    args = (a.data_ptr(), a.stride(2), a.stride(0), a.stride(1), w.data_ptr(), w.stride(2), w.stride(0), w.stride(1), out.data_ptr(),
+            out.stride(2), out.stride(0), out.stride(1), Zo, Zi, M, N, K)
     if a.dtype in HALF:
         assert w.dtype == a.dtype
-        rc = _fn16(lib, "haff_gemm_bf16_batched", a.dtype)(a.data_ptr(), a.stride(2), a.stride(0), a.stride(1), w.data_ptr(), w.stride(2),
-                                        w.stride(0), w.stride(1), out.data_ptr(), out.stride(2), out.stride(0),
-                                        out.stride(1), Zo, Zi, M, N, K, 1 if out.dtype == torch.float32 else 0, _s())
+        _call16("haff_gemm_bf16_batched", a.dtype, *args, 1 if out.dtype == torch.float32 else 0)
     else:
         assert out.dtype == torch.float32
-        rc = lib.haff_gemm_f32_batched(a.data_ptr(), a.stride(2), a.stride(0), a.stride(1), w.data_ptr(), w.stride(2),
-                                       w.stride(0), w.stride(1), out.data_ptr(), out.stride(2), out.stride(0),
-                                       out.stride(1), Zo, Zi, M, N, K, _s())
-    check(rc, "haff_gemm_batched")
+        _call("haff_gemm_f32_batched", *args)
     return out
 
 
@@ -112,16 +120,13 @@ def gemm_tn_supported(a, b):
 def gemm_tn(a, b, out_dtype=None):
     """a [M, N1], b [M, N2] (bf16 or fp16, row strides free) -> a^T @ b [N1, N2]: the contraction runs over the ROWS, no transposed copy
     of either operand (haff_gemm_tn_bf16 / _f16)."""
-    lib = load_library()
     assert gemm_tn_supported(a, b)
     M, N1 = a.shape
     N2 = b.shape[1]
     out = torch.empty((N1, N2), dtype=out_dtype or a.dtype, device=a.device)
-    n_ws = lib.haff_gemm_tn_workspace_elems(M, N1, N2)
-    assert n_ws > 0
-    ws = torch.empty((n_ws,), dtype=torch.float32, device=a.device)
-    check(_fn16(lib, "haff_gemm_tn_bf16", a.dtype)(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), M, N1, N2, ws.data_ptr(), n_ws, out.data_ptr(),
-                                1 if out.dtype == torch.float32 else 0, _s()), "haff_gemm_tn_bf16")
+    ws = _f32_workspace("haff_gemm_tn_workspace_elems", a.device, M, N1, N2)
+    _call16("haff_gemm_tn_bf16", a.dtype, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), M, N1, N2, ws.data_ptr(), ws.numel(), out.data_ptr(),
+            1 if out.dtype == torch.float32 else 0)
     return out
 
 
@@ -631,20 +636,18 @@ def _forward_ranks(a_s, xds, on, per_adapter):
     return tT
 
 
-def _lora_tn(lib, sT, big, out, transposed, scale_):
+def _lora_tn(sT, big, out, transposed, scale_):
     """out = scale * sT[:, :M] . big, the contraction over the M rows of csrc/lora.hip: sT [R][Mp] (R = 8 or 16, zero padding),
     big [M][n], out [j][n] or, transposed, [n][j] (j <= R rows of sT wanted). The only caller of haff_lora_tn."""
     R, (M, n) = sT.shape[0], big.shape
-    n_ws = lib.haff_lora_tn_workspace_elems(M, R, n)
-    assert n_ws > 0
-    ws = torch.empty((n_ws,), dtype=torch.float32, device=big.device)
-    check(_fn16(lib, "haff_lora_tn", big.dtype)(sT.data_ptr(), sT.stride(0), R, big.data_ptr(), big.stride(0), M, n, ws.data_ptr(),
-                                                ws.numel(), out.data_ptr(), out.stride(0), 1 if out.dtype == torch.float32 else 0,
-                                                1 if transposed else 0, out.shape[1 if transposed else 0], scale_, _s()), "haff_lora_tn")
+    ws = _f32_workspace("haff_lora_tn_workspace_elems", big.device, M, R, n)
+    _call16("haff_lora_tn", big.dtype, sT.data_ptr(), sT.stride(0), R, big.data_ptr(), big.stride(0), M, n, ws.data_ptr(), ws.numel(),
+            out.data_ptr(), out.stride(0), 1 if out.dtype == torch.float32 else 0, 1 if transposed else 0,
+            out.shape[1 if transposed else 0], scale_)
     return out
 
 
-def _lora_dx(lib, dtT, a_s, masks, per_adapter, dx, scale_):
+def _lora_dx(dtT, a_s, masks, per_adapter, dx, scale_):
     """dx += scale * sum over the adapter slots of keep_i o (dt_i . A_i), dtT [8 n][Mp] and A stack [8 n][K] with n = 2 or 3 slots.
     The one choice among the entry points: haff_lora_dx3 for three slots (one mask for all travels as keep_q alone), haff_lora_dx2
     for two slots with a mask each, haff_lora_dx for two slots with one mask or none."""
@@ -656,8 +659,7 @@ def _lora_dx(lib, dtT, a_s, masks, per_adapter, dx, scale_):
         name = "haff_lora_dx2"
     else:
         name, ptrs = "haff_lora_dx", ptrs[:1]
-    check(_fn16(lib, name, dx.dtype)(dtT.data_ptr(), dtT.stride(0), a_s.data_ptr(), K, *ptrs, K, dx.data_ptr(), dx.stride(0), 1, M, K,
-                                     scale_, _s()), name)
+    _call16(name, dx.dtype, dtT.data_ptr(), dtT.stride(0), a_s.data_ptr(), K, *ptrs, K, dx.data_ptr(), dx.stride(0), 1, M, K, scale_)
 
 
 class LoraQKVRopeFn(Function):
@@ -678,7 +680,6 @@ class LoraQKVRopeFn(Function):
 
     @staticmethod
     def forward(ctx, x, wqkv, wqkv_t, aq, bq, av, bv, ak, bk, cos_sin, T, heads, scale_, keep):
-        lib = load_library()
         M, K = x.shape
         fw = ctx.frozen = frozen(wqkv, wqkv_t)
         H = fw.shape[0] // 3
@@ -694,16 +695,14 @@ class LoraQKVRopeFn(Function):
         tT = _forward_ranks(a_s, xds, on, per_adapter)
         q, k, v = (torch.empty((M, H), dtype=x.dtype, device=dev) for _ in range(3))
         name = "haff_lora_qkv_rope_fwd" if n == 2 else "haff_lora_qkv3_rope_fwd"
-        check(_fn16(lib, name, x.dtype)(qkv.data_ptr(), qkv.stride(0), tT.data_ptr(), tT.stride(0), *[b.data_ptr() for b in b_s], 8,
-                                        cos_sin.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), H, M, H, H // heads, int(T),
-                                        float(scale_), _s()), name)
+        _call16(name, x.dtype, qkv.data_ptr(), qkv.stride(0), tT.data_ptr(), tT.stride(0), *[b.data_ptr() for b in b_s], 8, cos_sin.data_ptr(),
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), H, M, H, H // heads, int(T), float(scale_))
         ctx.save_for_backward(a_s, b_s, tT, cos_sin, *xds, *masks)
         ctx.cfg = (int(T), heads, float(scale_), r, on, per_adapter)
         return q, k, v
 
     @staticmethod
     def backward(ctx, dq, dk, dv):
-        lib = load_library()
         a_s, b_s, tT, cos_sin, *rest = ctx.saved_tensors
         T, heads, scale_, r, on, per_adapter = ctx.cfg
         n, H = b_s.shape[0], b_s.shape[1]
@@ -712,8 +711,8 @@ class LoraQKVRopeFn(Function):
         dev, dt_ = xds[0].device, xds[0].dtype
         dq, dk, dv = dq.contiguous(), dk.contiguous(), dv.contiguous()
         dqkv = torch.empty((M, 3 * H), dtype=dt_, device=dev)
-        check(_fn16(lib, "haff_lora_qkv_rope_bwd", dt_)(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), H, cos_sin.data_ptr(), dqkv.data_ptr(),
-                                                        3 * H, M, H, H // heads, T, _s()), "haff_lora_qkv_rope_bwd")
+        _call16("haff_lora_qkv_rope_bwd", dt_, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), H, cos_sin.data_ptr(), dqkv.data_ptr(), 3 * H, M, H,
+                H // heads, T)
         cols = [dqkv[:, :H], dqkv[:, 2 * H:], dqkv[:, H:2 * H]]   # q, v, k: the adapters' order in t^T
         rows = [slice(8 * i, 8 * i + 8) for i in range(n)]
         b_t = b_s.transpose(1, 2).contiguous()                     # [n][8][H]
@@ -723,7 +722,7 @@ class LoraQKVRopeFn(Function):
             ops.linear(b_t[i], cols[i], out=dtT[rows[i], :M])
 
         def d_b(i):
-            return _lora_tn(lib, tT[rows[i]], cols[i], torch.empty((H, r), dtype=dt_, device=dev), True, scale_)
+            return _lora_tn(tT[rows[i]], cols[i], torch.empty((H, r), dtype=dt_, device=dev), True, scale_)
 
         da, db = [None] * 3, [None] * 3
         if n == 2:
@@ -733,20 +732,20 @@ class LoraQKVRopeFn(Function):
             da2 = torch.empty((16, K), dtype=dt_, device=dev)
             if per_adapter:   # each adapter's dA against ITS dropped input
                 for i in range(2):
-                    _lora_tn(lib, dtT[rows[i]], xds[i], da2[rows[i]], False, scale_)
+                    _lora_tn(dtT[rows[i]], xds[i], da2[rows[i]], False, scale_)
             else:
-                _lora_tn(lib, dtT, xds[0], da2, False, scale_)
+                _lora_tn(dtT, xds[0], da2, False, scale_)
             da[0], da[1] = da2[0:r], da2[8:8 + r]
         else:
             for i in range(3):
                 if on[i]:
                     dt_rows(i)
                     db[i] = d_b(i)
-                    da[i] = _lora_tn(lib, dtT[rows[i]], xds[i], torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
+                    da[i] = _lora_tn(dtT[rows[i]], xds[i], torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.linear(dqkv, ctx.frozen.w_t())
-            _lora_dx(lib, dtT, a_s, masks, per_adapter, dx, scale_)
+            _lora_dx(dtT, a_s, masks, per_adapter, dx, scale_)
         return dx, None, None, da[0], db[0], da[1], db[1], da[2], db[2], None, None, None, None, None
 
 
@@ -774,7 +773,6 @@ class LoraLinearFn(Function):
 
     @staticmethod
     def forward(ctx, x, w, w_t, resid, a, b, scale_, keep):
-        lib = load_library()
         M, K = x.shape
         fw = ctx.frozen = frozen(w, w_t)
         N = fw.shape[0]
@@ -783,15 +781,13 @@ class LoraLinearFn(Function):
         (xd,), (keep,), _ = _adapter_inputs(x, keep, 1)
         a8, b8, r, on = _stack_adapters([(a, b)], K, N, x.dtype, x.device)
         tT = _forward_ranks(a8, [xd], on, False)
-        check(_fn16(lib, "haff_lora_out", x.dtype)(tT.data_ptr(), tT.stride(0), b8.data_ptr(), y.data_ptr(), y.stride(0), M, N,
-                                                   float(scale_), _s()), "haff_lora_out")
+        _call16("haff_lora_out", x.dtype, tT.data_ptr(), tT.stride(0), b8.data_ptr(), y.data_ptr(), y.stride(0), M, N, float(scale_))
         ctx.save_for_backward(xd, a8, b8[0], tT, keep)
         ctx.cfg = (float(scale_), r, resid is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         xd, a8, b8, tT, keep = ctx.saved_tensors
         scale_, r, has_resid = ctx.cfg
         M, K = xd.shape
@@ -801,12 +797,12 @@ class LoraLinearFn(Function):
         # haff_lora_dx reads 16 rank rows (two adapter slots) of dt^T and A: this adapter's in rows 0-7, rows 8-15 zero
         dtT = torch.zeros((16, tT.shape[1]), dtype=dt_, device=dev)
         ops.linear(b8.t().contiguous(), dy, out=dtT[0:8, :M])
-        db = _lora_tn(lib, tT, dy, torch.empty((N, r), dtype=dt_, device=dev), True, scale_)
-        da = _lora_tn(lib, dtT[0:8], xd, torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
+        db = _lora_tn(tT, dy, torch.empty((N, r), dtype=dt_, device=dev), True, scale_)
+        da = _lora_tn(dtT[0:8], xd, torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.linear(dy, ctx.frozen.w_t())
-            _lora_dx(lib, dtT, torch.cat([a8, torch.zeros_like(a8)], 0), [keep], False, dx, scale_)
+            _lora_dx(dtT, torch.cat([a8, torch.zeros_like(a8)], 0), [keep], False, dx, scale_)
         return dx, None, None, (dy if has_resid else None), da, db, None, None
 
 
@@ -821,7 +817,6 @@ class LoraGateUpSwigluFn(Function):
 
     @staticmethod
     def forward(ctx, x, wgu, wgu_t, ag, bg, au, bu, scale_, keep):
-        lib = load_library()
         M, K = x.shape
         fw = ctx.frozen = frozen(wgu, wgu_t)
         F = fw.shape[0] // 2
@@ -831,15 +826,14 @@ class LoraGateUpSwigluFn(Function):
         a2, b2, r, on = _stack_adapters([(ag, bg), (au, bu)], K, F, x.dtype, x.device)
         tT = _forward_ranks(a2, xds, on, per_adapter)
         y = torch.empty((M, F), dtype=x.dtype, device=x.device)
-        check(_fn16(lib, "haff_lora_gu_swiglu", x.dtype)(tT.data_ptr(), tT.stride(0), b2[0].data_ptr(), b2[1].data_ptr(), gu.data_ptr(),
-                                                         gu.stride(0), y.data_ptr(), F, M, F, float(scale_), _s()), "haff_lora_gu_swiglu")
+        _call16("haff_lora_gu_swiglu", x.dtype, tT.data_ptr(), tT.stride(0), b2[0].data_ptr(), b2[1].data_ptr(), gu.data_ptr(), gu.stride(0),
+                y.data_ptr(), F, M, F, float(scale_))
         ctx.save_for_backward(gu, a2, b2, tT, *xds, *masks)
         ctx.cfg = (float(scale_), r, on, per_adapter)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = load_library()
         gu, a2, b2, tT, xg, xu, *masks = ctx.saved_tensors
         scale_, r, on, per_adapter = ctx.cfg
         M, K = xg.shape
@@ -856,18 +850,18 @@ class LoraGateUpSwigluFn(Function):
         dtT = _rank_rows(M, 16, dt_, dev)
         ops.linear(blk.view(16, 2 * F), dgu, out=dtT[:, :M])
         dag = dbg = dau = dbu = None
-        db_all = _lora_tn(lib, tT, dgu, torch.empty((2 * F, 16), dtype=dt_, device=dev), True, scale_)
+        db_all = _lora_tn(tT, dgu, torch.empty((2 * F, 16), dtype=dt_, device=dev), True, scale_)
         db_all = db_all.view(F // 16, 2, 16, 16)
         if on[0]:
             dbg = db_all[:, 0, :, 0:r].reshape(F, r)
-            dag = _lora_tn(lib, dtT[0:8], xg, torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
+            dag = _lora_tn(dtT[0:8], xg, torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
         if on[1]:
             dbu = db_all[:, 1, :, 8:8 + r].reshape(F, r)
-            dau = _lora_tn(lib, dtT[8:16], xu, torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
+            dau = _lora_tn(dtT[8:16], xu, torch.empty((r, K), dtype=dt_, device=dev), False, scale_)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.linear(dgu, ctx.frozen.w_t())
-            _lora_dx(lib, dtT, a2, masks, per_adapter, dx, scale_)
+            _lora_dx(dtT, a2, masks, per_adapter, dx, scale_)
         return dx, None, None, dag, dbg, dau, dbu, None, None
 
 

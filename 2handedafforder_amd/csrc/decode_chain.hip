@@ -571,6 +571,20 @@ __global__ __launch_bounds__(64 * CH_KW) void decode_chain_kernel(ChainArgs a) {
 
 }  // namespace
 
+// The ONE admission rule of the chained step and the workgroups of its five stages: 0 with nb filled; -1 for a layer or row count
+// out of range; else -2 for a geometry the kernel does not serve. The launch and haff_decode_chain_supported both ask here.
+static int chain_geometry(int M, int hidden, int ffn, int heads, int n_layers, int nb[CH_STAGES]) {
+  if (n_layers <= 0 || n_layers > CH_MAXL || M <= 0 || M > 8) return HAFF_ERR_BAD_ARG;
+  if (hidden <= 0 || ffn <= 0 || (hidden % 256) || (ffn % 256) || hidden != heads * CH_D || hidden / 16 > 512) return HAFF_ERR_UNSUPPORTED;
+  nb[0] = 3 * hidden / 16; nb[1] = M * heads; nb[2] = 2 * (hidden / 16); nb[3] = 2 * ffn / 32; nb[4] = 2 * (hidden / 16);
+  return HAFF_OK;
+}
+
+// The sync buffer: `counters` words (16 lines per (layer, stage)), the sticky error word at [counters] on a line of its own, then
+// `tickets` words at [counters + CH_LINE], one per K-split tile
+struct ChainSync { long counters, tickets; };
+static ChainSync chain_sync(int n_layers, int hidden) { return {(long)n_layers * CH_STAGES * CH_STAGE_WORDS, (long)n_layers * 2 * (hidden / 16)}; }
+
 // One KV-cached decode step of n_layers Llama layers at M <= 8 rows in ONE launch (see the head of this file).
 //   layers: HOST array of n_layers {wqkv, wo, wgu, wd, kcache, vcache} DEVICE pointers (passed to the kernel by value):
 //           wqkv [3H][H] with input_layernorm's gamma folded into its columns, wo [H][H], wgu [2F][H] in 16-row [gate | up] groups with
@@ -582,25 +596,21 @@ __global__ __launch_bounds__(64 * CH_KW) void decode_chain_kernel(ChainArgs a) {
 //   sync: DEVICE uint32 [haff_decode_chain_sync_words(n_layers)], zeroed once by the caller: the launch re-zeroes the counters, the
 //   last word is a sticky error flag (a wait ran out of patience: haff_decode_chain_status).
 //   per_stage_launches != 0: the same kernel as n_layers * 5 launches, one per stage (tests / A-B: identical arithmetic, no chaining).
-// hidden % 256 == 0, ffn % 256 == 0, hidden == heads * 128, hidden / 16 <= 512, M <= 8, n_layers <= 48; 16-B aligned pointers.
+// chain_geometry: hidden % 256 == 0, ffn % 256 == 0, hidden == heads * 128, hidden / 16 <= 512, M <= 8, n_layers <= 48; 16-B aligned pointers.
 extern "C" int haff_decode_chain_bf16(const haff_chain_layer* layers, int n_layers, int M, int hidden, int ffn, int heads, void* x,
                                       void* qkv, void* att, void* g, float* ssq_a, float* ssq_b, float* ws, const float* stats0, float eps,
                                       const float* cos_sin, const int* nk_rows, int tmax, float scale, unsigned* sync,
                                       int per_stage_launches, void* stream) {
-  if (!layers || n_layers <= 0 || n_layers > CH_MAXL || M <= 0 || M > 8) return HAFF_ERR_BAD_ARG;
-  if (hidden <= 0 || ffn <= 0 || (hidden % 256) || (ffn % 256) || hidden != heads * CH_D || hidden / 16 > 512) return HAFF_ERR_UNSUPPORTED;
-  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 15)) return HAFF_ERR_BAD_ARG;
-  if (!x || !qkv || !att || !g || !ssq_a || !ssq_b || !stats0 || !cos_sin || !nk_rows || !sync || tmax <= 0) return HAFF_ERR_BAD_ARG;
-  const uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(att) |
-                       reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(ssq_a) | reinterpret_cast<uintptr_t>(ssq_b);
-  if (al & 15) return HAFF_ERR_BAD_ARG;
   ChainArgs a;
+  if (!layers) return HAFF_ERR_BAD_ARG;
+  if (const int refused = chain_geometry(M, hidden, ffn, heads, n_layers, a.nb)) return refused;   // its -2 before every -1 below
+  if (!ws || !x || !qkv || !att || !g || !ssq_a || !ssq_b || !stats0 || !cos_sin || !nk_rows || !sync || tmax <= 0) return HAFF_ERR_BAD_ARG;
+  for (const void* p : {(const void*)ws, (const void*)x, (const void*)qkv, (const void*)att, (const void*)g, (const void*)ssq_a, (const void*)ssq_b})
+    if (!haff_aligned(p)) return HAFF_ERR_BAD_ARG;
   for (int i = 0; i < n_layers; ++i) {
     const haff_chain_layer& s = layers[i];
-    if (!s.wqkv || !s.wo || !s.wgu || !s.wd || !s.kcache || !s.vcache) return HAFF_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(s.wqkv) | reinterpret_cast<uintptr_t>(s.wo) | reinterpret_cast<uintptr_t>(s.wgu) |
-         reinterpret_cast<uintptr_t>(s.wd) | reinterpret_cast<uintptr_t>(s.kcache) | reinterpret_cast<uintptr_t>(s.vcache)) & 15)
-      return HAFF_ERR_BAD_ARG;
+    for (const void* p : {s.wqkv, s.wo, s.wgu, s.wd, (const void*)s.kcache, (const void*)s.vcache})
+      if (!p || !haff_aligned(p)) return HAFF_ERR_BAD_ARG;
     a.L[i] = ChainLayer{reinterpret_cast<const bf16_t*>(s.wqkv), reinterpret_cast<const bf16_t*>(s.wo), reinterpret_cast<const bf16_t*>(s.wgu),
                         reinterpret_cast<const bf16_t*>(s.wd), reinterpret_cast<bf16_t*>(s.kcache), reinterpret_cast<bf16_t*>(s.vcache)};
   }
@@ -609,14 +619,12 @@ extern "C" int haff_decode_chain_bf16(const haff_chain_layer* layers, int n_laye
   a.g = reinterpret_cast<bf16_t*>(g);
   a.ssq_a = ssq_a; a.ssq_b = ssq_b; a.ws = ws; a.stats0 = stats0; a.cos_sin = cos_sin; a.nk_rows = nk_rows; a.sync = sync;
   a.n_layers = n_layers; a.M = M; a.H = hidden; a.F = ffn; a.nh = heads; a.tmax = tmax; a.eps = eps; a.scale = scale;
-  a.nb[0] = 3 * hidden / 16; a.nb[1] = M * heads; a.nb[2] = 2 * (hidden / 16); a.nb[3] = 2 * ffn / 32; a.nb[4] = 2 * (hidden / 16);
   a.per_layer = a.nb[0] + a.nb[1] + a.nb[2] + a.nb[3] + a.nb[4];
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t s = haff_stream(stream);
   // arrival counters, then (behind the sticky error line, which stays) the tickets of the K-split tiles
-  {
-    const long na = (long)n_layers * CH_STAGES * CH_STAGE_WORDS, nt = (long)n_layers * 2 * (hidden / 16);
-    hipLaunchKernelGGL(chain_zero_kernel, dim3((unsigned)((na + nt + 255) / 256)), dim3(256), 0, s, sync, na, sync + na + CH_LINE, nt);
-  }
+  const ChainSync w = chain_sync(n_layers, hidden);
+  hipLaunchKernelGGL(chain_zero_kernel, dim3((unsigned)((w.counters + w.tickets + 255) / 256)), dim3(256), 0, s, sync, w.counters,
+                     sync + w.counters + CH_LINE, w.tickets);
   a.block0 = 0;
   if (!per_stage_launches) {
     hipLaunchKernelGGL(decode_chain_kernel, dim3((unsigned)(n_layers * a.per_layer)), dim3(64 * CH_KW), 0, s, a);
@@ -636,22 +644,22 @@ extern "C" int haff_decode_chain_bf16(const haff_chain_layer* layers, int n_laye
 extern "C" int haff_decode_chain_status(const unsigned* sync, int n_layers, void* stream) {
   if (!sync || n_layers <= 0 || n_layers > CH_MAXL) return HAFF_ERR_BAD_ARG;
   unsigned v = 0;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemcpyAsync(&v, sync + (long)n_layers * CH_STAGES * CH_STAGE_WORDS, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess)
-    return HAFF_ERR_LAUNCH;
+  hipStream_t s = haff_stream(stream);
+  if (hipMemcpyAsync(&v, sync + chain_sync(n_layers, 0).counters, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess) return HAFF_ERR_LAUNCH;
   if (hipStreamSynchronize(s) != hipSuccess) return HAFF_ERR_LAUNCH;
   return v ? 1 : 0;
 }
 
-// uint32 words of the sync buffer: 16 counter lines per (layer, stage), the sticky error word (a line of its own), one ticket per K-split tile
+// uint32 words of the sync buffer (chain_sync: the counters, the error word's line, the tickets)
 extern "C" int haff_decode_chain_sync_words(int n_layers, int hidden) {
   if (n_layers <= 0 || n_layers > CH_MAXL || hidden <= 0) return 0;
-  return n_layers * CH_STAGES * CH_STAGE_WORDS + CH_LINE + n_layers * 2 * (hidden / 16);
+  const ChainSync w = chain_sync(n_layers, hidden);
+  return (int)(w.counters + CH_LINE + w.tickets);
 }
 
-// Workgroups per layer the chained launch uses (for sizing / reporting): 0 when the geometry is unsupported.
+// Workgroups per layer the chained launch uses (for sizing / reporting): 0 for whatever chain_geometry refuses.
 extern "C" int haff_decode_chain_supported(int M, int hidden, int ffn, int heads, int n_layers) {
-  if (n_layers <= 0 || n_layers > CH_MAXL || M <= 0 || M > 8) return 0;
-  if (hidden <= 0 || ffn <= 0 || (hidden % 256) || (ffn % 256) || hidden != heads * CH_D || hidden / 16 > 512) return 0;
-  return 3 * hidden / 16 + M * heads + 2 * (hidden / 16) + 2 * ffn / 32 + 2 * (hidden / 16);
+  int nb[CH_STAGES];
+  if (chain_geometry(M, hidden, ffn, heads, n_layers, nb)) return 0;
+  return nb[0] + nb[1] + nb[2] + nb[3] + nb[4];
 }

@@ -148,25 +148,20 @@ template <bool F16>
 static int gemm_tn_impl(const void* A, long lda, const void* B, long ldb, long M, int N1, int N2, float* workspace,
                         long workspace_elems, void* out, int out_f32, void* stream) {
   if (M <= 0 || N1 <= 0 || N2 <= 0 || !A || !B || !workspace || !out || lda < N1 || ldb < N2) return HAFF_ERR_BAD_ARG;
-  if (reinterpret_cast<uintptr_t>(workspace) & 15) return HAFF_ERR_BAD_ARG;   // the partials are written and read 16 bytes at a time
-  if ((N1 & 7) || (N2 & 7) || (lda & 7) || (ldb & 7) || (reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15) ||
-      (reinterpret_cast<uintptr_t>(out) & 15))
-    return HAFF_ERR_UNSUPPORTED;
+  if (!haff_aligned(workspace)) return HAFF_ERR_BAD_ARG;   // the partials are written and read 16 bytes at a time
+  // a misaligned operand is -2 here (the caller transposes and takes the NT product) where lora.hip, which has no other route, says -1
+  if ((N1 & 7) || (N2 & 7) || (lda & 7) || (ldb & 7) || !haff_aligned(A) || !haff_aligned(B) || !haff_aligned(out)) return HAFF_ERR_UNSUPPORTED;
   long rps;
   int splits;
   tn_geometry(M, N1, N2, rps, splits);
   const long n = (long)N1 * N2;
   if (workspace_elems < (long)splits * n) return HAFF_ERR_BAD_ARG;
   TnArgs p{(const bf16_t*)A, (const bf16_t*)B, lda, ldb, M, N1, N2, rps, workspace};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t s = haff_stream(stream);
   hipLaunchKernelGGL((gemm_tn_kernel<F16>), dim3((N1 + TT - 1) / TT, (N2 + TT - 1) / TT, splits), dim3(256), 0, s, p);
-  long g = (n / 4 + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  if (out_f32) hipLaunchKernelGGL((gemm_tn_reduce_kernel<float>), dim3((unsigned)g), dim3(256), 0, s, workspace, splits, n, (float*)out);
-  else if (F16) hipLaunchKernelGGL((gemm_tn_reduce_kernel<f16_t>), dim3((unsigned)g), dim3(256), 0, s, workspace, splits, n, (f16_t*)out);
-  else hipLaunchKernelGGL((gemm_tn_reduce_kernel<bf16_t>), dim3((unsigned)g), dim3(256), 0, s, workspace, splits, n, (bf16_t*)out);
-  return hipGetLastError() == hipSuccess ? HAFF_OK : HAFF_ERR_LAUNCH;
+  HAFF_DISPATCH_OUT16(out_f32, F16, hipLaunchKernelGGL((gemm_tn_reduce_kernel<T>), dim3(haff_grid(n / 4, 256, 4096)), dim3(256), 0, s, workspace,
+                                                        splits, n, (T*)out));
+  return haff_check_launch();
 }
 
 // out [N1][N2] (contiguous; bf16 or f32) = A^T . B with A [M][lda] (N1 columns), B [M][ldb] (N2 columns), both bf16.

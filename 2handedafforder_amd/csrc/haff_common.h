@@ -259,6 +259,9 @@ static inline int haff_grid(long total, int block, long cap) {
 // the statement with the compile-time constant NAME = (cond), true first
 #define HAFF_DISPATCH_BOOL(cond, NAME, ...) \
   do { if (cond) { constexpr bool NAME = true; __VA_ARGS__; } else { constexpr bool NAME = false; __VA_ARGS__; } } while (0)
+// the statement with T = the output type of the TN products' reduce kernels: float when out_f32 is set, else f16_t (F16) or bf16_t
+#define HAFF_DISPATCH_OUT16(out_f32, F16, ...) \
+  do { if (out_f32) { using T = float; __VA_ARGS__; } else if (F16) { using T = f16_t; __VA_ARGS__; } else { using T = bf16_t; __VA_ARGS__; } } while (0)
 // host side: p sits on a `bytes` boundary (a power of two; 16 = one dwordx4 access). A null pointer passes.
 static inline bool haff_aligned(const void* p, unsigned bytes = 16) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 // host side: the (batch, head, token) strides of q / k / v are multiples of in_mask + 1 elements, those of the output of out_mask + 1

@@ -426,9 +426,22 @@ __global__ __launch_bounds__(256) void lora_gu_swiglu_kernel(const bf16_t* tT, l
   }
 }
 
-inline hipStream_t HS(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
+
+// rows of the 2-D launches (x = gx column groups: heads, or 128-column groups): 16-row tiles, four per workgroup (one per wave),
+// capped at ~2048 workgroups in all (8 per CU); the waves stride over the row tiles that are left
+static unsigned lora_rows_grid(long M, int gx) {
+  const long gy = ((M + 15) / 16 + 3) / 4, cap = (2048 + gx - 1) / gx;
+  return (unsigned)(gy > cap ? cap : gy);
+}
+
+static void lora_fwd_args(LoraFwdArgs& p, const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, const void* Bk,
+                          int ldb, const float* cos_sin, void* q_out, void* k_out, void* v_out, long ldo, long M, int H, int T, float scale) {
+  p.qkv = (const bf16_t*)qkv; p.ld_qkv = ld_qkv; p.tT = (const bf16_t*)tT; p.ldt = ldt;
+  p.Bq = (const bf16_t*)Bq; p.Bv = (const bf16_t*)Bv; p.Bk = (const bf16_t*)Bk; p.ldb = ldb; p.cs = cos_sin;
+  p.qo = (bf16_t*)q_out; p.ko = (bf16_t*)k_out; p.vo = (bf16_t*)v_out; p.ldo = ldo;
+  p.M = M; p.H = H; p.T = T; p.scale = scale;
+}
 
 template <bool F16, int NA>
 static int lora_qkv_rope_fwd_impl(const void* qkv, long ld_qkv, const void* tT, long ldt, const void* Bq, const void* Bv, const void* Bk,
@@ -438,17 +451,12 @@ static int lora_qkv_rope_fwd_impl(const void* qkv, long ld_qkv, const void* tT, 
   if (NA == 3 && (!Bk || !haff_aligned(Bk))) return HAFF_ERR_BAD_ARG;
   if (d != HD || H % HD || ldb != 8) return HAFF_ERR_UNSUPPORTED;
   if (ld_qkv < 3L * H || ldo < H || ldt < M || (ld_qkv & 7) || (ldo & 7)) return HAFF_ERR_BAD_ARG;
-  if (!haff_aligned(qkv) || !haff_aligned(Bq) || !haff_aligned(Bv) || !haff_aligned(cos_sin) || !haff_aligned(q_out) ||
-      !haff_aligned(k_out) || !haff_aligned(v_out))
-    return HAFF_ERR_BAD_ARG;
-  LoraFwdArgs p{(const bf16_t*)qkv, ld_qkv, (const bf16_t*)tT, ldt, (const bf16_t*)Bq, (const bf16_t*)Bv, ldb, cos_sin,
-                (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, ldo, M, H, T, scale, (const bf16_t*)Bk};
-  const long n_rt = (M + 15) / 16;
-  long gy = (n_rt + 3) / 4;
+  for (const void* x : {qkv, Bq, Bv, (const void*)cos_sin, (const void*)q_out, (const void*)k_out, (const void*)v_out})
+    if (!haff_aligned(x)) return HAFF_ERR_BAD_ARG;
+  LoraFwdArgs p;
+  lora_fwd_args(p, qkv, ld_qkv, tT, ldt, Bq, Bv, Bk, ldb, cos_sin, q_out, k_out, v_out, ldo, M, H, T, scale);
   const int nh = H / HD;
-  const long cap = (2048 + nh - 1) / nh;   // ~2048 workgroups: 8 per CU
-  if (gy > cap) gy = cap;
-  hipLaunchKernelGGL((lora_qkv_rope_fwd_kernel<F16, NA>), dim3(nh, (unsigned)gy), dim3(256), 0, HS(stream), p);
+  hipLaunchKernelGGL((lora_qkv_rope_fwd_kernel<F16, NA>), dim3(nh, lora_rows_grid(M, nh)), dim3(256), 0, haff_stream(stream), p);
   return haff_check_launch();
 }
 
@@ -459,30 +467,38 @@ static int lora_qkv_rope_bwd_impl(const void* dq, const void* dk, const void* dv
   if (d != HD || H % HD) return HAFF_ERR_UNSUPPORTED;
   if (ld_in < H || ld_out < 3L * H || (ld_in & 7) || (ld_out & 7)) return HAFF_ERR_BAD_ARG;
   if (!haff_aligned(dq) || !haff_aligned(dk) || !haff_aligned(dv) || !haff_aligned(cos_sin) || !haff_aligned(dqkv)) return HAFF_ERR_BAD_ARG;
-  const long total = M * (H / HD) * 8;
-  long g = (total + 255) / 256;
-  if (g > 16384) g = 16384;
-  hipLaunchKernelGGL((lora_qkv_rope_bwd_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)dq, (const bf16_t*)dk,
-                     (const bf16_t*)dv, ld_in, cos_sin, (bf16_t*)dqkv, ld_out, M, H, T);
+  hipLaunchKernelGGL((lora_qkv_rope_bwd_kernel<F16>), dim3(haff_grid(M * (H / HD) * 8, 256, 16384)), dim3(256), 0, haff_stream(stream),
+                     (const bf16_t*)dq, (const bf16_t*)dk, (const bf16_t*)dv, ld_in, cos_sin, (bf16_t*)dqkv, ld_out, M, H, T);
   return haff_check_launch();
 }
 
+// The dropout masks each dx entry point takes (its `masks` = how many it has parameters for): haff_lora_dx none or its one; haff_lora_dx2
+// both; haff_lora_dx3 none, keep_q alone (one mask for every adapter) or all three. A parameter the entry point lacks arrives null.
+static bool lora_dx_masks_ok(int masks, const void* keep_q, const void* keep_v, const void* keep_k) {
+  if (masks == 2) return keep_q && keep_v;
+  return (!keep_v && !keep_k) || (masks == 3 && keep_q && keep_v && keep_k);
+}
+
+static void lora_dx_args(LoraDxArgs& p, const void* dtT, long ldt, const void* A, long lda, const void* keep_q, const void* keep_v,
+                         const void* keep_k, long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, int na) {
+  p.dtT = (const bf16_t*)dtT; p.ldt = ldt; p.A2 = (const bf16_t*)A; p.lda = lda;
+  p.keep = (const bf16_t*)keep_q; p.keep_v = (const bf16_t*)keep_v; p.keep_k = (const bf16_t*)keep_k; p.ldk = ldk;
+  p.dx = (bf16_t*)dx; p.ldx = ldx; p.M = M; p.K = K; p.accumulate = accumulate; p.scale = scale; p.na = na;
+}
+
+// masks: the mask parameters of the entry point (1, 2 or 3, see lora_dx_masks_ok); na: the adapter slots of dt^T / A (2, or 3 for _dx3)
 template <bool F16>
-static int lora_dx_launch(const void* dtT, long ldt, const void* A2, long lda, const void* keep, const void* keep_v, long ldk, void* dx,
-                          long ldx, int accumulate, long M, int K, float scale, void* stream, int na = 2, const void* keep_k = nullptr) {
-  if (M <= 0 || K <= 0 || !dtT || !A2 || !dx || (keep_v && !keep) || (keep_k && !keep_v)) return HAFF_ERR_BAD_ARG;
-  if (keep_k && !haff_aligned(keep_k)) return HAFF_ERR_BAD_ARG;
+static int lora_dx_launch(int masks, int na, const void* dtT, long ldt, const void* A, long lda, const void* keep_q, const void* keep_v,
+                          const void* keep_k, long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
+  if (M <= 0 || K <= 0 || !dtT || !A || !dx || !lora_dx_masks_ok(masks, keep_q, keep_v, keep_k)) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(keep_k)) return HAFF_ERR_BAD_ARG;   // judged BEFORE the K % 128 rule, keep_q / keep_v after it: recorded, kept as it is
   if (K % 128) return HAFF_ERR_UNSUPPORTED;
-  if (ldt < M || lda < K || ldx < K || (ldx & 7) || (keep && (ldk < K || (ldk & 7)))) return HAFF_ERR_BAD_ARG;
-  if (!haff_aligned(dx) || (keep && !haff_aligned(keep)) || (keep_v && !haff_aligned(keep_v))) return HAFF_ERR_BAD_ARG;
-  LoraDxArgs p{(const bf16_t*)dtT, ldt, (const bf16_t*)A2, lda, (const bf16_t*)keep, ldk, (bf16_t*)dx, ldx, M, K, accumulate, scale,
-               (const bf16_t*)keep_v, (const bf16_t*)keep_k, na};
-  const long n_rt = (M + 15) / 16;
-  long gy = (n_rt + 3) / 4;
+  if (ldt < M || lda < K || ldx < K || (ldx & 7) || (keep_q && (ldk < K || (ldk & 7)))) return HAFF_ERR_BAD_ARG;
+  if (!haff_aligned(dx) || !haff_aligned(keep_q) || !haff_aligned(keep_v)) return HAFF_ERR_BAD_ARG;
+  LoraDxArgs p;
+  lora_dx_args(p, dtT, ldt, A, lda, keep_q, keep_v, keep_k, ldk, dx, ldx, accumulate, M, K, scale, na);
   const int gx = K / 128;
-  const long cap = (2048 + gx - 1) / gx;
-  if (gy > cap) gy = cap;
-  hipLaunchKernelGGL((lora_dx_kernel<F16>), dim3(gx, (unsigned)gy), dim3(256), 0, HS(stream), p);
+  hipLaunchKernelGGL((lora_dx_kernel<F16>), dim3(gx, lora_rows_grid(M, gx)), dim3(256), 0, haff_stream(stream), p);
   return haff_check_launch();
 }
 
@@ -501,26 +517,18 @@ static int lora_tn_impl(const void* sT, long lds, int R, const void* big, long l
                         void* out, long ldo, int out_f32, int transposed, int j_valid, float scale, void* stream) {
   if (M <= 0 || N <= 0 || !sT || !big || !workspace || !out || j_valid <= 0 || j_valid > R) return HAFF_ERR_BAD_ARG;
   if (R != 8 && R != 16) return HAFF_ERR_UNSUPPORTED;
-  if ((lds & 7) || lds < (M + 15) / 16 * 16 || !haff_aligned(sT) || (N & 1) || (ldb & 1) || ldb < N || (reinterpret_cast<uintptr_t>(big) & 3))
+  if ((lds & 7) || lds < (M + 15) / 16 * 16 || !haff_aligned(sT) || (N & 1) || (ldb & 1) || ldb < N || !haff_aligned(big, 4))
     return HAFF_ERR_BAD_ARG;
   if (workspace_elems < lora_tn_ws(M, R, N)) return HAFF_ERR_BAD_ARG;
   if (ldo < (transposed ? j_valid : N)) return HAFF_ERR_BAD_ARG;
   const long rpb = lora_tn_rows_per_block(M);
   const int nrb = (int)((M + rpb - 1) / rpb);
   const dim3 g((N + 127) / 128, nrb), b(256);
-  if (R == 8)
-    hipLaunchKernelGGL((lora_tn_kernel<8, F16>), g, b, 0, HS(stream), (const bf16_t*)sT, lds, (const bf16_t*)big, ldb, M, N, (int)rpb, workspace);
-  else
-    hipLaunchKernelGGL((lora_tn_kernel<16, F16>), g, b, 0, HS(stream), (const bf16_t*)sT, lds, (const bf16_t*)big, ldb, M, N, (int)rpb, workspace);
-  const long total = (long)j_valid * N;
-  long gr = (total + 255) / 256;
-  if (gr > 4096) gr = 4096;
-  if (out_f32)
-    hipLaunchKernelGGL((lora_tn_reduce_kernel<float>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (float*)out, ldo, transposed, j_valid, scale);
-  else if (F16)
-    hipLaunchKernelGGL((lora_tn_reduce_kernel<f16_t>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (f16_t*)out, ldo, transposed, j_valid, scale);
-  else
-    hipLaunchKernelGGL((lora_tn_reduce_kernel<bf16_t>), dim3((unsigned)gr), b, 0, HS(stream), workspace, nrb, R, N, (bf16_t*)out, ldo, transposed, j_valid, scale);
+  hipStream_t s = haff_stream(stream);
+  HAFF_DISPATCH_BOOL(R == 8, R8, hipLaunchKernelGGL((lora_tn_kernel<R8 ? 8 : 16, F16>), g, b, 0, s, (const bf16_t*)sT, lds, (const bf16_t*)big, ldb, M, N,
+                                                    (int)rpb, workspace));
+  HAFF_DISPATCH_OUT16(out_f32, F16, hipLaunchKernelGGL((lora_tn_reduce_kernel<T>), dim3(haff_grid((long)j_valid * N, 256, 4096)), b, 0, s, workspace,
+                                                        nrb, R, N, (T*)out, ldo, transposed, j_valid, scale));
   return haff_check_launch();
 }
 
@@ -538,15 +546,15 @@ extern "C" int haff_lora_qkv_rope_bwd(const void* dq, const void* dk, const void
 
 extern "C" int haff_lora_dx(const void* dtT, long ldt, const void* A2, long lda, const void* keep, long ldk, void* dx, long ldx,
                             int accumulate, long M, int K, float scale, void* stream) {
-  return lora_dx_launch<false>(dtT, ldt, A2, lda, keep, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
+  return lora_dx_launch<false>(1, 2, dtT, ldt, A2, lda, keep, nullptr, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
 }
 
 // haff_lora_dx with TWO dropout masks (peft: one lora_dropout module per adapted Linear, 2Haff/train_ds.py:218-230):
-//   dx (+)= scale * ( keep_q o (dt[0:8]^T . A2[0:8]) + keep_v o (dt[8:16]^T . A2[8:16]) ),   both masks bf16 [M][ldk] of values.
+//   dx (+)= scale * ( keep_q o (dt[0:8]^T . A2[0:8]) + keep_v o (dt[8:16]^T . A2[8:16]) ),   both masks bf16 [M][ldk] of values,
+//   both required (lora_dx_masks_ok; haff_lora_dx3 below: no mask, keep_q alone for every adapter, or all three).
 extern "C" int haff_lora_dx2(const void* dtT, long ldt, const void* A2, long lda, const void* keep_q, const void* keep_v, long ldk,
                              void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
-  if (!keep_q || !keep_v) return HAFF_ERR_BAD_ARG;
-  return lora_dx_launch<false>(dtT, ldt, A2, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream);
+  return lora_dx_launch<false>(2, 2, dtT, ldt, A2, lda, keep_q, keep_v, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
 }
 
 extern "C" int haff_lora_tn_workspace_elems(long M, int R, int N) {   // f32 values haff_lora_tn wants; < 0: does not fit an int
@@ -572,12 +580,11 @@ extern "C" int haff_lora_qkv_rope_bwd_f16(const void* dq, const void* dk, const 
 }
 extern "C" int haff_lora_dx_f16(const void* dtT, long ldt, const void* A2, long lda, const void* keep, long ldk, void* dx, long ldx,
                                 int accumulate, long M, int K, float scale, void* stream) {
-  return lora_dx_launch<true>(dtT, ldt, A2, lda, keep, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
+  return lora_dx_launch<true>(1, 2, dtT, ldt, A2, lda, keep, nullptr, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
 }
 extern "C" int haff_lora_dx2_f16(const void* dtT, long ldt, const void* A2, long lda, const void* keep_q, const void* keep_v, long ldk,
                                  void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
-  if (!keep_q || !keep_v) return HAFF_ERR_BAD_ARG;
-  return lora_dx_launch<true>(dtT, ldt, A2, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream);
+  return lora_dx_launch<true>(2, 2, dtT, ldt, A2, lda, keep_q, keep_v, nullptr, ldk, dx, ldx, accumulate, M, K, scale, stream);
 }
 extern "C" int haff_lora_tn_f16(const void* sT, long lds, int R, const void* big, long ldb, long M, int N, float* workspace,
                                 long workspace_elems, void* out, long ldo, int out_f32, int transposed, int j_valid, float scale,
@@ -591,13 +598,10 @@ template <bool F16>
 static int lora_out_impl(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream) {
   if (M <= 0 || N <= 0 || !tT || !B || !y) return HAFF_ERR_BAD_ARG;
   if (N % 8) return HAFF_ERR_UNSUPPORTED;
-  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || (reinterpret_cast<uintptr_t>(tT) & 7) || ldy < N || (ldy & 7) || !haff_aligned(y) || !haff_aligned(B))
+  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || !haff_aligned(tT, 8) || ldy < N || (ldy & 7) || !haff_aligned(y) || !haff_aligned(B))
     return HAFF_ERR_BAD_ARG;
-  const long total = (M + 3) / 4 * (N / 8);
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL((lora_out_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)tT, ldt, (const bf16_t*)B, (bf16_t*)y,
-                     ldy, M, N, scale);
+  hipLaunchKernelGGL((lora_out_kernel<F16>), dim3(haff_grid((M + 3) / 4 * (N / 8), 256, 8192)), dim3(256), 0, haff_stream(stream),
+                     (const bf16_t*)tT, ldt, (const bf16_t*)B, (bf16_t*)y, ldy, M, N, scale);
   return haff_check_launch();
 }
 
@@ -606,14 +610,11 @@ static int lora_gu_swiglu_impl(const void* tT, long ldt, const void* Bg, const v
                                float scale, void* stream) {
   if (M <= 0 || F <= 0 || !tT || !Bg || !Bu || !gu || !y) return HAFF_ERR_BAD_ARG;
   if (F % 16) return HAFF_ERR_UNSUPPORTED;
-  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || (reinterpret_cast<uintptr_t>(tT) & 7) || ldg < 2L * F || (ldg & 7) || ldy < F || (ldy & 7))
+  if (ldt < (M + 3) / 4 * 4 || (ldt & 3) || !haff_aligned(tT, 8) || ldg < 2L * F || (ldg & 7) || ldy < F || (ldy & 7))
     return HAFF_ERR_BAD_ARG;
   if (!haff_aligned(Bg) || !haff_aligned(Bu) || !haff_aligned(gu) || !haff_aligned(y)) return HAFF_ERR_BAD_ARG;
-  const long total = (M + 3) / 4 * (F / 8);
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL((lora_gu_swiglu_kernel<F16>), dim3((unsigned)g), dim3(256), 0, HS(stream), (const bf16_t*)tT, ldt, (const bf16_t*)Bg,
-                     (const bf16_t*)Bu, (bf16_t*)gu, ldg, (bf16_t*)y, ldy, M, F, scale);
+  hipLaunchKernelGGL((lora_gu_swiglu_kernel<F16>), dim3(haff_grid((M + 3) / 4 * (F / 8), 256, 8192)), dim3(256), 0, haff_stream(stream),
+                     (const bf16_t*)tT, ldt, (const bf16_t*)Bg, (const bf16_t*)Bu, (bf16_t*)gu, ldg, (bf16_t*)y, ldy, M, F, scale);
   return haff_check_launch();
 }
 
@@ -624,8 +625,7 @@ extern "C" int haff_lora_qkv3_rope_fwd(const void* qkv, long ld_qkv, const void*
 }
 extern "C" int haff_lora_dx3(const void* dtT, long ldt, const void* A3, long lda, const void* keep_q, const void* keep_v, const void* keep_k,
                              long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
-  if (keep_v && !keep_k) return HAFF_ERR_BAD_ARG;   // no mask, one shared mask (keep_q), or three
-  return lora_dx_launch<false>(dtT, ldt, A3, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream, 3, keep_k);
+  return lora_dx_launch<false>(3, 3, dtT, ldt, A3, lda, keep_q, keep_v, keep_k, ldk, dx, ldx, accumulate, M, K, scale, stream);
 }
 extern "C" int haff_lora_out(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream) {
   return lora_out_impl<false>(tT, ldt, B, y, ldy, M, N, scale, stream);
@@ -641,8 +641,7 @@ extern "C" int haff_lora_qkv3_rope_fwd_f16(const void* qkv, long ld_qkv, const v
 }
 extern "C" int haff_lora_dx3_f16(const void* dtT, long ldt, const void* A3, long lda, const void* keep_q, const void* keep_v,
                                  const void* keep_k, long ldk, void* dx, long ldx, int accumulate, long M, int K, float scale, void* stream) {
-  if (keep_v && !keep_k) return HAFF_ERR_BAD_ARG;
-  return lora_dx_launch<true>(dtT, ldt, A3, lda, keep_q, keep_v, ldk, dx, ldx, accumulate, M, K, scale, stream, 3, keep_k);
+  return lora_dx_launch<true>(3, 3, dtT, ldt, A3, lda, keep_q, keep_v, keep_k, ldk, dx, ldx, accumulate, M, K, scale, stream);
 }
 extern "C" int haff_lora_out_f16(const void* tT, long ldt, const void* B, void* y, long ldy, long M, int N, float scale, void* stream) {
   return lora_out_impl<true>(tT, ldt, B, y, ldy, M, N, scale, stream);
